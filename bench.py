@@ -21,9 +21,18 @@ as in a task that has just decoded its plan (rust/executor/src/flight_service.rs
 
 Prints ONE JSON line (rank 0).  `value` = driving-table rows of the whole job / max-over-ranks wall time.
 `roofline`: algorithmic bytes of one launch of the dominant kernel / its average duration, timed
-with HIP events on the stream it ran on (BHIP_KERNEL_TIMING=1).  `cpu_baseline`: the oracle's threaded port of the
-same query in DataFusion's structure (oracle/oracle_ops.c) on a bounded sample, on the host cores of the same box;
-`cpu_baseline_acero`: Arrow C++ (pyarrow) on the same sample, a second, independent CPU engine.
+with HIP events on the stream it ran on (BHIP_KERNEL_TIMING=1).
+
+A plain run measures the headline query only.  `--full` adds what takes runs of its own: `cpu_baseline` (the oracle's
+threaded port of the same query in DataFusion's structure, oracle/oracle_ops.c, on a bounded sample, on the host cores of
+the same box), `cpu_baseline_acero` (Arrow C++ / pyarrow on the same sample, a second, independent CPU engine), the
+weak-scaling figure (N > 1) and, for N = 1 and Q1, the other single-GPU configurations under `configs`.
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes the result of its last timed step as DIR/<column>.npy
+                       (numbers as float64, or float32 where the column is Float32; NULL = NaN; Utf8 as a rows x bytes
+                       matrix of its UTF-8 bytes, 0-padded); the tables come from a fixed seed, so two builds run with
+                       the same arguments can be compared output for output.  Float64 sums of two runs of one build can
+                       differ in the last bit (Q1 SF100: 2e-16 relative), so compare them with a relative tolerance.
 """
 import argparse
 import json
@@ -57,8 +66,12 @@ def parse(argv=None):
     ap.add_argument("--join-exchange", default="shuffle", choices=["shuffle", "broadcast"],
                     help="N > 1, q3 / q5: hash-partition both sides of the order-key join (config #5) or broadcast the build side")
     ap.add_argument("--chunk-rows", type=int, default=0, help="N > 1, --join-exchange shuffle: rows per chunk of the streaming shuffle (0 = the library's default, 64 Mi)")
-    ap.add_argument("--configs", default="q6,q3,q5", help="N = 1 and --query q1 (the default run): further queries measured after Q1 and "
-                    "reported under \"configs\" (\"\" = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure beyond the headline: CPU baselines, weak scaling (N > 1), the further queries of --configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<column>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--configs", default=None, help="N = 1 and --query q1: further queries measured after Q1 and "
+                    "reported under \"configs\" (default: q6,q3,q5 with --full, none without; \"\" = none)")
     ap.add_argument("--config-steps", type=int, default=10, help="timed steps of each query under --configs")
     ap.add_argument("--config-cpu-rows", type=int, default=48_000_000, help="CPU-baseline sample rows of each query under --configs")
     ap.add_argument("--allow-host-exchange", action="store_true",
@@ -66,7 +79,10 @@ def parse(argv=None):
                          "instead of exiting non-zero (the line then says so in exchange_backend)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="transport for N > 1 (nccl = RCCL; gloo only to rehearse the N-rank flow on a box with fewer GPUs)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -191,8 +207,61 @@ def pmc_traffic(kernel, rows, query):
     return None, None
 
 
-def measure(query, args, ctx, group, world, rank, n, cpu_rows, cpu_budget_s, steps, warmup):
-    """load `query`'s tables, time `steps` steps of it, return (line dict on rank 0 | None).  Frees the tables on return."""
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(result, out_dir):
+    """the batches of one step's result as out_dir/<column>.npy: numbers as float64 (Float32 stays float32), NULL = NaN, Utf8
+    as a rows x bytes float64 matrix of its UTF-8 bytes (0-padded).  Over DUMP_LIMIT_BYTES in all, the same fixed, seeded
+    sample of rows is kept of every column."""
+    import re
+    import numpy as np
+    from ballista_amd import expr as E
+
+    os.makedirs(out_dir, exist_ok=True)
+    result = [b for b in result if b.num_rows > 0] or result[:1]
+    if not result:
+        return {}
+    cols = {}
+    for i in range(result[0].num_columns):
+        name, dtype = result[0].column_info(i)[:2]
+        parts = []
+        for b in result:
+            _, values, valid = b.column(i)
+            if dtype == E.UTF8:
+                raw = [v.encode() for v in values]
+                a = np.zeros((len(raw), max([1] + [len(r) for r in raw])), np.float64)
+                for k, r in enumerate(raw):
+                    a[k, :len(r)] = np.frombuffer(r, np.uint8)
+            else:
+                a = np.asarray(values, np.float32 if dtype == E.FLOAT32 else np.float64)
+            if valid is not None:
+                a = a.copy()
+                a[~valid] = np.nan
+            parts.append(a)
+        if dtype == E.UTF8:
+            width = max(p.shape[1] for p in parts)
+            parts = [np.pad(p, ((0, 0), (0, width - p.shape[1]))) for p in parts]
+        cols[name] = np.concatenate(parts)
+    n_rows = len(next(iter(cols.values())))
+    total = sum(a.nbytes for a in cols.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, int(n_rows * DUMP_LIMIT_BYTES / total))
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+        cols = {k: a[rows] for k, a in cols.items()}
+    written = {}
+    for name, a in cols.items():
+        fn = re.sub(r"[^A-Za-z0-9_.-]+", "_", name).strip("._") or "column"
+        while fn in written:
+            fn += "_"
+        np.save(os.path.join(out_dir, fn + ".npy"), a)
+        written[fn] = list(a.shape)
+    return dict(dir=out_dir, rows=n_rows, sampled_rows=len(next(iter(cols.values()))), arrays=written)
+
+
+def measure(query, args, ctx, group, world, rank, n, cpu_rows, cpu_budget_s, steps, warmup, dump_dir=None):
+    """load `query`'s tables, time `steps` steps of it, return (line dict on rank 0 | None).  Frees the tables on return.
+    `dump_dir`: rank 0 writes the result of the last timed step there (dump_outputs)."""
     import ballista_amd as ba                                       # noqa: F401
     from ballista_amd import distributed as D
 
@@ -234,11 +303,12 @@ def measure(query, args, ctx, group, world, rank, n, cpu_rows, cpu_budget_s, ste
     elapsed, result, kstats = timed(W.step, steps, warmup)
     exch = W.exchange_stats(reset=True)
     host = W.host_overhead(reset=True)
+    dumped = dump_outputs(result, dump_dir) if dump_dir and rank == 0 else None
 
     weak = None
     # weak scaling (every rank its own full-size block) is defined for the scans only: a join's row blocks of different ranks must
     # come from ONE pair of tables for their keys to meet
-    if world > 1 and not args.no_weak and query in ("q1", "q6"):
+    if args.full and world > 1 and not args.no_weak and query in ("q1", "q6"):
         W.load(mode="weak")
         w_steps = max(3, steps // 4)
         w_elapsed, _, _ = timed(W.step, w_steps, 1)
@@ -284,10 +354,12 @@ def measure(query, args, ctx, group, world, rank, n, cpu_rows, cpu_budget_s, ste
             out["weak_scaling"] = weak
         if exch:
             out["exchange"] = exch
+        if dumped is not None:
+            out["dump_outputs"] = dumped
     del result
     W.unload()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and cpu_rows > 0:      # the CPU legs run at N=1 only
+        if args.full and world == 1 and not args.no_cpu_baseline and cpu_rows > 0:      # the CPU legs run at N=1 only
             sample = min(cpu_rows, n["lineitem"])
             out["cpu_baseline"] = cpu_baseline(query, args.sf, sample, cpu_budget_s)
             acero = cpu_baseline_acero(query, args.sf, sample, min(5.0, cpu_budget_s))
@@ -319,10 +391,11 @@ def main():
     if args.rows:
         n["lineitem"] = args.rows
 
-    out = measure(args.query, args, ctx, group, world, rank, n, args.cpu_rows, 10.0, args.steps, args.warmup)
+    out = measure(args.query, args, ctx, group, world, rank, n, args.cpu_rows, 10.0, args.steps, args.warmup, args.dump_outputs)
     # the other single-GPU configurations of BASELINE.json (#3 Q6, #4 Q3, and the one-GPU leg of #5: Q5 at SF100), each with its own
     # step time, dominant-kernel roofline and CPU baseline; the headline metric / value / roofline / cpu_baseline stay Q1's
-    extra = [q for q in args.configs.split(",") if q and q != args.query] if (world == 1 and args.query == "q1") else []
+    config_list = args.configs if args.configs is not None else ("q6,q3,q5" if args.full else "")
+    extra = [q for q in config_list.split(",") if q and q != args.query] if (world == 1 and args.query == "q1") else []
     configs = {}
     for q in extra:
         if q not in ("q1", "q6", "q3", "q5"):

@@ -282,12 +282,17 @@ def test_three_rank_routing_gloo():
         assert msg == "ok", f"rank {rank}:\n{msg}"
 
 
-def test_bench_self_launches_its_ranks(monkeypatch):
-    """`python bench.py --gpus N` without a launcher spawns torch.distributed.run as a child and relays rank 0's line"""
+def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_self_launches_its_ranks(monkeypatch):
+    """`python bench.py --gpus N` without a launcher spawns torch.distributed.run as a child and relays rank 0's line"""
+    bench = _bench_module()
     seen = {}
 
     class Done:
@@ -303,3 +308,56 @@ def test_bench_self_launches_its_ranks(monkeypatch):
     cmd = seen["cmd"]
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node=4" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "4", "--steps", "2"]
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """--full is off by default and no further queries are named, so a plain run times the headline query alone"""
+    bench = _bench_module()
+    plain, full = bench.parse(["--steps", "3"]), bench.parse(["--steps", "3", "--full"])
+    assert not plain.full and plain.configs is None and plain.dump_outputs is None and plain.steps == 3
+    assert full.full and full.configs is None
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_bench_dump_outputs_writes_every_column(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per result column, numbers as float64 (Float32 kept), NULL = NaN, Utf8 as its bytes; a result
+    over the size limit is cut to the same seeded sample of rows in every column"""
+    from ballista_amd import expr as E
+    bench = _bench_module()
+
+    class Batch:
+        def __init__(self, cols):
+            self.cols = cols
+            self.num_rows = len(cols[0][2])
+            self.num_columns = len(cols)
+
+        def column_info(self, i):
+            name, dtype, values, valid = self.cols[i]
+            return name, dtype, valid is not None, 0, valid is not None
+
+        def column(self, i):
+            _, dtype, values, valid = self.cols[i]
+            return dtype, values, valid
+
+    b0 = Batch([("l_returnflag", E.UTF8, ["A", "NO"], None), ("sum(qty)", E.FLOAT64, np.array([1.5, 2.5]), None),
+                ("n", E.INT64, np.array([3, 4], np.int64), np.array([True, False])), ("f", E.FLOAT32, np.array([1, 2], np.float32), None)])
+    b1 = Batch([("l_returnflag", E.UTF8, ["R"], None), ("sum(qty)", E.FLOAT64, np.array([7.0]), None),
+                ("n", E.INT64, np.array([5], np.int64), None), ("f", E.FLOAT32, np.array([3], np.float32), None)])
+    info = bench.dump_outputs([b0, b1], str(tmp_path / "out"))
+    assert info["rows"] == info["sampled_rows"] == 3
+    assert sorted(os.listdir(tmp_path / "out")) == ["f.npy", "l_returnflag.npy", "n.npy", "sum_qty.npy"]
+    flag = np.load(tmp_path / "out" / "l_returnflag.npy")
+    assert flag.dtype == np.float64 and flag.tolist() == [[65, 0], [78, 79], [82, 0]]
+    assert np.load(tmp_path / "out" / "sum_qty.npy").tolist() == [1.5, 2.5, 7.0]
+    n = np.load(tmp_path / "out" / "n.npy")
+    assert n.dtype == np.float64 and n[0] == 3 and np.isnan(n[1]) and n[2] == 5
+    assert np.load(tmp_path / "out" / "f.npy").dtype == np.float32
+
+    big = Batch([("x", E.FLOAT64, np.arange(4000, dtype=np.float64), None), ("y", E.INT32, np.arange(4000, dtype=np.int32), None)])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16000)
+    for d in ("s1", "s2"):
+        info = bench.dump_outputs([big], str(tmp_path / d))
+        assert info["rows"] == 4000 and info["sampled_rows"] == 1000
+    x, y = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s1" / "y.npy")
+    assert np.array_equal(x, y) and np.all(np.diff(x) > 0) and np.array_equal(x, np.load(tmp_path / "s2" / "x.npy"))

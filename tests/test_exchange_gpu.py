@@ -63,7 +63,18 @@ def test_pack_unpack_roundtrip(ctx, n):
                                   key_cols=["d"])
 
 
-def test_rccl_communicator_world_of_one(ctx):
+def test_rccl_communicator_world_of_one():
+    """in a child process that holds only what the library loads: once a process has imported torch (the CPU tier's gloo tests
+    do, earlier in a whole-suite run), torch's bundled HIP runtime and librccl sit beside the system's, dlopen("librccl.so.1")
+    returns torch's copy, and that RCCL cannot use the library's device context"""
+    code = ("import sys; sys.path[:0] = [%r, %r]; import ballista_amd as ba; import test_exchange_gpu as t; "
+            "t.rccl_world_of_one(ba.Context(0)); print('rccl world of one: ok')") % (ROOT, os.path.join(ROOT, "tests"))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and r.stdout.strip().endswith("rccl world of one: ok"), r.stdout[-2000:] + "\n" + r.stderr[-4000:]
+
+
+def rccl_world_of_one(ctx):
     uid = ba.plan.Communicator.unique_id()
     assert len(uid) == 128 and any(uid)
     comm = ba.plan.Communicator(ctx, uid, 1, 0)
