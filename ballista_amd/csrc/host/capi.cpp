@@ -98,6 +98,16 @@ const char* bhip_ctx_kernel_name(bhip_ctx* ctx) {
     return name.c_str();
 }
 
+int32_t bhip_ctx_device_cus(bhip_ctx* ctx) {
+    return ctx ? ctx->p->cus() : 0;
+}
+
+const char* bhip_ctx_kernel_variant(bhip_ctx* ctx) {
+    static thread_local std::string name;
+    name = ctx ? ctx->p->kernel_variant() : std::string();
+    return name.c_str();
+}
+
 // ---- batches ------------------------------------------------------------------------------------------
 static bhip_batch* wrap_batch(BatchPtr b) {
     auto h = new bhip_batch();

@@ -255,12 +255,13 @@ void Context::release_stream(hipStream_t s) {
     stream_pool_.push_back(s);
 }
 
-void Context::add_kernel_time(double ms, uint64_t launches, const char* kernel) {
+void Context::add_kernel_time(double ms, uint64_t launches, const char* kernel, const char* variant) {
     std::lock_guard<std::mutex> g(mu_);
     k_ms_ += ms;
     k_launches_ += launches;
     if (kernel && launches) {
         k_name_ = kernel;
+        k_variant_ = variant ? variant : "";
         auto& st = k_stats_[kernel];
         st.ms += ms;
         st.launches += launches;
@@ -309,6 +310,11 @@ std::map<std::string, Context::KernelStat> Context::kernel_stats(bool reset) {
 std::string Context::kernel_name() {
     std::lock_guard<std::mutex> g(mu_);
     return k_name_;
+}
+
+std::string Context::kernel_variant() {
+    std::lock_guard<std::mutex> g(mu_);
+    return k_variant_;
 }
 
 void Context::kernel_time(bool reset, double* ms, uint64_t* launches) {

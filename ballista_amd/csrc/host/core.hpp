@@ -76,8 +76,9 @@ public:
     void wait_stream(hipStream_t stream, const void* dev_src = nullptr, void* host_dst = nullptr, size_t bytes = 0);
 
     // kernel timing hook (bench roofline): accumulated by the aggregate operator
-    void add_kernel_time(double ms, uint64_t launches, const char* kernel = nullptr);
+    void add_kernel_time(double ms, uint64_t launches, const char* kernel = nullptr, const char* variant = nullptr);
     std::string kernel_name();
+    std::string kernel_variant();   // instantiation of kernel_name() that ran ("" where the call site names none)
     void kernel_time(bool reset, double* ms, uint64_t* launches);
     bool timing_enabled() const { return timing_ > 0; }
     int timing_level() const { return timing_; }
@@ -103,7 +104,7 @@ private:
     bool spin_wait_ = true;
     double k_ms_ = 0;
     uint64_t k_launches_ = 0;
-    std::string k_name_;
+    std::string k_name_, k_variant_;
     struct PendingTimed { hipEvent_t a, b; const char* name; uint64_t bytes; };
     std::vector<PendingTimed> pending_timed_;
     std::vector<hipEvent_t> event_pool_;

@@ -169,6 +169,7 @@ struct TimedLaunches {
         if (on) HIP_CHECK(hipEventRecord(ev.back().second, ex.stream));
     }
     const char* kernel = nullptr;
+    const char* variant = nullptr;   // which instantiation of `kernel` ran (the lean path: generic or a specialised shape)
     void collect() {   // call after the stream was synchronised
         if (!on) return;
         double ms = 0;
@@ -178,7 +179,7 @@ struct TimedLaunches {
             hipEventDestroy(p.first);
             hipEventDestroy(p.second);
         }
-        ex.ctx->add_kernel_time(ms, ev.size(), kernel);
+        ex.ctx->add_kernel_time(ms, ev.size(), kernel, variant);
         ev.clear();
     }
 };
@@ -850,11 +851,17 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
             ProgramBuilder::bind(P, pb.columns(), *b, nullable);
             int grid = 0;
             const bool timed = b->n_rows >= (1 << 16);   // the bench hook times the dominant (large) launches only
-            if (timed) { timer.begin(); timer.kernel = lean_now ? "scan_agg_lean_kernel" : sop_now ? "scan_agg_sop_kernel" : "scan_agg_lowcard_kernel"; }
+            if (timed) {
+                timer.begin();
+                timer.kernel = lean_now ? "scan_agg_lean_kernel" : sop_now ? "scan_agg_sop_kernel" : "scan_agg_lowcard_kernel";
+                timer.variant = nullptr;
+            }
             if (lean_now) {
                 bind_sop(sop, *b);
+                const char* variant = nullptr;
                 HIP_CHECK(launch_scan_agg_lean(cfg, sop.prog, tmp.get<SopProgram>(1), gmax, partials + (size_t)n_part * gmax,
-                                               partial_ng + n_part, max_grid, status, &grid));
+                                               partial_ng + n_part, max_grid, status, &grid, &variant));
+                if (timed) timer.variant = variant;
             } else if (sop_now) {
                 bind_sop(sop, *b);
                 HIP_CHECK(launch_scan_agg_sop(cfg, sop.prog, tmp.get<SopProgram>(1), gmax, partials + (size_t)n_part * gmax,

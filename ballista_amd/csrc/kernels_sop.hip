@@ -1,6 +1,7 @@
 // kernels_sop.hip — dispatcher of the register-resident scan + aggregate fast path
 // (kernel: sop_kernel.h; instantiations: kernels_sop_g{1,4,8}.hip; plan table: sop.h).
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 #include "sop.h"
 
 namespace bhip {
@@ -21,10 +22,22 @@ hipError_t launch_scan_agg_sop(const LaunchCfg& cfg, const SopProgram& S, SopPro
 
 hipError_t launch_scan_agg_lean_g1(const LaunchCfg&, const SopProgram&, SopProgram*, GroupRec*, uint32_t*, int, ScanStatus*, int*);
 hipError_t launch_scan_agg_lean_g4(const LaunchCfg&, const SopProgram&, SopProgram*, GroupRec*, uint32_t*, int, ScanStatus*, int*);
+hipError_t launch_scan_agg_lean_spec(const LaunchCfg&, const SopProgram&, SopProgram*, int, GroupRec*, uint32_t*, int, ScanStatus*, int*,
+                                     bool*, const char**);
 
-// wide-load variant (lean_kernel.h; instantiations: kernels_lean_g{1,4}.hip)
+// wide-load variant: the shape-specialised kernel when S has one of its shapes (lean_spec_kernel.h;
+// kernels_lean_spec.hip), else the generic one (lean_kernel.h; kernels_lean_g{1,4}.hip).  BHIP_LEAN_GENERIC=1: always generic.
 hipError_t launch_scan_agg_lean(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
-                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out) {
+                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant) {
+    static const bool generic_only = [] { const char* v = getenv("BHIP_LEAN_GENERIC"); return v && atoi(v) != 0; }();
+    const char* name = "lean_generic";
+    if (!variant) variant = &name;
+    if (!generic_only) {
+        bool ran = false;
+        const hipError_t e = launch_scan_agg_lean_spec(cfg, S, dprog, gmax, partials, partial_ng, max_grid, status, grid_out, &ran, variant);
+        if (ran || e != hipSuccess) return e;
+    }
+    *variant = "lean_generic";
     switch (gmax) {
         case 1: return launch_scan_agg_lean_g1(cfg, S, dprog, partials, partial_ng, max_grid, status, grid_out);
         case 4: return launch_scan_agg_lean_g4(cfg, S, dprog, partials, partial_ng, max_grid, status, grid_out);

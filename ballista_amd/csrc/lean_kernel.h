@@ -85,6 +85,189 @@ __device__ inline uint32_t lean_str_word(uint32_t raw, uint32_t len) {
     return (__builtin_amdgcn_ubfe(raw, 0u, len << 3) << 8) | len;
 }
 
+// The workgroup's key table: a wave-uniform register copy of lds.keys / lds.ng, and the lookup protocol.
+template <int GMAX, int NSTEP>
+struct LeanKeyTable {
+    int ng_c = 0;
+    uint64_t gk[GMAX];
+    __device__ LeanKeyTable() {
+#pragma unroll
+        for (int g = 0; g < GMAX; ++g) gk[g] = 0;
+    }
+    // group slot of every row (-1: filtered out); appends unknown keys under the LDS lock (rare).  false: more than GMAX
+    // groups.  Every branch that leaves the loop is wave-uniform (readfirstlane), so the caller's loop stays one path.
+    __device__ bool lookup(LeanLds<GMAX, NSTEP>& lds, int lane, const uint64_t (&key)[LEAN_ROWS], const bool (&live)[LEAN_ROWS],
+                           int (&lg)[LEAN_ROWS]) {
+        if constexpr (GMAX == 1) {
+#pragma unroll
+            for (int r = 0; r < LEAN_ROWS; ++r) lg[r] = live[r] ? 0 : -1;
+            return true;
+        } else {
+            volatile uint32_t* v_ng = &lds.ng;
+            volatile uint32_t* v_over = &lds.overflow;
+            for (;;) {
+                bool pending = false;
+#pragma unroll
+                for (int r = 0; r < LEAN_ROWS; ++r) {
+                    int found = -2;
+#pragma unroll
+                    for (int g2 = 0; g2 < GMAX; ++g2) found = (g2 < ng_c && key[r] == gk[g2]) ? g2 : found;
+                    lg[r] = live[r] ? found : -1;
+                    pending |= (lg[r] == -2);
+                }
+                const uint64_t pmask = __ballot(pending);
+                if (__builtin_expect(pmask == 0, 1)) return true;   // steady state: no LDS access
+                if (__builtin_amdgcn_readfirstlane(*v_over)) return false;
+                if (__builtin_amdgcn_readfirstlane(*v_ng) == (uint32_t)ng_c) {
+                    if (lane == (int)__builtin_ctzll(pmask)) {
+                        uint64_t mine = 0;
+#pragma unroll
+                        for (int r = LEAN_ROWS - 1; r >= 0; --r)
+                            if (lg[r] == -2) mine = key[r];
+                        while (atomicCAS(&lds.lock, 0u, 1u) != 0u) {}
+                        const int n2 = (int)*v_ng;                 // another wave may have appended it meanwhile
+                        bool have = false;
+                        for (int g2 = 0; g2 < n2; ++g2) have |= (lds.keys[g2] == mine);
+                        if (!have) {
+                            if (n2 < GMAX) {
+                                lds.keys[n2] = mine;
+                                __threadfence_block();             // key before count
+                                *v_ng = (uint32_t)(n2 + 1);
+                            } else {
+                                *v_over = 1;
+                            }
+                        }
+                        __threadfence_block();
+                        atomicExch(&lds.lock, 0u);
+                    }
+                }
+                ng_c = __builtin_amdgcn_readfirstlane((int)*v_ng);
+#pragma unroll
+                for (int g2 = 0; g2 < GMAX; ++g2) gk[g2] = lean_uniform_u64(lds.keys[g2]);
+            }
+        }
+    }
+};
+
+// The ragged tail (< 1024 rows) after the full tiles: one row per thread and pass, the plan read from S (a cold path).
+// accumulate(lg, tv[NSTEP]) adds one row.  false: more than GMAX groups.
+template <int GMAX, int NSTEP, int NRANGE, class Lookup, class Accumulate>
+__device__ inline bool lean_tail(const SopProgram& S, int64_t tail0, int64_t n_rows, uint32_t& bad_len, Lookup&& lookup,
+                                 Accumulate&& accumulate) {
+    constexpr int NKEY = 2;
+    const int tid = threadIdx.x;
+    for (int k = 0; k < LEAN_TILE / BLOCK; ++k) {
+        const int64_t i = tail0 + (int64_t)k * BLOCK + tid;
+        const bool in = i < n_rows;
+        bool ok = in;
+        uint32_t w[NKEY] = {0, 0};
+        double tv[NSTEP];
+#pragma unroll
+        for (int s = 0; s < NSTEP; ++s) tv[s] = 0.0;
+        if (in) {
+#pragma unroll
+            for (int p = 0; p < NRANGE; ++p)
+                if (p < S.n_ranges) {
+                    const SopRange rg = S.ranges[p];
+                    const BHIP_GLOBAL char* base = (const BHIP_GLOBAL char*)S.cols[rg.col].data;
+                    const double x = rg.is32 ? (double)*(const BHIP_GLOBAL int32_t*)(base + i * 4) : *(const BHIP_GLOBAL double*)(base + i * 8);
+                    ok = ok && x >= rg.lo && x <= rg.hi;
+                    const BHIP_GLOBAL uint64_t* vb = (const BHIP_GLOBAL uint64_t*)S.cols[rg.col].validity;
+                    if (vb) ok = ok && ((vb[i >> 6] >> (i & 63)) & 1ull);
+                }
+#pragma unroll
+            for (int q = 0; q < NKEY; ++q)
+                if (q < S.n_keys) {
+                    const SopColumn c = S.cols[S.keys[q].col];
+                    if (S.keys[q].kind == SOP_KEY_UTF8) {
+                        const uint32_t o0 = (uint32_t)c.offsets[i];
+                        uint32_t len = (uint32_t)c.offsets[i + 1] - o0;
+                        bad_len |= len;
+                        len = len > LEAN_MAX_STR ? LEAN_MAX_STR : len;
+                        w[q] = lean_str_word((uint32_t)((const BHIP_GLOBAL PackedU64*)((const BHIP_GLOBAL char*)c.data + o0))->v, len);
+                    } else {
+                        w[q] = *(const BHIP_GLOBAL uint32_t*)((const BHIP_GLOBAL char*)c.data + i * 4);
+                    }
+                }
+#pragma unroll
+            for (int s = 0; s < NSTEP; ++s)
+                if (s < S.n_steps) {
+                    const SopStep st = S.steps[s];
+                    const bool plain = st.sgn == 1.0 && st.add == 0.0 && __builtin_signbit(st.add);   // 1.0 * x + (-0.0) == x
+                    const uint32_t flip = st.sgn < 0.0 ? 0x80000000u : 0u;
+                    const double x = *(const BHIP_GLOBAL double*)((const BHIP_GLOBAL char*)S.cols[st.col].data + i * 8);
+                    const double f = plain ? x : u2d(d2u(x) ^ ((uint64_t)flip << 32)) + st.add;
+                    tv[s] = (s > 0 && !st.start) ? tv[s - (s > 0)] * f : f;
+                }
+        }
+        // the lookup is a wave-level protocol: every lane takes part, rows beyond the end as "filtered out"
+        uint64_t key[LEAN_ROWS];
+        bool live[LEAN_ROWS];
+        int lg[LEAN_ROWS];
+#pragma unroll
+        for (int r = 0; r < LEAN_ROWS; ++r) { key[r] = 0; live[r] = false; }
+        key[0] = ((uint64_t)w[1] << 32) | w[0];
+        live[0] = ok;
+        if (!lookup(key, live, lg)) return false;
+        accumulate(lg[0], tv);
+    }
+    return true;
+}
+
+// Fixed-order workgroup reduction (lanes: shuffle tree, then waves 0..3) and the workgroup's partial groups.
+// acc / rows1: the GMAX == 1 accumulators (registers); GMAX > 1 reads the LDS slots.
+template <int GMAX, int NSTEP>
+__device__ inline void lean_finish(LeanLds<GMAX, NSTEP>& lds, const SopProgram& S, const double (&acc)[NSTEP], uint32_t rows1,
+                                   uint32_t bad_len, GroupRec* partials, uint32_t* partial_ng, ScanStatus* status) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __syncthreads();
+    uint64_t tot_rows = 0;
+    double tot_acc = 0.0;
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g) {
+        const uint32_t mine = GMAX == 1 ? rows1 : lds.cnt[(GMAX > 1 ? g : 0) * BLOCK + tid];
+        const uint64_t v = wave_reduce((uint64_t)mine, ACC_COUNT_ROWS);
+        if (lane == 0) lds.rowred[wave][g] = v;
+    }
+#pragma unroll
+    for (int g = 0; g < GMAX; ++g)
+#pragma unroll
+        for (int s = 0; s < NSTEP; ++s) {
+            const double mine = GMAX == 1 ? acc[s] : lds.acc[(GMAX > 1 ? (g * NSTEP + s) : 0) * BLOCK + tid];
+            const uint64_t v = wave_reduce(d2u(mine), ACC_SUM_F64);
+            if (lane == 0) lds.red[wave][g * NSTEP + s] = v;
+        }
+    __syncthreads();
+    if (tid < GMAX) {
+        tot_rows = lds.rowred[0][tid] + lds.rowred[1][tid] + lds.rowred[2][tid] + lds.rowred[3][tid];
+        lds.rowtot[tid] = tot_rows;
+    }
+    if (tid < GMAX * NSTEP)
+        tot_acc = ((u2d(lds.red[0][tid]) + u2d(lds.red[1][tid])) + u2d(lds.red[2][tid])) + u2d(lds.red[3][tid]);
+    __syncthreads();
+
+    GroupRec* out = partials + (size_t)blockIdx.x * GMAX;
+    if (tid < GMAX) {
+        // the packed-key layout of sop_kernel.h: part 0 -> word 0, part 1 -> word 1
+        out[tid].k0 = lds.keys[tid] & 0xFFFFFFFFull;
+        out[tid].k1 = lds.keys[tid] >> 32;
+        out[tid].rows = tot_rows;
+    }
+    if (tid < GMAX * NSTEP) {
+        const int g = tid / NSTEP, s = tid % NSTEP;
+        if (s < S.n_steps && S.steps[s].acc != 0xFF) {
+            out[g].acc[S.steps[s].acc] = d2u(tot_acc);
+            out[g].nvalid[S.steps[s].acc] = lds.rowtot[g];
+        }
+    }
+    if (tid == 0) {
+        // without GROUP BY the one group (key 0) exists once a row has passed the filter
+        partial_ng[blockIdx.x] = GMAX == 1 ? (tot_rows > 0 ? 1u : 0u) : lds.ng;
+        if (lds.overflow) atomicOr(&status->flags, SCAN_OVERFLOW_GROUPS);
+    }
+    if (bad_len > LEAN_MAX_STR) atomicOr(&status->flags, SCAN_ERR_KEY_TOO_LONG);
+}
+
 template <int GMAX, int NSTEP, int NRANGE>
 __global__ void __launch_bounds__(BLOCK, (GMAX == 1 && NSTEP <= 5) ? 4 : 3)
 scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint32_t* partial_ng, ScanStatus* status) {
@@ -92,7 +275,7 @@ scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint
     constexpr int U = LEAN_U;
     constexpr int NKEY = 2;
     __shared__ LeanLds<GMAX, NSTEP> lds;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
 
     // ---- resolve the plan into wave-uniform registers
     const int n_ranges = S.n_ranges, n_keys = S.n_keys, n_steps = S.n_steps;
@@ -160,62 +343,10 @@ scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint
     if (tid == 0) { lds.ng = 0; lds.overflow = 0; lds.lock = 0; }
     if (tid < AGG_GMAX) lds.keys[tid] = 0;
     __syncthreads();
-    volatile uint32_t* v_ng = &lds.ng;
-    volatile uint32_t* v_over = &lds.overflow;
     uint32_t bad_len = 0;
-    int ng_c = 0;                              // register copy of the workgroup's key table
-    uint64_t gk[GMAX];
-#pragma unroll
-    for (int g = 0; g < GMAX; ++g) gk[g] = 0;
-
-    // group slot of every row (-1: filtered out); appends unknown keys under the LDS lock (rare)
+    LeanKeyTable<GMAX, NSTEP> table;
     auto lookup = [&](const uint64_t (&key)[LEAN_ROWS], const bool (&live)[LEAN_ROWS], int (&lg)[LEAN_ROWS]) -> bool {
-        if constexpr (GMAX == 1) {
-#pragma unroll
-            for (int r = 0; r < LEAN_ROWS; ++r) lg[r] = live[r] ? 0 : -1;
-            return true;
-        } else {
-            for (;;) {
-                bool pending = false;
-#pragma unroll
-                for (int r = 0; r < LEAN_ROWS; ++r) {
-                    int found = -2;
-#pragma unroll
-                    for (int g2 = 0; g2 < GMAX; ++g2) found = (g2 < ng_c && key[r] == gk[g2]) ? g2 : found;
-                    lg[r] = live[r] ? found : -1;
-                    pending |= (lg[r] == -2);
-                }
-                const uint64_t pmask = __ballot(pending);
-                if (pmask == 0) return true;                       // steady state: no LDS access
-                if (*v_over) return false;
-                if ((int)*v_ng == ng_c) {
-                    if (lane == (int)__builtin_ctzll(pmask)) {
-                        uint64_t mine = 0;
-#pragma unroll
-                        for (int r = LEAN_ROWS - 1; r >= 0; --r)
-                            if (lg[r] == -2) mine = key[r];
-                        while (atomicCAS(&lds.lock, 0u, 1u) != 0u) {}
-                        const int n2 = (int)*v_ng;                 // another wave may have appended it meanwhile
-                        bool have = false;
-                        for (int g2 = 0; g2 < n2; ++g2) have |= (lds.keys[g2] == mine);
-                        if (!have) {
-                            if (n2 < GMAX) {
-                                lds.keys[n2] = mine;
-                                __threadfence_block();             // key before count
-                                *v_ng = (uint32_t)(n2 + 1);
-                            } else {
-                                *v_over = 1;
-                            }
-                        }
-                        __threadfence_block();
-                        atomicExch(&lds.lock, 0u);
-                    }
-                }
-                ng_c = __builtin_amdgcn_readfirstlane((int)*v_ng);
-#pragma unroll
-                for (int g2 = 0; g2 < GMAX; ++g2) gk[g2] = lean_uniform_u64(lds.keys[g2]);
-            }
-        }
+        return table.lookup(lds, lane, key, live, lg);
     };
     // one row's chain values into its group's accumulators
     auto accumulate = [&](int lgr, const double (&tv)[NSTEP]) {
@@ -461,115 +592,17 @@ scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint
         if (more1) load_steps();
     }
 
-    // ---- ragged tail (< 1024 rows): the workgroup next in line takes it, one row per thread and pass
-    if (!over && (int64_t)blockIdx.x == n_tiles % grid && n_tiles * LEAN_TILE < n_rows) {
-        const int64_t tail0 = n_tiles * LEAN_TILE;
-        for (int k = 0; k < LEAN_TILE / BLOCK; ++k) {
-            const int64_t i = tail0 + (int64_t)k * BLOCK + tid;
-            const bool in = i < n_rows;
-            bool ok = in;
-            uint32_t w[NKEY] = {0, 0};
-            double tv[NSTEP];
-#pragma unroll
-            for (int s = 0; s < NSTEP; ++s) tv[s] = 0.0;
-            if (in) {
-#pragma unroll
-                for (int p = 0; p < NRANGE; ++p)
-                    if (p < n_ranges) {
-                        const BHIP_GLOBAL char* base = (const BHIP_GLOBAL char*)S.cols[S.ranges[p].col].data;
-                        const double x = r32[p] ? (double)*(const BHIP_GLOBAL int32_t*)(base + i * 4) : *(const BHIP_GLOBAL double*)(base + i * 8);
-                        ok = ok && x >= rlo[p] && x <= rhi[p];
-                        const BHIP_GLOBAL uint64_t* vb = (const BHIP_GLOBAL uint64_t*)S.cols[S.ranges[p].col].validity;
-                        if (vb) ok = ok && ((vb[i >> 6] >> (i & 63)) & 1ull);
-                    }
-#pragma unroll
-                for (int q = 0; q < NKEY; ++q)
-                    if (q < n_keys) {
-                        const SopColumn c = S.cols[S.keys[q].col];
-                        if (kutf[q]) {
-                            const uint32_t o0 = (uint32_t)c.offsets[i];
-                            uint32_t len = (uint32_t)c.offsets[i + 1] - o0;
-                            bad_len |= len;
-                            len = len > LEAN_MAX_STR ? LEAN_MAX_STR : len;
-                            w[q] = lean_str_word((uint32_t)((const BHIP_GLOBAL PackedU64*)((const BHIP_GLOBAL char*)c.data + o0))->v, len);
-                        } else {
-                            w[q] = *(const BHIP_GLOBAL uint32_t*)((const BHIP_GLOBAL char*)c.data + i * 4);
-                        }
-                    }
-#pragma unroll
-                for (int s = 0; s < NSTEP; ++s)
-                    if (s < n_steps) {
-                        const double x = *(const BHIP_GLOBAL double*)((const BHIP_GLOBAL char*)S.cols[S.steps[s].col].data + i * 8);
-                        const double f = xplain[s] ? x : u2d(d2u(x) ^ ((uint64_t)xflip[s] << 32)) + xadd[s];
-                        tv[s] = (s > 0 && !xstart[s]) ? tv[s - (s > 0)] * f : f;
-                    }
-            }
-            // the lookup is a wave-level protocol: every lane takes part, rows beyond the end as "filtered out"
-            uint64_t key[LEAN_ROWS];
-            bool live[LEAN_ROWS];
-            int lg[LEAN_ROWS];
-#pragma unroll
-            for (int r = 0; r < LEAN_ROWS; ++r) { key[r] = 0; live[r] = false; }
-            key[0] = ((uint64_t)w[1] << 32) | w[0];
-            live[0] = ok;
-            if (!lookup(key, live, lg)) { over = true; break; }
-            accumulate(lg[0], tv);
-        }
-    }
+    // ---- ragged tail (< 1024 rows): the workgroup next in line takes it
+    if (!over && (int64_t)blockIdx.x == n_tiles % grid && n_tiles * LEAN_TILE < n_rows)
+        over = !lean_tail<GMAX, NSTEP, NRANGE>(S, n_tiles * LEAN_TILE, n_rows, bad_len, lookup, accumulate);
 
-    // ---- fixed-order workgroup reduction: lanes (shuffle tree) -> waves 0..3
-    __syncthreads();
-    uint64_t tot_rows = 0;
-    double tot_acc = 0.0;
-#pragma unroll
-    for (int g = 0; g < GMAX; ++g) {
-        const uint32_t mine = GMAX == 1 ? rows1 : lds.cnt[(GMAX > 1 ? g : 0) * BLOCK + tid];
-        const uint64_t v = wave_reduce((uint64_t)mine, ACC_COUNT_ROWS);
-        if (lane == 0) lds.rowred[wave][g] = v;
-    }
-#pragma unroll
-    for (int g = 0; g < GMAX; ++g)
-#pragma unroll
-        for (int s = 0; s < NSTEP; ++s) {
-            const double mine = GMAX == 1 ? acc[s] : lds.acc[(GMAX > 1 ? (g * NSTEP + s) : 0) * BLOCK + tid];
-            const uint64_t v = wave_reduce(d2u(mine), ACC_SUM_F64);
-            if (lane == 0) lds.red[wave][g * NSTEP + s] = v;
-        }
-    __syncthreads();
-    if (tid < GMAX) {
-        tot_rows = lds.rowred[0][tid] + lds.rowred[1][tid] + lds.rowred[2][tid] + lds.rowred[3][tid];
-        lds.rowtot[tid] = tot_rows;
-    }
-    if (tid < GMAX * NSTEP)
-        tot_acc = ((u2d(lds.red[0][tid]) + u2d(lds.red[1][tid])) + u2d(lds.red[2][tid])) + u2d(lds.red[3][tid]);
-    __syncthreads();
-
-    GroupRec* out = partials + (size_t)blockIdx.x * GMAX;
-    if (tid < GMAX) {
-        // the packed-key layout of sop_kernel.h: part 0 -> word 0, part 1 -> word 1
-        out[tid].k0 = lds.keys[tid] & 0xFFFFFFFFull;
-        out[tid].k1 = lds.keys[tid] >> 32;
-        out[tid].rows = tot_rows;
-    }
-    if (tid < GMAX * NSTEP) {
-        const int g = tid / NSTEP, s = tid % NSTEP;
-        if (s < S.n_steps && S.steps[s].acc != 0xFF) {
-            out[g].acc[S.steps[s].acc] = d2u(tot_acc);
-            out[g].nvalid[S.steps[s].acc] = lds.rowtot[g];
-        }
-    }
-    if (tid == 0) {
-        // without GROUP BY the one group (key 0) exists once a row has passed the filter
-        partial_ng[blockIdx.x] = GMAX == 1 ? (tot_rows > 0 ? 1u : 0u) : lds.ng;
-        if (lds.overflow) atomicOr(&status->flags, SCAN_OVERFLOW_GROUPS);
-    }
-    if (bad_len > LEAN_MAX_STR) atomicOr(&status->flags, SCAN_ERR_KEY_TOO_LONG);
+    lean_finish<GMAX, NSTEP>(lds, S, acc, rows1, bad_len, partials, partial_ng, status);
 }
 
-template <int GMAX, int NSTEP, int NRANGE>
-static hipError_t launch_lean_t(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, GroupRec* partials,
-                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out) {
-    auto k = scan_agg_lean_kernel<GMAX, NSTEP, NRANGE>;
+// grid: the CUs x the blocks per CU the kernel's resources admit (BHIP_AGG_BLOCKS_PER_CU overrides), at most one per tile
+template <typename Kernel>
+static hipError_t launch_lean_kernel(Kernel k, const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, GroupRec* partials,
+                                     uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out) {
     const int64_t n_tiles = (S.n_rows + LEAN_TILE - 1) / LEAN_TILE;
     int per_cu = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k), BLOCK, 0);
@@ -586,6 +619,12 @@ static hipError_t launch_lean_t(const LaunchCfg& cfg, const SopProgram& S, SopPr
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(BLOCK), 0, cfg.stream, (const SopProgram*)dprog, partials, partial_ng, status);
     *grid_out = (int)grid;
     return hipGetLastError();
+}
+
+template <int GMAX, int NSTEP, int NRANGE>
+static hipError_t launch_lean_t(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, GroupRec* partials,
+                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out) {
+    return launch_lean_kernel(scan_agg_lean_kernel<GMAX, NSTEP, NRANGE>, cfg, S, dprog, partials, partial_ng, max_grid, status, grid_out);
 }
 
 template <int GMAX>

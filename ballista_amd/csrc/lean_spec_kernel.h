@@ -1,0 +1,347 @@
+// lean_spec_kernel.h — lean_kernel.h with the plan SHAPE fixed at compile time, for the hot plans
+// (instantiated in kernels_lean_spec.hip; picked by launch_scan_agg_lean_spec, else the generic kernel runs).
+//
+// Same rows per thread, same per-row arithmetic, same per-thread summation order per accumulator, the same grid and the
+// same fixed-order workgroup reduction as scan_agg_lean_kernel.  What differs is the main loop.
+// The shape facts that decide WHICH loads exist are template parameters — the number of ranges and the width of each
+// (NULL-free range columns only), the kind of each key part, the exact number of chain steps — so the loop body is
+// straight-line code with no branch around a load.  The generic kernel's loop drains the memory queue at every turn:
+// its loads sit behind runtime `if`s, so the values that cross the back edge are phis of "loaded" and "kept", which the
+// compiler resolves with register copies, and a copy of a register still being loaded waits for it (s_waitcnt vmcnt(0)).
+// Here:
+//   * the tile loop is unrolled by two with explicit even / odd register sets for the Float64 step values and the Utf8
+//     offsets, so no register that is still being loaded is copied across the back edge;
+//   * loads are issued unconditionally; the offsets prefetch two tiles ahead is re-pointed at the workgroup's last own
+//     tile instead of running past the end (no extra HBM bytes: that tile was just read);
+//   * per tile t: once the ranges and key bytes of t are consumed, ranges(t+1), Int32 keys(t+1), key bytes(t+1) from
+//     offsets(t+1) and offsets(t+2); then, step column by step column, the sums of t and the loads of steps(t+1);
+//   * the ragged tail and the key-append path of the lookup stay out of the fast path, as in the generic kernel.
+#pragma once
+#include "lean_kernel.h"
+
+namespace bhip {
+
+enum LeanKeyKind : int { LK_NONE = 0, LK_I32 = 1, LK_UTF8 = 2 };
+
+// NR ranges (bit p of R32: range p reads a 32-bit integer column, else Float64), key parts K0 / K1, exactly NS steps
+template <int GMAX, int NR, int R32, int K0, int K1, int NS>
+__global__ void __launch_bounds__(BLOCK, (GMAX == 1 && NS <= 5) ? 4 : 3)
+scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint32_t* partial_ng, ScanStatus* status) {
+    static_assert(NR >= 1 && NR <= SOP_NRANGE && NS >= 1 && NS <= SOP_NSTEP && (K0 != LK_NONE || K1 == LK_NONE), "lean shape");
+    const SopProgram& S = *Sp;
+    constexpr int U = LEAN_U;
+    constexpr int NKEY = 2;
+    constexpr int KK[NKEY] = {K0, K1};
+    __shared__ LeanLds<GMAX, NS> lds;
+    const int tid = threadIdx.x, lane = tid & 63;
+
+    // ---- plan: wave-uniform bases and constants (addresses are rebuilt per tile from the tile index)
+    const int64_t n_rows = S.n_rows;
+    const int64_t n_tiles = n_rows / LEAN_TILE;
+    const int64_t grid = gridDim.x;
+    const int64_t my_tiles = (int64_t)blockIdx.x < n_tiles ? (n_tiles - 1 - (int64_t)blockIdx.x) / grid + 1 : 0;
+
+    const BHIP_GLOBAL char* rbase[NR];
+    double rlo[NR], rhi[NR];
+#pragma unroll
+    for (int p = 0; p < NR; ++p) {
+        rbase[p] = (const BHIP_GLOBAL char*)S.cols[S.ranges[p].col].data;
+        rlo[p] = S.ranges[p].lo; rhi[p] = S.ranges[p].hi;
+    }
+    const BHIP_GLOBAL char* kbase[NKEY];       // Int32 key: values.  Utf8 key: the offsets
+    const BHIP_GLOBAL char* kdat[NKEY];        // Utf8 key: bytes (absolute offsets)
+#pragma unroll
+    for (int q = 0; q < NKEY; ++q) {
+        kbase[q] = nullptr; kdat[q] = nullptr;
+        if (KK[q] != LK_NONE) {
+            const SopColumn c = S.cols[S.keys[q].col];
+            kbase[q] = KK[q] == LK_UTF8 ? (const BHIP_GLOBAL char*)c.offsets : (const BHIP_GLOBAL char*)c.data;
+            kdat[q] = (const BHIP_GLOBAL char*)c.data;
+        }
+    }
+    const BHIP_GLOBAL char* xbase[NS];
+    bool xstart[NS], xplain[NS];
+    uint32_t xflip[NS];
+    double xadd[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const SopStep st = S.steps[s];
+        xstart[s] = st.start != 0;
+        xplain[s] = st.sgn == 1.0 && st.add == 0.0 && __builtin_signbit(st.add);
+        xflip[s] = st.sgn < 0.0 ? 0x80000000u : 0u;
+        xadd[s] = st.add;
+        xbase[s] = (const BHIP_GLOBAL char*)S.cols[st.col].data;
+    }
+    const int64_t tile_of0 = blockIdx.x;
+    auto tile_row = [&](int64_t k) -> int64_t {   // first row of the workgroup's k-th tile, clamped to its last one
+        const int64_t kk = k < my_tiles ? k : my_tiles - 1;
+        return (tile_of0 + kk * grid) * LEAN_TILE;
+    };
+
+    // ---- accumulators
+    double acc[NS];                            // GMAX == 1 only
+    uint32_t rows1 = 0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) acc[s] = 0.0;
+    if constexpr (GMAX > 1) {
+#pragma unroll
+        for (int j = 0; j < GMAX * NS; ++j) lds.acc[j * BLOCK + tid] = 0.0;
+#pragma unroll
+        for (int j = 0; j < GMAX; ++j) lds.cnt[j * BLOCK + tid] = 0;
+    }
+    if (tid == 0) { lds.ng = 0; lds.overflow = 0; lds.lock = 0; }
+    if (tid < AGG_GMAX) lds.keys[tid] = 0;
+    __syncthreads();
+    uint32_t bad_len = 0;
+    LeanKeyTable<GMAX, NS> table;
+    auto lookup = [&](const uint64_t (&key)[LEAN_ROWS], const bool (&live)[LEAN_ROWS], int (&lg)[LEAN_ROWS]) -> bool {
+        return table.lookup(lds, lane, key, live, lg);
+    };
+    // one row's value of step s / the row itself into its group's accumulators, without a branch: a filtered-out row
+    // adds +0.0 (and a count of 0) to group 0's slot, which leaves it bit-for-bit as it was (the slots start at +0.0,
+    // and x + (+0.0) == x for every x other than -0.0, which a sum that starts at +0.0 never holds)
+    auto add_step = [&](int lgr, int s, double v) {
+        const double a = lgr >= 0 ? v : 0.0;
+        if constexpr (GMAX == 1) {
+            acc[s] += a;
+        } else {
+            const int g = lgr >= 0 ? lgr : 0;
+            __hip_atomic_fetch_add(&lds.acc[(g * NS + s) * BLOCK + tid], a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
+    auto add_row = [&](int lgr) {
+        if constexpr (GMAX == 1) {
+            rows1 += lgr >= 0 ? 1u : 0u;
+        } else {
+            const int g = lgr >= 0 ? lgr : 0;
+            __hip_atomic_fetch_add(&lds.cnt[g * BLOCK + tid], lgr >= 0 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
+
+    // ---- registers.  Row j of sub-tile u: tile row u*512 + 2*tid + j.
+    LeanU4 rv[NR][U];            // 32-bit column: .x .y = rows 0 1; Float64: (.x .y) (.z .w)
+    uint32_t kv[NKEY][U][2];     // Int32 key: the two values.  Utf8 key: lengths of the two strings
+    uint64_t kb[NKEY][U];        // Utf8 key: 8 bytes at the first string's offset
+    LeanU3 ko[2][NKEY][U];       // Utf8 key offsets, by parity of the tile they belong to
+    LeanU4 xv[NS][U];            // Float64 step values
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int p = 0; p < NR; ++p) rv[p][u] = LeanU4{0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < NKEY; ++q) {
+            kv[q][u][0] = kv[q][u][1] = 0; kb[q][u] = 0;
+            ko[0][q][u] = ko[1][q][u] = LeanU3{0, 0, 0};
+        }
+    }
+    const uint32_t t8 = (uint32_t)tid * 8u, t16 = (uint32_t)tid * 16u;
+
+    auto load_step = [&](int s, int64_t row) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[s][u] = lean_ld4(xbase[s] + (row + u * LEAN_SUB) * 8 + t16);
+    };
+    auto load_ranges = [&](int64_t row) {
+#pragma unroll
+        for (int p = 0; p < NR; ++p) {
+            if ((R32 >> p) & 1) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const LeanU2 v = lean_ld2(rbase[p] + (row + u * LEAN_SUB) * 4 + t8);
+                    rv[p][u].x = v.x; rv[p][u].y = v.y;
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) rv[p][u] = lean_ld4(rbase[p] + (row + u * LEAN_SUB) * 8 + t16);
+            }
+        }
+    };
+    auto load_int_keys = [&](int64_t row) {
+#pragma unroll
+        for (int q = 0; q < NKEY; ++q)
+            if (KK[q] == LK_I32) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const LeanU2 v = lean_ld2(kbase[q] + (row + u * LEAN_SUB) * 4 + t8);
+                    kv[q][u][0] = v.x; kv[q][u][1] = v.y;
+                }
+            }
+    };
+    auto load_offsets = [&](LeanU3 (&o)[NKEY][U], int64_t row) {
+#pragma unroll
+        for (int q = 0; q < NKEY; ++q)
+            if (KK[q] == LK_UTF8) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const BHIP_GLOBAL char* a = kbase[q] + (row + u * LEAN_SUB) * 4 + t8;
+                    const LeanU2 v = lean_ld2(a);
+                    o[q][u].a = v.x; o[q][u].b = v.y;
+                    o[q][u].c = *(const BHIP_GLOBAL uint32_t*)(a + 8);
+                }
+            }
+    };
+    // Utf8 key: lengths from the offsets + the bytes at the first string
+    auto load_key_bytes = [&](const LeanU3 (&o)[NKEY][U]) {
+#pragma unroll
+        for (int q = 0; q < NKEY; ++q)
+            if (KK[q] == LK_UTF8) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const uint32_t l0 = o[q][u].b - o[q][u].a, l1 = o[q][u].c - o[q][u].b;
+                    bad_len |= (l0 | l1);
+                    kv[q][u][0] = l0; kv[q][u][1] = l1;
+                    kb[q][u] = ((const BHIP_GLOBAL PackedU64*)(kdat[q] + o[q][u].a))->v;   // buffers carry 16 B of slack
+                }
+            }
+    };
+
+    auto eval_live = [&](bool (&live)[LEAN_ROWS]) {
+#pragma unroll
+        for (int r = 0; r < LEAN_ROWS; ++r) live[r] = true;
+#pragma unroll
+        for (int p = 0; p < NR; ++p) {
+            if ((R32 >> p) & 1) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const double a = (double)(int32_t)rv[p][u].x, b = (double)(int32_t)rv[p][u].y;
+                    live[2 * u] = live[2 * u] && a >= rlo[p] && a <= rhi[p];
+                    live[2 * u + 1] = live[2 * u + 1] && b >= rlo[p] && b <= rhi[p];
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const double a = u2d(((uint64_t)rv[p][u].y << 32) | rv[p][u].x), b = u2d(((uint64_t)rv[p][u].w << 32) | rv[p][u].z);
+                    live[2 * u] = live[2 * u] && a >= rlo[p] && a <= rhi[p];
+                    live[2 * u + 1] = live[2 * u + 1] && b >= rlo[p] && b <= rhi[p];
+                }
+            }
+        }
+    };
+    auto eval_keys = [&](uint64_t (&key)[LEAN_ROWS]) {
+        uint32_t w[NKEY][LEAN_ROWS];
+#pragma unroll
+        for (int q = 0; q < NKEY; ++q) {
+#pragma unroll
+            for (int r = 0; r < LEAN_ROWS; ++r) w[q][r] = 0;
+            if (KK[q] == LK_UTF8) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const uint32_t l0 = kv[q][u][0] > LEAN_MAX_STR ? LEAN_MAX_STR : kv[q][u][0];
+                    const uint32_t l1 = kv[q][u][1] > LEAN_MAX_STR ? LEAN_MAX_STR : kv[q][u][1];
+                    w[q][2 * u] = lean_str_word((uint32_t)kb[q][u], l0);
+                    w[q][2 * u + 1] = lean_str_word((uint32_t)(kb[q][u] >> (l0 << 3)), l1);
+                }
+            } else if (KK[q] == LK_I32) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) { w[q][2 * u] = kv[q][u][0]; w[q][2 * u + 1] = kv[q][u][1]; }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < LEAN_ROWS; ++r) key[r] = ((uint64_t)w[1][r] << 32) | w[0][r];
+    };
+    // ---- one tile: k-th of the workgroup, parity P of its offsets set.  NEXT: issue the loads of tile k+1 (and the
+    // offsets of k+2) — ranges and keys once this tile's are consumed, each step column once this tile's is summed
+    auto tile = [&](auto P_, auto NEXT_, int64_t k) -> bool {
+        constexpr int P = decltype(P_)::value;
+        constexpr bool NEXT = decltype(NEXT_)::value;
+        const int64_t row1 = tile_row(k + 1);
+        bool live[LEAN_ROWS];
+        uint64_t key[LEAN_ROWS];
+        eval_live(live);
+        eval_keys(key);
+        if constexpr (NEXT) {
+            load_ranges(row1);
+            load_int_keys(row1);
+            load_key_bytes(ko[P ^ 1]);                                   // offsets(k+1) -> lengths + bytes(k+1)
+            load_offsets(ko[P], tile_row(k + 2));                        // clamped to the last own tile
+        }
+        int lg[LEAN_ROWS];
+        if (!lookup(key, live, lg)) return false;
+        // chain values f = sgn*x + add ; t = (start ? 1 : t_prev) * f, summed step by step: each accumulator still
+        // receives this thread's rows in row order
+        double tp[LEAN_ROWS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            double tv[LEAN_ROWS];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const LeanU4 x = xv[s][u];
+                double a = u2d(((uint64_t)x.y << 32) | x.x), b = u2d(((uint64_t)x.w << 32) | x.z);
+                if (!xplain[s]) {
+                    a = u2d(((uint64_t)(x.y ^ xflip[s]) << 32) | x.x) + xadd[s];
+                    b = u2d(((uint64_t)(x.w ^ xflip[s]) << 32) | x.z) + xadd[s];
+                }
+                tv[2 * u] = a; tv[2 * u + 1] = b;
+            }
+            if (s > 0 && !xstart[s]) {
+#pragma unroll
+                for (int r = 0; r < LEAN_ROWS; ++r) tv[r] = tp[r] * tv[r];
+            }
+#pragma unroll
+            for (int r = 0; r < LEAN_ROWS; ++r) { add_step(lg[r], s, tv[r]); tp[r] = tv[r]; }
+            if constexpr (NEXT) load_step(s, row1);
+        }
+#pragma unroll
+        for (int r = 0; r < LEAN_ROWS; ++r) add_row(lg[r]);
+        return true;
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using BT = std::integral_constant<bool, true>;
+    using BF = std::integral_constant<bool, false>;
+
+    bool over = false;
+    if (my_tiles > 0) {
+        const int64_t row0 = tile_row(0);
+        load_offsets(ko[0], row0);
+        load_key_bytes(ko[0]);                                           // the one exposed dependent load
+        load_ranges(row0);
+        load_int_keys(row0);
+        load_offsets(ko[1], tile_row(1));
+#pragma unroll
+        for (int s = 0; s < NS; ++s) load_step(s, row0);
+        // Drain the prologue once.  The loop head is entered from here and from its back edge, and the compiler's wait at
+        // a join assumes the worse of the two; with nothing in flight here the prologue's load order (key bytes behind the
+        // step loads) cannot lower the head's counts.  (The even tile's head still waits vmcnt(10..8): DESIGN.md §3.1.)
+        __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
+        int64_t k = 0;
+        for (; k + 2 < my_tiles; k += 2) {
+            if (!tile(I0{}, BT{}, k) || !tile(I1{}, BT{}, k + 1)) { over = true; break; }
+        }
+        if (!over) {
+            if (my_tiles - k == 2) over = !tile(I0{}, BT{}, k) || !tile(I1{}, BF{}, k + 1);
+            else over = !tile(I0{}, BF{}, k);
+        }
+    }
+
+    // ---- ragged tail (< 1024 rows): the workgroup next in line takes it
+    if (!over && (int64_t)blockIdx.x == n_tiles % grid && n_tiles * LEAN_TILE < n_rows) {
+        auto accumulate = [&](int lgr, const double (&tv)[NS]) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) add_step(lgr, s, tv[s]);
+            add_row(lgr);
+        };
+        over = !lean_tail<GMAX, NS, NR>(S, n_tiles * LEAN_TILE, n_rows, bad_len, lookup, accumulate);
+    }
+    lean_finish<GMAX, NS>(lds, S, acc, rows1, bad_len, partials, partial_ng, status);
+}
+
+// does plan S have exactly this shape (range widths, no NULLs in a range column, key kinds, step count)?
+template <int NR, int R32, int K0, int K1, int NS>
+static bool lean_shape_matches(const SopProgram& S) {
+    if (S.n_ranges != NR || S.n_steps != NS) return false;
+    for (int p = 0; p < NR; ++p) {
+        if ((S.ranges[p].is32 != 0) != (((R32 >> p) & 1) != 0)) return false;
+        if (S.cols[S.ranges[p].col].validity) return false;
+    }
+    const int kk[2] = {K0, K1};
+    int n_keys = 0;
+    for (int q = 0; q < 2; ++q) {
+        if (kk[q] == LK_NONE) continue;
+        ++n_keys;
+        if (S.n_keys <= q) return false;
+        if (S.keys[q].kind != (kk[q] == LK_UTF8 ? SOP_KEY_UTF8 : SOP_KEY_I32)) return false;
+    }
+    return S.n_keys == n_keys;
+}
+
+}  // namespace bhip

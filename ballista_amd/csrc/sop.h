@@ -66,9 +66,10 @@ struct SopProgram {
 hipError_t launch_scan_agg_sop(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out);
 
-// wide-load variant (lean_kernel.h): gmax 1 or 4, plans accepted by host/sop.cpp::lean_eligible
+// wide-load variant (lean_kernel.h, lean_spec_kernel.h): gmax 1 or 4, plans accepted by host/sop.cpp::lean_eligible;
+// *variant (optional) names the kernel that ran: "lean_generic" or the specialised shape (kernels_lean_spec.hip)
 hipError_t launch_scan_agg_lean(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
-                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out);
+                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant = nullptr);
 
 // FilterExec's predicate pass for AND-of-ranges predicates (kernels_range.hip): selection bitmap + kept rows per
 // 1024-row tile, the interface of launch_scan_pred_bitmap

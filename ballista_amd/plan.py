@@ -75,8 +75,19 @@ class Context:
         L.check(L.lib().bhip_ctx_kernel_time(self._h, 1 if reset else 0, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
-    def kernel_name(self):
-        return L.lib().bhip_ctx_kernel_name(self._h).decode()
+    def kernel_name(self, variant=False):
+        """name of the dominant scan kernel of the last timed launches; variant=True appends, after a "/", which
+        instantiation of it ran where the library says (the lean path: "lean_generic" or "lean_spec_<shape>")"""
+        name = L.lib().bhip_ctx_kernel_name(self._h).decode()
+        if variant:
+            v = L.lib().bhip_ctx_kernel_variant(self._h).decode()
+            if v:
+                name += "/" + v
+        return name
+
+    def device_cus(self):
+        """compute units of the device (the kernels size their grids by it)"""
+        return int(L.lib().bhip_ctx_device_cus(self._h))
 
     def kernel_stats(self, reset=False):
         """{kernel name: (total ms, launches, algorithmic bytes)} of every kernel timed since the last reset (BHIP_KERNEL_TIMING=1)"""

@@ -480,6 +480,11 @@ bhip_status bhip_ctx_kernel_time(bhip_ctx* ctx, int32_t reset, double* ms, uint6
 bhip_status bhip_ctx_kernel_stats(bhip_ctx* ctx, int32_t reset, char* buf, size_t cap);
 /* name of the kernel those launches ran ("" before the first timed launch); valid until the next call */
 const char* bhip_ctx_kernel_name(bhip_ctx* ctx);
+/* which instantiation of that kernel ran, where the call site says ("lean_generic", "lean_spec_q1", ...; "" otherwise);
+ * valid until the next call */
+const char* bhip_ctx_kernel_variant(bhip_ctx* ctx);
+/* compute units of the context's device (what the kernels size their grids by) */
+int32_t bhip_ctx_device_cus(bhip_ctx* ctx);
 
 #ifdef __cplusplus
 }

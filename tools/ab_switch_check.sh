@@ -40,3 +40,5 @@ run BHIP_NO_TINY_BUILD=1 "$J"
 run BHIP_NO_STREAMING_SHUFFLE=1 "tests/test_exchange_gpu.py -k not(streaming_shuffle)"
 run BHIP_PARQUET_PAGEABLE=1 "tests/test_parquet_gpu.py"
 run BHIP_PARQUET_PER_PAGE=1 "tests/test_parquet_gpu.py"
+# round 4
+run BHIP_LEAN_GENERIC=1 "$A tests/test_full_size_gpu.py"
