@@ -25,6 +25,21 @@ static int sum_type(int t) {
     return DT_INT64;
 }
 
+// MIN / MAX accumulator of a value type: floats as doubles, unsigned types compare unsigned (a UInt64 at or above 2^63 is no
+// negative number), every other type as a signed 64-bit integer
+static int minmax_kind(int t, bool is_min) {
+    if (dt_is_float(t)) return is_min ? ACC_MIN_F64 : ACC_MAX_F64;
+    if (dt_is_unsigned(t)) return is_min ? ACC_MIN_U64 : ACC_MAX_U64;
+    return is_min ? ACC_MIN_I64 : ACC_MAX_I64;
+}
+
+// the register path's launches by group width, timed at BHIP_KERNEL_TIMING=2 only (the tests read which width ran; the dominant
+// launches are timed at level 1 as scan_agg_lowcard_kernel)
+static const char* lowcard_launch_name(int gmax, bool batches) {
+    if (batches) return gmax == 1 ? "scan_agg_lowcard_g1_batches" : gmax == 4 ? "scan_agg_lowcard_g4_batches" : "scan_agg_lowcard_g8_batches";
+    return gmax == 1 ? "scan_agg_lowcard_g1" : gmax == 4 ? "scan_agg_lowcard_g4" : "scan_agg_lowcard_g8";
+}
+
 static const char* agg_name(int fn) {
     switch (fn) {
         case BHIP_AGG_SUM: return "SUM";
@@ -527,7 +542,7 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
                     if (t == DT_UTF8) fail(BHIP_ENOTIMPL, "MIN/MAX over Utf8 on the packed-key path (run_strings handles it)");
                     if (t == DT_BOOLEAN) fail(BHIP_ENOTIMPL, "MIN/MAX over Boolean");
                     const bool is_min = a.fn == BHIP_AGG_MIN;
-                    const int kind = dt_is_float(t) ? (is_min ? ACC_MIN_F64 : ACC_MAX_F64) : (is_min ? ACC_MIN_I64 : ACC_MAX_I64);
+                    const int kind = minmax_kind(t, is_min);
                     emit(EMIT_VALUE, add_acc(kind, arg), 0, t);
                 } break;
             }
@@ -548,7 +563,7 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
                 case BHIP_AGG_COUNT: emit(EMIT_RAW, add_acc(ACC_SUM_I64, st0), 0, DT_UINT64); break;
                 default: {
                     const bool is_min = a.fn == BHIP_AGG_MIN;
-                    const int kind = dt_is_float(t) ? (is_min ? ACC_MIN_F64 : ACC_MAX_F64) : (is_min ? ACC_MIN_I64 : ACC_MAX_I64);
+                    const int kind = minmax_kind(t, is_min);
                     emit(EMIT_VALUE, add_acc(kind, st0), 0, t);
                 } break;
             }
@@ -842,7 +857,8 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
             Ps.assign(cur.size(), P0);
             for (size_t i = 0; i < cur.size(); ++i) ProgramBuilder::bind(Ps[i], pb.columns(), *cur[i], nullable);
             int grid = 0;
-            HIP_CHECK(launch_scan_agg_lowcard(cfg, Ps[0], tmp.get<ScanParams>(cur.size()), gmax, partials, partial_ng, max_grid, status, &grid, (int)cur.size()));
+            TIMED_LAUNCH(ex, lowcard_launch_name(gmax, true),
+                         launch_scan_agg_lowcard(cfg, Ps[0], tmp.get<ScanParams>(cur.size()), gmax, partials, partial_ng, max_grid, status, &grid, (int)cur.size()));
             n_part = grid;
         }
         for (auto& b : cur) {
@@ -867,8 +883,9 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
                 HIP_CHECK(launch_scan_agg_sop(cfg, sop.prog, tmp.get<SopProgram>(1), gmax, partials + (size_t)n_part * gmax,
                                               partial_ng + n_part, max_grid, status, &grid));
             } else
-                HIP_CHECK(launch_scan_agg_lowcard(cfg, P, tmp.get<ScanParams>(1), gmax, partials + (size_t)n_part * gmax,
-                                                  partial_ng + n_part, max_grid, status, &grid));
+                TIMED_LAUNCH(ex, lowcard_launch_name(gmax, false),
+                             launch_scan_agg_lowcard(cfg, P, tmp.get<ScanParams>(1), gmax, partials + (size_t)n_part * gmax,
+                                                     partial_ng + n_part, max_grid, status, &grid));
             if (timed) timer.end();
             n_part += grid;
         }
@@ -917,10 +934,12 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
         memset(&id, 0, sizeof(id));
         for (int i = 0; i < n_acc; ++i) {
             switch (P0.acc[i].kind) {
-                case ACC_MIN_F64: { double v = __builtin_huge_val(); memcpy(&id.acc[i], &v, 8); } break;
-                case ACC_MAX_F64: { double v = -__builtin_huge_val(); memcpy(&id.acc[i], &v, 8); } break;
+                case ACC_MIN_F64:
+                case ACC_MAX_F64: { double v = __builtin_nan(""); memcpy(&id.acc[i], &v, 8); } break;
                 case ACC_MIN_I64: id.acc[i] = (uint64_t)INT64_MAX; break;
                 case ACC_MAX_I64: id.acc[i] = (uint64_t)INT64_MIN; break;
+                case ACC_MIN_U64: id.acc[i] = UINT64_MAX; break;
+                case ACC_MAX_U64: id.acc[i] = 0; break;
                 default: break;
             }
         }

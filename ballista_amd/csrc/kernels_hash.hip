@@ -23,6 +23,8 @@ __device__ inline void atomic_acc(uint64_t* p, uint64_t v, int kind) {
         case ACC_MAX_F64: atomicMax(reinterpret_cast<double*>(p), u2d(v)); break;
         case ACC_MIN_I64: atomicMin(reinterpret_cast<long long*>(p), (long long)v); break;
         case ACC_MAX_I64: atomicMax(reinterpret_cast<long long*>(p), (long long)v); break;
+        case ACC_MIN_U64: atomicMin(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v); break;
+        case ACC_MAX_U64: atomicMax(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v); break;
         default: atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v); break;
     }
 }

@@ -13,12 +13,16 @@ __device__ inline uint64_t shfl_down_u64(uint64_t v, int delta) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// Float MIN / MAX skip NaN unless a group holds nothing else: the identity is NaN, and a combine (or the
+// minnum / maxnum of the hash path's atomics) replaces a NaN accumulator by any number
 __device__ inline uint64_t acc_identity(int kind) {
     switch (kind) {
-        case ACC_MIN_F64: return d2u(__builtin_huge_val());
-        case ACC_MAX_F64: return d2u(-__builtin_huge_val());
+        case ACC_MIN_F64:
+        case ACC_MAX_F64: return d2u(__builtin_nan(""));
         case ACC_MIN_I64: return (uint64_t)INT64_MAX;
         case ACC_MAX_I64: return (uint64_t)INT64_MIN;
+        case ACC_MIN_U64: return UINT64_MAX;
+        case ACC_MAX_U64: return 0;
         default: return 0;
     }
 }
@@ -26,10 +30,12 @@ __device__ inline uint64_t acc_identity(int kind) {
 __device__ inline uint64_t acc_combine(uint64_t a, uint64_t b, int kind) {
     switch (kind) {
         case ACC_SUM_F64: return d2u(u2d(a) + u2d(b));
-        case ACC_MIN_F64: return u2d(b) < u2d(a) ? b : a;
-        case ACC_MAX_F64: return u2d(b) > u2d(a) ? b : a;
+        case ACC_MIN_F64: return (u2d(a) != u2d(a) || u2d(b) < u2d(a)) ? b : a;
+        case ACC_MAX_F64: return (u2d(a) != u2d(a) || u2d(b) > u2d(a)) ? b : a;
         case ACC_MIN_I64: return (int64_t)b < (int64_t)a ? b : a;
         case ACC_MAX_I64: return (int64_t)b > (int64_t)a ? b : a;
+        case ACC_MIN_U64: return b < a ? b : a;
+        case ACC_MAX_U64: return b > a ? b : a;
         default: return a + b;   // integer sums and counts
     }
 }

@@ -222,7 +222,7 @@ struct KeyPart {
 enum AccKind : uint8_t {
     ACC_SUM_F64 = 0, ACC_SUM_I64 = 1, ACC_COUNT_VALID = 2, ACC_COUNT_ROWS = 3,
     ACC_MIN_F64 = 4, ACC_MAX_F64 = 5, ACC_MIN_I64 = 6, ACC_MAX_I64 = 7,
-    ACC_COUNT_VALID_B = 8
+    ACC_COUNT_VALID_B = 8, ACC_MIN_U64 = 9, ACC_MAX_U64 = 10
 };
 struct AccSpec {
     uint8_t kind;

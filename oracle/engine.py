@@ -348,18 +348,26 @@ def _key_tuples(cols):
     return list(zip(*lists)) if lists else []
 
 
+def float_bits(v):
+    """the bit pattern of a float value as a double (a Float32 value widens exactly, NaN payload included)"""
+    return int(np.float64(v).view(np.uint64))
+
+
 def _factorize(cols, n):
-    """dense group ids in first-appearance order (NULL is a group value of its own)."""
+    """dense group ids in first-appearance order (NULL is a group value of its own).  Float keys are equal when their bit
+    patterns are: -0.0 and +0.0 are two groups, NaNs of one bit pattern are one group."""
     if not cols:
         return np.zeros(n, np.int32), [()]
     ids = np.empty(n, np.int32)
     table = {}
     keys = []
+    is_float = [c.dtype in FLOAT_TYPES for c in cols]
     for i, t in enumerate(_key_tuples(cols)):
-        g = table.get(t)
+        h = tuple(("f", float_bits(v)) if f and v is not None else v for v, f in zip(t, is_float))
+        g = table.get(h)
         if g is None:
             g = len(keys)
-            table[t] = g
+            table[h] = g
             keys.append(t)
         ids[i] = g
     return ids, keys
@@ -407,16 +415,24 @@ def _sum_type(t):
 
 
 def _minmax(col: OCol, gid, ngroups, is_min):
+    """MIN / MAX: integers compare as their type (unsigned as unsigned), strings by code point (= by
+    unsigned UTF-8 bytes); a float NaN is skipped unless the group's non-NULL values are all NaN, which gives NaN; NULL only
+    for a group without a non-NULL value"""
     out = [None] * ngroups
+    saw_nan = [False] * ngroups
     ok = col.is_valid()
     for v, g, o in zip(col.values, gid, ok):
         if not o:
             continue
         if col.dtype in FLOAT_TYPES and v != v:
+            saw_nan[g] = True
             continue
         cur = out[g]
         if cur is None or (v < cur if is_min else v > cur):
             out[g] = v
+    for g in range(ngroups):
+        if out[g] is None and saw_nan[g]:
+            out[g] = math.nan
     z = "" if col.dtype == "Utf8" else 0
     return OCol(col.dtype, [z if x is None else x for x in out], [x is not None for x in out])
 

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import math
 import os
+import struct
 from collections import OrderedDict
 
 import numpy as np
@@ -52,8 +53,20 @@ def rows_of(batch):
     return list(zip(*cols)) if cols else []
 
 
-def _sort_key(row):
-    return tuple((0, "") if v is None else (1, v) if not isinstance(v, float) else (1, v) for v in row)
+def _float_order(v):
+    """IEEE-754 totalOrder of a double as an integer: numeric order, -0.0 before +0.0, NaNs ordered by sign and payload"""
+    b = struct.unpack("<Q", struct.pack("<d", v))[0]
+    return b ^ 0xFFFFFFFFFFFFFFFF if b >> 63 else b | 0x8000000000000000
+
+
+def _sort_key(row, loose=()):
+    """loose: positions of value columns whose NaN bit pattern (and, for zero_sign_cols, zero sign) the comparison below does
+    not look at: they order as one NaN and as +0.0"""
+    def f(i, v):
+        if i in loose:
+            v = math.nan if v != v else 0.0 if v == 0 and loose[i] else v
+        return _float_order(v)
+    return tuple((0, "") if v is None else (1, f(i, v)) if isinstance(v, float) else (1, v) for i, v in enumerate(row))
 
 
 def concat(batches):
@@ -68,10 +81,11 @@ def assert_same_schema(got, want):
         assert got[k].dtype == want[k].dtype, (k, got[k].dtype, want[k].dtype)
 
 
-def assert_rows_equal(got, want, ordered=False, float_rtol=0.0, key_cols=None):
+def assert_rows_equal(got, want, ordered=False, float_rtol=0.0, key_cols=None, zero_sign_cols=()):
     """compare two oracle-style batches.  Float64 columns compare with float_rtol (0 = bit exact),
-    everything else exactly.  Unordered: rows are matched after sorting on the non-float columns
-    (or key_cols)."""
+    everything else exactly; NaN matches NaN.  Unordered: rows are matched after sorting on the non-float columns
+    (or key_cols).  zero_sign_cols: float columns whose zero results may carry either sign (a MIN / MAX tie of -0.0
+    and +0.0)."""
     if not got or not want:
         # a stream may end without yielding a batch: equivalent to zero rows
         assert len(rows_of(got)) == 0 and len(rows_of(want)) == 0, (len(rows_of(got)), len(rows_of(want)))
@@ -86,7 +100,9 @@ def assert_rows_equal(got, want, ordered=False, float_rtol=0.0, key_cols=None):
             kidx = [i for i in range(len(names)) if i not in fcols] or list(range(len(names)))
         else:
             kidx = [names.index(k) for k in key_cols]
-        keyf = lambda r: _sort_key(tuple(r[i] for i in kidx)) + _sort_key(tuple(r[i] for i in range(len(r)) if i not in kidx))
+        rest = [i for i in range(len(names)) if i not in kidx]
+        loose = {j: names[i] in zero_sign_cols for j, i in enumerate(rest) if i in fcols}
+        keyf = lambda r: _sort_key(tuple(r[i] for i in kidx)) + _sort_key(tuple(r[i] for i in rest), loose)
         g, w = sorted(g, key=keyf), sorted(w, key=keyf)
     for ri, (a, b) in enumerate(zip(g, w)):
         for ci, (x, y) in enumerate(zip(a, b)):
@@ -94,9 +110,13 @@ def assert_rows_equal(got, want, ordered=False, float_rtol=0.0, key_cols=None):
                 assert x is None and y is None, f"row {ri} col {names[ci]}: {x!r} vs {y!r}"
             elif ci in fcols and float_rtol > 0:
                 if math.isnan(y):
-                    assert math.isnan(x)
+                    assert math.isnan(x), f"row {ri} col {names[ci]}: {x!r} vs {y!r}"
+                elif math.isinf(y):
+                    assert x == y, f"row {ri} col {names[ci]}: {x!r} vs {y!r}"
                 else:
                     assert abs(x - y) <= float_rtol * max(abs(y), 1e-300), f"row {ri} col {names[ci]}: {x!r} vs {y!r}"
+            elif ci in fcols and names[ci] in zero_sign_cols and x == 0 and y == 0:
+                pass
             elif ci in fcols:
                 assert (x == y and math.copysign(1, x) == math.copysign(1, y)) or (math.isnan(x) and math.isnan(y)), \
                     f"row {ri} col {names[ci]}: {x!r} vs {y!r} (bit exact expected)"

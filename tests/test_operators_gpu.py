@@ -288,7 +288,7 @@ def test_hash_aggregate_wide_group_keys(ctx, gi):
         for name, mod in (("i64", 5), ("u64", 3), ("d", 4)):
             c = b[name]
             b[name] = OCol(c.dtype, (c.values % mod).astype(c.values.dtype), c.valid)
-        b["f"] = OCol("Float64", np.round(b["f"].values / 100) + 0.0, b["f"].valid)       # + 0.0: no -0.0 among the keys
+        b["f"] = OCol("Float64", np.round(b["f"].values / 100), b["f"].valid)             # (-0.0 and +0.0 are two keys)
     m = helpers.memory_exec(ctx, [[bs[0]], [bs[1]]])
     group = [(col(a), n) for a, n in names]
     aggs = [E.Sum(col("g"), "sg"), E.Avg(col("f"), "af"), E.Count(col("f"), "cf"), E.Count(lit(1, E.UINT8), "n"),

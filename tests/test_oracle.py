@@ -187,3 +187,93 @@ def test_join_sort_repartition_properties():
     for pi, p in enumerate(parts):
         for k in p["k2"].values:
             assert seen.setdefault(int(k), pi) == pi          # equal keys co-locate
+
+
+# ---- MIN / MAX and float keys at the value-domain edges ---------------------------------------------
+
+NEG_NAN = np.array([0xFFF8000000000000], np.uint64).view(np.float64)[0]
+PAYLOAD_NAN = np.array([0x7FFC000000000123], np.uint64).view(np.float64)[0]
+
+
+def test_minmax_over_uint64_compares_unsigned():
+    b = {"k": OCol("Int32", [0, 0, 1, 1, 2]), "v": OCol("UInt64", [3, 2**63 + 5, 2**63, 2**64 - 1, 2**63 - 1])}
+    aggs = [E.Min(col("v"), "mn"), E.Max(col("v"), "mx")]
+    p = og.hash_aggregate(b, "Partial", [(col("k"), "k")], aggs)
+    assert p["mn[min]"].to_pylist() == [3, 2**63, 2**63 - 1] and p["mx[max]"].to_pylist() == [2**63 + 5, 2**64 - 1, 2**63 - 1]
+    f = og.hash_aggregate(og.concat_batches([p, helpers.slice_batch(p, 0, 1)]), "Final", [(col("k"), "k")], aggs)
+    assert f["mn"].dtype == "UInt64" and f["mn"].to_pylist() == [3, 2**63, 2**63 - 1]
+    assert f["mx"].to_pylist() == [2**63 + 5, 2**64 - 1, 2**63 - 1]
+
+
+def test_float_minmax_skips_nan_unless_the_group_holds_nothing_else():
+    nan = math.nan
+    b = {"k": OCol("Int32", [0, 0, 1, 1, 2, 2, 3, 4, 4]),
+         "v": OCol("Float64", [nan, 2.0, nan, NEG_NAN, nan, 7.0, 1.0, -math.inf, nan],
+                   [True, True, True, True, True, False, False, True, True])}
+    for mode_aggs in ([E.Min(col("v"), "m")], [E.Max(col("v"), "m")]):
+        p = og.hash_aggregate(b, "Partial", [(col("k"), "k")], mode_aggs)
+        got = list(p.values())[1].to_pylist()
+        assert got[0] == 2.0                                   # NaN skipped
+        assert math.isnan(got[1]) and math.isnan(got[2])       # all non-NULL values NaN -> NaN, valid
+        assert got[3] is None                                  # no non-NULL value -> NULL
+        assert got[4] == -math.inf
+        # across partitions: an all-NaN partial state merges with a numeric one
+        f = og.hash_aggregate(og.concat_batches([p, p]), "Final", [(col("k"), "k")], mode_aggs)
+        fin = f["m"].to_pylist()
+        assert fin[0] == 2.0 and math.isnan(fin[1]) and fin[3] is None
+    p1 = og.hash_aggregate(helpers.slice_batch(b, 0, 1), "Partial", [(col("k"), "k")], [E.Min(col("v"), "m")])
+    p2 = og.hash_aggregate(helpers.slice_batch(b, 1, 2), "Partial", [(col("k"), "k")], [E.Min(col("v"), "m")])
+    assert math.isnan(p1["m[min]"].to_pylist()[0])
+    f = og.hash_aggregate(og.concat_batches([p1, p2]), "Final", [(col("k"), "k")], [E.Min(col("v"), "m")])
+    assert f["m"].to_pylist() == [2.0]
+
+
+def test_float_group_keys_are_equal_by_bit_pattern():
+    nan = math.nan
+    vals = [nan, nan, -0.0, 0.0, 1.0, NEG_NAN, PAYLOAD_NAN, -0.0, 0.0]
+    for dtype in ("Float64", "Float32"):
+        b = {"k": OCol(dtype, vals, [True] * 8 + [False]), "x": OCol("Int32", list(range(9)))}
+        p = og.hash_aggregate(b, "Partial", [(col("k"), "k")], [E.Count(col("x"), "c")])
+        keys = p["k"].to_pylist()
+        # NaN (x2 -> one group), -0.0 (x2), +0.0, 1.0, negative NaN, payload NaN, NULL
+        assert len(keys) == 7, keys
+        assert p["c[count]"].to_pylist() == [2, 2, 1, 1, 1, 1, 1]
+        assert math.copysign(1, keys[1]) == -1 and math.copysign(1, keys[2]) == 1 and keys[6] is None
+        bits = [og.float_bits(k) for k in keys[:6]]
+        assert bits[4] == 0xFFF8000000000000 and (dtype == "Float32" or bits[5] == 0x7FFC000000000123)
+        # Partial over two partitions, then Final: the same groups as one partition
+        halves = [og.hash_aggregate(helpers.slice_batch(b, lo, hi), "Partial", [(col("k"), "k")], [E.Count(col("x"), "c")])
+                  for lo, hi in ((0, 4), (4, 9))]
+        f = og.hash_aggregate(og.concat_batches(halves), "Final", [(col("k"), "k")], [E.Count(col("x"), "c")])
+        assert sorted(zip(map(og.float_bits, f["k"].to_pylist()[:6]), f["c"].to_pylist()[:6])) == sorted(zip(bits, [2, 2, 1, 1, 1, 1]))
+        # hash repartitioning keeps every group in one partition
+        parts = og.repartition_hash(b, [col("k")], 3)
+        seen = {}
+        for pi, part in enumerate(parts):
+            for k in part["k"].to_pylist():
+                key = None if k is None else og.float_bits(k)
+                assert seen.setdefault(key, pi) == pi
+
+
+def test_assert_rows_equal_handles_infinities_nan_and_signed_zeros():
+    inf, nan = math.inf, math.nan
+    a = {"k": OCol("Float64", [inf, -inf, nan, -0.0, 0.0, NEG_NAN]), "v": OCol("Float64", [inf, -inf, nan, 1.0, 2.0, 3.0])}
+    shuffled = {k: c.take(np.array([5, 3, 1, 4, 0, 2])) for k, c in a.items()}
+    helpers.assert_rows_equal(shuffled, a, float_rtol=1e-9, key_cols=["k"])
+    helpers.assert_rows_equal(shuffled, a, key_cols=["k"])
+    for bad in ([inf, inf, nan, 1.0, 2.0, 3.0], [-inf, -inf, nan, 1.0, 2.0, 3.0], [1e308, -inf, nan, 1.0, 2.0, 3.0],
+                [inf, -inf, 1.0, 1.0, 2.0, 3.0]):
+        b = {"k": a["k"], "v": OCol("Float64", bad)}
+        with pytest.raises(AssertionError):
+            helpers.assert_rows_equal(b, a, ordered=True, float_rtol=1e-9)
+    # -0.0 and +0.0 keys are different rows: swapping their values is caught
+    sw = {"k": a["k"], "v": OCol("Float64", [inf, -inf, nan, 2.0, 1.0, 3.0])}
+    with pytest.raises(AssertionError):
+        helpers.assert_rows_equal(sw, a, float_rtol=1e-9, key_cols=["k"])
+    # zero results of either sign match only where the column allows it
+    z = {"m": OCol("Float64", [0.0])}
+    with pytest.raises(AssertionError):
+        helpers.assert_rows_equal(z, {"m": OCol("Float64", [-0.0])})
+    helpers.assert_rows_equal(z, {"m": OCol("Float64", [-0.0])}, zero_sign_cols=("m",))
+    with pytest.raises(AssertionError):
+        helpers.assert_rows_equal({"m": OCol("Float64", [1.0])}, {"m": OCol("Float64", [-0.0])}, zero_sign_cols=("m",))
