@@ -4,7 +4,10 @@ cannot run: size-independent properties of the operators themselves.
   * linearity of the Partial / Final split (rust/scheduler/src/planner.rs:136-171): Q1 over the whole table ==
     Final merge of Q1 partials over two disjoint halves — groups and counts exactly, sums within 1e-9 relative;
   * the filter's row count: sum of count_order == number of rows FilterExec keeps for the same predicate (exact);
-  * Q6 likewise; and both agree with the 96 M-row prefix the CPU port can still check (cpu leg of bench.py).
+  * Q6 likewise.
+
+These are checks of the device against itself.  The comparison of the full-size results with an independent CPU reference
+(every group of Q1 / Q6 / Q3 / Q5 at SF100, through bench.py's Workload) is tests/test_full_size_oracle_gpu.py.
 
 The halves are generated separately on the device (the generator is a pure function of the row index), so the
 whole-table run and the split run share no intermediate state."""
