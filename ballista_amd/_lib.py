@@ -91,6 +91,10 @@ class ShuffleStats(C.Structure):
                 ("rows_to", C.c_uint64 * SHUFFLE_MAX_PEERS), ("ms_count", C.c_double), ("ms_total", C.c_double)]
 
 
+class CsvOpts(C.Structure):
+    _fields_ = [("delimiter", C.c_uint8), ("has_header", C.c_int32)]
+
+
 class TpchOpts(C.Structure):
     _fields_ = [("key64", C.c_int32), ("with_dates", C.c_int32), ("sparse_keys", C.c_int32), ("n_columns", C.c_int32),
                 ("key_base", C.c_int64), ("columns", C.POINTER(C.c_char_p))]
@@ -121,6 +125,8 @@ SYMBOLS = {
     "bhip_batch_from_host": (C.c_int32, [_P, C.c_int32, C.POINTER(ColumnDesc), C.c_int64, _PP]),
     "bhip_batch_from_device": (C.c_int32, [_P, C.c_int32, C.POINTER(ColumnDesc), C.c_int64, _PP]),
     "bhip_batch_from_tbl": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ColumnDesc), C.c_int32, C.POINTER(C.c_int32), _PP]),
+    "bhip_batch_from_csv": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ColumnDesc), C.c_int32, C.POINTER(C.c_int32),
+                                        C.POINTER(CsvOpts), _PP]),
     "bhip_batch_import_arrow": (C.c_int32, [_P, _P, _P, _PP]),
     "bhip_batch_export_arrow": (C.c_int32, [_P, _P, _P]),
     "bhip_batch_retain": (None, [_P]),

@@ -139,6 +139,15 @@ bhip_status bhip_batch_from_tbl(bhip_ctx* ctx, const void* text, int64_t n_bytes
     BHIP_API_END
 }
 
+bhip_status bhip_batch_from_csv(bhip_ctx* ctx, const void* text, int64_t n_bytes, int32_t n_fields, const bhip_column_desc* fields,
+                                int32_t n_projection, const int32_t* projection, const bhip_csv_opts* opts, bhip_batch** out) {
+    BHIP_API_BEGIN
+    need(ctx, "ctx"); need(out, "out"); need(fields, "fields");
+    const bhip_csv_opts o = opts ? *opts : bhip_csv_opts{',', 1};
+    *out = wrap_batch(batch_from_csv(ctx->p, text, n_bytes, n_fields, fields, n_projection, projection, o));
+    BHIP_API_END
+}
+
 void bhip_batch_retain(bhip_batch* b) { if (b) b->rc.fetch_add(1); }
 void bhip_batch_release(bhip_batch* b) {
     if (b && b->rc.fetch_sub(1) == 1) delete b;

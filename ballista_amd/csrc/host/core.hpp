@@ -253,6 +253,9 @@ void column_to_host(const Batch& b, int i, void* data, int32_t* offsets, uint8_t
 // '|'-separated TPC-H text (host memory) -> device batch of the projected fields (tbl.cpp, kernels_tbl.hip)
 BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
                         int n_proj, const int32_t* projection);
+// general CSV text (any one-byte delimiter, quoted fields, NULLs, optional header) -> device batch (csv.cpp, kernels_csv.hip)
+BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
+                        int n_proj, const int32_t* projection, const bhip_csv_opts& opts);
 
 // whole-batch operations (ops_basic.cpp)
 // permutation: `indices` holds every input row exactly once (Utf8 value bytes are then known without a read-back)

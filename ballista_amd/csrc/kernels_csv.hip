@@ -1,0 +1,442 @@
+// kernels_csv.hip — general CSV text -> Arrow columns on the device: one-byte delimiter of the caller's choice, fields quoted
+// with '"' ("" inside is one '"'; delimiter, '\r' and '\n' inside are data), records ended by '\n' or '\r\n' outside quotes, an
+// empty field of a nullable column is NULL.  Stands where the reference has CsvExec with `has_header` / `delimiter` from the wire
+// plan (rust/core/src/serde/physical_plan/from_proto.rs:93-110; `--format csv`, rust/benchmarks/tpch/src/main.rs:129-150).
+//
+// A '\n' ends a record only when the number of '"' before it is even, and that parity is a prefix property of the whole text:
+//   1. count   per 16 KiB chunk: '"' count, and '\n' counts at even and at odd quote parity counted from the chunk's first byte.
+//              A scan of the quote counts gives the parity each chunk starts in, which picks one of the two counters; a scan of
+//              the picked counters gives each chunk's first record rank.
+//   2. starts  the chunk staged in LDS, 64 consecutive bytes per thread as bit masks; the thread's parity is carried across the
+//              wave by a ballot + masked popcount, across the waves through LDS; '\n' outside quotes are ranked and written.
+//   3. parse   one thread per record, fields found quote-aware; validity, Boolean and ""-mark bits leave as one ballot word per
+//              wave.
+//   4. copy    Utf8 bytes behind an exclusive scan of the lengths, "" collapsed where marked.
+// The value grammar is the `.tbl` scan's (kernels_tbl.hip) plus Boolean; the conversions are repeated here rather than shared, so
+// that the `.tbl` kernels compile to exactly what they were.  What two CSV readers would read differently (a '"' inside an
+// unquoted field, bytes behind a closing quote, a bare '\r') raises CSV_ERR_STRAY_QUOTE: the caller keeps its CPU reader.
+#include <hip/hip_runtime.h>
+#include "kernels.h"
+#include "csv_kernels.h"
+#include "vm_device.h"
+#include "vm_isa.h"
+
+namespace bhip {
+
+constexpr int CSV_THREAD_BYTES = TBL_CHUNK / BLOCK;      // 64 bytes per thread and chunk
+constexpr int CSV_WAVES = BLOCK / 64;
+constexpr int CSV_PIECES = TBL_CHUNK / (BLOCK * 16);     // 16-byte pieces per thread in the coalesced passes
+static_assert(CSV_THREAD_BYTES == 64, "a thread's bytes are one 64-bit mask");
+
+// bit b = byte b of `w` equals the byte replicated in `rep`.  Exact: 0x80 is left in every zero byte of x and in no other (the
+// per-byte sum cannot carry into the next byte), and the multiply gathers the four bits without two of them meeting.
+__device__ inline uint32_t eq_mask4(uint32_t w, uint32_t rep) {
+    const uint32_t x = w ^ rep;
+    const uint32_t t = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+    return (((t >> 7) * 0x00204081u) >> 21) & 0xFu;
+}
+constexpr uint32_t REP_QUOTE = 0x22222222u, REP_NL = 0x0A0A0A0Au;
+
+// lanes below this one whose bit is set in `ballot`
+__device__ inline uint32_t lanes_below(uint64_t ballot) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// 16 bytes at p as four dwords; bytes at and behind n_bytes read as 0: neither a quote nor a newline
+__device__ inline uint4 load_piece(const uint8_t* text, int64_t p, int64_t n_bytes) {
+    if (p + 16 <= n_bytes) return *reinterpret_cast<const uint4*>(text + p);        // text is 256-byte aligned, p a multiple of 16
+    uint32_t w[4] = {0, 0, 0, 0};
+    for (int64_t q = p; q < n_bytes && q < p + 16; ++q) w[(q - p) >> 2] |= (uint32_t)text[q] << (8 * ((q - p) & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// pass 1.  Piece order is text order: (k, wave, lane).  A lane turns its 16 bytes into a quote mask and a newline mask; the prefix
+// XOR of the quote mask is the parity at every byte, counted from the lane's first byte; the lanes before it in the wave (one
+// ballot) flip it.  That leaves one pair of counters per 1 KiB segment, relative to the segment's start; thread 0 chains the 16
+// segments of the chunk.
+__global__ void __launch_bounds__(BLOCK)
+csv_count_kernel(const uint8_t* text, int64_t n_bytes, uint32_t* quotes, uint32_t* newlines) {
+    __shared__ uint32_t s_quotes, s_odd;
+    __shared__ uint32_t s_seg[CSV_PIECES * CSV_WAVES];           // even | odd << 16 (at most 1024 each)
+    const int tid = threadIdx.x, wave = tid >> 6;
+    if (tid < CSV_PIECES * CSV_WAVES) s_seg[tid] = 0;
+    if (tid == 0) { s_quotes = 0; s_odd = 0; }
+    __syncthreads();
+    const int64_t chunk0 = (int64_t)blockIdx.x * TBL_CHUNK;
+    uint32_t nq = 0;
+#pragma unroll
+    for (int k = 0; k < CSV_PIECES; ++k) {
+        const uint4 v = load_piece(text, chunk0 + ((int64_t)k * BLOCK + tid) * 16, n_bytes);
+        const uint32_t qm = eq_mask4(v.x, REP_QUOTE) | eq_mask4(v.y, REP_QUOTE) << 4 | eq_mask4(v.z, REP_QUOTE) << 8 | eq_mask4(v.w, REP_QUOTE) << 12;
+        const uint32_t nm = eq_mask4(v.x, REP_NL) | eq_mask4(v.y, REP_NL) << 4 | eq_mask4(v.z, REP_NL) << 8 | eq_mask4(v.w, REP_NL) << 12;
+        const uint32_t q = __popc(qm);
+        nq += q;
+        uint32_t pm = qm ^ (qm << 1);                            // bit b = parity of the quotes in bytes 0..b
+        pm ^= pm << 2;
+        pm ^= pm << 4;
+        pm ^= pm << 8;
+        const uint64_t odd = __ballot(q & 1u);
+        if (lanes_below(odd) & 1u) pm = ~pm;
+        const uint32_t c = __popc(nm & ~pm & 0xFFFFu) | __popc(nm & pm & 0xFFFFu) << 16;
+        const int seg = k * CSV_WAVES + wave;
+        if (c) atomicAdd(&s_seg[seg], c);
+        if ((tid & 63) == 0 && (__popcll(odd) & 1)) atomicOr(&s_odd, 1u << seg);
+    }
+    if (nq) atomicAdd(&s_quotes, nq);
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t even = 0, odd = 0, parity = 0;
+        for (int s = 0; s < CSV_PIECES * CSV_WAVES; ++s) {
+            const uint32_t a = s_seg[s] & 0xFFFFu, b = s_seg[s] >> 16;
+            even += parity ? b : a;
+            odd += parity ? a : b;
+            parity ^= (s_odd >> s) & 1u;
+        }
+        quotes[blockIdx.x] = s_quotes;
+        newlines[2 * (int64_t)blockIdx.x] = even;
+        newlines[2 * (int64_t)blockIdx.x + 1] = odd;
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK)
+csv_pick_kernel(const uint64_t* quotes_before, const uint32_t* newlines, int64_t n_chunks, uint32_t* records) {
+    const int64_t c = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (c < n_chunks) records[c] = newlines[2 * c + (int64_t)(quotes_before[c] & 1u)];
+}
+
+// pass 2: the staging of tbl_starts_kernel (rows of 16 dwords padded to 17: the 64 lanes of a wave read 64 different banks); a
+// thread's 64 bytes become a quote mask and a newline mask, and the parity it starts in is
+//   chunk (scan of pass 1) ^ waves before it (LDS) ^ lanes before it (ballot + masked popcount).
+__global__ void __launch_bounds__(BLOCK)
+csv_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_before, const uint64_t* chunk_base, uint64_t* starts) {
+    __shared__ uint32_t s_text[BLOCK * 17];
+    __shared__ uint32_t s_scan[BLOCK];
+    __shared__ uint32_t s_wave_odd[CSV_WAVES];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const int64_t chunk0 = (int64_t)blockIdx.x * TBL_CHUNK;
+#pragma unroll
+    for (int k = 0; k < CSV_PIECES; ++k) {
+        const int piece = k * BLOCK + tid;                       // 16-byte piece of the chunk
+        const uint4 v = load_piece(text, chunk0 + (int64_t)piece * 16, n_bytes);
+        const int row = piece >> 2, col = (piece & 3) * 4;       // row = owning thread (64 bytes = 4 pieces)
+        s_text[row * 17 + col + 0] = v.x; s_text[row * 17 + col + 1] = v.y;
+        s_text[row * 17 + col + 2] = v.z; s_text[row * 17 + col + 3] = v.w;
+    }
+    __syncthreads();
+    uint64_t qm = 0, nm = 0;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) {
+        const uint32_t w = s_text[tid * 17 + d];
+        qm |= (uint64_t)eq_mask4(w, REP_QUOTE) << (4 * d);
+        nm |= (uint64_t)eq_mask4(w, REP_NL) << (4 * d);
+    }
+    const uint64_t odd = __ballot(__popcll(qm) & 1);
+    if ((tid & 63) == 0) s_wave_odd[wave] = (uint32_t)__popcll(odd) & 1u;
+    uint64_t pm = qm ^ (qm << 1);                               // bit b = parity of the quotes in bytes 0..b of this thread
+    pm ^= pm << 2;
+    pm ^= pm << 4;
+    pm ^= pm << 8;
+    pm ^= pm << 16;
+    pm ^= pm << 32;
+    __syncthreads();
+    uint32_t in = (uint32_t)(quotes_before[blockIdx.x] & 1u) ^ (lanes_below(odd) & 1u);
+    for (int w = 0; w < wave; ++w) in ^= s_wave_odd[w];
+    if (in) pm = ~pm;
+    uint64_t ends = nm & ~pm;                                   // '\n' outside quotes
+    const uint32_t c = (uint32_t)__popcll(ends);
+    s_scan[tid] = c;
+    __syncthreads();
+    for (int d = 1; d < BLOCK; d <<= 1) {                       // inclusive Hillis-Steele scan of the thread counts
+        const uint32_t v = tid >= d ? s_scan[tid - d] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    if (c == 0) return;
+    uint64_t rank = chunk_base[blockIdx.x] + (s_scan[tid] - c);
+    const int64_t base = chunk0 + (int64_t)tid * CSV_THREAD_BYTES;
+    while (ends) {
+        const int b = __ffsll((unsigned long long)ends) - 1;
+        starts[++rank] = (uint64_t)(base + b) + 1;
+        ends &= ends - 1;
+    }
+}
+
+__device__ inline int64_t csv_days_from_civil(int64_t y, unsigned m, unsigned d) {
+    y -= m <= 2;
+    const int64_t era = (y >= 0 ? y : y - 399) / 400;
+    const unsigned yoe = (unsigned)(y - era * 400);
+    const unsigned doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
+    const unsigned doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+    return era * 146097 + (int64_t)doe - 719468;
+}
+
+__constant__ double CSV_POW10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
+                                     1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+
+// byte sources of the field walk: the text in HBM, or the records of one workgroup staged in LDS
+struct CsvGlobalReader {
+    const uint8_t* text;
+    __device__ uint8_t operator()(int64_t pos) const { return text[pos]; }
+};
+struct CsvLdsReader {
+    const uint8_t* buf;          // LDS copy of text[origin, origin + ...)
+    int64_t origin;
+    __device__ uint8_t operator()(int64_t pos) const { return buf[pos - origin]; }
+};
+
+// a non-empty value [a, b) of a fixed-width column -> row i of `data`; returns the error flags.  Int32 / Int64 / Float64 / Date32
+// as in kernels_tbl.hip (one exact division for decimals).  A Boolean comes back in `truth`.
+template <class R>
+__device__ inline uint32_t csv_convert(const R& rd, int64_t a, int64_t b, int dt, void* data, int64_t i, bool& truth) {
+    uint32_t err = 0;
+    if (dt == DT_BOOLEAN) {
+        const char* word = (b - a) == 4 ? "true" : "false";
+        bool ok = (b - a) == 4 || (b - a) == 5;
+        for (int k = 0; ok && k < (int)(b - a); ++k) ok = (rd(a + k) | 0x20) == (uint8_t)word[k];
+        truth = ok && (b - a) == 4;
+        return ok ? 0u : (uint32_t)TBL_ERR_BAD_VALUE;
+    }
+    if (dt == DT_DATE32) {
+        // YYYY-MM-DD
+        bool ok = (b - a) == 10 && rd(a + 4) == '-' && rd(a + 7) == '-';
+        int v[8];
+        const int pos[8] = {0, 1, 2, 3, 5, 6, 8, 9};
+        for (int k = 0; k < 8 && ok; ++k) {
+            const int c = (int)rd(a + pos[k]) - '0';
+            ok = c >= 0 && c <= 9;
+            v[k] = c;
+        }
+        int32_t days = 0;
+        if (ok) {
+            const int y = v[0] * 1000 + v[1] * 100 + v[2] * 10 + v[3], m = v[4] * 10 + v[5], d = v[6] * 10 + v[7];
+            ok = m >= 1 && m <= 12 && d >= 1 && d <= 31;
+            days = (int32_t)csv_days_from_civil(y, (unsigned)m, (unsigned)d);
+        }
+        if (!ok) err |= TBL_ERR_BAD_VALUE;
+        reinterpret_cast<int32_t*>(data)[i] = days;
+        return err;
+    }
+    int64_t r = a;
+    bool neg = false;
+    if (rd(r) == '-' || rd(r) == '+') { neg = rd(r) == '-'; ++r; }
+    uint64_t m = 0;
+    int digits = 0, frac = 0;
+    bool seen_dot = false, ok = r < b;
+    for (; r < b; ++r) {
+        const uint8_t ch = rd(r);
+        if (ch >= '0' && ch <= '9') {
+            if (digits >= 19) {                                  // 19 digits still fit 64 bits
+                if (dt == DT_FLOAT64) { err |= TBL_ERR_PRECISION; m = 0; frac = 0; r = b; break; }
+                ok = false;
+                break;
+            }
+            m = m * 10 + (uint64_t)(ch - '0');
+            if (m != 0 || seen_dot) ++digits;             // leading zeros of the integer part are free
+            if (seen_dot) ++frac;
+        } else if (ch == '.' && !seen_dot && dt == DT_FLOAT64) {
+            seen_dot = true;
+        } else { ok = false; break; }
+    }
+    if (dt == DT_FLOAT64) {
+        if (!ok) err |= TBL_ERR_BAD_VALUE;
+        else if (m >= (1ull << 53) || frac > 22) { err |= TBL_ERR_PRECISION; ok = false; }
+        const double v = ok ? (double)m / CSV_POW10[frac] : 0.0;
+        reinterpret_cast<double*>(data)[i] = neg ? -v : v;
+    } else {
+        if (!ok || seen_dot) err |= TBL_ERR_BAD_VALUE;
+        if (m > (neg ? (1ull << 63) : (1ull << 63) - 1ull)) err |= TBL_ERR_BAD_VALUE;      // beyond Int64
+        const int64_t v = neg ? (int64_t)(0ull - m) : (int64_t)m;
+        if (dt == DT_INT32) {
+            if (v > 2147483647ll || v < -2147483648ll) err |= TBL_ERR_BAD_VALUE;
+            reinterpret_cast<int32_t*>(data)[i] = (int32_t)v;
+        } else {
+            reinterpret_cast<int64_t*>(data)[i] = v;
+        }
+    }
+    return err;
+}
+
+// one record [p, e) per lane.  Every lane of the wave walks all the fields, with or without a record (`active`), because the bits
+// of a column leave as one ballot word per wave: `word` is the wave's word in every bitmap, or -1 when the wave has no record.
+template <bool QUOTED, class R>
+__device__ inline uint32_t csv_parse_record(const R& rd, bool active, int64_t p, int64_t e, int64_t i, int64_t word, const CsvPlan& plan,
+                                            uint32_t& null_slots) {
+    uint32_t err = 0;
+    const bool writer = (threadIdx.x & 63) == 0 && word >= 0;
+    const uint8_t delim = (uint8_t)plan.delimiter;
+    if (active) {
+        if (e > p && rd(e - 1) == '\r') --e;
+        if (e <= p) { err |= TBL_ERR_BLANK_LINE; active = false; }
+    }
+    for (int f = 0; f < plan.n_fields; ++f) {
+        if (active && p > e) { err |= TBL_ERR_MISSING_FIELD; active = false; }
+        int64_t a = p, b = p;                            // content of the field
+        uint32_t pairs = 0;                              // "" inside it
+        if (active) {
+            if (QUOTED && p < e && rd(p) == '"') {
+                int64_t q = p + 1;
+                bool closed = false;
+                while (q < e) {
+                    if (rd(q) != '"') { ++q; continue; }
+                    if (q + 1 < e && rd(q + 1) == '"') { ++pairs; q += 2; continue; }
+                    closed = true;
+                    break;
+                }
+                a = p + 1;
+                b = q;
+                if (!closed) { err |= CSV_ERR_STRAY_QUOTE; b = a; active = false; }
+                else if (q + 1 < e && rd(q + 1) != delim) { err |= CSV_ERR_STRAY_QUOTE; active = false; }
+                p = q + 2;                               // behind the closing quote and the delimiter (or the record's end)
+            } else {
+                int64_t q = p;
+                for (; q < e; ++q) {
+                    const uint8_t ch = rd(q);
+                    if (ch == delim) break;
+                    if ((QUOTED && ch == '"') || ch == '\r') err |= CSV_ERR_STRAY_QUOTE;
+                }
+                b = q;
+                p = q + 1;
+            }
+        }
+        const int out = plan.out[f];
+        if (out < 0) continue;
+        const int dt = plan.dtype[f];
+        if (dt == DT_UTF8) {
+            if (active) {
+                plan.str_start[out][i] = (uint32_t)a;
+                plan.str_len[out][i] = (uint32_t)(b - a) - pairs;
+            }
+            if (QUOTED) {
+                const uint64_t marks = __ballot(active && pairs != 0);
+                if (writer) plan.str_esc[out][word] = marks;
+            }
+            continue;
+        }
+        bool valid = false, truth = false;
+        if (active) {
+            if (b == a) {
+                if (!plan.nullable[f]) err |= CSV_ERR_NULL;
+                if (dt == DT_FLOAT64 || dt == DT_INT64) reinterpret_cast<uint64_t*>(plan.data[out])[i] = 0;
+                else if (dt != DT_BOOLEAN) reinterpret_cast<uint32_t*>(plan.data[out])[i] = 0;
+            } else {
+                valid = true;
+                if (pairs) err |= TBL_ERR_BAD_VALUE;
+                err |= csv_convert(rd, a, b, dt, plan.data[out], i, truth);
+            }
+        }
+        if (plan.validity[out]) {
+            const uint64_t bits = __ballot(valid);
+            if (__ballot(active && !valid)) null_slots |= 1u << out;
+            if (writer) plan.validity[out][word] = bits;
+        }
+        if (dt == DT_BOOLEAN) {
+            const uint64_t bits = __ballot(truth);
+            if (writer) reinterpret_cast<uint64_t*>(plan.data[out])[word] = bits;
+        }
+    }
+    return err;
+}
+
+// pass 3: a workgroup takes 256 consecutive records.  Their text is one contiguous span: it is staged in LDS with coalesced
+// 16-byte loads and every thread walks its own record there; a span that does not fit (very long records) is walked in HBM.
+// Record i0 is a multiple of 256, so wave w of the workgroup owns bitmap word i0 / 64 + w of every column.
+constexpr int CSV_STAGE = 48 * 1024;
+template <bool QUOTED>
+__global__ void __launch_bounds__(BLOCK)
+csv_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_records, int64_t n_bytes, CsvPlan plan, uint32_t* flags) {
+    __shared__ __align__(16) uint8_t s_buf[CSV_STAGE];
+    uint32_t err = 0, null_slots = 0;
+    const int tid = threadIdx.x;
+    for (int64_t i0 = (int64_t)blockIdx.x * BLOCK; i0 < n_records; i0 += (int64_t)gridDim.x * BLOCK) {
+        const int64_t n_here = n_records - i0 < BLOCK ? n_records - i0 : BLOCK;
+        const int64_t span0 = (int64_t)starts[i0] & ~(int64_t)15;                 // 16-byte aligned (the text buffer is)
+        int64_t span1 = (int64_t)starts[i0 + n_here];
+        if (span1 > n_bytes) span1 = n_bytes;
+        const bool staged = span1 - span0 <= CSV_STAGE - 16;       // the copy below moves whole 16-byte pieces
+        if (staged) {
+            for (int64_t k = (int64_t)tid * 16; k < span1 - span0; k += BLOCK * 16) {
+                const int64_t g = span0 + k;
+                if (g + 16 <= n_bytes) *reinterpret_cast<uint4*>(s_buf + k) = *reinterpret_cast<const uint4*>(text + g);
+                else
+                    for (int64_t b = g; b < n_bytes; ++b) s_buf[b - span0] = text[b];
+            }
+        }
+        __syncthreads();
+        const bool active = tid < n_here;
+        const int64_t i = i0 + tid;
+        const int64_t p = active ? (int64_t)starts[i] : 0;
+        const int64_t e = active ? (int64_t)starts[i + 1] - 1 : 0;     // the newline (or one past the text for an unterminated last record)
+        const int64_t word = (tid & ~63) < n_here ? (i0 + (tid & ~63)) >> 6 : -1;
+        if (staged) err |= csv_parse_record<QUOTED>(CsvLdsReader{s_buf, span0}, active, p, e, i, word, plan, null_slots);
+        else err |= csv_parse_record<QUOTED>(CsvGlobalReader{text}, active, p, e, i, word, plan, null_slots);
+        __syncthreads();
+    }
+    if (err) atomicOr(flags, err);
+    if (null_slots && (tid & 63) == 0) atomicOr(flags + 1, null_slots);
+}
+
+// pass 4: one thread per row.  Inside a quoted field every '"' is the first of a "" pair: the second is skipped.
+__global__ void __launch_bounds__(BLOCK)
+csv_copy_strings_kernel(const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len, const uint64_t* str_esc,
+                        const int32_t* offsets, int64_t n, uint8_t* out) {
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        const uint8_t* s = text + str_start[i];
+        uint8_t* d = out + offsets[i];
+        const uint32_t len = str_len[i];
+        if (str_esc && ((str_esc[i >> 6] >> (i & 63)) & 1ull)) {
+            for (uint32_t b = 0; b < len; ++b) {
+                const uint8_t ch = *s;
+                d[b] = ch;
+                s += ch == '"' ? 2 : 1;
+            }
+        } else {
+            for (uint32_t b = 0; b < len; ++b) d[b] = s[b];
+        }
+    }
+}
+
+static int csv_grid_rows(const LaunchCfg& cfg, int64_t n) {
+    int64_t g = (n + BLOCK - 1) / BLOCK;
+    const int64_t cap = (int64_t)cfg.device_cus * 16;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+hipError_t launch_csv_count(const LaunchCfg& cfg, const uint8_t* text, int64_t n_bytes, uint32_t* quotes, uint32_t* newlines) {
+    const int64_t n_chunks = (n_bytes + TBL_CHUNK - 1) / TBL_CHUNK;
+    if (n_chunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(csv_count_kernel, dim3((unsigned)n_chunks), dim3(BLOCK), 0, cfg.stream, text, n_bytes, quotes, newlines);
+    return hipGetLastError();
+}
+hipError_t launch_csv_pick(const LaunchCfg& cfg, const uint64_t* quotes_before, const uint32_t* newlines, int64_t n_chunks, uint32_t* records) {
+    if (n_chunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(csv_pick_kernel, dim3((unsigned)((n_chunks + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, cfg.stream, quotes_before, newlines,
+                       n_chunks, records);
+    return hipGetLastError();
+}
+hipError_t launch_csv_starts(const LaunchCfg& cfg, const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_before,
+                             const uint64_t* chunk_base, uint64_t* starts) {
+    const int64_t n_chunks = (n_bytes + TBL_CHUNK - 1) / TBL_CHUNK;
+    if (n_chunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(csv_starts_kernel, dim3((unsigned)n_chunks), dim3(BLOCK), 0, cfg.stream, text, n_bytes, quotes_before, chunk_base, starts);
+    return hipGetLastError();
+}
+hipError_t launch_csv_parse(const LaunchCfg& cfg, const uint8_t* text, const uint64_t* starts, int64_t n_records, int64_t n_bytes,
+                            const CsvPlan& plan, bool quoted, uint32_t* flags) {
+    if (n_records == 0) return hipSuccess;
+    const dim3 grid(csv_grid_rows(cfg, n_records));
+    if (quoted) hipLaunchKernelGGL(csv_parse_kernel<true>, grid, dim3(BLOCK), 0, cfg.stream, text, starts, n_records, n_bytes, plan, flags);
+    else hipLaunchKernelGGL(csv_parse_kernel<false>, grid, dim3(BLOCK), 0, cfg.stream, text, starts, n_records, n_bytes, plan, flags);
+    return hipGetLastError();
+}
+hipError_t launch_csv_copy_strings(const LaunchCfg& cfg, const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len,
+                                   const uint64_t* str_esc, const int32_t* offsets, int64_t n, uint8_t* out) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(csv_copy_strings_kernel, dim3(csv_grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, text, str_start, str_len, str_esc,
+                       offsets, n, out);
+    return hipGetLastError();
+}
+
+}  // namespace bhip

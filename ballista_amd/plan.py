@@ -346,6 +346,41 @@ class RecordBatch:
         return RecordBatch(h, ctx)
 
     @staticmethod
+    def from_csv(ctx: Context, text, schema, columns=None, delimiter=",", has_header=True) -> "RecordBatch":
+        """bhip_batch_from_csv: CSV text (bytes or a path) parsed on the device — the scan leaf the reference builds as
+        CsvExec(schema, has_header, delimiter) for `--format csv` (rust/benchmarks/tpch/src/main.rs:129-150).  Fields may
+        be quoted with '"' ("" inside is one '"'; delimiters and line ends inside are data).  schema: [(name, dtype)] or
+        [(name, dtype, nullable)] of the file's fields in order; an empty field of a nullable column that is not Utf8 is
+        NULL.  columns: names to materialise, in output order (None: all).  delimiter: one byte."""
+        if isinstance(text, str):
+            with open(text, "rb") as f:
+                text = f.read()
+        text = bytes(text)
+        delim = delimiter.encode() if isinstance(delimiter, str) else bytes(delimiter)
+        if len(delim) != 1:
+            raise L.PlanError(L.EINVAL, f"csv delimiter must be one byte, got {delimiter!r}")
+        descs, keep = [], []
+        for name, dtype, *nullable in schema:
+            d = L.ColumnDesc()
+            nb = name.encode()
+            keep.append(nb)
+            d.name, d.dtype, d.nullable = nb, DTYPE_ID[dtype], 1 if nullable and nullable[0] else 0
+            descs.append(d)
+        arr = (L.ColumnDesc * max(1, len(descs)))(*descs)
+        proj, n_proj = None, 0
+        if columns is not None:
+            names = [f[0] for f in schema]
+            idx = [names.index(c) for c in columns]
+            proj = (C.c_int32 * max(1, len(idx)))(*idx)
+            n_proj = len(idx)
+        opts = L.CsvOpts(delim[0], 1 if has_header else 0)
+        h = C.c_void_p()
+        # the bytes object itself is the text buffer (no copy on the Python side)
+        L.check(L.lib().bhip_batch_from_csv(ctx._h, C.c_char_p(text) if text else None, len(text), len(descs), arr, n_proj, proj,
+                                            C.byref(opts), C.byref(h)))
+        return RecordBatch(h, ctx)
+
+    @staticmethod
     def from_device_pointers(ctx: Context, columns, n_rows: int, keep=None) -> "RecordBatch":
         """bhip_batch_from_device over caller-owned device memory: columns = [(name, dtype, data_ptr)], fixed-width
         NULL-free columns (e.g. buffers an RCCL collective has just filled).  `keep`: whatever owns the memory."""

@@ -148,6 +148,25 @@ bhip_status bhip_batch_from_device(bhip_ctx* ctx, int32_t n_cols, const bhip_col
 bhip_status bhip_batch_from_tbl(bhip_ctx* ctx, const void* text, int64_t n_bytes, int32_t n_fields,
                                 const bhip_column_desc* fields, int32_t n_projection, const int32_t* projection,
                                 bhip_batch** out);
+/* Scan leaf for general CSV text — where the reference has CsvExec with the `has_header` and `delimiter` of the wire
+ * plan (`--format csv`: CsvReadOptions::new().schema(..).has_header(true), rust/benchmarks/tpch/src/main.rs:129-150).
+ * Arguments as for bhip_batch_from_tbl, plus `opts` (NULL: ',' and a header).  Accepted text: fields separated by
+ * `delimiter` (one byte, not '"', '\n' or '\r': else BHIP_EINVAL); records ended by '\n' or '\r\n' outside quotes,
+ * the last one may be unterminated; with `has_header` the first record is skipped (it is not compared with the
+ * schema).  A field whose first byte is '"' runs to the matching '"'; inside it "" is one '"', and delimiter, '\r'
+ * and '\n' are data.  Values as for `.tbl`, plus Boolean (true / false in any letter case).  An empty field
+ * (unquoted, or "") of a column that is not Utf8 is NULL when fields[i].nullable, BHIP_EEXEC when not; of a Utf8
+ * column it is the empty string.  A column in which no NULL occurred carries no validity buffer.  Fewer fields than
+ * the schema, a blank line, a malformed value -> BHIP_EEXEC.  A '"' inside an unquoted field, bytes between a
+ * closing quote and the next delimiter, a '\r' that is not part of a record end, an unclosed quote: CSV readers
+ * disagree on these -> BHIP_ENOTIMPL (keep the CPU reader).  Text < 4 GiB per call. */
+typedef struct bhip_csv_opts {
+    uint8_t delimiter;        /* e.g. ',' */
+    int32_t has_header;       /* != 0: the first record holds column names */
+} bhip_csv_opts;
+bhip_status bhip_batch_from_csv(bhip_ctx* ctx, const void* text, int64_t n_bytes, int32_t n_fields,
+                                const bhip_column_desc* fields, int32_t n_projection, const int32_t* projection,
+                                const bhip_csv_opts* opts, bhip_batch** out);
 /* Arrow C Data Interface: `array` is a struct array (one child per column) as produced by
  * RecordBatch export; it is consumed (released) on success. */
 bhip_status bhip_batch_import_arrow(bhip_ctx* ctx, struct ArrowArray* array, struct ArrowSchema* schema,
@@ -276,7 +295,8 @@ bhip_status bhip_plan_local_limit(bhip_plan* input, int64_t limit, bhip_plan** o
  * rules (compile_expr, :348-364).  Every leaf (CsvScan / ParquetScan / ShuffleReader / UnresolvedShuffle) is offered
  * to `resolve` (may be NULL): it returns BHIP_OK with *out = a plan that produces the leaf's rows (a bhip_plan_memory, a
  * bhip_plan_arrow_stream over a CPU reader ...; ownership of that handle passes to the library), or BHIP_OK with *out = NULL to leave the leaf to the library:
- * a CsvScan over '|'-separated header-less local files becomes the device `.tbl` scan (bhip_batch_from_tbl), any
+ * a CsvScan over '|'-separated header-less local files becomes the device `.tbl` scan (bhip_batch_from_tbl), a
+ * CsvScan over local files with any other one-byte delimiter or a header the device CSV scan (bhip_batch_from_csv), any
  * other leaf an operator that describes itself and fails on execute with BHIP_EEXEC
  * (UnresolvedShuffleExec::execute, rust/core/src/execution_plans/unresolved_shuffle.rs:83-90).
  * `ctx` may be NULL when every leaf is left unresolved: the plan can then be inspected (bhip_plan_display, _schema,

@@ -48,6 +48,13 @@ pub struct bhip_column_desc {
     pub data_bytes: i64,
 }
 
+/// Options of `bhip_batch_from_csv`.
+#[repr(C)]
+pub struct bhip_csv_opts {
+    pub delimiter: u8,
+    pub has_header: i32,
+}
+
 #[repr(C)]
 pub struct bhip_partition_location {
     pub job_id: *const c_char,
@@ -126,4 +133,16 @@ extern "C" {
     pub fn bhip_stream_release(stream: *mut bhip_stream);
     pub fn bhip_batch_export_arrow(batch: *mut bhip_batch, out_array: *mut FFI_ArrowArray, out_schema: *mut FFI_ArrowSchema) -> bhip_status;
     pub fn bhip_batch_release(batch: *mut bhip_batch);
+    /// CSV text in host memory -> device batch (the scan leaf of `--format csv`; `opts` null: ',' and a header).
+    pub fn bhip_batch_from_csv(
+        ctx: *mut bhip_ctx,
+        text: *const c_void,
+        n_bytes: i64,
+        n_fields: i32,
+        fields: *const bhip_column_desc,
+        n_projection: i32,
+        projection: *const i32,
+        opts: *const bhip_csv_opts,
+        out: *mut *mut bhip_batch,
+    ) -> bhip_status;
 }
