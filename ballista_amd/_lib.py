@@ -95,6 +95,13 @@ class CsvOpts(C.Structure):
     _fields_ = [("delimiter", C.c_uint8), ("has_header", C.c_int32)]
 
 
+class TextScanOpts(C.Structure):
+    _fields_ = [("format", C.c_int32), ("csv", CsvOpts), ("slab_bytes", C.c_int64)]
+
+
+TEXT_TBL, TEXT_CSV = 0, 1
+
+
 class TpchOpts(C.Structure):
     _fields_ = [("key64", C.c_int32), ("with_dates", C.c_int32), ("sparse_keys", C.c_int32), ("n_columns", C.c_int32),
                 ("key_base", C.c_int64), ("columns", C.POINTER(C.c_char_p))]
@@ -142,6 +149,8 @@ SYMBOLS = {
     "bhip_plan_arrow_stream": (C.c_int32, [_P, _P, _PP]),
     "bhip_plan_arrow_streams": (C.c_int32, [_P, C.c_int32, _PP, _PP]),
     "bhip_plan_parquet": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, _PP]),
+    "bhip_plan_text_scan": (C.c_int32, [_P, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(ColumnDesc), C.c_int32,
+                                        C.POINTER(C.c_int32), C.POINTER(TextScanOpts), _PP]),
     "bhip_plan_empty": (C.c_int32, [_P, C.c_int32, C.POINTER(ColumnDesc), C.c_int32, _PP]),
     "bhip_plan_filter": (C.c_int32, [_P, C.POINTER(Expr), _PP]),
     "bhip_plan_projection": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.POINTER(C.c_char_p), _PP]),

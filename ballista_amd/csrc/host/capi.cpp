@@ -356,6 +356,34 @@ bhip_status bhip_plan_parquet(bhip_ctx* ctx, int32_t n_files, const char* const*
     BHIP_API_END
 }
 
+bhip_status bhip_plan_text_scan(bhip_ctx* ctx, int32_t n_files, const char* const* paths, int32_t n_fields, const bhip_column_desc* fields,
+                                int32_t n_projection, const int32_t* projection, const bhip_text_scan_opts* opts, bhip_plan** out) {
+    BHIP_API_BEGIN
+    need(ctx, "ctx"); need(out, "out"); need(fields, "fields");
+    if (n_files > 0) need(paths, "paths");
+    std::vector<std::string> files;
+    for (int i = 0; i < n_files; ++i) { need(paths[i], "path"); files.push_back(paths[i]); }
+    if (files.empty()) fail(BHIP_EINVAL, "text scan without a file");
+    if (n_fields < 1 || n_fields > 32) fail(BHIP_EINVAL, "text scan schema must have 1..32 fields");
+    auto schema = std::make_shared<Schema>();
+    for (int i = 0; i < n_fields; ++i) {
+        if (!fields[i].name) fail(BHIP_EINVAL, "text scan field without a name");
+        schema->fields.push_back(Field{fields[i].name, fields[i].dtype, fields[i].nullable != 0});
+    }
+    std::vector<uint32_t> proj;
+    if (projection) {
+        for (int i = 0; i < n_projection; ++i) {
+            if (projection[i] < 0 || projection[i] >= n_fields) fail(BHIP_EINVAL, "text scan projection index out of range");
+            proj.push_back((uint32_t)projection[i]);
+        }
+    }
+    const bhip_text_scan_opts o = opts ? *opts : bhip_text_scan_opts{BHIP_TEXT_TBL, bhip_csv_opts{'|', 0}, 0};
+    const std::string path = files.size() == 1 ? files[0] : files[0] + " (+" + std::to_string(files.size() - 1) + ")";
+    *out = wrap_plan(make_text_scan_exec(ctx->p, path, files, schema, proj, projection != nullptr, o.format, o.csv.delimiter, o.csv.has_header != 0,
+                                         o.slab_bytes));
+    BHIP_API_END
+}
+
 bhip_status bhip_plan_from_proto(bhip_ctx* ctx, const void* bytes, size_t len, bhip_leaf_resolver resolve, void* user,
                                  bhip_plan** out) {
     BHIP_API_BEGIN

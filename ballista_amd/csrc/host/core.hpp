@@ -257,6 +257,10 @@ BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_
 BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
                         int n_proj, const int32_t* projection, const bhip_csv_opts& opts);
 
+// pinned host blocks from a process-wide pool, pageable memory when no pinned memory is left (parquet.cpp: PinnedPool)
+void* pinned_host_alloc(size_t bytes);
+void pinned_host_free(void* p, size_t bytes);
+
 // whole-batch operations (ops_basic.cpp)
 // permutation: `indices` holds every input row exactly once (Utf8 value bytes are then known without a read-back)
 BatchPtr take_batch(const Exec& ex, const Batch& in, const uint32_t* indices, int64_t n_out, SchemaPtr schema = nullptr,

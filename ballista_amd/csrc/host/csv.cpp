@@ -8,19 +8,14 @@
 #include "../csv_kernels.h"
 #include "../util_kernels.h"
 #include "core.hpp"
+#include "text_scan.hpp"
 
 namespace bhip {
 
-BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
-                        int n_proj, const int32_t* projection, const bhip_csv_opts& opts) {
-    if (n_bytes < 0 || n_bytes > 0xFFFFFFF0ll) fail(BHIP_EINVAL, "csv text must be < 4 GiB per call (split the file on record boundaries)");
+CsvScanSpec make_csv_spec(int n_fields, const bhip_column_desc* fields, int n_proj, const int32_t* projection, const bhip_csv_opts& opts) {
     if (n_fields < 1 || n_fields > TBL_MAX_FIELDS) fail(BHIP_EINVAL, "csv schema must have 1.." + std::to_string(TBL_MAX_FIELDS) + " fields");
-    if (n_bytes > 0 && !text_host) fail(BHIP_EINVAL, "csv text is null");
     if (opts.delimiter == '"' || opts.delimiter == '\n' || opts.delimiter == '\r')
         fail(BHIP_EINVAL, "csv delimiter must be one byte other than '\"', '\\n' and '\\r'");
-    ctx->set_device();
-    Exec ex{ctx, nullptr};
-    const LaunchCfg cfg = ex.cfg();
 
     // which fields to materialise, in which order
     std::vector<int> proj;
@@ -32,7 +27,8 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
     } else {
         for (int i = 0; i < n_fields; ++i) proj.push_back(i);
     }
-    CsvPlan plan;
+    CsvScanSpec spec;
+    CsvPlan& plan = spec.plan;
     memset(&plan, 0, sizeof(plan));
     plan.delimiter = opts.delimiter;
     int last_needed = -1;
@@ -51,17 +47,47 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
         if (plan.out[f] >= 0) fail(BHIP_EINVAL, std::string("csv projection names a field twice: ") + fields[f].name);
         plan.out[f] = (int)s;
         schema->fields.push_back(Field{fields[f].name, dt, fields[f].nullable != 0});
+        spec.dtype.push_back(dt);
+        spec.nullable.push_back(fields[f].nullable != 0);
         if (f > last_needed) last_needed = f;
     }
     plan.n_fields = last_needed + 1;                     // fields behind the last projected one are never walked
+    spec.schema = schema;
+    return spec;
+}
 
-    auto batch = std::make_shared<Batch>();
-    batch->ctx = ctx;
-    batch->schema = schema;
+BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
+                        int n_proj, const int32_t* projection, const bhip_csv_opts& opts) {
+    if (n_bytes < 0 || n_bytes > 0xFFFFFFF0ll) fail(BHIP_EINVAL, "csv text must be < 4 GiB per call (split the file on record boundaries)");
+    if (n_fields < 1 || n_fields > TBL_MAX_FIELDS) fail(BHIP_EINVAL, "csv schema must have 1.." + std::to_string(TBL_MAX_FIELDS) + " fields");
+    if (n_bytes > 0 && !text_host) fail(BHIP_EINVAL, "csv text is null");
+    const CsvScanSpec spec = make_csv_spec(n_fields, fields, n_proj, projection, opts);
+    ctx->set_device();
+    Exec ex{ctx, nullptr};
 
     Temp tmp(ex);
     uint8_t* text = tmp.get<uint8_t>((size_t)n_bytes + 64);
     if (n_bytes) HIP_CHECK(hipMemcpyAsync(text, text_host, (size_t)n_bytes, hipMemcpyHostToDevice, ex.stream));
+    TextSlab slab;
+    slab.text = text;
+    slab.n_bytes = n_bytes;
+    slab.unterminated = n_bytes > 0 && static_cast<const uint8_t*>(text_host)[n_bytes - 1] != '\n';
+    slab.header_here = opts.has_header != 0;
+    return parse_csv_slab(ex, spec, slab).batch;
+}
+
+TextParsed parse_csv_slab(const Exec& ex, const CsvScanSpec& spec, const TextSlab& slab) {
+    const LaunchCfg cfg = ex.cfg();
+    const uint8_t* text = slab.text;
+    const int64_t n_bytes = slab.n_bytes;
+    CsvPlan plan = spec.plan;
+    const size_t n_slots = spec.dtype.size();
+
+    auto batch = std::make_shared<Batch>();
+    batch->ctx = ex.ctx;
+    batch->schema = spec.schema;
+
+    Temp tmp(ex);
 
     // ---- records: quotes and both newline counters per chunk -> parity of every chunk -> its first record rank
     const int64_t n_chunks = (n_bytes + TBL_CHUNK - 1) / TBL_CHUNK;
@@ -81,19 +107,23 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
         HIP_CHECK(exclusive_scan_u32_u64(ex.stream, chunk_records, n_chunks, chunk_base, false, &totals_dev->newlines, scan_tmp));
         totals = read_device(ex, totals_dev);
     }
-    if (totals.quotes & 1) fail(BHIP_ENOTIMPL, "csv: a quoted field is not closed");
+    // a slab that is not the last yields its complete records only; what lies behind the last '\n' outside quotes is the next
+    // slab's carry, and a quote may still be open there
+    if (slab.last && (totals.quotes & 1)) fail(BHIP_ENOTIMPL, "csv: a quoted field is not closed");
     const bool quoted = totals.quotes != 0;
-    const bool unterminated = n_bytes > 0 && static_cast<const uint8_t*>(text_host)[n_bytes - 1] != '\n';
+    const bool unterminated = slab.last && slab.unterminated;
     const int64_t n_records = (int64_t)totals.newlines + (unterminated ? 1 : 0);
     if (n_records > 0xFFFFFFF0ll) fail(BHIP_EINVAL, "csv text holds more than 2^32-16 records");
-    const int64_t header = opts.has_header && n_records > 0 ? 1 : 0;
+    if (!slab.last && n_records == 0) return TextParsed{nullptr, slab.first_record};       // no record ends here: all of it is carry
+    const int64_t header = slab.header_here && n_records > 0 ? 1 : 0;
     const int64_t n_rows = n_records - header;
     batch->n_rows = n_rows;
 
     uint64_t* starts = tmp.get<uint64_t>((size_t)n_records + 2);
     if (n_records) {
         FillMany fill;
-        fill.add(starts, 8, 0);
+        fill.add(starts, 4, (uint32_t)slab.first_record);
+        fill.add(reinterpret_cast<uint32_t*>(starts) + 1, 4, 0);
         if (unterminated) {                                     // an unterminated last record "ends" one past the text (< 2^32)
             fill.add(starts + n_records, 4, (uint32_t)(n_bytes + 1));
             fill.add(reinterpret_cast<uint32_t*>(starts + n_records) + 1, 4, 0);
@@ -107,9 +137,9 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
     // ---- values
     uint32_t* flags = tmp.get<uint32_t>(2);
     HIP_CHECK(hipMemsetAsync(flags, 0, 8, ex.stream));
-    std::vector<uint32_t*> lens(proj.size(), nullptr);
-    for (size_t s = 0; s < proj.size(); ++s) {
-        const int dt = fields[proj[s]].dtype;
+    std::vector<uint32_t*> lens(n_slots, nullptr);
+    for (size_t s = 0; s < n_slots; ++s) {
+        const int dt = spec.dtype[s];
         Column c;
         c.dtype = dt;
         c.length = n_rows;
@@ -121,7 +151,7 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
         } else {
             c.data = make_buffer(ex, (dt == DT_BOOLEAN ? bitmap_bytes(n_rows) : (size_t)n_rows * dtype_width(dt)) + 8);
             plan.data[s] = c.data->ptr();
-            if (fields[proj[s]].nullable) {
+            if (spec.nullable[s]) {
                 c.validity = make_buffer(ex, bitmap_bytes(n_rows) + 8);
                 plan.validity[s] = c.validity->as<uint64_t>();
             }
@@ -131,17 +161,19 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
     HIP_CHECK(launch_csv_parse(cfg, text, starts + header, n_rows, n_bytes, plan, quoted, flags));
 
     // ---- strings: lengths -> offsets -> bytes; all totals and the flags in one read-back
-    uint64_t* totals_str = tmp.get<uint64_t>(proj.size() + 1);
+    uint64_t* totals_str = tmp.get<uint64_t>(n_slots + 1);
     std::vector<size_t> utf8;
-    for (size_t s = 0; s < proj.size(); ++s)
+    for (size_t s = 0; s < n_slots; ++s)
         if (lens[s]) {
             void* st = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_rows > 0 ? n_rows : 1));
             HIP_CHECK(exclusive_scan_u32_i32(ex.stream, lens[s], n_rows, batch->cols[s].offsets->as<int32_t>(), true, totals_str + s, st));
             utf8.push_back(s);
         }
-    std::vector<uint64_t> host_totals(proj.size() + 1, 0);
+    std::vector<uint64_t> host_totals(n_slots + 1, 0);
     uint32_t host_flags[2] = {0, 0};
-    if (!utf8.empty()) HIP_CHECK(hipMemcpyAsync(host_totals.data(), totals_str, proj.size() * 8, hipMemcpyDeviceToHost, ex.stream));
+    uint64_t cut = (uint64_t)n_bytes;
+    if (!slab.last) HIP_CHECK(hipMemcpyAsync(&cut, starts + n_records, 8, hipMemcpyDeviceToHost, ex.stream));  // behind the last complete record
+    if (!utf8.empty()) HIP_CHECK(hipMemcpyAsync(host_totals.data(), totals_str, n_slots * 8, hipMemcpyDeviceToHost, ex.stream));
     HIP_CHECK(hipMemcpyAsync(host_flags, flags, 8, hipMemcpyDeviceToHost, ex.stream));
     HIP_CHECK(hipStreamSynchronize(ex.stream));
     if (host_flags[0] & CSV_ERR_STRAY_QUOTE)
@@ -151,7 +183,7 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
     if (host_flags[0] & TBL_ERR_BAD_VALUE) fail(BHIP_EEXEC, "csv: a field is not a value of its column's type");
     if (host_flags[0] & CSV_ERR_NULL) fail(BHIP_EEXEC, "csv: an empty field in a column that is not nullable");
     if (host_flags[0] & TBL_ERR_PRECISION) fail(BHIP_ENOTIMPL, "csv: a decimal with more than 15 significant digits");
-    for (size_t s = 0; s < proj.size(); ++s)
+    for (size_t s = 0; s < n_slots; ++s)
         if (!(host_flags[1] >> s & 1u)) batch->cols[s].validity.reset();        // no NULL occurred: no validity buffer
     for (size_t s : utf8) {
         if (host_totals[s] > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
@@ -162,7 +194,7 @@ BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_
                                           c.data->as<uint8_t>()));
     }
     HIP_CHECK(hipStreamSynchronize(ex.stream));
-    return batch;
+    return TextParsed{batch, (int64_t)cut};
 }
 
 }  // namespace bhip

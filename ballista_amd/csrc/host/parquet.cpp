@@ -315,6 +315,10 @@ int decode_threads() {
 
 }  // namespace
 
+// the same blocks for other host-side readers (text_stream.cpp: the slab ring of the text scan)
+void* pinned_host_alloc(size_t bytes) { return pinned_alloc(bytes); }
+void pinned_host_free(void* p, size_t bytes) { pinned_free(p, bytes); }
+
 class ParquetExec : public ExecutionPlan {
 public:
     ParquetExec(ContextPtr ctx, std::vector<std::string> files, std::vector<uint32_t> projection, bool has_projection, int num_partitions) {

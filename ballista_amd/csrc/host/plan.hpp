@@ -282,6 +282,11 @@ private:
 // ParquetExec (parquet.cpp): one partition per chunk of files, one batch per row group
 PlanPtr make_parquet_exec(const ContextPtr& ctx, const std::vector<std::string>& files, const std::vector<uint32_t>& projection, bool has_projection,
                           int num_partitions);
+// CsvExec on the device (text_stream.cpp): one partition per file, each file streamed through the `.tbl` / CSV scan in slabs of
+// `slab_bytes` of text (0: BHIP_TEXT_SLAB_MB, else 64 MiB), one batch per slab.  ctx may be null (inspection only).
+PlanPtr make_text_scan_exec(const ContextPtr& ctx, std::string path, std::vector<std::string> files, SchemaPtr file_schema,
+                            std::vector<uint32_t> projection, bool has_projection, int format, uint8_t delimiter, bool has_header,
+                            int64_t slab_bytes);
 // the wire plan (proto.cpp): protobuf PhysicalPlanNode -> operator tree; ctx may be null (inspection only)
 PlanPtr plan_from_proto(const ContextPtr& ctx, const void* bytes, size_t len, bhip_leaf_resolver resolver, void* user);
 ExprPtr expr_from_proto(const void* bytes, size_t len);

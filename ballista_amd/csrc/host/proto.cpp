@@ -514,125 +514,6 @@ private:
     int partitions_;
 };
 
-// CsvExec over TPC-H `.tbl` text, parsed on the device: one partition per file (CsvExec::try_new(path, options, projection,
-// batch_size), from_proto.rs:93-110; the files of a directory in name order, as DataFusion lists them)
-class TblScanExec : public ExecutionPlan {
-public:
-    TblScanExec(ContextPtr ctx, std::string path, std::vector<std::string> files, SchemaPtr file_schema, std::vector<uint32_t> proj,
-                bool has_proj)
-        : path_(std::move(path)), files_(std::move(files)), file_schema_(std::move(file_schema)), proj_(std::move(proj)), has_proj_(has_proj) {
-        ctx_ = std::move(ctx);
-        schema_ = project_schema(file_schema_, proj_, has_proj_);
-    }
-    const char* name() const override { return "CsvExec"; }
-    SchemaPtr schema() const override { return schema_; }
-    Partitioning output_partitioning() const override { return Partitioning{BHIP_PART_UNKNOWN, (int)std::max<size_t>(1, files_.size()), {}}; }
-    std::vector<PlanPtr> children() const override { return {}; }
-    PlanPtr with_new_children(const std::vector<PlanPtr>& c) const override {
-        if (!c.empty()) fail(BHIP_EINVAL, "CsvExec has no children");
-        return shared_from_this();
-    }
-    std::string describe() const override {
-        std::string s = "CsvExec: path=" + path_ + ", delimiter='|', device scan, projection=[";
-        for (size_t i = 0; i < schema_->fields.size(); ++i) s += (i ? ", " : "") + schema_->fields[i].name;
-        return s + "], files=" + std::to_string(files_.size());
-    }
-    StreamPtr execute(int partition, const Exec& ex) const override {
-        check_partition(*this, partition);
-        auto self = std::static_pointer_cast<const TblScanExec>(shared_from_this());
-        return StreamPtr(new LazyStream(schema_, [self, partition, ex]() -> std::vector<BatchPtr> {
-            if (self->files_.empty()) return {};
-            const std::string& fn = self->files_[partition];
-            std::ifstream in(fn, std::ios::binary | std::ios::ate);
-            if (!in) fail(BHIP_EEXEC, "Ballista Error: cannot open " + fn);
-            const std::streamsize n = in.tellg();
-            if (n >= (std::streamsize)0xFFFF0000ll) fail(BHIP_ENOTIMPL, fn + ": files of 4 GiB and more need a chunked reader");
-            std::string text((size_t)n, '\0');
-            in.seekg(0);
-            if (n && !in.read(&text[0], n)) fail(BHIP_EEXEC, "Ballista Error: cannot read " + fn);
-            std::vector<bhip_column_desc> fields(self->file_schema_->fields.size());
-            for (size_t i = 0; i < fields.size(); ++i) {
-                memset(&fields[i], 0, sizeof(fields[i]));
-                fields[i].name = self->file_schema_->fields[i].name.c_str();
-                fields[i].dtype = self->file_schema_->fields[i].dtype;
-                fields[i].nullable = self->file_schema_->fields[i].nullable;
-            }
-            std::vector<int32_t> proj(self->proj_.begin(), self->proj_.end());
-            BatchPtr b = batch_from_tbl(ex.ctx, text.data(), (int64_t)text.size(), (int)fields.size(), fields.data(),
-                                        self->has_proj_ ? (int)proj.size() : 0, self->has_proj_ ? proj.data() : nullptr);
-            return {b};
-        }));
-    }
-private:
-    std::string path_;
-    std::vector<std::string> files_;
-    SchemaPtr file_schema_, schema_;
-    std::vector<uint32_t> proj_;
-    bool has_proj_;
-};
-
-// CsvExec over general CSV text (the delimiter and has_header of the wire plan, quoted fields, NULLs), parsed on the device: one
-// partition per file, listed as TblScanExec lists them
-class CsvScanExec : public ExecutionPlan {
-public:
-    CsvScanExec(ContextPtr ctx, std::string path, std::vector<std::string> files, SchemaPtr file_schema, std::vector<uint32_t> proj,
-                bool has_proj, uint8_t delimiter, bool has_header)
-        : path_(std::move(path)), files_(std::move(files)), file_schema_(std::move(file_schema)), proj_(std::move(proj)), has_proj_(has_proj),
-          delimiter_(delimiter), has_header_(has_header) {
-        ctx_ = std::move(ctx);
-        schema_ = project_schema(file_schema_, proj_, has_proj_);
-    }
-    const char* name() const override { return "CsvExec"; }
-    SchemaPtr schema() const override { return schema_; }
-    Partitioning output_partitioning() const override { return Partitioning{BHIP_PART_UNKNOWN, (int)std::max<size_t>(1, files_.size()), {}}; }
-    std::vector<PlanPtr> children() const override { return {}; }
-    PlanPtr with_new_children(const std::vector<PlanPtr>& c) const override {
-        if (!c.empty()) fail(BHIP_EINVAL, "CsvExec has no children");
-        return shared_from_this();
-    }
-    std::string describe() const override {
-        std::string s = "CsvExec: path=" + path_ + ", delimiter='" + std::string(1, (char)delimiter_) + "', has_header=" +
-                        (has_header_ ? "true" : "false") + ", device scan, projection=[";
-        for (size_t i = 0; i < schema_->fields.size(); ++i) s += (i ? ", " : "") + schema_->fields[i].name;
-        return s + "], files=" + std::to_string(files_.size());
-    }
-    StreamPtr execute(int partition, const Exec& ex) const override {
-        check_partition(*this, partition);
-        auto self = std::static_pointer_cast<const CsvScanExec>(shared_from_this());
-        return StreamPtr(new LazyStream(schema_, [self, partition, ex]() -> std::vector<BatchPtr> {
-            if (self->files_.empty()) return {};
-            const std::string& fn = self->files_[partition];
-            std::ifstream in(fn, std::ios::binary | std::ios::ate);
-            if (!in) fail(BHIP_EEXEC, "Ballista Error: cannot open " + fn);
-            const std::streamsize n = in.tellg();
-            if (n >= (std::streamsize)0xFFFF0000ll) fail(BHIP_ENOTIMPL, fn + ": files of 4 GiB and more need a chunked reader");
-            std::string text((size_t)n, '\0');
-            in.seekg(0);
-            if (n && !in.read(&text[0], n)) fail(BHIP_EEXEC, "Ballista Error: cannot read " + fn);
-            std::vector<bhip_column_desc> fields(self->file_schema_->fields.size());
-            for (size_t i = 0; i < fields.size(); ++i) {
-                memset(&fields[i], 0, sizeof(fields[i]));
-                fields[i].name = self->file_schema_->fields[i].name.c_str();
-                fields[i].dtype = self->file_schema_->fields[i].dtype;
-                fields[i].nullable = self->file_schema_->fields[i].nullable;
-            }
-            std::vector<int32_t> proj(self->proj_.begin(), self->proj_.end());
-            const bhip_csv_opts opts{self->delimiter_, self->has_header_ ? 1 : 0};
-            BatchPtr b = batch_from_csv(ex.ctx, text.data(), (int64_t)text.size(), (int)fields.size(), fields.data(),
-                                        self->has_proj_ ? (int)proj.size() : 0, self->has_proj_ ? proj.data() : nullptr, opts);
-            return {b};
-        }));
-    }
-private:
-    std::string path_;
-    std::vector<std::string> files_;
-    SchemaPtr file_schema_, schema_;
-    std::vector<uint32_t> proj_;
-    bool has_proj_;
-    uint8_t delimiter_;
-    bool has_header_;
-};
-
 namespace {
 
 std::vector<std::string> list_files(const std::string& path, const std::string& ext) {
@@ -751,18 +632,17 @@ struct Decoder {
                 return p;
             }
         }
-        if (L.kind == BHIP_LEAF_CSV_SCAN && ctx && L.delimiter == "|" && !L.has_header) {
+        // CsvExec over local files, parsed on the device (text_stream.cpp): '|' without a header is the `.tbl` scan, every other
+        // one-byte delimiter / header combination the general CSV scan (a delimiter the scan refuses stays unresolved).  One
+        // partition per file (CsvExec::try_new(path, options, projection, batch_size), from_proto.rs:93-110; the files of a
+        // directory in name order, as DataFusion lists them), one batch per slab of text: batch_size is not used.
+        if (L.kind == BHIP_LEAF_CSV_SCAN && L.file_schema && L.delimiter.size() == 1 && L.delimiter != "\"" && L.delimiter != "\n" &&
+            L.delimiter != "\r") {
             std::vector<std::string> files = L.filenames.empty() ? list_files(L.path, L.file_extension) : L.filenames;
             if (!files.empty() || L.path.compare(0, 6, "mem://") != 0)
-                return std::make_shared<TblScanExec>(ctx, L.path, files, L.file_schema, L.projection, L.has_projection);
-        }
-        // every other one-byte delimiter / header combination: the general CSV scan (a delimiter the scan refuses stays unresolved)
-        if (L.kind == BHIP_LEAF_CSV_SCAN && ctx && L.delimiter.size() == 1 && L.delimiter != "\"" && L.delimiter != "\n" &&
-            L.delimiter != "\r" && !(L.delimiter == "|" && !L.has_header)) {
-            std::vector<std::string> files = L.filenames.empty() ? list_files(L.path, L.file_extension) : L.filenames;
-            if (!files.empty() || L.path.compare(0, 6, "mem://") != 0)
-                return std::make_shared<CsvScanExec>(ctx, L.path, files, L.file_schema, L.projection, L.has_projection,
-                                                     (uint8_t)L.delimiter[0], L.has_header);
+                return make_text_scan_exec(ctx, L.path, files, L.file_schema, L.projection, L.has_projection,
+                                           L.delimiter == "|" && !L.has_header ? BHIP_TEXT_TBL : BHIP_TEXT_CSV, (uint8_t)L.delimiter[0],
+                                           L.has_header, 0);
         }
         if (L.kind == BHIP_LEAF_PARQUET_SCAN) {
             // the file schema is not part of the wire plan: it is read from the files' footers, so this leaf needs the files —

@@ -7,17 +7,17 @@
 #include "../tbl_kernels.h"
 #include "../util_kernels.h"
 #include "core.hpp"
+#include "text_scan.hpp"
 
 namespace bhip {
 
-BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
-                        int n_proj, const int32_t* projection) {
-    if (n_bytes < 0 || n_bytes > 0xFFFFFFF0ll) fail(BHIP_EINVAL, "tbl text must be < 4 GiB per call (split the file on line boundaries)");
+void fail_record_too_long(const char* what) {
+    fail(BHIP_ENOTIMPL, std::string(what) + ": a record does not end within the carry (one slab at most) plus one slab: it is longer "
+                        "than the slab (raise slab_bytes / BHIP_TEXT_SLAB_MB), or a quoted field is not closed");
+}
+
+TblScanSpec make_tbl_spec(int n_fields, const bhip_column_desc* fields, int n_proj, const int32_t* projection) {
     if (n_fields < 1 || n_fields > TBL_MAX_FIELDS) fail(BHIP_EINVAL, "tbl schema must have 1.." + std::to_string(TBL_MAX_FIELDS) + " fields");
-    if (n_bytes > 0 && !text_host) fail(BHIP_EINVAL, "tbl text is null");
-    ctx->set_device();
-    Exec ex{ctx, nullptr};
-    const LaunchCfg cfg = ex.cfg();
 
     // which fields to materialise, in which order
     std::vector<int> proj;
@@ -29,7 +29,8 @@ BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_
     } else {
         for (int i = 0; i < n_fields; ++i) proj.push_back(i);
     }
-    TblPlan plan;
+    TblScanSpec spec;
+    TblPlan& plan = spec.plan;
     memset(&plan, 0, sizeof(plan));
     plan.n_fields = n_fields;
     int last_needed = -1;
@@ -48,17 +49,44 @@ BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_
         if (plan.out[f] >= 0) fail(BHIP_EINVAL, std::string("tbl projection names a field twice: ") + fields[f].name);
         plan.out[f] = (int)s;
         schema->fields.push_back(Field{fields[f].name, dt, fields[f].nullable != 0});
+        spec.dtype.push_back(dt);
         if (f > last_needed) last_needed = f;
     }
     plan.n_fields = last_needed + 1;                     // fields behind the last projected one are never walked
+    spec.schema = schema;
+    return spec;
+}
 
-    auto batch = std::make_shared<Batch>();
-    batch->ctx = ctx;
-    batch->schema = schema;
+BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
+                        int n_proj, const int32_t* projection) {
+    if (n_bytes < 0 || n_bytes > 0xFFFFFFF0ll) fail(BHIP_EINVAL, "tbl text must be < 4 GiB per call (split the file on line boundaries)");
+    const TblScanSpec spec = make_tbl_spec(n_fields, fields, n_proj, projection);
+    if (n_bytes > 0 && !text_host) fail(BHIP_EINVAL, "tbl text is null");
+    ctx->set_device();
+    Exec ex{ctx, nullptr};
 
     Temp tmp(ex);
     uint8_t* text = tmp.get<uint8_t>((size_t)n_bytes + 64);
     if (n_bytes) HIP_CHECK(hipMemcpyAsync(text, text_host, (size_t)n_bytes, hipMemcpyHostToDevice, ex.stream));
+    TextSlab slab;
+    slab.text = text;
+    slab.n_bytes = n_bytes;
+    slab.unterminated = n_bytes > 0 && static_cast<const uint8_t*>(text_host)[n_bytes - 1] != '\n';
+    return parse_tbl_slab(ex, spec, slab).batch;
+}
+
+TextParsed parse_tbl_slab(const Exec& ex, const TblScanSpec& spec, const TextSlab& slab) {
+    const LaunchCfg cfg = ex.cfg();
+    const uint8_t* text = slab.text;
+    const int64_t n_bytes = slab.n_bytes;
+    TblPlan plan = spec.plan;
+    const size_t n_slots = spec.dtype.size();
+
+    auto batch = std::make_shared<Batch>();
+    batch->ctx = ex.ctx;
+    batch->schema = spec.schema;
+
+    Temp tmp(ex);
 
     // ---- lines
     const int64_t n_chunks = (n_bytes + TBL_CHUNK - 1) / TBL_CHUNK;
@@ -72,25 +100,32 @@ BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_
         HIP_CHECK(exclusive_scan_u32_u64(ex.stream, chunk_lines, n_chunks, chunk_base, false, total, scan_tmp));
         n_newlines = (int64_t)read_device(ex, total);
     }
-    const bool unterminated = n_bytes > 0 && static_cast<const uint8_t*>(text_host)[n_bytes - 1] != '\n';
+    // a slab that is not the last yields its complete lines only; what lies behind the last newline is the next slab's carry
+    const bool unterminated = slab.last && slab.unterminated;
     const int64_t n_lines = n_newlines + (unterminated ? 1 : 0);
     if (n_lines > 0xFFFFFFF0ll) fail(BHIP_EINVAL, "tbl text holds more than 2^32-16 lines");
+    if (!slab.last && n_lines == 0) return TextParsed{nullptr, slab.first_record};       // no record ends here: all of it is carry
     batch->n_rows = n_lines;
 
     uint64_t* starts = tmp.get<uint64_t>((size_t)n_lines + 2);
     if (n_lines) {
-        const uint64_t zero = 0, end = (uint64_t)n_bytes + 1;          // an unterminated last line "ends" one past the text
-        HIP_CHECK(hipMemcpyAsync(starts, &zero, 8, hipMemcpyHostToDevice, ex.stream));
+        FillMany fill;                                          // the two ends the line pass does not write (values < 2^32)
+        fill.add(starts, 4, (uint32_t)slab.first_record);
+        fill.add(reinterpret_cast<uint32_t*>(starts) + 1, 4, 0);
+        if (unterminated) {                                     // an unterminated last line "ends" one past the text
+            fill.add(starts + n_lines, 4, (uint32_t)(n_bytes + 1));
+            fill.add(reinterpret_cast<uint32_t*>(starts + n_lines) + 1, 4, 0);
+        }
+        HIP_CHECK(launch_fill_many(cfg, fill));
         HIP_CHECK(launch_tbl_starts(cfg, text, n_bytes, chunk_base, starts));
-        if (unterminated) HIP_CHECK(hipMemcpyAsync(starts + n_lines, &end, 8, hipMemcpyHostToDevice, ex.stream));
     }
 
     // ---- values
     uint32_t* flags = tmp.get<uint32_t>(2);
     HIP_CHECK(hipMemsetAsync(flags, 0, 8, ex.stream));
-    std::vector<uint32_t*> lens(proj.size(), nullptr);
-    for (size_t s = 0; s < proj.size(); ++s) {
-        const int dt = fields[proj[s]].dtype;
+    std::vector<uint32_t*> lens(n_slots, nullptr);
+    for (size_t s = 0; s < n_slots; ++s) {
+        const int dt = spec.dtype[s];
         Column c;
         c.dtype = dt;
         c.length = n_lines;
@@ -107,17 +142,19 @@ BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_
     HIP_CHECK(launch_tbl_parse(cfg, text, starts, n_lines, n_bytes, plan, flags));
 
     // ---- strings: lengths -> offsets -> bytes; all totals in one read-back
-    uint64_t* totals = tmp.get<uint64_t>(proj.size() + 1);
+    uint64_t* totals = tmp.get<uint64_t>(n_slots + 1);
     std::vector<size_t> utf8;
-    for (size_t s = 0; s < proj.size(); ++s)
+    for (size_t s = 0; s < n_slots; ++s)
         if (lens[s]) {
             void* st = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_lines > 0 ? n_lines : 1));
             HIP_CHECK(exclusive_scan_u32_i32(ex.stream, lens[s], n_lines, batch->cols[s].offsets->as<int32_t>(), true, totals + s, st));
             utf8.push_back(s);
         }
-    std::vector<uint64_t> host_totals(proj.size() + 1, 0);
+    std::vector<uint64_t> host_totals(n_slots + 1, 0);
     uint32_t host_flags = 0;
-    if (!utf8.empty()) HIP_CHECK(hipMemcpyAsync(host_totals.data(), totals, proj.size() * 8, hipMemcpyDeviceToHost, ex.stream));
+    uint64_t cut = (uint64_t)n_bytes;
+    if (!slab.last) HIP_CHECK(hipMemcpyAsync(&cut, starts + n_lines, 8, hipMemcpyDeviceToHost, ex.stream));    // behind the last complete line
+    if (!utf8.empty()) HIP_CHECK(hipMemcpyAsync(host_totals.data(), totals, n_slots * 8, hipMemcpyDeviceToHost, ex.stream));
     HIP_CHECK(hipMemcpyAsync(&host_flags, flags, 4, hipMemcpyDeviceToHost, ex.stream));
     HIP_CHECK(hipStreamSynchronize(ex.stream));
     if (host_flags & TBL_ERR_MISSING_FIELD) fail(BHIP_EEXEC, "tbl: a line has fewer fields than the schema");
@@ -132,7 +169,7 @@ BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_
         HIP_CHECK(launch_tbl_copy_strings(cfg, text, plan.str_start[s], lens[s], c.offsets->as<int32_t>(), n_lines, c.data->as<uint8_t>()));
     }
     HIP_CHECK(hipStreamSynchronize(ex.stream));
-    return batch;
+    return TextParsed{batch, (int64_t)cut};
 }
 
 }  // namespace bhip

@@ -11,6 +11,7 @@ describe plans and move batches across the boundary.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -729,6 +730,51 @@ class ParquetExec(ExecutionPlan):
                                           proj if projection is not None else None, num_partitions, C.byref(h)))
         super().__init__(h, ctx)
         self.filenames, self.projection = list(filenames), projection
+
+
+TEXT_SLAB_MIN, TEXT_SLAB_MAX, TEXT_SLAB_STEP, TEXT_SLAB_DEFAULT = 16 << 10, 2 << 30, 16 << 10, 64 << 20
+
+
+class CsvExec(ExecutionPlan):
+    """CsvExec::try_new(path, options, projection, batch_size)  (from_proto.rs:93-110) on the device, over files of any size
+    (bhip_plan_text_scan): one partition per file, each file streamed in slabs of `slab_bytes` of text, one batch per slab;
+    concatenated, the batches are what RecordBatch.from_csv / from_tbl give on the whole text.  schema: [(name, dtype)] or
+    [(name, dtype, nullable)] of the file's fields in order; columns: names to materialise, in output order (None: all);
+    tbl=True: TPC-H `.tbl` text ('|', no header: delimiter and has_header are not used).  slab_bytes: a multiple of 16 KiB in
+    [16 KiB, 2 GiB]; 0: BHIP_TEXT_SLAB_MB of the environment, else 64 MiB.  A record must fit one slab."""
+
+    def __init__(self, ctx: Context, paths: Sequence[str], schema, columns: Optional[Sequence[str]] = None, delimiter=",",
+                 has_header: bool = True, tbl: bool = False, slab_bytes: int = 0):
+        if isinstance(paths, (str, bytes)):
+            paths = [paths]
+        delim = b"|" if tbl else (delimiter.encode() if isinstance(delimiter, str) else bytes(delimiter))
+        if len(delim) != 1:
+            raise L.PlanError(L.EINVAL, f"csv delimiter must be one byte, got {delimiter!r}")
+        slab_bytes = int(slab_bytes)
+        if slab_bytes != 0 and (slab_bytes < TEXT_SLAB_MIN or slab_bytes > TEXT_SLAB_MAX or slab_bytes % TEXT_SLAB_STEP):
+            raise L.PlanError(L.EINVAL, f"slab_bytes = {slab_bytes}: a slab is a multiple of 16 KiB between 16 KiB and 2 GiB")
+        if not paths:
+            raise L.PlanError(L.EINVAL, "CsvExec without a file")
+        descs, keep = [], []
+        for name, dtype, *nullable in schema:
+            d = L.ColumnDesc()
+            nb = name.encode()
+            keep.append(nb)
+            d.name, d.dtype, d.nullable = nb, DTYPE_ID[dtype], 1 if nullable and nullable[0] else 0
+            descs.append(d)
+        arr = (L.ColumnDesc * max(1, len(descs)))(*descs)
+        proj, n_proj = None, 0
+        if columns is not None:
+            names = [f[0] for f in schema]
+            idx = [names.index(c) for c in columns]
+            proj = (C.c_int32 * max(1, len(idx)))(*idx)
+            n_proj = len(idx)
+        files = (C.c_char_p * len(paths))(*[os.fsencode(f) for f in paths])
+        opts = L.TextScanOpts(L.TEXT_TBL if tbl else L.TEXT_CSV, L.CsvOpts(delim[0], 0 if tbl else (1 if has_header else 0)), slab_bytes)
+        h = C.c_void_p()
+        L.check(L.lib().bhip_plan_text_scan(ctx._h, len(paths), files, len(descs), arr, n_proj, proj, C.byref(opts), C.byref(h)))
+        super().__init__(h, ctx)
+        self.paths, self.columns, self.slab_bytes = list(paths), columns, slab_bytes
 
 
 class FilterExec(ExecutionPlan):

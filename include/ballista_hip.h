@@ -141,7 +141,7 @@ bhip_status bhip_batch_from_device(bhip_ctx* ctx, int32_t n_cols, const bhip_col
 /* Scan leaf for TPC-H `.tbl` text — where the reference has CsvExec(delimiter '|', no header, explicit schema):
  * rust/benchmarks/tpch/src/main.rs:129-150, rust/core/src/serde/physical_plan/from_proto.rs:93-110.
  * `text` (host memory, < 4 GiB, whole lines) is copied to the device once; lines, fields and values are found
- * there.  fields[i].name / .dtype / .nullable describe the file's fields in order (data pointers unused);
+ * there.  A file of any size goes through bhip_plan_text_scan, which streams it in slabs.  fields[i].name / .dtype / .nullable describe the file's fields in order (data pointers unused);
  * `projection` = indices of the fields to materialise, in output order (NULL: all).  Int32, Int64, Float64
  * ([-]digits[.digits], converted exactly), Date32 (YYYY-MM-DD) and Utf8 columns.  Malformed text -> BHIP_EEXEC;
  * decimals beyond 15 significant digits or other column types -> BHIP_ENOTIMPL (keep the CPU reader). */
@@ -159,7 +159,8 @@ bhip_status bhip_batch_from_tbl(bhip_ctx* ctx, const void* text, int64_t n_bytes
  * column it is the empty string.  A column in which no NULL occurred carries no validity buffer.  Fewer fields than
  * the schema, a blank line, a malformed value -> BHIP_EEXEC.  A '"' inside an unquoted field, bytes between a
  * closing quote and the next delimiter, a '\r' that is not part of a record end, an unclosed quote: CSV readers
- * disagree on these -> BHIP_ENOTIMPL (keep the CPU reader).  Text < 4 GiB per call. */
+ * disagree on these -> BHIP_ENOTIMPL (keep the CPU reader).  Text < 4 GiB per call; a file of any size goes through
+ * bhip_plan_text_scan. */
 typedef struct bhip_csv_opts {
     uint8_t delimiter;        /* e.g. ',' */
     int32_t has_header;       /* != 0: the first record holds column names */
@@ -269,6 +270,27 @@ bhip_status bhip_plan_arrow_streams(bhip_ctx* ctx, int32_t n_partitions, struct 
  * UNCOMPRESSED / SNAPPY; anything else is BHIP_ENOTIMPL. */
 bhip_status bhip_plan_parquet(bhip_ctx* ctx, int32_t n_files, const char* const* paths, int32_t n_projection, const uint32_t* projection,
                               int32_t num_partitions, bhip_plan** out);
+/* CsvExec on the device over files of any size (CsvExec::try_new(path, options, projection, batch_size), from_proto.rs:93-110):
+ * one partition per file, each file streamed through the `.tbl` scan (BHIP_TEXT_TBL: bhip_batch_from_tbl's grammar) or the CSV
+ * scan (BHIP_TEXT_CSV: bhip_batch_from_csv's, with `csv`) in slabs of `slab_bytes` of text, ONE BATCH PER SLAB: a reader thread
+ * fills pinned host buffers while the slab before crosses PCIe and the one before that is parsed.  A slab is cut wherever its
+ * bytes end; the records that end in it form its batch and the rest is carried to the next slab on the device.  Concatenated,
+ * the batches are what the one-shot call gives on the whole text.  slab_bytes: a multiple of 16 KiB in [16 KiB, 2 GiB], or 0 for
+ * the environment's BHIP_TEXT_SLAB_MB (MiB, fractions allowed), else 64 MiB; anything else is BHIP_EINVAL.  The one limit: a
+ * record must fit one slab — a record that does not end within the carry (one slab at most) plus one slab, i.e. not in the
+ * slab it starts in nor in the next one (or a quote that is never closed), is BHIP_ENOTIMPL.  Errors surface at the bhip_stream_next that parses the offending slab, with the file name and the byte offset
+ * of the slab's start; batches before it have been delivered.  The reference's reader cuts batches by rows (batch_size); this
+ * one cuts by bytes of text.  opts NULL: `.tbl`, default slab. */
+#define BHIP_TEXT_TBL 0
+#define BHIP_TEXT_CSV 1
+typedef struct bhip_text_scan_opts {
+    int32_t format;        /* BHIP_TEXT_TBL | BHIP_TEXT_CSV */
+    bhip_csv_opts csv;     /* CSV only */
+    int64_t slab_bytes;    /* 0: default / BHIP_TEXT_SLAB_MB */
+} bhip_text_scan_opts;
+bhip_status bhip_plan_text_scan(bhip_ctx* ctx, int32_t n_files, const char* const* paths, int32_t n_fields,
+                                const bhip_column_desc* fields, int32_t n_projection, const int32_t* projection,
+                                const bhip_text_scan_opts* opts, bhip_plan** out);
 bhip_status bhip_plan_empty(bhip_ctx* ctx, int32_t n_cols, const bhip_column_desc* schema, int32_t produce_one_row,
                             bhip_plan** out);
 bhip_status bhip_plan_filter(bhip_plan* input, const bhip_expr* predicate, bhip_plan** out);          /* :81-92  */
@@ -295,8 +317,9 @@ bhip_status bhip_plan_local_limit(bhip_plan* input, int64_t limit, bhip_plan** o
  * rules (compile_expr, :348-364).  Every leaf (CsvScan / ParquetScan / ShuffleReader / UnresolvedShuffle) is offered
  * to `resolve` (may be NULL): it returns BHIP_OK with *out = a plan that produces the leaf's rows (a bhip_plan_memory, a
  * bhip_plan_arrow_stream over a CPU reader ...; ownership of that handle passes to the library), or BHIP_OK with *out = NULL to leave the leaf to the library:
- * a CsvScan over '|'-separated header-less local files becomes the device `.tbl` scan (bhip_batch_from_tbl), a
- * CsvScan over local files with any other one-byte delimiter or a header the device CSV scan (bhip_batch_from_csv), any
+ * a CsvScan over '|'-separated header-less local files becomes the device `.tbl` scan, a CsvScan over local files with
+ * any other one-byte delimiter or a header the device CSV scan (both as bhip_plan_text_scan: files of any size, one batch per
+ * slab; the node's batch_size is not used), any
  * other leaf an operator that describes itself and fails on execute with BHIP_EEXEC
  * (UnresolvedShuffleExec::execute, rust/core/src/execution_plans/unresolved_shuffle.rs:83-90).
  * `ctx` may be NULL when every leaf is left unresolved: the plan can then be inspected (bhip_plan_display, _schema,
