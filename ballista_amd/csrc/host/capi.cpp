@@ -135,7 +135,7 @@ bhip_status bhip_batch_from_tbl(bhip_ctx* ctx, const void* text, int64_t n_bytes
                                 int32_t n_projection, const int32_t* projection, bhip_batch** out) {
     BHIP_API_BEGIN
     need(ctx, "ctx"); need(out, "out"); need(fields, "fields");
-    *out = wrap_batch(batch_from_tbl(ctx->p, text, n_bytes, n_fields, fields, n_projection, projection));
+    *out = wrap_batch(batch_from_text(ctx->p, BHIP_TEXT_TBL, text, n_bytes, n_fields, fields, n_projection, projection, bhip_csv_opts{'|', 0}));
     BHIP_API_END
 }
 
@@ -144,7 +144,7 @@ bhip_status bhip_batch_from_csv(bhip_ctx* ctx, const void* text, int64_t n_bytes
     BHIP_API_BEGIN
     need(ctx, "ctx"); need(out, "out"); need(fields, "fields");
     const bhip_csv_opts o = opts ? *opts : bhip_csv_opts{',', 1};
-    *out = wrap_batch(batch_from_csv(ctx->p, text, n_bytes, n_fields, fields, n_projection, projection, o));
+    *out = wrap_batch(batch_from_text(ctx->p, BHIP_TEXT_CSV, text, n_bytes, n_fields, fields, n_projection, projection, o));
     BHIP_API_END
 }
 

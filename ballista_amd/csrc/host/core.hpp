@@ -250,12 +250,10 @@ using BatchPtr = std::shared_ptr<const Batch>;
 // host <-> device movement
 BatchPtr batch_from_host(const ContextPtr& ctx, int n_cols, const bhip_column_desc* cols, int64_t n_rows, bool device_ptrs);
 void column_to_host(const Batch& b, int i, void* data, int32_t* offsets, uint8_t* validity);
-// '|'-separated TPC-H text (host memory) -> device batch of the projected fields (tbl.cpp, kernels_tbl.hip)
-BatchPtr batch_from_tbl(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
-                        int n_proj, const int32_t* projection);
-// general CSV text (any one-byte delimiter, quoted fields, NULLs, optional header) -> device batch (csv.cpp, kernels_csv.hip)
-BatchPtr batch_from_csv(const ContextPtr& ctx, const void* text_host, int64_t n_bytes, int n_fields, const bhip_column_desc* fields,
-                        int n_proj, const int32_t* projection, const bhip_csv_opts& opts);
+// text in host memory -> device batch of the projected fields (text_scan.cpp).  BHIP_TEXT_TBL: '|'-separated TPC-H text
+// (kernels_tbl.hip); BHIP_TEXT_CSV: any one-byte delimiter, quoted fields, NULLs, optional header (kernels_csv.hip, csv_opts)
+BatchPtr batch_from_text(const ContextPtr& ctx, int format, const void* text_host, int64_t n_bytes, int n_fields,
+                         const bhip_column_desc* fields, int n_proj, const int32_t* projection, const bhip_csv_opts& csv_opts);
 
 // pinned host blocks from a process-wide pool, pageable memory when no pinned memory is left (parquet.cpp: PinnedPool)
 void* pinned_host_alloc(size_t bytes);

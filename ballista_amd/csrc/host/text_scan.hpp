@@ -1,4 +1,4 @@
-// text_scan.hpp — the two text scans (tbl.cpp, csv.cpp) as functions over text that is already on the device, so that the
+// text_scan.hpp — the `.tbl` and CSV scans (text_scan.cpp) as one function over text that is already on the device, so that the
 // one-shot entry points (bhip_batch_from_tbl / _csv: the whole text in one call) and the slab pipeline of the scan leaf
 // (text_stream.cpp: a file of any size, one batch per slab) run the same passes.
 #pragma once
@@ -29,26 +29,23 @@ struct TextParsed {
     int64_t cut = 0;
 };
 
-struct TblScanSpec {
-    TblPlan plan;                   // field walk; the per-slot pointers are filled per slab
-    SchemaPtr schema;
-    std::vector<int> dtype;         // [slot]
-};
-struct CsvScanSpec {
-    CsvPlan plan;
+// what one scan reads: the schema and the projection, validated once.  The plan structs are the kernels' own arguments (both are
+// filled, the format's own is used); their per-slot pointers are filled per slab.
+struct TextScanSpec {
+    int format = BHIP_TEXT_TBL;     // BHIP_TEXT_TBL | BHIP_TEXT_CSV
+    TblPlan tbl;                    // field walk
+    CsvPlan csv;                    // ... with the delimiter and which fields may be NULL
     SchemaPtr schema;
     std::vector<int> dtype;         // [slot]
     std::vector<char> nullable;     // [slot]
 };
-// validate the schema and the projection (BHIP_EINVAL / BHIP_ENOTIMPL as the one-shot entry points report them)
-TblScanSpec make_tbl_spec(int n_fields, const bhip_column_desc* fields, int n_proj, const int32_t* projection);
-CsvScanSpec make_csv_spec(int n_fields, const bhip_column_desc* fields, int n_proj, const int32_t* projection, const bhip_csv_opts& opts);
+// validate the schema and the projection (BHIP_EINVAL / BHIP_ENOTIMPL as the one-shot entry points report them); csv_opts: CSV only
+TextScanSpec make_text_spec(int format, int n_fields, const bhip_column_desc* fields, int n_proj, const int32_t* projection,
+                            const bhip_csv_opts& csv_opts);
+// the one place that says which bytes cannot separate fields (BHIP_EINVAL); the scan leaf asks when the plan is built
+void check_csv_delimiter(uint8_t delimiter);
 
-// Everything runs on ex.stream; returns once the batch is complete.
-TextParsed parse_tbl_slab(const Exec& ex, const TblScanSpec& spec, const TextSlab& slab);
-TextParsed parse_csv_slab(const Exec& ex, const CsvScanSpec& spec, const TextSlab& slab);
-
-// a record that does not end inside carry + slab (the stream decides: text_stream.cpp)
-[[noreturn]] void fail_record_too_long(const char* what);
+// records -> starts -> columns -> parse -> strings -> read-back.  Everything runs on ex.stream; returns once the batch is complete.
+TextParsed parse_text_slab(const Exec& ex, const TextScanSpec& spec, const TextSlab& slab);
 
 }  // namespace bhip

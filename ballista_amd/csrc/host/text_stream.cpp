@@ -2,7 +2,7 @@
 // (rust/benchmarks/tpch/src/main.rs:129-150, rust/core/src/serde/physical_plan/from_proto.rs:93-110) as a slab pipeline.
 //
 // A file is cut into slabs of `slab_bytes` of text, wherever those fall.  One reader thread preads slab k + 2 into a ring of
-// pinned host buffers while slab k + 1 crosses PCIe on a copy stream and slab k goes through the passes of tbl.cpp / csv.cpp on
+// pinned host buffers while slab k + 1 crosses PCIe on a copy stream and slab k goes through the passes of text_scan.cpp on
 // the task's stream; events order the three.  A slab yields the records that END in it: what lies behind its last record end
 // (the carry, `cut` of text_scan.hpp) is moved device-to-device in front of the next slab's bytes:
 //
@@ -40,6 +40,12 @@ constexpr int64_t CARRY_ROOM = 1ll << 20;
 constexpr int RING = 3;
 
 int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// a record that does not end inside carry + slab
+[[noreturn]] void fail_record_too_long(const char* what) {
+    fail(BHIP_ENOTIMPL, std::string(what) + ": a record does not end within the carry (one slab at most) plus one slab: it is longer "
+                        "than the slab (raise slab_bytes / BHIP_TEXT_SLAB_MB), or a quoted field is not closed");
+}
 
 void check_slab_bytes(int64_t v, const std::string& what) {
     if (v < SLAB_MIN || v > SLAB_MAX || v % TBL_CHUNK != 0)
@@ -165,8 +171,8 @@ private:
         const std::vector<int32_t> proj(cfg_->proj.begin(), cfg_->proj.end());
         const int n_proj = cfg_->has_proj ? (int)proj.size() : 0;
         const int32_t* projection = cfg_->has_proj ? proj.data() : nullptr;
-        if (cfg_->format == BHIP_TEXT_TBL) tbl_ = make_tbl_spec((int)fields.size(), fields.data(), n_proj, projection);
-        else csv_ = make_csv_spec((int)fields.size(), fields.data(), n_proj, projection, bhip_csv_opts{cfg_->delimiter, cfg_->has_header ? 1 : 0});
+        spec_ = make_text_spec(cfg_->format, (int)fields.size(), fields.data(), n_proj, projection,
+                               bhip_csv_opts{cfg_->delimiter, cfg_->has_header ? 1 : 0});
         // a file that fits one slab needs one buffer of its own size (+ 1: the read that tells the end) and no room for a carry
         const bool one_slab = file_bytes_ < cfg_->slab_bytes;
         slot_bytes_ = one_slab ? align_up(file_bytes_ + 1, 4096) : cfg_->slab_bytes;
@@ -240,7 +246,7 @@ private:
         TextParsed parsed;
         try {
             if (slab.n_bytes > 0xFFFFFFF0ll) fail_record_too_long(what);       // 32-bit offsets in the kernels
-            parsed = cfg_->format == BHIP_TEXT_TBL ? parse_tbl_slab(ex_, tbl_, slab) : parse_csv_slab(ex_, csv_, slab);
+            parsed = parse_text_slab(ex_, spec_, slab);
             // no record ends in the slab: all of it waits for the next one, as long as what waits is no more than one slab
             if (!parsed.batch && slab.n_bytes - parsed.cut > cfg_->slab_bytes) fail_record_too_long(what);
         } catch (const Error& e) {
@@ -296,8 +302,7 @@ private:
     std::shared_ptr<const TextScanConfig> cfg_;
     std::string file_;
     Exec ex_;
-    TblScanSpec tbl_;
-    CsvScanSpec csv_;
+    TextScanSpec spec_;
     bool open_ = false, done_ = false;
     int fd_ = -1;
     int64_t file_bytes_ = 0, slot_bytes_ = 0, carry_room_ = 0;
@@ -378,8 +383,7 @@ PlanPtr make_text_scan_exec(const ContextPtr& ctx, std::string path, std::vector
     cfg->format = format;
     cfg->delimiter = format == BHIP_TEXT_TBL ? (uint8_t)'|' : delimiter;
     cfg->has_header = format == BHIP_TEXT_CSV && has_header;
-    if (cfg->delimiter == '"' || cfg->delimiter == '\n' || cfg->delimiter == '\r')
-        fail(BHIP_EINVAL, "csv delimiter must be one byte other than '\"', '\\n' and '\\r'");
+    check_csv_delimiter(cfg->delimiter);
     cfg->slab_bytes = resolve_slab_bytes(slab_bytes);
     if (!file_schema) fail(BHIP_EINVAL, "text scan without a schema");
     cfg->file_schema = std::move(file_schema);

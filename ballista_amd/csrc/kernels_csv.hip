@@ -12,21 +12,20 @@
 //   3. parse   one thread per record, fields found quote-aware; validity, Boolean and ""-mark bits leave as one ballot word per
 //              wave.
 //   4. copy    Utf8 bytes behind an exclusive scan of the lengths, "" collapsed where marked.
-// The value grammar is the `.tbl` scan's (kernels_tbl.hip) plus Boolean; the conversions are repeated here rather than shared, so
-// that the `.tbl` kernels compile to exactly what they were.  What two CSV readers would read differently (a '"' inside an
+// The value grammar is the `.tbl` scan's (kernels_tbl.hip) plus Boolean.  The LDS staging, the byte readers and the helpers of
+// the conversions are shared with that scan: text_device.h.  What two CSV readers would read differently (a '"' inside an
 // unquoted field, bytes behind a closing quote, a bare '\r') raises CSV_ERR_STRAY_QUOTE: the caller keeps its CPU reader.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "csv_kernels.h"
+#include "text_device.h"
 #include "vm_device.h"
 #include "vm_isa.h"
 
 namespace bhip {
 
-constexpr int CSV_THREAD_BYTES = TBL_CHUNK / BLOCK;      // 64 bytes per thread and chunk
 constexpr int CSV_WAVES = BLOCK / 64;
-constexpr int CSV_PIECES = TBL_CHUNK / (BLOCK * 16);     // 16-byte pieces per thread in the coalesced passes
-static_assert(CSV_THREAD_BYTES == 64, "a thread's bytes are one 64-bit mask");
+static_assert(TEXT_THREAD_BYTES == 64, "a thread's bytes are one 64-bit mask");
 
 // bit b = byte b of `w` equals the byte replicated in `rep`.  Exact: 0x80 is left in every zero byte of x and in no other (the
 // per-byte sum cannot carry into the next byte), and the multiply gathers the four bits without two of them meeting.
@@ -42,14 +41,6 @@ __device__ inline uint32_t lanes_below(uint64_t ballot) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
 }
 
-// 16 bytes at p as four dwords; bytes at and behind n_bytes read as 0: neither a quote nor a newline
-__device__ inline uint4 load_piece(const uint8_t* text, int64_t p, int64_t n_bytes) {
-    if (p + 16 <= n_bytes) return *reinterpret_cast<const uint4*>(text + p);        // text is 256-byte aligned, p a multiple of 16
-    uint32_t w[4] = {0, 0, 0, 0};
-    for (int64_t q = p; q < n_bytes && q < p + 16; ++q) w[(q - p) >> 2] |= (uint32_t)text[q] << (8 * ((q - p) & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // pass 1.  Piece order is text order: (k, wave, lane).  A lane turns its 16 bytes into a quote mask and a newline mask; the prefix
 // XOR of the quote mask is the parity at every byte, counted from the lane's first byte; the lanes before it in the wave (one
 // ballot) flip it.  That leaves one pair of counters per 1 KiB segment, relative to the segment's start; thread 0 chains the 16
@@ -57,15 +48,15 @@ __device__ inline uint4 load_piece(const uint8_t* text, int64_t p, int64_t n_byt
 __global__ void __launch_bounds__(BLOCK)
 csv_count_kernel(const uint8_t* text, int64_t n_bytes, uint32_t* quotes, uint32_t* newlines) {
     __shared__ uint32_t s_quotes, s_odd;
-    __shared__ uint32_t s_seg[CSV_PIECES * CSV_WAVES];           // even | odd << 16 (at most 1024 each)
+    __shared__ uint32_t s_seg[TEXT_PIECES * CSV_WAVES];           // even | odd << 16 (at most 1024 each)
     const int tid = threadIdx.x, wave = tid >> 6;
-    if (tid < CSV_PIECES * CSV_WAVES) s_seg[tid] = 0;
+    if (tid < TEXT_PIECES * CSV_WAVES) s_seg[tid] = 0;
     if (tid == 0) { s_quotes = 0; s_odd = 0; }
     __syncthreads();
     const int64_t chunk0 = (int64_t)blockIdx.x * TBL_CHUNK;
     uint32_t nq = 0;
 #pragma unroll
-    for (int k = 0; k < CSV_PIECES; ++k) {
+    for (int k = 0; k < TEXT_PIECES; ++k) {
         const uint4 v = load_piece(text, chunk0 + ((int64_t)k * BLOCK + tid) * 16, n_bytes);
         const uint32_t qm = eq_mask4(v.x, REP_QUOTE) | eq_mask4(v.y, REP_QUOTE) << 4 | eq_mask4(v.z, REP_QUOTE) << 8 | eq_mask4(v.w, REP_QUOTE) << 12;
         const uint32_t nm = eq_mask4(v.x, REP_NL) | eq_mask4(v.y, REP_NL) << 4 | eq_mask4(v.z, REP_NL) << 8 | eq_mask4(v.w, REP_NL) << 12;
@@ -86,7 +77,7 @@ csv_count_kernel(const uint8_t* text, int64_t n_bytes, uint32_t* quotes, uint32_
     __syncthreads();
     if (tid == 0) {
         uint32_t even = 0, odd = 0, parity = 0;
-        for (int s = 0; s < CSV_PIECES * CSV_WAVES; ++s) {
+        for (int s = 0; s < TEXT_PIECES * CSV_WAVES; ++s) {
             const uint32_t a = s_seg[s] & 0xFFFFu, b = s_seg[s] >> 16;
             even += parity ? b : a;
             odd += parity ? a : b;
@@ -104,8 +95,8 @@ csv_pick_kernel(const uint64_t* quotes_before, const uint32_t* newlines, int64_t
     if (c < n_chunks) records[c] = newlines[2 * c + (int64_t)(quotes_before[c] & 1u)];
 }
 
-// pass 2: the staging of tbl_starts_kernel (rows of 16 dwords padded to 17: the 64 lanes of a wave read 64 different banks); a
-// thread's 64 bytes become a quote mask and a newline mask, and the parity it starts in is
+// pass 2: the staging of tbl_starts_kernel (stage_chunk_rows); a thread's 64 bytes become a quote mask and a newline mask, and
+// the parity it starts in is
 //   chunk (scan of pass 1) ^ waves before it (LDS) ^ lanes before it (ballot + masked popcount).
 __global__ void __launch_bounds__(BLOCK)
 csv_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_before, const uint64_t* chunk_base, uint64_t* starts) {
@@ -114,14 +105,7 @@ csv_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_b
     __shared__ uint32_t s_wave_odd[CSV_WAVES];
     const int tid = threadIdx.x, wave = tid >> 6;
     const int64_t chunk0 = (int64_t)blockIdx.x * TBL_CHUNK;
-#pragma unroll
-    for (int k = 0; k < CSV_PIECES; ++k) {
-        const int piece = k * BLOCK + tid;                       // 16-byte piece of the chunk
-        const uint4 v = load_piece(text, chunk0 + (int64_t)piece * 16, n_bytes);
-        const int row = piece >> 2, col = (piece & 3) * 4;       // row = owning thread (64 bytes = 4 pieces)
-        s_text[row * 17 + col + 0] = v.x; s_text[row * 17 + col + 1] = v.y;
-        s_text[row * 17 + col + 2] = v.z; s_text[row * 17 + col + 3] = v.w;
-    }
+    stage_chunk_rows(s_text, tid, text, chunk0, n_bytes);
     __syncthreads();
     uint64_t qm = 0, nm = 0;
 #pragma unroll
@@ -154,7 +138,7 @@ csv_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_b
     }
     if (c == 0) return;
     uint64_t rank = chunk_base[blockIdx.x] + (s_scan[tid] - c);
-    const int64_t base = chunk0 + (int64_t)tid * CSV_THREAD_BYTES;
+    const int64_t base = chunk0 + (int64_t)tid * TEXT_THREAD_BYTES;
     while (ends) {
         const int b = __ffsll((unsigned long long)ends) - 1;
         starts[++rank] = (uint64_t)(base + b) + 1;
@@ -162,31 +146,10 @@ csv_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_b
     }
 }
 
-__device__ inline int64_t csv_days_from_civil(int64_t y, unsigned m, unsigned d) {
-    y -= m <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const unsigned yoe = (unsigned)(y - era * 400);
-    const unsigned doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
-    const unsigned doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + (int64_t)doe - 719468;
-}
-
-__constant__ double CSV_POW10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
-                                     1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-
-// byte sources of the field walk: the text in HBM, or the records of one workgroup staged in LDS
-struct CsvGlobalReader {
-    const uint8_t* text;
-    __device__ uint8_t operator()(int64_t pos) const { return text[pos]; }
-};
-struct CsvLdsReader {
-    const uint8_t* buf;          // LDS copy of text[origin, origin + ...)
-    int64_t origin;
-    __device__ uint8_t operator()(int64_t pos) const { return buf[pos - origin]; }
-};
-
 // a non-empty value [a, b) of a fixed-width column -> row i of `data`; returns the error flags.  Int32 / Int64 / Float64 / Date32
 // as in kernels_tbl.hip (one exact division for decimals).  A Boolean comes back in `truth`.
+// Everything below the Boolean case is a second copy of the conversion in tbl_parse_line (kernels_tbl.hip) and has to change with
+// it: sharing it changes the code of tbl_parse_kernel, and that version has not been timed on the device (see there).
 template <class R>
 __device__ inline uint32_t csv_convert(const R& rd, int64_t a, int64_t b, int dt, void* data, int64_t i, bool& truth) {
     uint32_t err = 0;
@@ -211,7 +174,7 @@ __device__ inline uint32_t csv_convert(const R& rd, int64_t a, int64_t b, int dt
         if (ok) {
             const int y = v[0] * 1000 + v[1] * 100 + v[2] * 10 + v[3], m = v[4] * 10 + v[5], d = v[6] * 10 + v[7];
             ok = m >= 1 && m <= 12 && d >= 1 && d <= 31;
-            days = (int32_t)csv_days_from_civil(y, (unsigned)m, (unsigned)d);
+            days = (int32_t)days_from_civil(y, (unsigned)m, (unsigned)d);
         }
         if (!ok) err |= TBL_ERR_BAD_VALUE;
         reinterpret_cast<int32_t*>(data)[i] = days;
@@ -241,7 +204,7 @@ __device__ inline uint32_t csv_convert(const R& rd, int64_t a, int64_t b, int dt
     if (dt == DT_FLOAT64) {
         if (!ok) err |= TBL_ERR_BAD_VALUE;
         else if (m >= (1ull << 53) || frac > 22) { err |= TBL_ERR_PRECISION; ok = false; }
-        const double v = ok ? (double)m / CSV_POW10[frac] : 0.0;
+        const double v = ok ? (double)m / TEXT_POW10[frac] : 0.0;
         reinterpret_cast<double*>(data)[i] = neg ? -v : v;
     } else {
         if (!ok || seen_dot) err |= TBL_ERR_BAD_VALUE;
@@ -338,38 +301,26 @@ __device__ inline uint32_t csv_parse_record(const R& rd, bool active, int64_t p,
     return err;
 }
 
-// pass 3: a workgroup takes 256 consecutive records.  Their text is one contiguous span: it is staged in LDS with coalesced
-// 16-byte loads and every thread walks its own record there; a span that does not fit (very long records) is walked in HBM.
+// pass 3: a workgroup takes 256 consecutive records and walks them in LDS (stage_span), or in HBM when they do not fit.
 // Record i0 is a multiple of 256, so wave w of the workgroup owns bitmap word i0 / 64 + w of every column.
-constexpr int CSV_STAGE = 48 * 1024;
 template <bool QUOTED>
 __global__ void __launch_bounds__(BLOCK)
 csv_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_records, int64_t n_bytes, CsvPlan plan, uint32_t* flags) {
-    __shared__ __align__(16) uint8_t s_buf[CSV_STAGE];
+    __shared__ __align__(16) uint8_t s_buf[TEXT_STAGE];
     uint32_t err = 0, null_slots = 0;
     const int tid = threadIdx.x;
     for (int64_t i0 = (int64_t)blockIdx.x * BLOCK; i0 < n_records; i0 += (int64_t)gridDim.x * BLOCK) {
         const int64_t n_here = n_records - i0 < BLOCK ? n_records - i0 : BLOCK;
-        const int64_t span0 = (int64_t)starts[i0] & ~(int64_t)15;                 // 16-byte aligned (the text buffer is)
-        int64_t span1 = (int64_t)starts[i0 + n_here];
-        if (span1 > n_bytes) span1 = n_bytes;
-        const bool staged = span1 - span0 <= CSV_STAGE - 16;       // the copy below moves whole 16-byte pieces
-        if (staged) {
-            for (int64_t k = (int64_t)tid * 16; k < span1 - span0; k += BLOCK * 16) {
-                const int64_t g = span0 + k;
-                if (g + 16 <= n_bytes) *reinterpret_cast<uint4*>(s_buf + k) = *reinterpret_cast<const uint4*>(text + g);
-                else
-                    for (int64_t b = g; b < n_bytes; ++b) s_buf[b - span0] = text[b];
-            }
-        }
+        int64_t span0;
+        const bool staged = stage_span(s_buf, tid, text, starts, i0, n_here, n_bytes, span0);
         __syncthreads();
         const bool active = tid < n_here;
         const int64_t i = i0 + tid;
         const int64_t p = active ? (int64_t)starts[i] : 0;
         const int64_t e = active ? (int64_t)starts[i + 1] - 1 : 0;     // the newline (or one past the text for an unterminated last record)
         const int64_t word = (tid & ~63) < n_here ? (i0 + (tid & ~63)) >> 6 : -1;
-        if (staged) err |= csv_parse_record<QUOTED>(CsvLdsReader{s_buf, span0}, active, p, e, i, word, plan, null_slots);
-        else err |= csv_parse_record<QUOTED>(CsvGlobalReader{text}, active, p, e, i, word, plan, null_slots);
+        if (staged) err |= csv_parse_record<QUOTED>(TextLdsReader{s_buf, span0}, active, p, e, i, word, plan, null_slots);
+        else err |= csv_parse_record<QUOTED>(TextGlobalReader{text}, active, p, e, i, word, plan, null_slots);
         __syncthreads();
     }
     if (err) atomicOr(flags, err);
@@ -396,14 +347,6 @@ csv_copy_strings_kernel(const uint8_t* text, const uint32_t* str_start, const ui
     }
 }
 
-static int csv_grid_rows(const LaunchCfg& cfg, int64_t n) {
-    int64_t g = (n + BLOCK - 1) / BLOCK;
-    const int64_t cap = (int64_t)cfg.device_cus * 16;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 hipError_t launch_csv_count(const LaunchCfg& cfg, const uint8_t* text, int64_t n_bytes, uint32_t* quotes, uint32_t* newlines) {
     const int64_t n_chunks = (n_bytes + TBL_CHUNK - 1) / TBL_CHUNK;
     if (n_chunks == 0) return hipSuccess;
@@ -426,7 +369,7 @@ hipError_t launch_csv_starts(const LaunchCfg& cfg, const uint8_t* text, int64_t 
 hipError_t launch_csv_parse(const LaunchCfg& cfg, const uint8_t* text, const uint64_t* starts, int64_t n_records, int64_t n_bytes,
                             const CsvPlan& plan, bool quoted, uint32_t* flags) {
     if (n_records == 0) return hipSuccess;
-    const dim3 grid(csv_grid_rows(cfg, n_records));
+    const dim3 grid(grid_rows(cfg, n_records));
     if (quoted) hipLaunchKernelGGL(csv_parse_kernel<true>, grid, dim3(BLOCK), 0, cfg.stream, text, starts, n_records, n_bytes, plan, flags);
     else hipLaunchKernelGGL(csv_parse_kernel<false>, grid, dim3(BLOCK), 0, cfg.stream, text, starts, n_records, n_bytes, plan, flags);
     return hipGetLastError();
@@ -434,7 +377,7 @@ hipError_t launch_csv_parse(const LaunchCfg& cfg, const uint8_t* text, const uin
 hipError_t launch_csv_copy_strings(const LaunchCfg& cfg, const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len,
                                    const uint64_t* str_esc, const int32_t* offsets, int64_t n, uint8_t* out) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(csv_copy_strings_kernel, dim3(csv_grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, text, str_start, str_len, str_esc,
+    hipLaunchKernelGGL(csv_copy_strings_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, text, str_start, str_len, str_esc,
                        offsets, n, out);
     return hipGetLastError();
 }

@@ -12,17 +12,17 @@
 //                        division is the correctly rounded value of the decimal text (what str::parse::<f64> returns)
 //        Date32          YYYY-MM-DD -> days since 1970-01-01 (proleptic Gregorian)
 //        Utf8            (offset, length) of the field; a second pass copies the bytes behind an exclusive scan
+// The LDS staging, the byte readers and the helpers of the conversions are shared with the CSV scan: text_device.h.
 // Anything else in the text (exponents, > 15 significant digits, missing fields, blank lines) raises a flag and the
 // host reports BHIP_EEXEC / BHIP_ENOTIMPL: the caller keeps its CPU reader for that file.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "tbl_kernels.h"
+#include "text_device.h"
 #include "vm_device.h"
 #include "vm_isa.h"
 
 namespace bhip {
-
-constexpr int TBL_THREAD_BYTES = TBL_CHUNK / BLOCK;      // 64 bytes per thread and chunk
 
 // newlines among the four bytes of `w` (byte by byte: the subtract-and-mask zero-byte trick can flag a 0x0B byte that
 // sits right above a newline, and these counts must equal the line count exactly)
@@ -59,29 +59,14 @@ tbl_count_kernel(const uint8_t* text, int64_t n_bytes, uint32_t* chunk_lines) {
 }
 
 // pass 2: starts[i] = offset of the first byte of line i (starts[0] = 0 is written by the host).  The chunk is staged
-// in LDS with coalesced 16-byte loads; each thread then owns 64 CONSECUTIVE bytes (rows of 16 dwords padded to 17,
-// so the 64 lanes of a wave read 64 different banks), which keeps the newline ranks in text order.
+// in LDS (stage_chunk_rows); each thread then owns 64 CONSECUTIVE bytes, which keeps the newline ranks in text order.
 __global__ void __launch_bounds__(BLOCK)
 tbl_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* chunk_base, uint64_t* starts) {
     __shared__ uint32_t s_text[BLOCK * 17];
     __shared__ uint32_t s_scan[BLOCK];
     const int tid = threadIdx.x;
     const int64_t chunk0 = (int64_t)blockIdx.x * TBL_CHUNK;
-#pragma unroll
-    for (int k = 0; k < TBL_CHUNK / (BLOCK * 16); ++k) {
-        const int piece = k * BLOCK + tid;                       // 16-byte piece of the chunk
-        const int64_t p = chunk0 + (int64_t)piece * 16;
-        uint4 v = make_uint4(0, 0, 0, 0);                        // bytes past the text read as 0: never a newline
-        if (p + 16 <= n_bytes) v = *reinterpret_cast<const uint4*>(text + p);
-        else {
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (int64_t q = p; q < n_bytes && q < p + 16; ++q) w[(q - p) >> 2] |= (uint32_t)text[q] << (8 * ((q - p) & 3));
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        const int row = piece >> 2, col = (piece & 3) * 4;       // row = owning thread (64 bytes = 4 pieces)
-        s_text[row * 17 + col + 0] = v.x; s_text[row * 17 + col + 1] = v.y;
-        s_text[row * 17 + col + 2] = v.z; s_text[row * 17 + col + 3] = v.w;
-    }
+    stage_chunk_rows(s_text, tid, text, chunk0, n_bytes);          // bytes past the text read as 0: never a newline
     __syncthreads();
     uint32_t c = 0;
 #pragma unroll
@@ -96,7 +81,7 @@ tbl_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* chunk_ba
     }
     if (c == 0) return;
     uint64_t rank = chunk_base[blockIdx.x] + (s_scan[tid] - c);
-    const int64_t base = chunk0 + (int64_t)tid * TBL_THREAD_BYTES;
+    const int64_t base = chunk0 + (int64_t)tid * TEXT_THREAD_BYTES;
     for (int d = 0; d < 16; ++d) {
         const uint32_t w = s_text[tid * 17 + d];
 #pragma unroll
@@ -105,30 +90,11 @@ tbl_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* chunk_ba
     }
 }
 
-__device__ inline int64_t days_from_civil(int64_t y, unsigned m, unsigned d) {
-    y -= m <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const unsigned yoe = (unsigned)(y - era * 400);
-    const unsigned doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
-    const unsigned doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + (int64_t)doe - 719468;
-}
-
-__constant__ double TBL_POW10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
-                                     1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-
-// byte sources of the field walk: the text in HBM, or the lines of one workgroup staged in LDS
-struct TblGlobalReader {
-    const uint8_t* text;
-    __device__ uint8_t operator()(int64_t pos) const { return text[pos]; }
-};
-struct TblLdsReader {
-    const uint8_t* buf;          // LDS copy of text[origin, origin + ...)
-    int64_t origin;
-    __device__ uint8_t operator()(int64_t pos) const { return buf[pos - origin]; }
-};
-
 // one line [p, e): walk the fields, convert the projected ones.  Returns the error flags.
+// The Date32 / Int32 / Int64 / Float64 conversion below is a second copy of csv_convert (kernels_csv.hip) and has to change with
+// it.  It is not shared yet because routing this walk through one conversion function, even with Boolean compiled out, changes
+// the code of tbl_parse_kernel (61 -> 52 VGPRs, most of its instructions reordered), the hottest kernel of the scan, and that
+// version has not been timed on the device (profiles/text_scan_unified.txt).
 template <class R>
 __device__ inline uint32_t tbl_parse_line(const R& rd, int64_t p, int64_t e, int64_t i, const TblPlan& plan) {
     uint32_t err = 0;
@@ -187,7 +153,7 @@ __device__ inline uint32_t tbl_parse_line(const R& rd, int64_t p, int64_t e, int
                 if (dt == DT_FLOAT64) {
                     if (!ok) err |= TBL_ERR_BAD_VALUE;
                     else if (m >= (1ull << 53) || frac > 22) { err |= TBL_ERR_PRECISION; ok = false; }
-                    double v = ok ? (double)m / TBL_POW10[frac] : 0.0;
+                    double v = ok ? (double)m / TEXT_POW10[frac] : 0.0;
                     reinterpret_cast<double*>(plan.data[out])[i] = neg ? -v : v;
                 } else {
                     if (!ok || seen_dot) err |= TBL_ERR_BAD_VALUE;
@@ -207,36 +173,23 @@ __device__ inline uint32_t tbl_parse_line(const R& rd, int64_t p, int64_t e, int
     return err;
 }
 
-// pass 3: a workgroup takes 256 consecutive lines.  Their text is one contiguous span: it is staged in LDS with
-// coalesced 16-byte loads (a thread walking its line byte by byte in HBM issues one dependent load per byte), and
-// every thread then walks its own line in LDS.  A span that does not fit (very long lines) is walked in HBM.
-constexpr int TBL_STAGE = 48 * 1024;
+// pass 3: a workgroup takes 256 consecutive lines and walks them in LDS (stage_span), or in HBM when they do not fit.
 __global__ void __launch_bounds__(BLOCK)
 tbl_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_lines, int64_t n_bytes, TblPlan plan, uint32_t* flags) {
-    __shared__ __align__(16) uint8_t s_buf[TBL_STAGE];
+    __shared__ __align__(16) uint8_t s_buf[TEXT_STAGE];
     uint32_t err = 0;
     const int tid = threadIdx.x;
     for (int64_t i0 = (int64_t)blockIdx.x * BLOCK; i0 < n_lines; i0 += (int64_t)gridDim.x * BLOCK) {
         const int64_t n_here = n_lines - i0 < BLOCK ? n_lines - i0 : BLOCK;
-        const int64_t span0 = (int64_t)starts[i0] & ~(int64_t)15;                 // 16-byte aligned (the text buffer is)
-        int64_t span1 = (int64_t)starts[i0 + n_here];
-        if (span1 > n_bytes) span1 = n_bytes;
-        const bool staged = span1 - span0 <= TBL_STAGE - 16;       // the copy below moves whole 16-byte pieces
-        if (staged) {
-            for (int64_t k = (int64_t)tid * 16; k < span1 - span0; k += BLOCK * 16) {
-                const int64_t g = span0 + k;
-                if (g + 16 <= n_bytes) *reinterpret_cast<uint4*>(s_buf + k) = *reinterpret_cast<const uint4*>(text + g);
-                else
-                    for (int64_t b = g; b < n_bytes; ++b) s_buf[b - span0] = text[b];
-            }
-        }
+        int64_t span0;
+        const bool staged = stage_span(s_buf, tid, text, starts, i0, n_here, n_bytes, span0);
         __syncthreads();
         if (tid < n_here) {
             const int64_t i = i0 + tid;
             const int64_t p = (int64_t)starts[i];
             const int64_t e = (int64_t)starts[i + 1] - 1;       // the newline (or one past the text for an unterminated last line)
-            if (staged) err |= tbl_parse_line(TblLdsReader{s_buf, span0}, p, e, i, plan);
-            else err |= tbl_parse_line(TblGlobalReader{text}, p, e, i, plan);
+            if (staged) err |= tbl_parse_line(TextLdsReader{s_buf, span0}, p, e, i, plan);
+            else err |= tbl_parse_line(TextGlobalReader{text}, p, e, i, plan);
         }
         __syncthreads();
     }
@@ -252,14 +205,6 @@ tbl_copy_strings_kernel(const uint8_t* text, const uint32_t* str_start, const ui
         const uint32_t len = str_len[i];
         for (uint32_t b = 0; b < len; ++b) d[b] = s[b];
     }
-}
-
-static int grid_rows(const LaunchCfg& cfg, int64_t n) {
-    int64_t g = (n + BLOCK - 1) / BLOCK;
-    const int64_t cap = (int64_t)cfg.device_cus * 16;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 hipError_t launch_tbl_count(const LaunchCfg& cfg, const uint8_t* text, int64_t n_bytes, uint32_t* chunk_lines) {

@@ -9,7 +9,8 @@
                                   step that fails ends the run.  Per-kernel times come from `rocprofv3 --kernel-trace --stats` runs
                                   (no counters), three per format, alternating; end-to-end times (text in host memory, copy included)
                                   from unprofiled runs, against pyarrow.csv.read_csv with 16 threads on the text of b.
-  exp_csv.py --other-tree DIR     also alternates format a on another built checkout of this repository (e.g. the parent commit) with this one
+  exp_csv.py --other-tree DIR     also alternates every format on another built checkout of this repository (e.g. the parent commit)
+                                  with this one, and judges this one by the other's own run-to-run spread
   exp_csv.py --out DIR            where the profiler's traces go (default: a fresh temporary directory)
   exp_csv.py scan FORMAT          one child: 4 scans of FORMAT, prints the median end-to-end time as one JSON line
   exp_csv.py cpu                  one child: pyarrow.csv.read_csv on the text of b
@@ -110,8 +111,9 @@ def main():
     os.makedirs(out, exist_ok=True)
     runs = {}
     order = []
-    for k in range(3):                                   # alternating: a, (a on the other build), b, c — three times
-        order += [(f"a{k}", "a", None)] + ([(f"a_other{k}", "a", {"BHIP_EXP_TREE": other})] if other else []) + [(f"b{k}", "b", None), (f"c{k}", "c", None)]
+    for k in range(3):                                   # alternating: a, (a on the other build), b, (b ...), c, (c ...) — three times
+        for fmt in "abc":
+            order += [(f"{fmt}{k}", fmt, None)] + ([(f"{fmt}_other{k}", fmt, {"BHIP_EXP_TREE": other})] if other else [])
     for label, fmt, env in order:
         runs[label] = kernel_times(out, label, fmt, env)
         print(f"{label:9s} " + "  ".join(f"{n} {ms:.3f}" for n, ms in sorted(runs[label].items())) + f"  | sum {sum(runs[label].values()):.3f} ms", flush=True)
@@ -128,10 +130,16 @@ def main():
     for ta, tb in (("tbl_count_kernel", "csv_count_kernel"), ("tbl_starts_kernel", "tbl_starts_kernel"), ("tbl_parse_kernel", "csv_parse_kernel<false>"),
                    ("tbl_copy_strings_kernel", "csv_copy_strings_kernel")):
         print(f"  pass {ta:24s} a {med('a', ta):.3f} ms   b {tb:24s} {med('b', tb):.3f} ms")
-    if other:
-        o_sums = [sum(runs[f"a_other{k}"].values()) for k in range(3)]
-        print(f"format a on the other checkout: runs {', '.join('%.3f' % s for s in o_sums)} ms; this checkout - the other (medians) = "
-              f"{statistics.median(a_sums) - statistics.median(o_sums):+.3f} ms against a spread of {spread:.3f} ms")
+    for fmt in "abc" if other else "":                   # the yardstick is the other checkout's own spread, measured in this run
+        sums = [sum(runs[f"{fmt}{k}"].values()) for k in range(3)]
+        o_sums = [sum(runs[f"{fmt}_other{k}"].values()) for k in range(3)]
+        o_spread = max(o_sums) - min(o_sums)
+        diff = statistics.median(sums) - statistics.median(o_sums)
+        print(f"format {fmt}: this checkout runs {', '.join('%.3f' % s for s in sums)} ms, median {statistics.median(sums):.3f};  the other "
+              f"{', '.join('%.3f' % s for s in o_sums)} ms, median {statistics.median(o_sums):.3f}, spread {o_spread:.3f};  this - the other = "
+              f"{diff:+.3f} ms: {'within' if diff <= o_spread else 'BEYOND'} the other's spread")
+        for n in names(fmt):
+            print(f"    {n:28s} this {med(fmt, n):.3f} ms   the other {med(fmt + '_other', n):.3f} ms")
     print("\nend to end, text in host memory (copy included), profiler off:")
     for fmt in ("a", "b", "c"):
         print(step(f"scan {fmt}", [sys.executable, os.path.abspath(__file__), "scan", fmt], 240).strip().splitlines()[-1], flush=True)
