@@ -108,6 +108,12 @@ const char* bhip_ctx_kernel_variant(bhip_ctx* ctx) {
     return name.c_str();
 }
 
+const char* bhip_ctx_lean_key_form(bhip_ctx* ctx) {
+    static thread_local std::string name;
+    name = ctx ? ctx->p->lean_key_form() : std::string();
+    return name.c_str();
+}
+
 // ---- batches ------------------------------------------------------------------------------------------
 static bhip_batch* wrap_batch(BatchPtr b) {
     auto h = new bhip_batch();
@@ -616,6 +622,7 @@ static Column gen_char_col(const Exec& ex, int64_t n) {
     c.data = make_buffer(ex, (size_t)n + 8);
     c.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
     c.data_bytes = n;
+    c.offsets->set_uniform_width(n, 1);       // the generators write one byte per row
     return c;
 }
 

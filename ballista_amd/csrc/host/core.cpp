@@ -317,6 +317,16 @@ std::string Context::kernel_variant() {
     return k_variant_;
 }
 
+void Context::set_lean_key_form(const char* form) {
+    std::lock_guard<std::mutex> g(mu_);
+    k_key_form_ = form ? form : "";
+}
+
+std::string Context::lean_key_form() {
+    std::lock_guard<std::mutex> g(mu_);
+    return k_key_form_;
+}
+
 void Context::kernel_time(bool reset, double* ms, uint64_t* launches) {
     std::lock_guard<std::mutex> g(mu_);
     if (ms) *ms = k_ms_;

@@ -79,6 +79,10 @@ public:
     void add_kernel_time(double ms, uint64_t launches, const char* kernel = nullptr, const char* variant = nullptr);
     std::string kernel_name();
     std::string kernel_variant();   // instantiation of kernel_name() that ran ("" where the call site names none)
+    // how the last lean scan + aggregate launch (timed or not) read its Utf8 keys: "fixed" (known uniform width, no offsets),
+    // "offsets", or "none" (no Utf8 key); "" before the first one
+    void set_lean_key_form(const char* form);
+    std::string lean_key_form();
     void kernel_time(bool reset, double* ms, uint64_t* launches);
     bool timing_enabled() const { return timing_ > 0; }
     int timing_level() const { return timing_; }
@@ -104,7 +108,7 @@ private:
     bool spin_wait_ = true;
     double k_ms_ = 0;
     uint64_t k_launches_ = 0;
-    std::string k_name_, k_variant_;
+    std::string k_name_, k_variant_, k_key_form_;
     struct PendingTimed { hipEvent_t a, b; const char* name; uint64_t bytes; };
     std::vector<PendingTimed> pending_timed_;
     std::vector<hipEvent_t> event_pool_;
@@ -167,7 +171,24 @@ public:
     bool owned() const { return owned_ || parent_ != nullptr; }
     template <class T> T* as() const { return reinterpret_cast<T*>(ptr_); }
     void set_stream(hipStream_t s) { stream_ = s; }
+    // A fact about a Utf8 OFFSETS buffer, internal to the library (never part of bhip_column_desc): its first `rows` values are all
+    // `w` bytes long, so row i's bytes are data[offsets[0] + i*w, +w).  0: unknown.  It is set by producers that know it by
+    // construction and by the lean scan once it has read every length (ops_agg.cpp); whoever ignores it stays correct, the
+    // offsets are all there.  It lives here because the buffer is what every copy of a column shares and nothing rewrites: a
+    // take, a concatenation, an exchange or a slice builds new buffers, which start unknown.  Atomic: partitions that scan one
+    // column at the same time may learn it at the same time.
+    int32_t uniform_width(int64_t rows) const {
+        const uint64_t f = uniform_.load(std::memory_order_relaxed);
+        return (int64_t)(f >> 32) >= rows ? (int32_t)(f & 0x7FFFFFFFu) : 0;
+    }
+    void set_uniform_width(int64_t rows, int32_t w) {
+        if (w < 1 || rows < 1 || rows > 0xFFFFFFFFll) return;
+        const uint64_t f = ((uint64_t)rows << 32) | (uint32_t)w;
+        uint64_t cur = uniform_.load(std::memory_order_relaxed);
+        while ((cur >> 32) < (uint64_t)rows && !uniform_.compare_exchange_weak(cur, f, std::memory_order_relaxed)) {}
+    }
 private:
+    std::atomic<uint64_t> uniform_{0};
     ContextPtr ctx_;
     void* ptr_;
     size_t bytes_;
@@ -205,6 +226,12 @@ struct Column {
     BufferPtr view_idx;
     bool view_may_null = false;
     bool is_view() const { return (bool)view_base; }
+    // Utf8: the one width of the first `rows` values where it is known (Buffer::uniform_width), else 0.
+    // INVARIANT this rests on: a Column has no row offset — its row i is entry i of `offsets` — and whatever makes a column of
+    // other rows (slice, take, concatenation, exchange) makes a NEW offsets Buffer.  A slicing path that shared the offsets
+    // BufferPtr with a shifted start would have to carry the shift here (or drop the fact), or the fixed-width key form
+    // would read the wrong bytes.
+    int32_t utf8_width(int64_t rows) const { return dtype == DT_UTF8 && offsets ? offsets->uniform_width(rows) : 0; }
     ColumnRef ref() const {
         ColumnRef r;
         r.data = data ? data->ptr() : nullptr;

@@ -852,6 +852,7 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
         int64_t cur_rows = 0;
         for (auto& b : cur) cur_rows += b->n_rows;
         const bool together = !lean_now && !sop_now && cur.size() > 1 && cur.size() <= 4096 && cur_rows <= (1 << 20);
+        bool lens_seen = lean_now && !sampling;        // every launch of this round reports the lengths of all its Utf8 keys' values
         std::vector<ScanParams> Ps;                    // (lives until this round's host wait below: the copy to the device may read it late)
         if (together) {
             Ps.assign(cur.size(), P0);
@@ -875,9 +876,14 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
             if (lean_now) {
                 bind_sop(sop, *b);
                 const char* variant = nullptr;
+                bool fixed_keys = false;
                 HIP_CHECK(launch_scan_agg_lean(cfg, sop.prog, tmp.get<SopProgram>(1), gmax, partials + (size_t)n_part * gmax,
-                                               partial_ng + n_part, max_grid, status, &grid, &variant));
+                                               partial_ng + n_part, max_grid, status, &grid, &variant, &fixed_keys));
                 if (timed) timer.variant = variant;
+                bool utf8_key = false;
+                for (int q = 0; q < sop.prog.n_keys; ++q) utf8_key = utf8_key || sop.prog.keys[q].kind == SOP_KEY_UTF8;
+                ex.ctx->set_lean_key_form(fixed_keys ? "fixed" : utf8_key ? "offsets" : "none");
+                lens_seen = lens_seen && !fixed_keys;
             } else if (sop_now) {
                 bind_sop(sop, *b);
                 HIP_CHECK(launch_scan_agg_sop(cfg, sop.prog, tmp.get<SopProgram>(1), gmax, partials + (size_t)n_part * gmax,
@@ -922,6 +928,20 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
             if (probe8 && st.n_groups <= 4) gmax = 4;
             sample.clear();
             continue;
+        }
+        // The scan read the length of every value of its Utf8 key columns (before the range test, so of filtered-out rows
+        // too) and ORed / ANDed them per key part.  Equal, and 1..3: every value of those columns has that width, which the
+        // next scan of the same buffers then takes as given (Buffer::uniform_width; lean_spec_kernel.h reads no offsets).
+        // Only for a column scanned whole: not a head-only launch, not one that gave up on too many groups.
+        if (lens_seen) {
+            for (int q = 0; q < sop.prog.n_keys && q < 2; ++q) {
+                const uint32_t w = sop.prog.keys[q].kind == SOP_KEY_UTF8 ? scan_len_uniform(st.flags, q) : 0;
+                if (w < 1 || w > 3) continue;
+                for (auto& b : cur) {
+                    const Column& c = b->cols[sop.col_map[sop.prog.keys[q].col]];
+                    if (c.offsets && c.length == b->n_rows) c.offsets->set_uniform_width(b->n_rows, (int32_t)w);
+                }
+            }
         }
         n_groups = st.n_groups;
         break;

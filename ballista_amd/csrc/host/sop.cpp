@@ -234,6 +234,8 @@ void bind_sop(SopPlan& plan, const Batch& b) {
         sc.validity = c.validity ? c.validity->as<uint64_t>() : nullptr;
         sc.dtype = c.dtype;
         sc.data_bytes = (int32_t)c.data_bytes;
+        sc.width = c.utf8_width(b.n_rows);
+        sc.pad = 0;
     }
 }
 

@@ -85,6 +85,7 @@ Column eval_literal(const Exec& ex, const Expr& e, int64_t n) {
     out.data_bytes = n * lit.len;
     out.data = make_buffer(ex, (size_t)out.data_bytes + 8);
     TIMED_LAUNCH_N(ex, "str_broadcast", n, launch_str_broadcast(ex.cfg(), lit, n, out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
+    out.offsets->set_uniform_width(n, lit.len);      // n copies of one value (an empty literal: width unknown, as for every 0)
     return out;
 }
 
@@ -130,6 +131,7 @@ Column eval_sha(const Exec& ex, const Batch& in, const Expr& e) {
     out.data = make_buffer(ex, (size_t)out.data_bytes + 8);
     if (arg.validity) HIP_CHECK(hipMemsetAsync(out.data->ptr(), 0, (size_t)out.data_bytes + 8, ex.stream));    // a NULL row's bytes stay defined
     TIMED_LAUNCH_N(ex, "sha2", n, launch_sha2(ex.cfg(), bits, arg.ref(), n, out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
+    out.offsets->set_uniform_width(n, bits / 8);     // a digest per row, a NULL row's (zeroed) one included
     out.validity = arg.validity;
     return out;
 }

@@ -23,18 +23,22 @@ hipError_t launch_scan_agg_sop(const LaunchCfg& cfg, const SopProgram& S, SopPro
 hipError_t launch_scan_agg_lean_g1(const LaunchCfg&, const SopProgram&, SopProgram*, GroupRec*, uint32_t*, int, ScanStatus*, int*);
 hipError_t launch_scan_agg_lean_g4(const LaunchCfg&, const SopProgram&, SopProgram*, GroupRec*, uint32_t*, int, ScanStatus*, int*);
 hipError_t launch_scan_agg_lean_spec(const LaunchCfg&, const SopProgram&, SopProgram*, int, GroupRec*, uint32_t*, int, ScanStatus*, int*,
-                                     bool*, const char**);
+                                     bool*, const char**, bool*);
 
 // wide-load variant: the shape-specialised kernel when S has one of its shapes (lean_spec_kernel.h;
 // kernels_lean_spec.hip), else the generic one (lean_kernel.h; kernels_lean_g{1,4}.hip).  BHIP_LEAN_GENERIC=1: always generic.
 hipError_t launch_scan_agg_lean(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
-                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant) {
+                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant,
+                                bool* fixed_keys) {
     static const bool generic_only = [] { const char* v = getenv("BHIP_LEAN_GENERIC"); return v && atoi(v) != 0; }();
     const char* name = "lean_generic";
+    bool fixed = false;
     if (!variant) variant = &name;
+    if (!fixed_keys) fixed_keys = &fixed;
+    *fixed_keys = false;
     if (!generic_only) {
         bool ran = false;
-        const hipError_t e = launch_scan_agg_lean_spec(cfg, S, dprog, gmax, partials, partial_ng, max_grid, status, grid_out, &ran, variant);
+        const hipError_t e = launch_scan_agg_lean_spec(cfg, S, dprog, gmax, partials, partial_ng, max_grid, status, grid_out, &ran, variant, fixed_keys);
         if (ran || e != hipSuccess) return e;
     }
     *variant = "lean_generic";

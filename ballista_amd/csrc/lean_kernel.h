@@ -85,6 +85,23 @@ __device__ inline uint32_t lean_str_word(uint32_t raw, uint32_t len) {
     return (__builtin_amdgcn_ubfe(raw, 0u, len << 3) << 8) | len;
 }
 
+// What a thread has seen of the lengths of each Utf8 key part: their OR (a length above LEAN_MAX_STR raises
+// SCAN_ERR_KEY_TOO_LONG) and their AND.  Over all rows OR == AND exactly when every length is the same, which the host
+// then records for the column (SCAN_LEN_* in ScanStatus::flags, lean_finish; ops_agg.cpp).
+// ON = false (the GMAX == 1 kernels: a plan without GROUP BY has no key part to learn about) keeps the one OR of all
+// lengths those kernels have always kept, so their code is what it was.
+template <bool ON>
+struct LeanLens {
+    uint32_t any[2] = {0u, 0u};
+    uint32_t all[2] = {~0u, ~0u};
+    __device__ void see(int q, uint32_t len) { any[q] |= len; all[q] &= len; }
+};
+template <>
+struct LeanLens<false> {
+    uint32_t bad = 0;
+    __device__ void see(int, uint32_t len) { bad |= len; }
+};
+
 // The workgroup's key table: a wave-uniform register copy of lds.keys / lds.ng, and the lookup protocol.
 template <int GMAX, int NSTEP>
 struct LeanKeyTable {
@@ -151,8 +168,8 @@ struct LeanKeyTable {
 
 // The ragged tail (< 1024 rows) after the full tiles: one row per thread and pass, the plan read from S (a cold path).
 // accumulate(lg, tv[NSTEP]) adds one row.  false: more than GMAX groups.
-template <int GMAX, int NSTEP, int NRANGE, class Lookup, class Accumulate>
-__device__ inline bool lean_tail(const SopProgram& S, int64_t tail0, int64_t n_rows, uint32_t& bad_len, Lookup&& lookup,
+template <int GMAX, int NSTEP, int NRANGE, class Lens, class Lookup, class Accumulate>
+__device__ inline bool lean_tail(const SopProgram& S, int64_t tail0, int64_t n_rows, Lens& lens, Lookup&& lookup,
                                  Accumulate&& accumulate) {
     constexpr int NKEY = 2;
     const int tid = threadIdx.x;
@@ -182,7 +199,7 @@ __device__ inline bool lean_tail(const SopProgram& S, int64_t tail0, int64_t n_r
                     if (S.keys[q].kind == SOP_KEY_UTF8) {
                         const uint32_t o0 = (uint32_t)c.offsets[i];
                         uint32_t len = (uint32_t)c.offsets[i + 1] - o0;
-                        bad_len |= len;
+                        lens.see(q, len);
                         len = len > LEAN_MAX_STR ? LEAN_MAX_STR : len;
                         w[q] = lean_str_word((uint32_t)((const BHIP_GLOBAL PackedU64*)((const BHIP_GLOBAL char*)c.data + o0))->v, len);
                     } else {
@@ -218,8 +235,18 @@ __device__ inline bool lean_tail(const SopProgram& S, int64_t tail0, int64_t n_r
 // acc / rows1: the GMAX == 1 accumulators (registers); GMAX > 1 reads the LDS slots.
 template <int GMAX, int NSTEP>
 __device__ inline void lean_finish(LeanLds<GMAX, NSTEP>& lds, const SopProgram& S, const double (&acc)[NSTEP], uint32_t rows1,
-                                   uint32_t bad_len, GroupRec* partials, uint32_t* partial_ng, ScanStatus* status) {
+                                   const LeanLens<(GMAX > 1)>& lens, GroupRec* partials, uint32_t* partial_ng, ScanStatus* status) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the lengths this thread saw, as SCAN_LEN_* bits (a thread without rows adds none); lds.pad is free since the loop ended
+    if constexpr (GMAX > 1) {
+        uint32_t len_bits = 0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const uint32_t b = (lens.any[q] & 3u) | (lens.any[q] > LEAN_MAX_STR ? 4u : 0u) | ((~lens.all[q] & 3u) << 3);
+            len_bits |= b << (SCAN_LEN_SHIFT + q * SCAN_LEN_BITS);
+        }
+        if (len_bits) atomicOr(&lds.pad, len_bits);
+    }
     __syncthreads();
     uint64_t tot_rows = 0;
     double tot_acc = 0.0;
@@ -263,9 +290,18 @@ __device__ inline void lean_finish(LeanLds<GMAX, NSTEP>& lds, const SopProgram& 
     if (tid == 0) {
         // without GROUP BY the one group (key 0) exists once a row has passed the filter
         partial_ng[blockIdx.x] = GMAX == 1 ? (tot_rows > 0 ? 1u : 0u) : lds.ng;
-        if (lds.overflow) atomicOr(&status->flags, SCAN_OVERFLOW_GROUPS);
+        if constexpr (GMAX > 1) {
+            const uint32_t lb = lds.pad;
+            const bool too_long = (lb & ((4u << SCAN_LEN_SHIFT) | (4u << (SCAN_LEN_SHIFT + SCAN_LEN_BITS)))) != 0;
+            const uint32_t f = lb | (lds.overflow ? (uint32_t)SCAN_OVERFLOW_GROUPS : 0u) | (too_long ? (uint32_t)SCAN_ERR_KEY_TOO_LONG : 0u);
+            if (f) atomicOr(&status->flags, f);
+        } else {
+            if (lds.overflow) atomicOr(&status->flags, SCAN_OVERFLOW_GROUPS);
+        }
     }
-    if (bad_len > LEAN_MAX_STR) atomicOr(&status->flags, SCAN_ERR_KEY_TOO_LONG);
+    if constexpr (GMAX == 1) {
+        if (lens.bad > LEAN_MAX_STR) atomicOr(&status->flags, SCAN_ERR_KEY_TOO_LONG);
+    }
 }
 
 template <int GMAX, int NSTEP, int NRANGE>
@@ -341,9 +377,10 @@ scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint
         for (int j = 0; j < GMAX; ++j) lds.cnt[j * BLOCK + tid] = 0;
     }
     if (tid == 0) { lds.ng = 0; lds.overflow = 0; lds.lock = 0; }
+    if (GMAX > 1 && tid == 0) lds.pad = 0;
     if (tid < AGG_GMAX) lds.keys[tid] = 0;
     __syncthreads();
-    uint32_t bad_len = 0;
+    LeanLens<(GMAX > 1)> lens;
     LeanKeyTable<GMAX, NSTEP> table;
     auto lookup = [&](const uint64_t (&key)[LEAN_ROWS], const bool (&live)[LEAN_ROWS], int (&lg)[LEAN_ROWS]) -> bool {
         return table.lookup(lds, lane, key, live, lg);
@@ -427,7 +464,7 @@ scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const uint32_t l0 = ko[q][u].b - ko[q][u].a, l1 = ko[q][u].c - ko[q][u].b;
-                        bad_len |= (l0 | l1);
+                        lens.see(q, l0); lens.see(q, l1);
                         kv[q][u][0] = l0; kv[q][u][1] = l1;
                         kb[q][u] = ((const BHIP_GLOBAL PackedU64*)(kdat[q] + ko[q][u].a))->v;   // buffers carry 16 B of slack
                     }
@@ -594,9 +631,9 @@ scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint
 
     // ---- ragged tail (< 1024 rows): the workgroup next in line takes it
     if (!over && (int64_t)blockIdx.x == n_tiles % grid && n_tiles * LEAN_TILE < n_rows)
-        over = !lean_tail<GMAX, NSTEP, NRANGE>(S, n_tiles * LEAN_TILE, n_rows, bad_len, lookup, accumulate);
+        over = !lean_tail<GMAX, NSTEP, NRANGE>(S, n_tiles * LEAN_TILE, n_rows, lens, lookup, accumulate);
 
-    lean_finish<GMAX, NSTEP>(lds, S, acc, rows1, bad_len, partials, partial_ng, status);
+    lean_finish<GMAX, NSTEP>(lds, S, acc, rows1, lens, partials, partial_ng, status);
 }
 
 // grid: the CUs x the blocks per CU the kernel's resources admit (BHIP_AGG_BLOCKS_PER_CU overrides), at most one per tile

@@ -16,12 +16,19 @@
 //   * per tile t: once the ranges and key bytes of t are consumed, ranges(t+1), Int32 keys(t+1), key bytes(t+1) from
 //     offsets(t+1) and offsets(t+2); then, step column by step column, the sums of t and the loads of steps(t+1);
 //   * the ragged tail and the key-append path of the lookup stay out of the fast path, as in the generic kernel.
+//
+// The fixed-width key form (LK_UTF8_FIXED): every value of the key column is w bytes long (SopColumn::width, 1..3), so
+// offsets[i] = offsets[0] + i*w and the lengths are the constant w.  The kernel then reads offsets[0] once and no other
+// offset: there is no load_offsets, no `ko` register set and no re-pointed prefetch, and the key bytes of tile t+1 are
+// loaded straight from data + offsets[0] + row*w where the offsets form issues its (dependent) key-byte load.  Key words
+// are still lean_str_word(raw, w), so keys, sums and their order are what the offsets form gives.  Nothing can be too
+// long and nothing is learnt about lengths in this form; the ragged tail still goes through the offsets (lean_tail).
 #pragma once
 #include "lean_kernel.h"
 
 namespace bhip {
 
-enum LeanKeyKind : int { LK_NONE = 0, LK_I32 = 1, LK_UTF8 = 2 };
+enum LeanKeyKind : int { LK_NONE = 0, LK_I32 = 1, LK_UTF8 = 2, LK_UTF8_FIXED = 3 };
 
 // NR ranges (bit p of R32: range p reads a 32-bit integer column, else Float64), key parts K0 / K1, exactly NS steps
 template <int GMAX, int NR, int R32, int K0, int K1, int NS>
@@ -32,6 +39,9 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
     constexpr int U = LEAN_U;
     constexpr int NKEY = 2;
     constexpr int KK[NKEY] = {K0, K1};
+    constexpr bool HAS_OFFSETS = K0 == LK_UTF8 || K1 == LK_UTF8;
+    constexpr bool HAS_FIXED = K0 == LK_UTF8_FIXED || K1 == LK_UTF8_FIXED;
+    static_assert(!(HAS_OFFSETS && HAS_FIXED), "no mixed key forms: one unknown width sends the plan to the offsets form");
     __shared__ LeanLds<GMAX, NS> lds;
     const int tid = threadIdx.x, lane = tid & 63;
 
@@ -49,14 +59,19 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
         rlo[p] = S.ranges[p].lo; rhi[p] = S.ranges[p].hi;
     }
     const BHIP_GLOBAL char* kbase[NKEY];       // Int32 key: values.  Utf8 key: the offsets
-    const BHIP_GLOBAL char* kdat[NKEY];        // Utf8 key: bytes (absolute offsets)
+    const BHIP_GLOBAL char* kdat[NKEY];        // Utf8 key: bytes (absolute offsets).  Fixed width: the bytes of row 0
+    uint32_t kw[NKEY];                         // fixed-width Utf8 key: the width, 1..3
 #pragma unroll
     for (int q = 0; q < NKEY; ++q) {
-        kbase[q] = nullptr; kdat[q] = nullptr;
+        kbase[q] = nullptr; kdat[q] = nullptr; kw[q] = 0;
         if (KK[q] != LK_NONE) {
             const SopColumn c = S.cols[S.keys[q].col];
             kbase[q] = KK[q] == LK_UTF8 ? (const BHIP_GLOBAL char*)c.offsets : (const BHIP_GLOBAL char*)c.data;
             kdat[q] = (const BHIP_GLOBAL char*)c.data;
+            if (KK[q] == LK_UTF8_FIXED) {
+                kdat[q] += (uint32_t)c.offsets[0];            // wave-uniform, read once; not assumed to be 0
+                kw[q] = (uint32_t)c.width;
+            }
         }
     }
     const BHIP_GLOBAL char* xbase[NS];
@@ -89,10 +104,10 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
 #pragma unroll
         for (int j = 0; j < GMAX; ++j) lds.cnt[j * BLOCK + tid] = 0;
     }
-    if (tid == 0) { lds.ng = 0; lds.overflow = 0; lds.lock = 0; }
+    if (tid == 0) { lds.ng = 0; lds.overflow = 0; lds.lock = 0; lds.pad = 0; }
     if (tid < AGG_GMAX) lds.keys[tid] = 0;
     __syncthreads();
-    uint32_t bad_len = 0;
+    LeanLens<(GMAX > 1)> lens;
     LeanKeyTable<GMAX, NS> table;
     auto lookup = [&](const uint64_t (&key)[LEAN_ROWS], const bool (&live)[LEAN_ROWS], int (&lg)[LEAN_ROWS]) -> bool {
         return table.lookup(lds, lane, key, live, lg);
@@ -120,9 +135,9 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
 
     // ---- registers.  Row j of sub-tile u: tile row u*512 + 2*tid + j.
     LeanU4 rv[NR][U];            // 32-bit column: .x .y = rows 0 1; Float64: (.x .y) (.z .w)
-    uint32_t kv[NKEY][U][2];     // Int32 key: the two values.  Utf8 key: lengths of the two strings
+    uint32_t kv[NKEY][U][2];     // Int32 key: the two values.  Utf8 key: lengths of the two strings (fixed width: unused)
     uint64_t kb[NKEY][U];        // Utf8 key: 8 bytes at the first string's offset
-    LeanU3 ko[2][NKEY][U];       // Utf8 key offsets, by parity of the tile they belong to
+    LeanU3 ko[2][NKEY][U];       // Utf8 key offsets, by parity of the tile they belong to (fixed width: unused)
     LeanU4 xv[NS][U];            // Float64 step values
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -135,6 +150,9 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
         }
     }
     const uint32_t t8 = (uint32_t)tid * 8u, t16 = (uint32_t)tid * 16u;
+    uint32_t t2w[NKEY];          // fixed-width Utf8 key: byte offset of this thread's row pair within a sub-tile
+#pragma unroll
+    for (int q = 0; q < NKEY; ++q) t2w[q] = (uint32_t)tid * 2u * kw[q];
 
     auto load_step = [&](int s, int64_t row) {
 #pragma unroll
@@ -187,10 +205,22 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const uint32_t l0 = o[q][u].b - o[q][u].a, l1 = o[q][u].c - o[q][u].b;
-                    bad_len |= (l0 | l1);
+                    lens.see(q, l0); lens.see(q, l1);
                     kv[q][u][0] = l0; kv[q][u][1] = l1;
                     kb[q][u] = ((const BHIP_GLOBAL PackedU64*)(kdat[q] + o[q][u].a))->v;   // buffers carry 16 B of slack
                 }
+            }
+    };
+
+    // fixed-width Utf8 key: the bytes of both strings, straight from the row number (64-bit: rows go to 2^32 - 16; a
+    // sub-tile's rows * w < 2^31 since Arrow offsets are Int32).  The same 8-byte load as the offsets form issues.
+    auto load_key_bytes_fixed = [&](int64_t row) {
+#pragma unroll
+        for (int q = 0; q < NKEY; ++q)
+            if (KK[q] == LK_UTF8_FIXED) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    kb[q][u] = ((const BHIP_GLOBAL PackedU64*)(kdat[q] + (row + u * LEAN_SUB) * (int64_t)kw[q] + t2w[q]))->v;
             }
     };
 
@@ -230,6 +260,12 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
                     w[q][2 * u] = lean_str_word((uint32_t)kb[q][u], l0);
                     w[q][2 * u + 1] = lean_str_word((uint32_t)(kb[q][u] >> (l0 << 3)), l1);
                 }
+            } else if (KK[q] == LK_UTF8_FIXED) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    w[q][2 * u] = lean_str_word((uint32_t)kb[q][u], kw[q]);
+                    w[q][2 * u + 1] = lean_str_word((uint32_t)(kb[q][u] >> (kw[q] << 3)), kw[q]);
+                }
             } else if (KK[q] == LK_I32) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) { w[q][2 * u] = kv[q][u][0]; w[q][2 * u + 1] = kv[q][u][1]; }
@@ -252,7 +288,8 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
             load_ranges(row1);
             load_int_keys(row1);
             load_key_bytes(ko[P ^ 1]);                                   // offsets(k+1) -> lengths + bytes(k+1)
-            load_offsets(ko[P], tile_row(k + 2));                        // clamped to the last own tile
+            load_key_bytes_fixed(row1);                                  // ... or bytes(k+1) from the row number
+            if constexpr (HAS_OFFSETS) load_offsets(ko[P], tile_row(k + 2));   // clamped to the last own tile
         }
         int lg[LEAN_ROWS];
         if (!lookup(key, live, lg)) return false;
@@ -292,11 +329,12 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
     bool over = false;
     if (my_tiles > 0) {
         const int64_t row0 = tile_row(0);
-        load_offsets(ko[0], row0);
+        if constexpr (HAS_OFFSETS) load_offsets(ko[0], row0);
         load_key_bytes(ko[0]);                                           // the one exposed dependent load
+        load_key_bytes_fixed(row0);
         load_ranges(row0);
         load_int_keys(row0);
-        load_offsets(ko[1], tile_row(1));
+        if constexpr (HAS_OFFSETS) load_offsets(ko[1], tile_row(1));
 #pragma unroll
         for (int s = 0; s < NS; ++s) load_step(s, row0);
         // Drain the prologue once.  The loop head is entered from here and from its back edge, and the compiler's wait at
@@ -320,9 +358,11 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
             for (int s = 0; s < NS; ++s) add_step(lgr, s, tv[s]);
             add_row(lgr);
         };
-        over = !lean_tail<GMAX, NS, NR>(S, n_tiles * LEAN_TILE, n_rows, bad_len, lookup, accumulate);
+        // (fixed-width keys: what the tail sees of the lengths is dropped, it is not the whole column)
+        LeanLens<(GMAX > 1)> tail_lens;
+        over = !lean_tail<GMAX, NS, NR>(S, n_tiles * LEAN_TILE, n_rows, HAS_FIXED ? tail_lens : lens, lookup, accumulate);
     }
-    lean_finish<GMAX, NS>(lds, S, acc, rows1, bad_len, partials, partial_ng, status);
+    lean_finish<GMAX, NS>(lds, S, acc, rows1, lens, partials, partial_ng, status);
 }
 
 // does plan S have exactly this shape (range widths, no NULLs in a range column, key kinds, step count)?
@@ -339,7 +379,9 @@ static bool lean_shape_matches(const SopProgram& S) {
         if (kk[q] == LK_NONE) continue;
         ++n_keys;
         if (S.n_keys <= q) return false;
-        if (S.keys[q].kind != (kk[q] == LK_UTF8 ? SOP_KEY_UTF8 : SOP_KEY_I32)) return false;
+        if (S.keys[q].kind != (kk[q] == LK_I32 ? SOP_KEY_I32 : SOP_KEY_UTF8)) return false;
+        const int32_t w = S.cols[S.keys[q].col].width;
+        if (kk[q] == LK_UTF8_FIXED && (w < 1 || w > (int32_t)LEAN_MAX_STR)) return false;
     }
     return S.n_keys == n_keys;
 }

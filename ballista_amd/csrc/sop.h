@@ -27,6 +27,10 @@ struct SopColumn {
     const uint64_t* validity;   // only a column the predicate constrains may carry one (lean_kernel.h, kernels_range.hip)
     int32_t dtype;
     int32_t data_bytes;
+    // Utf8: every value is `width` bytes long, row i's bytes are data[offsets[0] + i * width, +width); 0: not known (bind_sop from
+    // Buffer::uniform_width).  Only lean_spec_kernel.h's fixed-width key form reads it.
+    int32_t width;
+    int32_t pad;
 };
 
 struct SopRange {
@@ -67,9 +71,11 @@ hipError_t launch_scan_agg_sop(const LaunchCfg& cfg, const SopProgram& S, SopPro
                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out);
 
 // wide-load variant (lean_kernel.h, lean_spec_kernel.h): gmax 1 or 4, plans accepted by host/sop.cpp::lean_eligible;
-// *variant (optional) names the kernel that ran: "lean_generic" or the specialised shape (kernels_lean_spec.hip)
+// *variant (optional) names the kernel that ran: "lean_generic" or the specialised shape (kernels_lean_spec.hip);
+// *fixed_keys (optional): it read its Utf8 keys in the fixed-width form (SopColumn::width), so it reports no lengths
 hipError_t launch_scan_agg_lean(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
-                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant = nullptr);
+                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant = nullptr,
+                                bool* fixed_keys = nullptr);
 
 // FilterExec's predicate pass for AND-of-ranges predicates (kernels_range.hip): selection bitmap + kept rows per
 // 1024-row tile, the interface of launch_scan_pred_bitmap

@@ -257,5 +257,16 @@ enum : uint32_t {
     SCAN_ERR_KEY_TOO_LONG = 2u,    // Utf8 key part longer than its packed width
     SCAN_OVERFLOW_GROUPS = 4u      // low-cardinality path saw more groups than it holds
 };
+// Not errors: what the wide-load scan (lean_kernel.h) saw of the value lengths of its Utf8 key parts, SCAN_LEN_BITS bits
+// per part from bit SCAN_LEN_SHIFT up (part q: << q * SCAN_LEN_BITS) —
+//   bits 0-1: OR of the lengths (mod 4), bit 2: some length above 3, bits 3-4: NOT of the AND of the lengths (mod 4).
+// All lengths equal w (1..3)  <=>  bit 2 clear, OR == AND == w.  No row seen: all five bits 0 (OR 0, AND 3).
+constexpr uint32_t SCAN_LEN_SHIFT = 16, SCAN_LEN_BITS = 5;
+// the one width of key part q's values as those bits tell it, else 0
+inline uint32_t scan_len_uniform(uint32_t flags, int q) {
+    const uint32_t b = flags >> (SCAN_LEN_SHIFT + (uint32_t)q * SCAN_LEN_BITS);
+    const uint32_t any = b & 3u, all = ~(b >> 3) & 3u;
+    return (b & 4u) == 0 && any == all ? any : 0u;
+}
 
 } // namespace bhip

@@ -86,6 +86,11 @@ class Context:
                 name += "/" + v
         return name
 
+    def lean_key_form(self):
+        """how the last wide-load scan + aggregate launch (timed or not) read its Utf8 group keys: "fixed" (columns whose
+        values are known to share one width: no offsets read), "offsets", "none" (no Utf8 key), "" before the first one"""
+        return L.lib().bhip_ctx_lean_key_form(self._h).decode()
+
     def device_cus(self):
         """compute units of the device (the kernels size their grids by it)"""
         return int(L.lib().bhip_ctx_device_cus(self._h))

@@ -526,6 +526,10 @@ const char* bhip_ctx_kernel_name(bhip_ctx* ctx);
 /* which instantiation of that kernel ran, where the call site says ("lean_generic", "lean_spec_q1", ...; "" otherwise);
  * valid until the next call */
 const char* bhip_ctx_kernel_variant(bhip_ctx* ctx);
+/* how the last wide-load scan + aggregate launch (timed or not) read its Utf8 group keys: "fixed" (every value of each key
+ * column is known to have one width: no offsets are read), "offsets", or "none" (no Utf8 key); "" before the first such launch;
+ * valid until the next call */
+const char* bhip_ctx_lean_key_form(bhip_ctx* ctx);
 /* compute units of the context's device (what the kernels size their grids by) */
 int32_t bhip_ctx_device_cus(bhip_ctx* ctx);
 

@@ -42,3 +42,5 @@ run BHIP_PARQUET_PAGEABLE=1 "tests/test_parquet_gpu.py"
 run BHIP_PARQUET_PER_PAGE=1 "tests/test_parquet_gpu.py"
 # round 4
 run BHIP_LEAN_GENERIC=1 "$A tests/test_full_size_gpu.py"
+# fixed-width Utf8 keys
+run BHIP_NO_FIXED_UTF8=1 "$A tests/test_full_size_gpu.py"
