@@ -77,10 +77,8 @@ Context::Context(int device) : device_(device) {
     hipDeviceProp_t prop;
     HIP_CHECK(hipGetDeviceProperties(&prop, device));
     cus_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    const char* t = getenv("BHIP_KERNEL_TIMING");
-    timing_ = t ? atoi(t) : 0;
-    const char* sp = getenv("BHIP_SPIN_WAIT");
-    spin_wait_ = !(sp && atoi(sp) == 0);
+    timing_ = env_int("BHIP_KERNEL_TIMING", 0);
+    spin_wait_ = env_int("BHIP_SPIN_WAIT", 1) != 0;
     if (spin_wait_) {
         void* p = nullptr;
         if (hipHostMalloc(&p, sizeof(HostSlot) * N_SLOTS, hipHostMallocDefault) == hipSuccess) {
@@ -93,7 +91,7 @@ Context::Context(int device) : device_(device) {
 }
 
 void trace_point(const char* what) {
-    static const bool on = [] { const char* v = getenv("BHIP_TRACE_HOST"); return v && atoi(v) != 0; }();
+    static const bool on = env_flag("BHIP_TRACE_HOST");
     if (!on) return;
     static const auto t0 = std::chrono::steady_clock::now();
     fprintf(stderr, "[bhip-host] %10.1f %s\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), what);

@@ -199,6 +199,8 @@ private:
 using BufferPtr = std::shared_ptr<Buffer>;
 BufferPtr make_buffer(const Exec& ex, size_t bytes);
 inline size_t bitmap_bytes(int64_t n_bits) { return (size_t)((n_bits + 63) / 64) * 8; }
+// slots of an open-addressing table over `rows` keys: the power of two >= 2 x rows, at least 1024
+inline uint64_t table_capacity(uint64_t rows) { uint64_t cap = 1024; while (cap < 2 * rows) cap <<= 1; return cap; }
 
 // scratch that lives for one operator call
 struct Temp {

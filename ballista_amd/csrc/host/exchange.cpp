@@ -255,7 +255,7 @@ struct LoopbackHub {
             cv.notify_all();
             return;
         }
-        static const int timeout_s = [] { const char* v = getenv("BHIP_LOOPBACK_TIMEOUT_S"); return v ? atoi(v) : 120; }();
+        static const int timeout_s = env_int("BHIP_LOOPBACK_TIMEOUT_S", 120);
         if (!cv.wait_for(g, std::chrono::seconds(timeout_s), [&] { return generation != gen || broken; })) {
             broken = true;
             cv.notify_all();
@@ -552,7 +552,7 @@ public:
         const int kw = kc.validity ? 0 : (kc.dtype == DT_INT32 || kc.dtype == DT_DATE32) ? 4 : (kc.dtype == DT_INT64 || kc.dtype == DT_UINT64) ? 8 : 0;
         bool fixed = kw != 0 && (int)in->cols.size() <= TAKE_MANY_MAX;
         for (auto& c : in->cols) fixed = fixed && !c.validity && !c.is_view() && c.dtype != DT_UTF8 && c.dtype != DT_BOOLEAN;
-        static const bool no_stream = [] { const char* v = getenv("BHIP_NO_STREAMING_SHUFFLE"); return v && atoi(v) != 0; }();
+        static const bool no_stream = env_flag("BHIP_NO_STREAMING_SHUFFLE");
         const auto t0 = std::chrono::steady_clock::now();
         // ONE gather tells every rank everything: each rank chunks its OWN rows (at most MAXC chunks: the matrix has a common size),
         // counts them per destination on the device and publishes [rows, "streams", chunks, counts[MAXC][world]].  Every rank must

@@ -24,7 +24,7 @@ bool key_width_error(const Error& e) {
 }  // namespace
 
 bool HashAggregateExec::run_single_partial(const Exec& ex, std::vector<BatchPtr>& out) const {
-    static const bool disabled = [] { const char* v = getenv("BHIP_NO_FINAL_ELISION"); return v && atoi(v) != 0; }();
+    static const bool disabled = env_flag("BHIP_NO_FINAL_ELISION");
     if (disabled || mode_ != BHIP_AGG_FINAL) return false;
     const ExecutionPlan* p = input_.get();
     PlanPtr below;
@@ -124,8 +124,7 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
         HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
         TIMED_LAUNCH(ex, "scan_keys", launch_scan_keys(cfg, P, nullptr, hashes, nullptr, st));
         check_scan_status(ex, st);
-        uint64_t cap = 1024;
-        while (cap < 2ull * (uint64_t)n) cap <<= 1;
+        const uint64_t cap = table_capacity((uint64_t)n);
         uint32_t* table = tmp.get<uint32_t>(cap);
         HIP_CHECK(hipMemsetAsync(table, 0, cap * 4, ex.stream));
         WideKeyCols K;

@@ -349,9 +349,9 @@ int64_t filter_indices(const Exec& ex, const Batch& in, const ExprPtr& predicate
     if (n == 0) { indices_out = make_buffer(ex, 8); return 0; }
     // AND of column-vs-literal comparisons over NULL-free numeric columns: the wide-load range kernel
     // (kernels_range.hip) writes the same bitmap + tile counts as the expression VM
-    static const bool range_disabled = [] { const char* v = getenv("BHIP_NO_RANGE_FILTER"); return v && atoi(v) != 0; }();
+    static const bool range_disabled = env_flag("BHIP_NO_RANGE_FILTER");
     // Utf8 column = / != literal (Q3's c_mktsegment = 'BUILDING'): offsets, the length test, the bytes — no interpreter
-    static const bool utf8_eq_disabled = [] { const char* v = getenv("BHIP_NO_UTF8_EQ_FILTER"); return v && atoi(v) != 0; }();
+    static const bool utf8_eq_disabled = env_flag("BHIP_NO_UTF8_EQ_FILTER");
     const Column* str_col = nullptr;
     Utf8Literal str_lit;
     bool str_negate = false;

@@ -170,7 +170,7 @@ int HashJoinExec::narrow_key_width() const {
 // A child of a join, executed so that the columns this join only passes on (everything but its keys) may arrive as views: the
 // child is a HashJoinExec, or a projection of plain columns over one (the shape of TPC-H's join chains).  Anything else: execute().
 static bool join_views_disabled() {
-    static const bool no_views = [] { const char* v = getenv("BHIP_NO_JOIN_VIEWS"); return v && atoi(v) != 0; }();
+    static const bool no_views = env_flag("BHIP_NO_JOIN_VIEWS");
     return no_views;
 }
 static StreamPtr open_join_child(const PlanPtr& child, int partition, const Exec& ex, const std::vector<std::string>& key_names) {
@@ -254,9 +254,9 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
     for (auto& p : on_) lcols.push_back(p.first);
     uint64_t cap = 1024;
     while (cap < 2ull * (uint64_t)n) cap <<= 1;
-    static const bool narrow_disabled = [] { const char* v = getenv("BHIP_NO_NARROW_JOIN"); return v && atoi(v) != 0; }();
+    static const bool narrow_disabled = env_flag("BHIP_NO_NARROW_JOIN");
     // BHIP_JOIN_TABLE=1: always the CAS table (+ key-set bitmap), the round-1 design — the A/B partner of the rank map
-    static const bool force_table = [] { const char* v = getenv("BHIP_JOIN_TABLE"); return v && atoi(v) != 0; }();
+    static const bool force_table = env_flag("BHIP_JOIN_TABLE");
     // the single-key structures over key column `kc` of width `nkw`: rank map, else CAS table; false: the keys are not unique
     auto try_narrow = [&](const Column& kc, int nkw) -> bool {
         // optimistic: the build side of a key join is almost always unique
@@ -269,8 +269,8 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
         // a dimension table's keys (<= 1024 rows spanning <= 2^16 values: Q5's nation and region): statistics, key set, packed map and
         // permutation in ONE launch and ONE host read (kernels_join.hip: tiny_rank_build_kernel) instead of four launches and two or
         // three reads; anything else — a wider span, duplicate keys — carries on below as if nothing had happened
-        static const bool no_tiny = [] { const char* v = getenv("BHIP_NO_TINY_BUILD"); return v && atoi(v) != 0; }();
-        static const bool radix_join_ab = [] { const char* v = getenv("BHIP_JOIN_RADIX"); return v && atoi(v) != 0; }();
+        static const bool no_tiny = env_flag("BHIP_NO_TINY_BUILD");
+        static const bool radix_join_ab = env_flag("BHIP_JOIN_RADIX");
         if (!no_tiny && !force_table && !radix_join_ab && n >= 1 && n <= tiny_rank_build_max_rows()) {
             BufferPtr rp = make_buffer(ex, tiny_rank_build_map_words() * 8 + 16), pm = make_buffer(ex, (size_t)n * 4 + 8);
             uint64_t* out = tmp.get<uint64_t>(3);
@@ -286,7 +286,7 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
                 bs->ntable.kmin = (uint32_t)kmin;
                 bs->ntable.rpack = rp->as<uint64_t>();
                 bs->ntable.rbits = nullptr;
-                static const bool no_scalar = [] { const char* v = getenv("BHIP_PROBE_NO_SCALAR_MAP"); return v && atoi(v) != 0; }();
+                static const bool no_scalar = env_flag("BHIP_PROBE_NO_SCALAR_MAP");
                 bs->ntable.scalar_map = no_scalar ? 0u : 1u;
                 bs->ntable.rzero = 2u * ((uint32_t)(range >> 6) + 1u);
                 bs->ntable.rperm = unsorted ? pm->as<uint32_t>() : nullptr;
@@ -317,7 +317,7 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
         // a window of at most 2^36 values (granule indices and `rzero` are 32-bit; SF1000 order keys span 1.5 - 6 x 10^9 and hash
         // partitioning does not narrow a rank's window) that is not absurdly sparse (<= 1 KiB of map per build row).
         // BHIP_RANK_WINDOW_LOG2 lowers the bound (30 = the round-2 limit: the A/B partner, profiles/r03_rank_window_ab.txt)
-        static const int window_log2 = [] { const char* v = getenv("BHIP_RANK_WINDOW_LOG2"); const int b = v ? atoi(v) : 36; return b < 10 ? 10 : (b > 36 ? 36 : b); }();
+        static const int window_log2 = [] { const int b = env_int("BHIP_RANK_WINDOW_LOG2", 36); return b < 10 ? 10 : (b > 36 ? 36 : b); }();
         const bool window_ok = any_key && range <= (1ull << window_log2) && range / 4096 <= (uint64_t)n + 256;
         if (window_ok && !force_table) {
             // ---- rank map ----------------------------------------------------------------------------------------------
@@ -351,13 +351,13 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
                 stream_wait(ex);                 // other tasks (other streams) read the map: complete before it is published
                 bs->ntable.rpack = bs->rpack->as<uint64_t>();
                 bs->ntable.rbits = bs->rbits ? bs->rbits->as<uint32_t>() : nullptr;
-                static const bool no_scalar_map = [] { const char* v = getenv("BHIP_PROBE_NO_SCALAR_MAP"); return v && atoi(v) != 0; }();
+                static const bool no_scalar_map = env_flag("BHIP_PROBE_NO_SCALAR_MAP");
                 bs->ntable.scalar_map = no_scalar_map ? 0u : 1u;
                 bs->ntable.rzero = (uint32_t)n_gran;
                 bs->ntable.rperm = bs->rperm ? bs->rperm->as<uint32_t>() : nullptr;
                 bs->ntable.krange64 = range;
                 bs->narrow = bs->unique = true;
-                static const bool radix_ab = [] { const char* v = getenv("BHIP_JOIN_RADIX"); return v && atoi(v) != 0; }();
+                static const bool radix_ab = env_flag("BHIP_JOIN_RADIX");
                 if (radix_ab && nkw == 4 && !ksel && n < (1ll << 31)) {
                     int lg = 0;
                     while ((n >> lg) > 1024 && lg < 16) ++lg;
@@ -774,7 +774,7 @@ StreamPtr HashJoinExec::execute_needed(int partition, const Exec& ex, const std:
             return pk;
         };
         const ProbeChain chain = probe_chain(self->right_);
-        static const bool fused_disabled = [] { const char* v = getenv("BHIP_NO_FUSED_PROBE"); return v && atoi(v) != 0; }();
+        static const bool fused_disabled = env_flag("BHIP_NO_FUSED_PROBE");
         if (chain.ok) {
             const SchemaPtr out_schema = self->right_->schema();
             std::vector<int> rmap;                             // right OUTPUT column k -> source column

@@ -77,7 +77,7 @@ StreamPtr SortExec::execute(int partition, const Exec& ex) const {
         BatchPtr in = concat_batches(ex, self->schema(), parts);
         const int64_t n = in->n_rows;
         const LaunchCfg cfg = ex.cfg();
-        static const bool no_rowsort = [] { const char* v = getenv("BHIP_NO_ROWSORT"); return v && atoi(v) != 0; }();
+        static const bool no_rowsort = env_flag("BHIP_NO_ROWSORT");
         if (!no_rowsort && n <= ROWSORT_MAX_ROWS && self->exprs_.size() <= (size_t)ROWSORT_MAX_KEYS && in->cols.size() <= (size_t)ROWSORT_MAX_COLS) {
             // a handful of rows (the result of a low-cardinality aggregate): ranks by row comparison + the gather of every column, one launch
             RowSortArgs A;
@@ -138,7 +138,7 @@ BufferPtr sort_permutation(const Exec& ex, const Batch& batch, const std::vector
     const LaunchCfg cfg = ex.cfg();
     // mid-sized inputs under fixed-width keys: one split + ranks inside the bins (kernels_sort.hip: bucket_sort); a bin that overflows
     // (the leading differing bits repeat heavily) falls through to the LSD passes below, which are few exactly then
-    static const bool no_bucket = [] { const char* v = getenv("BHIP_NO_BUCKET_SORT"); return v && atoi(v) != 0; }();
+    static const bool no_bucket = env_flag("BHIP_NO_BUCKET_SORT");
     if (!no_bucket && n > small_sort_max() && n <= bucket_sort_max_rows()) {
         BucketSortKeys K;
         memset(&K, 0, sizeof(K));
@@ -219,7 +219,7 @@ std::vector<BatchPtr> hash_partition_batch(const Exec& ex, const BatchPtr& in, c
         const int kw = !kc || kc->validity ? 0 : (kc->dtype == DT_INT32 || kc->dtype == DT_DATE32) ? 4 : (kc->dtype == DT_INT64 || kc->dtype == DT_UINT64) ? 8 : 0;
         bool fixed = kw != 0 && n > 0 && n_parts <= 256 && (int)in->cols.size() <= TAKE_MANY_MAX;
         for (auto& c : in->cols) fixed = fixed && !c.validity && c.dtype != DT_UTF8 && c.dtype != DT_BOOLEAN;
-        static const bool disabled = [] { const char* v = getenv("BHIP_NO_PARTITION_SCATTER"); return v && atoi(v) != 0; }();
+        static const bool disabled = env_flag("BHIP_NO_PARTITION_SCATTER");
         if (fixed && !disabled) {
             TakeMany tm;
             tm.n = 0;

@@ -95,7 +95,7 @@ private:
 void* pinned_alloc(size_t bytes) { return PinnedPool::get().alloc(bytes); }
 void pinned_free(void* p, size_t bytes) { PinnedPool::get().release(p, bytes); }
 void install_pinned_allocator() {
-    static const bool off = [] { const char* v = getenv("BHIP_PARQUET_PAGEABLE"); return v && atoi(v) != 0; }();       // A/B: plain malloc
+    static const bool off = env_flag("BHIP_PARQUET_PAGEABLE");       // A/B: plain malloc
     static std::once_flag once;
     if (!off) std::call_once(once, [] { pq::set_host_allocator(pinned_alloc, pinned_free); });
 }
@@ -172,7 +172,7 @@ Column upload_chunk(const Exec& ex, const PqColumn& pc, const HostChunk& hc, std
         bytes_total += pg.bytes.size();
         runs_total += pg.runs.size();
     }
-    static const bool per_page = [] { const char* v = getenv("BHIP_PARQUET_PER_PAGE"); return v && atoi(v) != 0; }();           // A/B: the page-at-a-time path
+    static const bool per_page = env_flag("BHIP_PARQUET_PER_PAGE");           // A/B: the page-at-a-time path
     if (!per_page && !any_nulls && hc.pages.size() > 1 && all_fixed && width) {
         Column c;
         c.dtype = pc.dtype;
@@ -306,8 +306,7 @@ private:
 
 int decode_threads() {
     static const int n = [] {
-        const char* v = getenv("BHIP_PARQUET_THREADS");
-        int t = v ? atoi(v) : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+        const int t = env_int("BHIP_PARQUET_THREADS", (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
         return t < 1 ? 1 : t;
     }();
     return n;
@@ -395,14 +394,14 @@ public:
             };
             std::vector<BatchPtr> out;
             // BHIP_PARQUET_TRACE=1: where the calling thread's time goes, per partition (stderr)
-            static const bool trace = [] { const char* v = getenv("BHIP_PARQUET_TRACE"); return v && atoi(v) != 0; }();
+            static const bool trace = env_flag("BHIP_PARQUET_TRACE");
             double t_walk = 0, t_issue = 0, t_dev = 0;
             auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
             // the host walks run AHEAD row groups in front of the device half (default 4: a row group has about as many chunks as
             // columns and its string chunks take several times as long as the others — with the device half down to ~60 ms of issue
             // work per GiB the calling thread otherwise waits for the slowest walker of every group: 215 / 265 / 271 M rows/s at
             // 2 / 3 / 4; every group in flight holds its decoded chunks in pinned memory, ~0.3 GB each for lineitem)
-            static const size_t ahead = [] { const char* v = getenv("BHIP_PARQUET_AHEAD"); const int a = v ? atoi(v) : 4; return (size_t)(a < 1 ? 1 : a > 8 ? 8 : a); }();
+            static const size_t ahead = [] { const int a = env_int("BHIP_PARQUET_AHEAD", 4); return (size_t)(a < 1 ? 1 : a > 8 ? 8 : a); }();
             std::deque<Parsed> inflight;
             size_t started = 0;
             for (; started < units.size() && started < ahead; ++started) inflight.push_back(start(units[started]));

@@ -486,7 +486,7 @@ void parse_dictionary(const PqColumn& pc, const uint8_t* vals, size_t nbytes, in
 
 // pages -> one set of chunk buffers where that is possible (parquet_host.hpp: ChunkStaging); BHIP_PARQUET_PER_PAGE=1 keeps the pages
 static void stage_chunk(HostChunk& hc, size_t width) {
-    static const bool per_page = [] { const char* v = getenv("BHIP_PARQUET_PER_PAGE"); return v && atoi(v) != 0; }();
+    static const bool per_page = env_flag("BHIP_PARQUET_PER_PAGE");
     if (per_page || hc.pages.size() < 2) return;
     bool any_nulls = false, all_dict = true, all_fixed = true;
     int64_t rows_total = 0;

@@ -15,6 +15,7 @@
 #include <functional>
 #include <mutex>
 
+#include "../util_kernels.h"
 #include "core.hpp"
 #include "expr.hpp"
 
@@ -217,6 +218,17 @@ private:
     mutable std::atomic<bool> wide_keys_{false};   // a run found key values the packed key cannot hold
     mutable std::atomic<int> clustered_hint_{0};   // hash path: 0 = unknown, 1 = the input came clustered by group key last time, -1 = it did not
 };
+
+// The aggregate's hash path (ops_agg_hash.cpp): one device-wide table over the packed keys of all `inputs`; scratch comes from `tmp`
+// and lives as long as it.  clustered_hint: what the operator learned about its input's clustering (HashAggregateExec::clustered_hint_).
+// slot_keys: the caller can emit from run slots (fixed-width, non-Boolean keys).
+struct HashAggResult {
+    GroupRec* table;       // n_groups dense records; null when `slots` is set
+    int64_t n_groups;
+    SlotSource slots;      // slots.valid: the input's runs are distinct groups, slot g IS group g — emit straight from the slot arrays
+};
+HashAggResult hash_aggregate(const Exec& ex, Temp& tmp, const ScanParams& P0, const ProgramBuilder& pb, const std::vector<BatchPtr>& inputs,
+                             bool nullable, ScanStatus* status, std::atomic<int>* clustered_hint, bool slot_keys);
 
 struct JoinBuildSide;
 class HashJoinExec : public ExecutionPlan {

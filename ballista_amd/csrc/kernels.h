@@ -3,9 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "vm_isa.h"
 
 namespace bhip {
+
+// A/B switches and tuning knobs from the environment: set to a non-zero integer / the integer, `dflt` when unset
+inline bool env_flag(const char* name) { const char* v = getenv(name); return v && atoi(v) != 0; }
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 
 // ---- group table: result of an aggregation (low-cardinality or hash path) --------------
 constexpr int AGG_NACC = 8;     // accumulators per group on the register (low-cardinality) path

@@ -434,16 +434,9 @@ static hipError_t launch_lowcard_t(const LaunchCfg& cfg, const ScanParams& P, Sc
     hipError_t e = set_lds(k, lds);
     if (e != hipSuccess) return e;
     // one grid-stride wave of resident workgroups: every workgroup gets the same number of tiles
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k), BLOCK, lds);
+    int64_t grid = 0;
+    e = agg_grid(reinterpret_cast<const void*>(k), lds, n_tiles, max_grid, cfg.device_cus, &grid);
     if (e != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    static const int forced_per_cu = [] { const char* v = getenv("BHIP_AGG_BLOCKS_PER_CU"); return v ? atoi(v) : 0; }();
-    if (forced_per_cu > 0) per_cu = forced_per_cu;
-    int64_t grid = (int64_t)cfg.device_cus * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    if (grid > max_grid) grid = max_grid;
-    if (grid < 1) grid = 1;
     e = hipMemcpyAsync(dparams, &P, sizeof(ScanParams) * (size_t)n_batches, hipMemcpyHostToDevice, cfg.stream);
     if (e != hipSuccess) return e;
     AggLowCardArgs<GMAX> A{partials, partial_ng, status};
@@ -459,8 +452,8 @@ static hipError_t launch_lowcard_n(const LaunchCfg& cfg, const ScanParams& P, Sc
                                    GroupRec* partials, uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, int n_batches) {
 #define BHIP_LC(R_, G_, PF_) launch_lowcard_t<R_, NULLS, G_, PF_>(cfg, P, dparams, partials, partial_ng, max_grid, status, grid_out, n_batches)
 #ifdef BHIP_TUNE
-    static const int r_env = [] { const char* v = getenv("BHIP_SCAN_R"); return v ? atoi(v) : 0; }();
-    static const int pf_env = [] { const char* v = getenv("BHIP_PREFETCH"); return v ? atoi(v) : -1; }();
+    static const int r_env = env_int("BHIP_SCAN_R", 0);
+    static const int pf_env = env_int("BHIP_PREFETCH", -1);
     if (!NULLS && gmax == 4 && (r_env > 0 || pf_env >= 0)) {
         const int r = r_env > 0 ? r_env : AGG_DEFAULT_R;
         const bool pf = pf_env >= 0 ? pf_env != 0 : AGG_DEFAULT_PREFETCH;

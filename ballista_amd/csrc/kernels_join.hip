@@ -915,7 +915,7 @@ hipError_t launch_join_filter_probe(const LaunchCfg& cfg, const NarrowJoinTable&
     if (n_right == 0) return hipSuccess;
     if ((resid_probe != nullptr) != (T.resid_build != nullptr)) return hipErrorInvalidValue;
     const int64_t n_tiles = ((int64_t)n_right + SEL_TILE - 1) / SEL_TILE;
-    static const int per_cu = [] { const char* v = getenv("BHIP_PROBE_BLOCKS_PER_CU"); return v && atoi(v) > 0 ? atoi(v) : 12; }();   // profiles/r02_probe_variants_q3_sf100.txt
+    static const int per_cu = [] { const int v = env_int("BHIP_PROBE_BLOCKS_PER_CU", 0); return v > 0 ? v : 12; }();   // profiles/r02_probe_variants_q3_sf100.txt
     int64_t grid = (int64_t)cfg.device_cus * per_cu;
     const int64_t need = (n_tiles + BLOCK / 64 - 1) / (BLOCK / 64);
     if (grid > need) grid = need;
@@ -923,15 +923,15 @@ hipError_t launch_join_filter_probe(const LaunchCfg& cfg, const NarrowJoinTable&
     // rows per lane and pass (4-byte keys).  r02: 8 (profiles/r02_probe_variants_q3_sf100.txt, at 62 registers either way); with two passes
     // of streamed rows in flight 8 rows cost 105-135 registers (3-4 waves per SIMD), 4 rows 62-78 (6-7 waves): Q3's probes 1.52 -> 1.42 ms,
     // Q5's 1.31 -> 1.28 (profiles/r03_probe_kernel_pmc_and_variants.txt); BHIP_PROBE_ROWS=8 for the A/B
-    static const int probe_rows = [] { const char* v = getenv("BHIP_PROBE_ROWS"); return v ? atoi(v) : 4; }();
+    static const int probe_rows = env_int("BHIP_PROBE_ROWS", 4);
     // the rank map without NULL probe keys and without a left join: the one-read kernel
     const bool direct = T.rpack != nullptr && rsel == nullptr && matched == nullptr && !right_outer && (staging != nullptr) == (staging_rows != nullptr);
     // the packed map through a buffer descriptor when its granules fit one (BHIP_PROBE_MAP_FLAT=1: the flat-load variant, the A/B partner)
-    static const bool map_flat = [] { const char* v = getenv("BHIP_PROBE_MAP_FLAT"); return v && atoi(v) != 0; }();
+    static const bool map_flat = env_flag("BHIP_PROBE_MAP_FLAT");
     // the packed map through a descriptor: shorter than 1 GiB for 4-byte keys (the kernel keeps their 32-bit offsets only), 2 GiB for 8-byte keys
     const bool map_buf = !map_flat && T.rpack != nullptr && (uint64_t)T.rzero * 8u < (key_width == 8 ? 0x7FFFFFF0ull : 0x3FFFFFF0ull);
     // nothing staged (a semi-join), sorted one-column build side: the key-set words alone (BHIP_PROBE_NO_BITS=1: the packed map, the A/B partner)
-    static const bool no_bits = [] { const char* v = getenv("BHIP_PROBE_NO_BITS"); return v && atoi(v) != 0; }();
+    static const bool no_bits = env_flag("BHIP_PROBE_NO_BITS");
     const bool bits_only = !no_bits && map_buf && T.rbits != nullptr && staging == nullptr && T.rperm == nullptr && resid_probe == nullptr;
 #define BHIP_PROBE_R(KW_, NF_, ROWS_, RESID_, PERM_)                                                                                  \
     launch_rank_probe<KW_, NF_, ROWS_, RESID_, PERM_>(cfg.stream, (unsigned)grid, map_buf, bits_only, T, F, rkeys, n_right, bitmap, tile_counts, staging, \

@@ -10,15 +10,15 @@ namespace bhip {
 hipError_t launch_scan_agg_lean_spec(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
                                      uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, bool* ran,
                                      const char** variant, bool* fixed) {
-    static const bool no_fixed = [] { const char* v = getenv("BHIP_NO_FIXED_UTF8"); return v && atoi(v) != 0; }();
+    static const bool no_fixed = env_flag("BHIP_NO_FIXED_UTF8");
 #define BHIP_LEAN_SPEC(NAME_, GMAX_, NR_, R32_, K0_, K1_, NS_)                                                            \
     if (gmax == GMAX_ && !(no_fixed && (K0_ == LK_UTF8_FIXED || K1_ == LK_UTF8_FIXED)) &&                                 \
         lean_shape_matches<NR_, R32_, K0_, K1_, NS_>(S)) {                                                                \
         *ran = true;                                                                                                      \
         *variant = NAME_;                                                                                                 \
         *fixed = K0_ == LK_UTF8_FIXED || K1_ == LK_UTF8_FIXED;                                                            \
-        return launch_lean_kernel(scan_agg_lean_spec_kernel<GMAX_, NR_, R32_, K0_, K1_, NS_>, cfg, S, dprog, partials,   \
-                                  partial_ng, max_grid, status, grid_out);                                                \
+        return launch_sop_program(scan_agg_lean_spec_kernel<GMAX_, NR_, R32_, K0_, K1_, NS_>, LEAN_TILE, cfg, S, dprog,   \
+                                  partials, partial_ng, max_grid, status, grid_out);                                      \
     }
     // TPC-H Q1: l_shipdate range, GROUP BY two 1-byte strings, 5 chain steps.  First the form for key columns whose values
     // all have one known width (every Utf8 key part of the plan: no mixed forms), then the one that reads the offsets.

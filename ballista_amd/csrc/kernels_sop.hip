@@ -30,7 +30,7 @@ hipError_t launch_scan_agg_lean_spec(const LaunchCfg&, const SopProgram&, SopPro
 hipError_t launch_scan_agg_lean(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
                                 uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant,
                                 bool* fixed_keys) {
-    static const bool generic_only = [] { const char* v = getenv("BHIP_LEAN_GENERIC"); return v && atoi(v) != 0; }();
+    static const bool generic_only = env_flag("BHIP_LEAN_GENERIC");
     const char* name = "lean_generic";
     bool fixed = false;
     if (!variant) variant = &name;

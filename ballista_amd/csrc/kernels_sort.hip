@@ -27,7 +27,7 @@ constexpr int SORT_CHUNK = SORT_BLOCK * SORT_ITEMS;  // 4096 rows per workgroup
 // 1.13 M rows 0.60 -> 0.52 ms, 4 M rows 1.08 -> 1.17 ms)
 constexpr int SORT_ITEMS_SMALL = 4;
 static int sort_items_for(int64_t n) {
-    static const int forced = [] { const char* v = getenv("BHIP_SORT_ITEMS"); return v ? atoi(v) : 0; }();       // 4 | 16: A/B
+    static const int forced = env_int("BHIP_SORT_ITEMS", 0);       // 4 | 16: A/B
     if (forced == SORT_ITEMS_SMALL || forced == SORT_ITEMS) return forced;
     return n <= (1ll << 21) ? SORT_ITEMS_SMALL : SORT_ITEMS;
 }

@@ -636,38 +636,11 @@ scan_agg_lean_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint
     lean_finish<GMAX, NSTEP>(lds, S, acc, rows1, lens, partials, partial_ng, status);
 }
 
-// grid: the CUs x the blocks per CU the kernel's resources admit (BHIP_AGG_BLOCKS_PER_CU overrides), at most one per tile
-template <typename Kernel>
-static hipError_t launch_lean_kernel(Kernel k, const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, GroupRec* partials,
-                                     uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out) {
-    const int64_t n_tiles = (S.n_rows + LEAN_TILE - 1) / LEAN_TILE;
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k), BLOCK, 0);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    static const int forced_per_cu = [] { const char* v = getenv("BHIP_AGG_BLOCKS_PER_CU"); return v ? atoi(v) : 0; }();
-    if (forced_per_cu > 0) per_cu = forced_per_cu;
-    int64_t grid = (int64_t)cfg.device_cus * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
-    if (grid > max_grid) grid = max_grid;
-    if (grid < 1) grid = 1;
-    e = hipMemcpyAsync(dprog, &S, sizeof(SopProgram), hipMemcpyHostToDevice, cfg.stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(BLOCK), 0, cfg.stream, (const SopProgram*)dprog, partials, partial_ng, status);
-    *grid_out = (int)grid;
-    return hipGetLastError();
-}
-
-template <int GMAX, int NSTEP, int NRANGE>
-static hipError_t launch_lean_t(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, GroupRec* partials,
-                                uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out) {
-    return launch_lean_kernel(scan_agg_lean_kernel<GMAX, NSTEP, NRANGE>, cfg, S, dprog, partials, partial_ng, max_grid, status, grid_out);
-}
-
+// smallest instantiated (NSTEP, NRANGE) that holds the plan
 template <int GMAX>
 static hipError_t launch_lean_g(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, GroupRec* partials,
                                 uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out) {
-#define BHIP_LEAN(NS_, NR_) launch_lean_t<GMAX, NS_, NR_>(cfg, S, dprog, partials, partial_ng, max_grid, status, grid_out)
+#define BHIP_LEAN(NS_, NR_) launch_sop_program(scan_agg_lean_kernel<GMAX, NS_, NR_>, LEAN_TILE, cfg, S, dprog, partials, partial_ng, max_grid, status, grid_out)
     const bool few = S.n_ranges <= 1;
     if (S.n_steps <= 2) return few ? BHIP_LEAN(2, 1) : BHIP_LEAN(2, 4);
     if (S.n_steps <= 5) return few ? BHIP_LEAN(5, 1) : BHIP_LEAN(5, 4);
