@@ -114,6 +114,12 @@ const char* bhip_ctx_lean_key_form(bhip_ctx* ctx) {
     return name.c_str();
 }
 
+const char* bhip_ctx_sort_limit_form(bhip_ctx* ctx) {
+    static thread_local std::string name;
+    name = ctx ? ctx->p->sort_limit_form() : std::string();
+    return name.c_str();
+}
+
 // ---- batches ------------------------------------------------------------------------------------------
 static bhip_batch* wrap_batch(BatchPtr b) {
     auto h = new bhip_batch();

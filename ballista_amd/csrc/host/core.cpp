@@ -325,6 +325,16 @@ std::string Context::lean_key_form() {
     return k_key_form_;
 }
 
+void Context::set_sort_limit_form(const char* form) {
+    std::lock_guard<std::mutex> g(mu_);
+    k_sort_limit_form_ = form ? form : "";
+}
+
+std::string Context::sort_limit_form() {
+    std::lock_guard<std::mutex> g(mu_);
+    return k_sort_limit_form_;
+}
+
 void Context::kernel_time(bool reset, double* ms, uint64_t* launches) {
     std::lock_guard<std::mutex> g(mu_);
     if (ms) *ms = k_ms_;

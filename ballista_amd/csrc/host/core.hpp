@@ -83,6 +83,10 @@ public:
     // "offsets", or "none" (no Utf8 key); "" before the first one
     void set_lean_key_form(const char* form);
     std::string lean_key_form();
+    // how the last limit directly over a sort ran: "topk" (threshold selection), "topk_fallback" (the selection declined every batch:
+    // the plain sort, cut to k), "sort" (the full-sort route: k >= the rows there were, or BHIP_NO_TOPK); "" before the first one
+    void set_sort_limit_form(const char* form);
+    std::string sort_limit_form();
     void kernel_time(bool reset, double* ms, uint64_t* launches);
     bool timing_enabled() const { return timing_ > 0; }
     int timing_level() const { return timing_; }
@@ -108,7 +112,7 @@ private:
     bool spin_wait_ = true;
     double k_ms_ = 0;
     uint64_t k_launches_ = 0;
-    std::string k_name_, k_variant_, k_key_form_;
+    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_;
     struct PendingTimed { hipEvent_t a, b; const char* name; uint64_t bytes; };
     std::vector<PendingTimed> pending_timed_;
     std::vector<hipEvent_t> event_pool_;

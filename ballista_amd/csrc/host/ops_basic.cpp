@@ -696,11 +696,20 @@ StreamPtr LimitExec::execute(int partition, const Exec& ex) const {
     check_partition(*this, partition);
     if (global_ && input_->output_partitioning().count != 1)
         fail(BHIP_EINVAL, "GlobalLimitExec requires a single input partition");
+    // a limit directly over a sort (CoalesceBatchesExec looked through: the sort's output is one batch either way) runs as a
+    // top-k selection: the same rows in the same order, without the sort of the rows that are then dropped (SortExec::execute_top)
+    const ExecutionPlan* below = input_.get();
+    while (auto co = dynamic_cast<const CoalesceBatchesExec*>(below)) below = co->children()[0].get();
+    const SortExec* sort_below = dynamic_cast<const SortExec*>(below);
+    static const bool no_topk = env_flag("BHIP_NO_TOPK");
+    if (sort_below && !no_topk) return sort_below->execute_top(limit_, ex);
     auto child = std::shared_ptr<RecordBatchStream>(input_->execute(partition, ex).release());
     SchemaPtr sch = schema();
     const int64_t limit = limit_;
-    return StreamPtr(new LazyStream(sch, [child, ex, limit]() {
+    const bool over_sort = sort_below != nullptr;
+    return StreamPtr(new LazyStream(sch, [child, ex, limit, over_sort]() {
         std::vector<BatchPtr> out;
+        if (over_sort && limit > 0) ex.ctx->set_sort_limit_form("sort");
         int64_t left = limit;
         while (left > 0) {
             BatchPtr b = child->next();

@@ -10,6 +10,7 @@
 // keys co-locate; rows keep their input order inside a partition); RoundRobinBatch(n): batch i ->
 // partition i mod n.
 #include "../sort_kernels.h"
+#include "../topk_kernels.h"
 #include "../util_kernels.h"
 #include "plan.hpp"
 
@@ -128,6 +129,101 @@ StreamPtr SortExec::execute(int partition, const Exec& ex) const {
         BufferPtr perm = sort_permutation(ex, *in, self->exprs_);
         BatchPtr out = take_batch(ex, *in, perm->as<uint32_t>(), n, nullptr, /*permutation=*/true);
         return {out};                                           // (no wait: scratch is released in stream order)
+    }));
+}
+
+// ---- a limit directly over the sort: top-k selection ------------------------------------------------------------------------
+// (kernels_topk.hip)  The first k rows of the stable sort of ONE batch.  Where the selection applies, the rows that can be among
+// them — first-key composite below the k-th row's, plus every row that ties with it — are compacted in input order and only they
+// go through sort_permutation; input order + a stable sort make the cut at k the head of the full sort, ties included.
+namespace {
+enum SortLimitForm { FORM_NONE = 0, FORM_SORT = 1, FORM_FALLBACK = 2, FORM_TOPK = 3 };   // what the hook reports: the highest any batch reached
+
+// the batch's rows perm[0..m) as a batch (m == n: the whole permutation)
+BatchPtr sorted_head(const Exec& ex, const BatchPtr& in, const std::vector<SortDesc>& exprs, int64_t m) {
+    BufferPtr perm = sort_permutation(ex, *in, exprs);
+    return take_batch(ex, *in, perm->as<uint32_t>(), m, nullptr, /*permutation=*/m == in->n_rows);
+}
+
+// below this many rows a batch keeps the plain sort (one small-sort launch per key needs no selection in front of it)
+int64_t topk_min_rows() { return small_sort_max(); }
+
+BatchPtr first_k(const Exec& ex, const BatchPtr& in, const std::vector<SortDesc>& exprs, int64_t k, int& form) {
+    const int64_t n = in->n_rows;
+    if (k >= n) { form = std::max(form, (int)FORM_SORT); return sorted_head(ex, in, exprs, n); }
+    Column key_col;
+    if (!exprs.empty() && n > topk_min_rows() && n <= 0xFFFFFFF0ll) key_col = evaluate_column(ex, *in, exprs[0].expr);
+    const bool selectable = key_col.data && topk_key_supported(key_col.dtype) && !key_col.is_view() && (key_col.dtype != DT_UTF8 || key_col.offsets);
+    if (selectable) {
+        const LaunchCfg cfg = ex.cfg();
+        TopkKey key;
+        key.col = key_col.ref();
+        key.descending = exprs[0].descending ? 1 : 0;
+        key.nulls_first = exprs[0].nulls_first ? 1 : 0;
+        Temp tmp(ex);
+        void* state = tmp.get<uint8_t>(topk_state_bytes());
+        // every pass is queued before anything is read: the picks leave prefix, mask and the rows still wanted in `state`
+        TIMED_LAUNCH_N(ex, "topk_diff", n, launch_topk_diff(cfg, key, n, k, state));
+        if (key.col.validity) TIMED_LAUNCH_N(ex, "topk_pick", n, launch_topk_pick(cfg, TOPK_NULL_BYTE, state));
+        const uint32_t bytes = topk_key_bytes(key_col.dtype);
+        for (int byte = 7; byte >= 0; --byte) {
+            if (!((bytes >> byte) & 1)) continue;
+            TIMED_LAUNCH_N(ex, "topk_hist", n, launch_topk_hist(cfg, key, n, byte, state));
+            TIMED_LAUNCH_N(ex, "topk_pick", n, launch_topk_pick(cfg, byte, state));
+        }
+        const TopkCount cnt = read_device(ex, topk_state_count(state));        // the one wait of the selection
+        const int64_t n_cand = (int64_t)(cnt.less + cnt.equal);
+        if (n_cand < k || n_cand > n) fail(BHIP_EEXEC, "top-k selection: inconsistent candidate count");
+        if (n_cand * 2 <= n) {
+            const int64_t n_tiles = (n + SEL_TILE - 1) / SEL_TILE;
+            uint64_t* bitmap = tmp.get<uint64_t>((size_t)(n + 63) / 64 + 1);
+            uint32_t* tile_counts = tmp.get<uint32_t>((size_t)n_tiles + 1);
+            uint64_t* tile_off = tmp.get<uint64_t>((size_t)n_tiles + 1);
+            void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_tiles));
+            TIMED_LAUNCH_N(ex, "topk_mark", n, launch_topk_mark(cfg, key, n, state, bitmap, tile_counts));
+            HIP_CHECK(exclusive_scan_u32_u64(ex.stream, tile_counts, n_tiles, tile_off, false, nullptr, scan_tmp));
+            BufferPtr idx = make_buffer(ex, (size_t)n_cand * 4 + 8);
+            TIMED_LAUNCH_N(ex, "select_indices", n, launch_select_indices(cfg, bitmap, tile_off, n, idx->as<uint32_t>()));
+            BatchPtr cand = take_batch(ex, *in, idx->as<uint32_t>(), n_cand);
+            form = std::max(form, (int)FORM_TOPK);
+            return sorted_head(ex, cand, exprs, k);
+        }
+        trace_point("top-k: more than half the rows are candidates, plain sort instead");
+    }
+    form = std::max(form, (int)FORM_FALLBACK);
+    return sorted_head(ex, in, exprs, k);
+}
+}  // namespace
+
+// cur = head_k(sort(cur ++ first_k(b))) for every input batch b: a row of b that is among the first k of (everything so far ++ b) is among
+// the first k of b alone, and both operands are in sorted order with cur's rows in front, so the stable sort keeps the global tie
+// order (batch order, then row order).  A batch is released before the next one is pulled: the peak is one input batch, its
+// candidates and 2k rows, whatever the input size.
+StreamPtr SortExec::execute_top(int64_t k, const Exec& ex) const {
+    if (input_->output_partitioning().count != 1) fail(BHIP_EINVAL, "SortExec requires a single input partition");
+    auto self = std::static_pointer_cast<const SortExec>(shared_from_this());
+    return StreamPtr(new LazyStream(schema(), [self, ex, k]() -> std::vector<BatchPtr> {
+        if (k <= 0) return {};                                  // the child is never pulled
+        BatchPtr cur;
+        int form = FORM_NONE;
+        {
+            auto s = self->input_->execute(0, ex);
+            while (BatchPtr b = s->next()) {
+                if (b->n_rows == 0) continue;
+                BatchPtr head = first_k(ex, b, self->exprs_, k, form);
+                b.reset();
+                if (cur) {
+                    BatchPtr both = concat_batches(ex, self->schema(), {cur, head});      // at most 2k rows: the plain sort
+                    cur = sorted_head(ex, both, self->exprs_, std::min(k, both->n_rows));
+                } else {
+                    cur = head;
+                }
+            }
+        }
+        static const char* const names[] = {"sort", "sort", "topk_fallback", "topk"};
+        ex.ctx->set_sort_limit_form(names[form]);
+        if (!cur) return {};
+        return {cur};
     }));
 }
 

@@ -270,6 +270,9 @@ public:
     Partitioning output_partitioning() const override { return Partitioning{BHIP_PART_UNKNOWN, 1, {}}; }
     PlanPtr with_new_children(const std::vector<PlanPtr>& c) const override;
     StreamPtr execute(int partition, const Exec& ex) const override;
+    // the first k rows of execute(0)'s batch, as a top-k selection per input batch (ops_sort.cpp); what a LimitExec directly above
+    // this node runs instead of execute() + a head slice.  Same rows, same order, one batch; the input is never held whole.
+    StreamPtr execute_top(int64_t k, const Exec& ex) const;
     std::string describe() const override;
 private:
     std::vector<SortDesc> exprs_;

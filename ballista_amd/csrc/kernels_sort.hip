@@ -12,6 +12,7 @@
 // passes whose byte is the same in every key are skipped (one OR-reduction per key tells).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+#include "sort_device.h"
 #include "sort_kernels.h"
 #include "util_kernels.h"
 #include "vm_device.h"
@@ -317,40 +318,7 @@ hipError_t radix_pass(const LaunchCfg& cfg, const uint64_t* keys, const uint32_t
 }
 
 // ---- key normalisation ---------------------------------------------------------------------------
-// order-preserving u64 image of a fixed-width value: unsigned order of the images == the type's order
-// (floats: total order by sign-magnitude flip, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN)
-__device__ inline uint64_t fixed_key_image(const ColumnRef& c, uint32_t row) {
-    constexpr uint64_t SIGN = 0x8000000000000000ull;
-    switch (c.dtype) {
-        case DT_INT8: return (uint64_t)(int64_t) reinterpret_cast<const int8_t*>(c.data)[row] ^ SIGN;
-        case DT_INT16: return (uint64_t)(int64_t) reinterpret_cast<const int16_t*>(c.data)[row] ^ SIGN;
-        case DT_INT32:
-        case DT_DATE32: return (uint64_t)(int64_t) reinterpret_cast<const int32_t*>(c.data)[row] ^ SIGN;
-        case DT_INT64:
-        case DT_DATE64:
-        case DT_TIMESTAMP_S:
-        case DT_TIMESTAMP_MS:
-        case DT_TIMESTAMP_US:
-        case DT_TIMESTAMP_NS: return reinterpret_cast<const uint64_t*>(c.data)[row] ^ SIGN;
-        case DT_UINT8: return reinterpret_cast<const uint8_t*>(c.data)[row];
-        case DT_UINT16: return reinterpret_cast<const uint16_t*>(c.data)[row];
-        case DT_UINT32: return reinterpret_cast<const uint32_t*>(c.data)[row];
-        case DT_UINT64: return reinterpret_cast<const uint64_t*>(c.data)[row];
-        case DT_BOOLEAN: return (reinterpret_cast<const uint8_t*>(c.data)[row >> 3] >> (row & 7)) & 1u;
-        case DT_FLOAT32: {
-            const uint32_t b = reinterpret_cast<const uint32_t*>(c.data)[row];
-            return (b >> 31) ? (uint32_t)~b : (b | 0x80000000u);
-        }
-        default: {   // Float64
-            const uint64_t b = reinterpret_cast<const uint64_t*>(c.data)[row];
-            return (b >> 63) ? ~b : (b | SIGN);
-        }
-    }
-}
-__device__ inline bool row_valid(const uint64_t* validity, uint32_t row) {
-    return validity == nullptr || ((validity[row >> 6] >> (row & 63)) & 1ull);
-}
-
+// order-preserving u64 images of the key values: sort_device.h (fixed_key_image, row_valid, utf8_key_image), shared with the top-k select
 // out[i] = order-preserving u64 image of column value at row perm[i]
 __global__ void __launch_bounds__(SORT_BLOCK)
 sort_key_fixed_kernel(ColumnRef c, const uint32_t* perm, int64_t n, int descending, uint64_t* out) {
@@ -677,22 +645,12 @@ hipError_t launch_rowsort(const LaunchCfg& cfg, const RowSortArgs& A) {
     return hipGetLastError();
 }
 
-// Utf8: chunk `chunk` = bytes [8*chunk, 8*chunk+8) big-endian, zero padded; chunk == -1: the length
+// Utf8: chunk `chunk` = bytes [8*chunk, 8*chunk+8) big-endian, zero padded; chunk == -1: the length (sort_device.h)
 __global__ void __launch_bounds__(SORT_BLOCK)
 sort_key_utf8_kernel(ColumnRef c, const uint32_t* perm, int64_t n, int chunk, int descending, uint64_t* out) {
     for (int64_t i = (int64_t)blockIdx.x * SORT_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * SORT_BLOCK) {
         const uint32_t row = perm[i];
-        const int32_t o0 = c.offsets[row], len = c.offsets[row + 1] - o0;
-        uint64_t k = 0;
-        if (chunk < 0) k = (uint64_t)(uint32_t)len;
-        else {
-            const uint8_t* s = reinterpret_cast<const uint8_t*>(c.data) + o0;
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const int p = chunk * 8 + b;
-                k = (k << 8) | (p < len ? s[p] : 0u);
-            }
-        }
+        uint64_t k = utf8_key_image(c, row, chunk);
         if (c.validity != nullptr && !((c.validity[row >> 6] >> (row & 63)) & 1ull)) k = 0;
         out[i] = descending ? ~k : k;
     }

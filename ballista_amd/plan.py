@@ -91,6 +91,11 @@ class Context:
         values are known to share one width: no offsets read), "offsets", "none" (no Utf8 key), "" before the first one"""
         return L.lib().bhip_ctx_lean_key_form(self._h).decode()
 
+    def sort_limit_form(self):
+        """how the last limit directly over a sort ran: "topk" (threshold selection on the first key), "topk_fallback" (the selection
+        declined every batch: plain sort, cut to k), "sort" (full-sort route: limit >= rows, or BHIP_NO_TOPK=1), "" before the first one"""
+        return L.lib().bhip_ctx_sort_limit_form(self._h).decode()
+
     def device_cus(self):
         """compute units of the device (the kernels size their grids by it)"""
         return int(L.lib().bhip_ctx_device_cus(self._h))

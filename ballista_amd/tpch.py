@@ -225,18 +225,19 @@ def q3_partial(j1: P.ExecutionPlan, li: P.ExecutionPlan) -> P.ExecutionPlan:
     return P.HashAggregateExec(P.PARTIAL, [(col(n), n) for n in Q3_GROUP], [Sum(revenue, "revenue")], j2)
 
 
-def q3_final(partial: P.ExecutionPlan) -> P.ExecutionPlan:
-    """Merge -> HashAggregate(Final) -> Projection -> Sort(revenue DESC, o_orderdate)"""
+def q3_final(partial: P.ExecutionPlan, limit=None) -> P.ExecutionPlan:
+    """Merge -> HashAggregate(Final) -> Projection -> Sort(revenue DESC, o_orderdate) [-> GlobalLimit(limit): q3.sql ends in `limit 10`]"""
     group = [(col(n), n) for n in Q3_GROUP]
     fin = P.HashAggregateExec(P.FINAL, group, [E.AggregateExpr("SUM", col("l_orderkey"), "revenue")], P.MergeExec(partial))
     proj = P.ProjectionExec([(col(n), n) for n in ["l_orderkey", "revenue", "o_orderdate", "o_shippriority"]], fin)
-    return P.SortExec([PhysicalSortExpr(col("revenue"), descending=True), PhysicalSortExpr(col("o_orderdate"))], proj)
+    srt = P.SortExec([PhysicalSortExpr(col("revenue"), descending=True), PhysicalSortExpr(col("o_orderdate"))], proj)
+    return srt if limit is None else P.GlobalLimitExec(srt, limit)
 
 
-def q3_plan(customer: P.ExecutionPlan, orders: P.ExecutionPlan, lineitem: P.ExecutionPlan) -> P.ExecutionPlan:
+def q3_plan(customer: P.ExecutionPlan, orders: P.ExecutionPlan, lineitem: P.ExecutionPlan, limit=None) -> P.ExecutionPlan:
     """customer(BUILDING) |x| orders(< 1995-03-15) |x| lineitem(> 1995-03-15); build side = left
-    (collect-left hash join, from_proto.rs:253-276)."""
-    return q3_final(q3_partial(q3_build_side(customer, orders), q3_probe_side(lineitem)))
+    (collect-left hash join, from_proto.rs:253-276).  limit: the query's `limit 10` as a GlobalLimitExec on top (None: no limit)."""
+    return q3_final(q3_partial(q3_build_side(customer, orders), q3_probe_side(lineitem)), limit)
 
 
 def q5_build_side(customer, orders, nation, region) -> P.ExecutionPlan:

@@ -530,6 +530,11 @@ const char* bhip_ctx_kernel_variant(bhip_ctx* ctx);
  * column is known to have one width: no offsets are read), "offsets", or "none" (no Utf8 key); "" before the first such launch;
  * valid until the next call */
 const char* bhip_ctx_lean_key_form(bhip_ctx* ctx);
+/* how the last GlobalLimitExec / LocalLimitExec directly over a SortExec ran: "topk" (the rows that can be among the first k were
+ * selected by a threshold on the first sort key, and only they were sorted), "topk_fallback" (the selection declined every batch —
+ * too many candidates, a small batch, a first key it does not image — and the plain sort was cut to k), "sort" (the full-sort
+ * route: the limit is not below the row count, or BHIP_NO_TOPK is set); "" before the first such execution; valid until the next call */
+const char* bhip_ctx_sort_limit_form(bhip_ctx* ctx);
 /* compute units of the context's device (what the kernels size their grids by) */
 int32_t bhip_ctx_device_cus(bhip_ctx* ctx);
 
