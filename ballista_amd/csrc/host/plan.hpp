@@ -249,6 +249,7 @@ public:
     std::string describe() const override;
 private:
     std::shared_ptr<const JoinBuildSide> build_side(const Exec& ex) const;
+    struct Probe;                    // the probe of one partition against the build side (ops_join.cpp)
     PlanPtr left_, right_;
     std::vector<std::pair<std::string, std::string>> on_;
     int join_type_;

@@ -91,6 +91,43 @@ def test_two_four_byte_keys(ctx, jt, unique, nulls, filtered):
     check(ba.HashJoinExec(lm, probe, [("la", "ra"), ("lb", "rb")], jt), ["la", "lb", "ra", "rb", "ry", "lx"])
 
 
+@pytest.mark.parametrize("jt", JOIN_TYPES)
+@pytest.mark.parametrize("build", ["narrow", "residual", "packed", "general"])
+@pytest.mark.parametrize("nulls", [False, True])
+def test_probe_side_projection_with_a_computed_column(ctx, jt, build, nulls):
+    """a probe side that is a projection with a computed column: no late materialisation, the join probes the projection's own
+    batches (two of them: a batch boundary, several selection tiles each) — against a build side with one unique Int32 key (narrow),
+    two 4-byte keys unique on the first (the second is the residual), two 4-byte keys unique as pairs only (packed into one key),
+    and duplicate keys (general table).  700 build rows in every case: few enough for the one-launch build of the rank map, which
+    the narrow and the residual build side (900 key values) take"""
+    rng = np.random.default_rng(17)
+    nl, nr = 700, 6000
+    if build in ("narrow", "residual"):
+        la = (rng.permutation(900)[:nl] - 30).astype(np.int32)
+    else:
+        la = rng.integers(-20, 60, nl).astype(np.int32)
+    lb = rng.integers(9000, 9012, nl).astype(np.int32)
+    if build == "packed":
+        pairs = sorted({(int(a), int(b)) for a, b in zip(rng.integers(-20, 60, 8 * nl), rng.integers(9000, 9012, 8 * nl))})
+        rng.shuffle(pairs)                                   # (nearly all of the 960 possible pairs: 700 of them)
+        la, lb = np.array([p[0] for p in pairs[:nl]], np.int32), np.array([p[1] for p in pairs[:nl]], np.int32)
+        assert len(la) == nl
+    ra = rng.integers(-40, 900 if build in ("narrow", "residual") else 65, nr).astype(np.int32)
+    rb = rng.integers(8998, 9014, nr).astype(np.int32)
+    if build == "residual":                                  # most probe rows that match on the first key agree on the second too
+        second = dict(zip(la.tolist(), lb.tolist()))
+        rb = np.where(rng.random(nr) < 0.7, np.array([second.get(int(a), 9000) for a in ra], np.int32), rb)
+    v = lambda n: (rng.random(n) > 0.1) if nulls else None
+    left = OrderedDict([("la", OCol("Int32", la, v(nl))), ("lb", OCol("Date32", lb, v(nl))), ("lx", OCol("Float64", rng.random(nl)))])
+    right = OrderedDict([("ra", OCol("Int32", ra, v(nr))), ("rb", OCol("Date32", rb, v(nr))), ("ry", OCol("Int64", rng.integers(0, 100, nr))),
+                         ("rs", OCol("Utf8", [f"r{i % 7}" for i in range(nr)]))])
+    lm = helpers.memory_exec(ctx, [[left]])
+    rm = helpers.memory_exec(ctx, [[helpers.slice_batch(right, 0, 2500), helpers.slice_batch(right, 2500, nr)]])
+    probe = ba.ProjectionExec([(col("ra"), "ra"), (col("ry") + lit(1), "y1"), (col("rb"), "rb"), (col("rs"), "rs")], rm)
+    on = [("la", "ra")] if build in ("narrow", "general") else [("la", "ra"), ("lb", "rb")]
+    check(ba.HashJoinExec(lm, probe, on, jt), ["la", "lb", "ra", "rb", "y1", "lx"])
+
+
 @pytest.mark.parametrize("jt_top", JOIN_TYPES)
 @pytest.mark.parametrize("jt_mid", JOIN_TYPES)
 @pytest.mark.parametrize("shape", ["probe_chain", "probe_direct", "build_chain"])

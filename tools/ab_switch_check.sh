@@ -13,7 +13,6 @@ if [ -z "$NEW_ONLY" ]; then          # NEW_ONLY=1: the switches added in round 3
 run BHIP_SPIN_WAIT=0 "$J $A"
 run BHIP_NO_JOIN_VIEWS=1 "$J"
 run BHIP_JOIN_TABLE=1 "$J"
-run BHIP_JOIN_RADIX=1 "$J"
 run BHIP_NO_NARROW_JOIN=1 "$J"
 run BHIP_NO_FUSED_PROBE=1 "$J"
 run BHIP_PROBE_ROWS=4 "tests/test_join_paths_gpu.py"
