@@ -120,6 +120,12 @@ const char* bhip_ctx_sort_limit_form(bhip_ctx* ctx) {
     return name.c_str();
 }
 
+const char* bhip_ctx_join_key_form(bhip_ctx* ctx) {
+    static thread_local std::string name;
+    name = ctx ? ctx->p->join_key_form() : std::string();
+    return name.c_str();
+}
+
 // ---- batches ------------------------------------------------------------------------------------------
 static bhip_batch* wrap_batch(BatchPtr b) {
     auto h = new bhip_batch();

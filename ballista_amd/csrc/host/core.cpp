@@ -335,6 +335,16 @@ std::string Context::sort_limit_form() {
     return k_sort_limit_form_;
 }
 
+void Context::set_join_key_form(const char* form) {
+    std::lock_guard<std::mutex> g(mu_);
+    k_join_key_form_ = form ? form : "";
+}
+
+std::string Context::join_key_form() {
+    std::lock_guard<std::mutex> g(mu_);
+    return k_join_key_form_;
+}
+
 void Context::kernel_time(bool reset, double* ms, uint64_t* launches) {
     std::lock_guard<std::mutex> g(mu_);
     if (ms) *ms = k_ms_;

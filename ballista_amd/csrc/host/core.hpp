@@ -87,6 +87,11 @@ public:
     // the plain sort, cut to k), "sort" (the full-sort route: k >= the rows there were, or BHIP_NO_TOPK); "" before the first one
     void set_sort_limit_form(const char* form);
     std::string sort_limit_form();
+    // the table form of the HashJoinExec build side most recently built or probed: "narrow" (one integer key, unique: rank map /
+    // CAS table), "packed" (the general table over 16-byte packed keys), "wide" (the table over row hashes that compares the key
+    // columns: keys of any width — also when a probe batch forced it beside a packed table); "" before the first one
+    void set_join_key_form(const char* form);
+    std::string join_key_form();
     void kernel_time(bool reset, double* ms, uint64_t* launches);
     bool timing_enabled() const { return timing_ > 0; }
     int timing_level() const { return timing_; }
@@ -112,7 +117,7 @@ private:
     bool spin_wait_ = true;
     double k_ms_ = 0;
     uint64_t k_launches_ = 0;
-    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_;
+    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_, k_join_key_form_;
     struct PendingTimed { hipEvent_t a, b; const char* name; uint64_t bytes; };
     std::vector<PendingTimed> pending_timed_;
     std::vector<hipEvent_t> event_pool_;

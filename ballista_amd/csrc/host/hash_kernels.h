@@ -104,7 +104,7 @@ struct JoinTable {
     uint32_t* head;           // [capacity] id+1 of the most recently inserted build row of the slot's key
     uint32_t* next;           // [n_left]   id+1 of the next build row with the same key
     uint64_t mask;
-    const uint64_t* keys128;  // packed keys of the build rows
+    const uint64_t* keys128;  // packed keys of the build rows (null: the wide form below, whose keys are the build side's columns)
     uint32_t* dup_flag;       // set by the build when two build rows share a key (may be null)
 };
 hipError_t launch_join_build(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* sel, uint32_t n_left);
@@ -118,6 +118,22 @@ hipError_t launch_join_probe_emit(const LaunchCfg& cfg, const JoinTable& T, cons
 hipError_t launch_join_probe_match(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel,
                                    uint32_t n_right, bool right_outer, uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts,
                                    uint32_t* matched);
+// keys of any width (T.keys128 == nullptr): the slot word is claimed with the high half of the 64-bit ROW HASH (scan_keys in
+// hash-only mode) as its tag, and a tag hit is confirmed on the key columns themselves — `build` row (owner) against `build` row
+// in the build kernel, `probe` row against `build` row (owner) in the probes.  Rows with a NULL key part are deselected by
+// sel / rsel and never reach a compare.  Fixed-width parts compare by their 64-bit image (dt_load: floats by bits, as the packed
+// key does), Utf8 parts by length, then bytes.  partner / bitmap / tile_counts / counts / offsets / left_idx / right_idx / matched
+// and right_outer mean what they mean for the packed launchers above.
+hipError_t launch_join_build_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
+                                  uint32_t n_left);
+hipError_t launch_join_probe_match_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* partner,
+                                        uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched);
+hipError_t launch_join_probe_count_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* counts);
+hipError_t launch_join_probe_emit_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                       const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, const uint64_t* offsets,
+                                       uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched);
 // one Int32 / Date32 key column, unique build side: key and build row share the slot (kernels_hash.hip)
 struct NarrowJoinTable {
     // CAS table (sparse keys): key width 4: [capacity] key | (build row + 1) << 32, 0 = empty;

@@ -15,13 +15,13 @@ namespace bhip {
 
 namespace {
 const char* const kRepName = "__group_rep";
+}  // namespace
 
 bool key_width_error(const Error& e) {
     if (e.code != BHIP_ENOTIMPL) return false;
     const std::string m = e.what();
     return m.find("packed key") != std::string::npos || m.find("packed-key") != std::string::npos;
 }
-}  // namespace
 
 bool HashAggregateExec::run_single_partial(const Exec& ex, std::vector<BatchPtr>& out) const {
     static const bool disabled = env_flag("BHIP_NO_FINAL_ELISION");

@@ -21,6 +21,8 @@ struct JoinBuildSide {
     JoinTable table;
     bool has_sel = false;
     bool unique = false;            // no two build rows share a key: probe rows have at most one partner
+    bool wide = false;              // keys of any width: `table` over row hashes (no `keys`), equality on the key columns `wkeys` of `batch`
+    WideKeyCols wkeys;
     bool narrow = false;            // ONE integer key, unique: NarrowJoinTable instead of JoinTable
     int narrow_width = 0;           // its key bytes (4: Int32 / Date32, 8: Int64 / UInt64)
     BufferPtr slots, present, rpack, rbits, rperm;
@@ -62,11 +64,21 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
         right_cols_.push_back((int)i);
     }
     schema_ = s;
-    // key layout must be valid (surfaces BHIP_ENOTIMPL at plan time)
-    ProgramBuilder pb(ls);
-    for (auto& p : on_) pb.add_key(make_column(p.first), true);
+    // key layout must be valid (surfaces BHIP_ENOTIMPL at plan time); one the packed key cannot hold goes to the wide-key table,
+    // whose row-hash program has to be valid instead
     ScanParams P;
-    pb.finish(P);
+    try {
+        ProgramBuilder pb(ls);
+        for (auto& p : on_) pb.add_key(make_column(p.first), true);
+        pb.finish(P);
+    } catch (const Error& e) {
+        if (!key_width_error(e)) throw;
+        static_wide_ = true;
+        ProgramBuilder hb(ls);
+        hb.set_hash_only();
+        for (auto& p : on_) hb.add_key(make_column(p.first), true);
+        hb.finish(P);
+    }
     cache_ = std::make_shared<BuildCache>();
 }
 
@@ -123,6 +135,39 @@ static void side_keys(const Exec& ex, const Batch& b, const std::vector<std::str
     ScanStatus* st = tmp.get<ScanStatus>(1);
     HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
     TIMED_LAUNCH_N(ex, "scan_keys", b.n_rows, launch_scan_keys(ex.cfg(), P, keys->as<uint64_t>(), nullptr, has_sel ? sel->as<uint64_t>() : nullptr, st));
+    check_scan_status(ex, st);
+}
+
+// the wide-key form of one side: 64-bit row hashes (+ "no NULL key" selection) and the key columns themselves
+static void side_hashes(const Exec& ex, const Batch& b, const std::vector<std::string>& cols, BufferPtr& hashes, BufferPtr& sel, bool& has_sel,
+                        WideKeyCols& K) {
+    ProgramBuilder pb(*b.schema);
+    pb.set_hash_only();
+    ExprPtr pred;
+    memset(&K, 0, sizeof(K));
+    for (auto& c : cols) {
+        const int ci = b.schema->index_of(c);
+        if (b.schema->fields[ci].nullable || b.cols[ci].validity) {
+            auto e = std::make_shared<Expr>();
+            e->kind = BHIP_EXPR_IS_NOT_NULL;
+            e->args = {make_column(c)};
+            pred = pred ? make_binary(pred, "And", e) : ExprPtr(e);
+        }
+        K.col[K.n++] = b.cols[ci].ref();
+    }
+    if (pred) pb.set_predicate(pred);
+    for (auto& c : cols) pb.add_key(make_column(c), true);
+    ScanParams P;
+    pb.finish(P);
+    ProgramBuilder::bind(P, pb.columns(), b, pb.creates_nulls());
+    hashes = make_buffer(ex, (size_t)b.n_rows * 8 + 16);
+    has_sel = (bool)pred;
+    if (has_sel) sel = make_buffer(ex, bitmap_bytes(b.n_rows) + 8);
+    if (b.n_rows == 0) return;
+    Temp tmp(ex);
+    ScanStatus* st = tmp.get<ScanStatus>(1);
+    HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
+    TIMED_LAUNCH_N(ex, "scan_keys", b.n_rows, launch_scan_keys(ex.cfg(), P, nullptr, hashes->as<uint64_t>(), has_sel ? sel->as<uint64_t>() : nullptr, st));
     check_scan_status(ex, st);
 }
 
@@ -372,10 +417,14 @@ static BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema) {
     return e;
 }
 
-// the general table over packed 16-byte keys: any key types, duplicates chained through next[]
-static void build_general_table(const Exec& ex, JoinBuildSide* bs, const std::vector<std::string>& key_names, uint64_t cap) {
+// the general table, duplicates chained through next[]: over packed 16-byte keys (any key types that fit them), or (wide) over
+// row hashes with the key columns of the build batch as the keys — any width
+static void build_general_table(const Exec& ex, JoinBuildSide* bs, const std::vector<std::string>& key_names, uint64_t cap, bool wide) {
     const int64_t n = bs->batch->n_rows;
-    side_keys(ex, *bs->batch, key_names, bs->keys, bs->sel, bs->has_sel);
+    BufferPtr hashes;
+    if (wide) side_hashes(ex, *bs->batch, key_names, hashes, bs->sel, bs->has_sel, bs->wkeys);
+    else side_keys(ex, *bs->batch, key_names, bs->keys, bs->sel, bs->has_sel);
+    bs->wide = wide;
     bs->owner = make_buffer(ex, cap * 8);
     bs->head = make_buffer(ex, cap * 4);
     bs->next = make_buffer(ex, (size_t)(n + 1) * 4);
@@ -385,20 +434,39 @@ static void build_general_table(const Exec& ex, JoinBuildSide* bs, const std::ve
     bs->table.head = bs->head->as<uint32_t>();
     bs->table.next = bs->next->as<uint32_t>();
     bs->table.mask = cap - 1;
-    bs->table.keys128 = bs->keys->as<uint64_t>();
+    bs->table.keys128 = wide ? nullptr : bs->keys->as<uint64_t>();
     bs->dup = make_buffer(ex, 8);
     HIP_CHECK(hipMemsetAsync(bs->dup->ptr(), 0, 8, ex.stream));
     bs->table.dup_flag = bs->dup->as<uint32_t>();
-    TIMED_LAUNCH_N(ex, "join_build", n, launch_join_build(ex.cfg(), bs->table, bs->has_sel ? bs->sel->as<uint64_t>() : nullptr, (uint32_t)n));
+    const uint64_t* sel = bs->has_sel ? bs->sel->as<uint64_t>() : nullptr;
+    if (wide) TIMED_LAUNCH_N(ex, "join_build_wide", n, launch_join_build_wide(ex.cfg(), bs->table, bs->wkeys, hashes->as<uint64_t>(), sel, (uint32_t)n));
+    else TIMED_LAUNCH_N(ex, "join_build", n, launch_join_build(ex.cfg(), bs->table, sel, (uint32_t)n));
     // other tasks (other HIP streams) will read the table: it must be complete before it is published
     bs->unique = read_device(ex, bs->dup->as<uint32_t>()) == 0;
     bs->table.dup_flag = nullptr;
 }
 
-// collect the left child -> the single-key structures where the key types allow -> else the general table -> cache
+// the wide-key table over the build batch of `packed`, beside it in the cache: for the probe batches whose keys outgrow the packed key
+std::shared_ptr<const JoinBuildSide> HashJoinExec::wide_sibling(const Exec& ex, const JoinBuildSide& packed) const {
+    std::lock_guard<std::mutex> g(cache_->mu);
+    if (!cache_->wide) {
+        auto w = std::make_shared<JoinBuildSide>();
+        w->batch = packed.batch;
+        std::vector<std::string> left_keys;
+        for (auto& p : on_) left_keys.push_back(p.first);
+        build_general_table(ex, w.get(), left_keys, table_capacity((uint64_t)w->batch->n_rows), true);
+        cache_->wide = w;
+    }
+    ex.ctx->set_join_key_form("wide");
+    return cache_->wide;
+}
+
+// collect the left child -> the single-key structures where the key types allow -> else the general table (packed keys where they
+// hold the key values, else wide) -> cache
 std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) const {
     std::lock_guard<std::mutex> g(cache_->mu);
-    if (cache_->built) return cache_->built;
+    auto report = [&](const JoinBuildSide& b) { ex.ctx->set_join_key_form(b.narrow ? "narrow" : (b.wide || cache_->wide) ? "wide" : "packed"); };
+    if (cache_->built) { report(*cache_->built); return cache_->built; }
     auto bs = std::make_shared<JoinBuildSide>();
     std::vector<BatchPtr> parts;
     const int np = left_->output_partitioning().count;
@@ -447,8 +515,23 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
             narrow = try_narrow(ex, bs.get(), n, cap, c0, nkw);
         }
     }
-    if (!narrow) build_general_table(ex, bs.get(), left_keys, cap);
+    if (!narrow) {
+        // BHIP_JOIN_WIDE=1 (read at every build: one process can run both forms): the wide table wherever the packed one would be built
+        bool wide = static_wide_ || wide_keys_.load() || env_flag("BHIP_JOIN_WIDE");
+        if (!wide) {
+            try {
+                build_general_table(ex, bs.get(), left_keys, cap, false);
+            } catch (const Error& e) {
+                if (!key_width_error(e)) throw;                 // a build value longer than its share of the packed key
+                wide_keys_.store(true);
+                bs->keys.reset();
+                wide = true;
+            }
+        }
+        if (wide) build_general_table(ex, bs.get(), left_keys, cap, true);
+    }
     cache_->built = bs;
+    report(*bs);
     return bs;
 }
 
@@ -675,20 +758,37 @@ struct HashJoinExec::Probe {
     }
 
     // ---- general table: `probe` holds the key columns of the probe rows under their names -----------------------------------------
+    // (a packed build side whose keys this batch's values outgrow: the batch goes through the wide table over the same build rows,
+    // HashJoinExec::wide_sibling; the wide kernels read row hashes `rkeys` and the key columns `K` where the packed ones read packed keys)
     void probe_general(const Batch& probe, const ProbeOut& o) {
         const int64_t n_right = probe.n_rows;
         if (n_right == 0) return;
+        std::shared_ptr<const JoinBuildSide> t = bs;
         BufferPtr rkeys, rsel;
         bool has_rsel = false;
-        side_keys(ex, probe, rcols, rkeys, rsel, has_rsel);
+        WideKeyCols K;
+        if (!t->wide) {
+            try {
+                side_keys(ex, probe, rcols, rkeys, rsel, has_rsel);
+            } catch (const Error& e) {
+                if (!key_width_error(e)) throw;
+                t = J.wide_sibling(ex, *bs);
+            }
+        }
+        if (t->wide) side_hashes(ex, probe, rcols, rkeys, rsel, has_rsel, K);
         Temp tmp(ex);
         const uint64_t* rselp = has_rsel ? rsel->as<uint64_t>() : nullptr;
-        if (bs->unique) {
+        if (t->unique) {
             // one probe per row -> selection bitmap -> indices (the index pass of FilterExec)
             TileSelection s(tmp, n_right, false, false);
-            TIMED_LAUNCH_N(ex, "join_probe_match", n_right,
-                           launch_join_probe_match(cfg, bs->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, s.partner,
-                                                   s.bitmap, s.tile_counts, matched_bits()));
+            if (t->wide)
+                TIMED_LAUNCH_N(ex, "join_probe_match_wide", n_right,
+                               launch_join_probe_match_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer,
+                                                            s.partner, s.bitmap, s.tile_counts, matched_bits()));
+            else
+                TIMED_LAUNCH_N(ex, "join_probe_match", n_right,
+                               launch_join_probe_match(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, s.partner,
+                                                       s.bitmap, s.tile_counts, matched_bits()));
             compact(tmp, s, o);
             return;
         }
@@ -696,8 +796,12 @@ struct HashJoinExec::Probe {
         uint32_t* counts = tmp.get<uint32_t>((size_t)n_right + 1);
         uint64_t* offsets = tmp.get<uint64_t>((size_t)n_right + 1);
         void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_right));
-        TIMED_LAUNCH_N(ex, "join_probe_count", n_right,
-                       launch_join_probe_count(cfg, bs->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, counts));
+        if (t->wide)
+            TIMED_LAUNCH_N(ex, "join_probe_count_wide", n_right,
+                           launch_join_probe_count_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, counts));
+        else
+            TIMED_LAUNCH_N(ex, "join_probe_count", n_right,
+                           launch_join_probe_count(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, counts));
         HIP_CHECK(exclusive_scan_u32_u64(ex.stream, counts, n_right, offsets, false, total, scan_tmp));
         const uint64_t n_out = read_device(ex, total);
         if (n_out > 0xFFFFFFF0ull) fail(BHIP_EEXEC, "join output of one probe batch exceeds 2^32 rows");
@@ -705,9 +809,14 @@ struct HashJoinExec::Probe {
         JoinIndices ix;
         ix.lidx = tmp.get<uint32_t>((size_t)n_out);
         ix.ridx = tmp.get<uint32_t>((size_t)n_out);
-        TIMED_LAUNCH_N(ex, "join_probe_emit", n_right,
-                       launch_join_probe_emit(cfg, bs->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, offsets,
-                                              ix.lidx, ix.ridx, matched_bits()));
+        if (t->wide)
+            TIMED_LAUNCH_N(ex, "join_probe_emit_wide", n_right,
+                           launch_join_probe_emit_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer,
+                                                       offsets, ix.lidx, ix.ridx, matched_bits()));
+        else
+            TIMED_LAUNCH_N(ex, "join_probe_emit", n_right,
+                           launch_join_probe_emit(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, offsets,
+                                                  ix.lidx, ix.ridx, matched_bits()));
         finish(tmp, o, ix, n_out);
     }
 

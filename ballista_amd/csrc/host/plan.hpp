@@ -259,8 +259,13 @@ private:
     bool pair_keys() const;          // TWO 4-byte integer key pairs: packed into one 8-byte key per side, then the single-key machinery
     // the build side (hash table over the whole left child) is built once and shared by every
     // partition's task, like DataFusion's collect-left build future
-    struct BuildCache { std::mutex mu; std::shared_ptr<const JoinBuildSide> built; };
+    // `wide`: the wide-key table over built->batch, made when a probe batch held a key value that `built`'s packed keys cannot
+    // hold (wide_sibling); such batches go through it, the others keep `built`
+    struct BuildCache { std::mutex mu; std::shared_ptr<const JoinBuildSide> built, wide; };
     std::shared_ptr<BuildCache> cache_;
+    std::shared_ptr<const JoinBuildSide> wide_sibling(const Exec& ex, const JoinBuildSide& packed) const;
+    bool static_wide_ = false;                      // the key LAYOUT does not fit the 16-byte packed key: always the wide-key table
+    mutable std::atomic<bool> wide_keys_{false};    // a build found key values the packed key cannot hold: later builds skip the attempt
 };
 
 class SortExec : public UnaryExec {
@@ -332,6 +337,9 @@ private:
 std::vector<BatchPtr> hash_partition_batch(const Exec& ex, const BatchPtr& in, const std::vector<ExprPtr>& exprs, int n);
 void check_scan_status(const Exec& ex, const ScanStatus* dev_status, ScanStatus* host_out = nullptr);
 void check_scan_flags(const ScanStatus& host_status);   // the same checks on a status already read back
+// `e` says that keys do not fit the 16-byte packed key — the layout at plan time, or a Utf8 value at run time (ops_agg_wide.cpp):
+// what HashAggregateExec and HashJoinExec answer with their wide-key forms
+bool key_width_error(const Error& e);
 // value of `e` over `in` as a column (a plain Column reference shares the input buffers)
 Column evaluate_column(const Exec& ex, const Batch& in, const ExprPtr& e);
 struct SortDesc;

@@ -521,6 +521,150 @@ wide_key_assign_kernel(const WideKeyCols K, const uint64_t* hashes, uint32_t* ta
     }
 }
 
+// ---- join keys of any width: the JoinTable over 64-bit row hashes, equality on the key columns ---------------------------
+// (HashJoinExec on c_name, a phone number, three Int64 columns ...: what the 16-byte packed key cannot hold.)  Slot word, chain
+// (head / next) and dup_flag are those of join_build_kernel; the tag is the high half of the row hash, so the columns are read
+// for true matches and about one in 2^32 others.  Row `a` of A against row `b` of B, column by column; both rows are known to
+// have no NULL key part (sel / rsel), so no validity is read.  Fixed-width parts: the 64-bit image the packed key holds (floats by
+// bits: -0.0 != +0.0, a NaN equals the NaN of the same bits).  Utf8: lengths, then 8 bytes at a time where 8 remain, then the
+// tail byte by byte — only bytes of the two values are read, nothing behind offsets[n].
+__device__ inline bool wide_rows_equal(const WideKeyCols& A, uint32_t a, const WideKeyCols& B, uint32_t b) {
+    for (int c = 0; c < A.n; ++c) {
+        const ColumnRef& ra = A.col[c];
+        const ColumnRef& rb = B.col[c];
+        switch (ra.dtype) {
+            case DT_UTF8: {
+                const int32_t a0 = ra.offsets[a], b0 = rb.offsets[b];
+                const int32_t len = ra.offsets[a + 1] - a0;
+                if (len != rb.offsets[b + 1] - b0) return false;
+                const uint8_t* x = static_cast<const uint8_t*>(ra.data) + a0;
+                const uint8_t* y = static_cast<const uint8_t*>(rb.data) + b0;
+                int32_t i = 0;
+                for (; i + 8 <= len; i += 8) {
+                    uint64_t u, v;
+                    __builtin_memcpy(&u, x + i, 8);
+                    __builtin_memcpy(&v, y + i, 8);
+                    if (u != v) return false;
+                }
+                for (; i < len; ++i)
+                    if (x[i] != y[i]) return false;
+            } break;
+            case DT_BOOLEAN: {
+                const uint8_t* x = static_cast<const uint8_t*>(ra.data);
+                const uint8_t* y = static_cast<const uint8_t*>(rb.data);
+                if (((x[a >> 3] >> (a & 7)) & 1) != ((y[b >> 3] >> (b & 7)) & 1)) return false;
+            } break;
+            default:
+                if (dt_load(ra.dtype, ra.data, a) != dt_load(rb.dtype, rb.data, b)) return false;
+                break;
+        }
+    }
+    return true;
+}
+
+__global__ void __launch_bounds__(BLOCK)
+join_build_wide_kernel(JoinTable T, const WideKeyCols K, const uint64_t* hashes, const uint64_t* sel, uint32_t n_left) {
+    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK) {
+        if (!bit_at(sel, row)) continue;                       // NULL keys never match
+        const uint64_t h = hashes[row];
+        const uint64_t tag = h >> 32;
+        const unsigned long long want = (unsigned long long)(row + 1u) | (tag << 32);
+        uint64_t slot = h & T.mask;
+        // (ends: the table has more slots than build rows, and an empty slot is claimed or turns out to be taken)
+        for (;;) {
+            unsigned long long o = T.owner[slot];
+            if (o == 0) {
+                o = atomicCAS(reinterpret_cast<unsigned long long*>(&T.owner[slot]), 0ull, want);
+                if (o == 0) break;                             // claimed: this row's key defines the slot
+            }
+            if ((o >> 32) == tag && wide_rows_equal(K, (uint32_t)o - 1u, K, row)) break;
+            slot = (slot + 1) & T.mask;
+        }
+        const uint32_t prev = atomicExch(&T.head[slot], row + 1u);     // push on the slot's chain
+        T.next[row] = prev;
+        if (prev != 0 && T.dup_flag) *T.dup_flag = 1u;                 // a second row with this key: not a unique build side
+    }
+}
+
+// slot whose owner's key equals probe row `row`'s, or 0xFFFFFFFF; *owner_row = that owner (read-only: the table is finished).
+// Ends at the first empty slot, and table_capacity() leaves at least half of the slots empty.
+__device__ inline uint32_t wide_table_find(const JoinTable& T, const WideKeyCols& B, const WideKeyCols& P, uint64_t h, uint32_t row,
+                                           uint32_t* owner_row) {
+    const uint64_t tag = h >> 32;
+    uint64_t slot = h & T.mask;
+    for (;;) {
+        const uint64_t o = T.owner[slot];
+        if (o == 0) return 0xFFFFFFFFu;
+        if ((o >> 32) == tag && wide_rows_equal(B, (uint32_t)o - 1u, P, row)) { *owner_row = (uint32_t)o - 1u; return (uint32_t)slot; }
+        slot = (slot + 1) & T.mask;
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK)
+join_probe_count_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
+                             uint32_t n_right, int right_outer, uint32_t* counts) {
+    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_right; row += gridDim.x * BLOCK) {
+        uint32_t c = 0;
+        if (bit_at(rsel, row)) {
+            uint32_t owner;
+            const uint32_t slot = wide_table_find(T, B, P, rhashes[row], row, &owner);
+            if (slot != 0xFFFFFFFFu)
+                for (uint32_t l = T.head[slot]; l != 0; l = T.next[l - 1u]) ++c;
+        }
+        counts[row] = (right_outer && c == 0) ? 1u : c;
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK)
+join_probe_emit_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
+                            uint32_t n_right, int right_outer, const uint64_t* offsets, uint32_t* left_idx, uint32_t* right_idx,
+                            uint32_t* matched) {
+    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_right; row += gridDim.x * BLOCK) {
+        uint64_t pos = offsets[row];
+        uint32_t c = 0;
+        if (bit_at(rsel, row)) {
+            uint32_t owner;
+            const uint32_t slot = wide_table_find(T, B, P, rhashes[row], row, &owner);
+            if (slot != 0xFFFFFFFFu)
+                for (uint32_t l = T.head[slot]; l != 0; l = T.next[l - 1u]) {
+                    left_idx[pos] = l - 1u;
+                    right_idx[pos] = row;
+                    if (matched) atomicOr(&matched[(l - 1u) >> 5], 1u << ((l - 1u) & 31));
+                    ++pos;
+                    ++c;
+                }
+        }
+        if (right_outer && c == 0) { left_idx[pos] = 0xFFFFFFFFu; right_idx[pos] = row; }
+    }
+}
+
+// unique build keys: partner[] + selection bitmap + tile counts, as join_probe_match_kernel leaves them; one row per lane and pass
+// (every lane of a wave makes the same number of passes, so the ballot sees all 64)
+__global__ void __launch_bounds__(BLOCK)
+join_probe_match_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
+                             uint32_t n_right, int right_outer, uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
+    static_assert(SEL_TILE % 64 == 0, "the rows of one pass of a wave lie in one selection tile");
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_round = ((uint64_t)n_right + 63u) & ~(uint64_t)63;
+    const uint64_t wave_id = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (BLOCK / 64);
+    for (uint64_t wbase = wave_id * 64ull; wbase < n_round; wbase += n_waves * 64ull) {
+        const uint64_t row64 = wbase + lane;
+        const bool in = row64 < n_right;
+        const uint32_t row = (uint32_t)row64;
+        uint32_t m = 0xFFFFFFFFu;
+        if (in && bit_at(rsel, row)) wide_table_find(T, B, P, rhashes[row], row, &m);
+        if (matched && m != 0xFFFFFFFFu) atomicOr(&matched[m >> 5], 1u << (m & 31));
+        const bool emit = in && (right_outer || m != 0xFFFFFFFFu);
+        if (emit) partner[row] = m;
+        const uint64_t word = __ballot(emit);
+        if (lane == 0) {
+            bitmap[wbase >> 6] = word;
+            if (word) atomicAdd(&tile_counts[wbase / SEL_TILE], (uint32_t)__popcll(word));
+        }
+    }
+}
+
 // ---- the same for ONE Int64 / UInt64 key (TPC-H at SF1000: l_orderkey / o_orderkey are Int64): 16-byte slots
 // {key, build row + 1}.  The build claims a slot with a 32-bit CAS on the row word and compares against the key
 // COLUMN of the claiming row (immutable input), so no reader ever depends on a half-written slot; the key word is
@@ -594,6 +738,38 @@ hipError_t launch_join_probe_match(const LaunchCfg& cfg, const JoinTable& T, con
     hipError_t e = hipMemsetAsync(tile_counts, 0, n_tiles * 4, cfg.stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(join_probe_match_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel,
+                       n_right, right_outer ? 1 : 0, partner, bitmap, tile_counts, matched);
+    return hipGetLastError();
+}
+hipError_t launch_join_build_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
+                                  uint32_t n_left) {
+    if (n_left == 0) return hipSuccess;
+    hipLaunchKernelGGL(join_build_wide_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, build, hashes, sel, n_left);
+    return hipGetLastError();
+}
+hipError_t launch_join_probe_count_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* counts) {
+    if (n_right == 0) return hipSuccess;
+    hipLaunchKernelGGL(join_probe_count_wide_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel,
+                       n_right, right_outer ? 1 : 0, counts);
+    return hipGetLastError();
+}
+hipError_t launch_join_probe_emit_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                       const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, const uint64_t* offsets,
+                                       uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched) {
+    if (n_right == 0) return hipSuccess;
+    hipLaunchKernelGGL(join_probe_emit_wide_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel,
+                       n_right, right_outer ? 1 : 0, offsets, left_idx, right_idx, matched);
+    return hipGetLastError();
+}
+hipError_t launch_join_probe_match_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* partner,
+                                        uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
+    if (n_right == 0) return hipSuccess;
+    const size_t n_tiles = ((size_t)n_right + SEL_TILE - 1) / SEL_TILE;
+    hipError_t e = hipMemsetAsync(tile_counts, 0, n_tiles * 4, cfg.stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(join_probe_match_wide_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel,
                        n_right, right_outer ? 1 : 0, partner, bitmap, tile_counts, matched);
     return hipGetLastError();
 }

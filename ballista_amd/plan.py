@@ -96,6 +96,12 @@ class Context:
         declined every batch: plain sort, cut to k), "sort" (full-sort route: limit >= rows, or BHIP_NO_TOPK=1), "" before the first one"""
         return L.lib().bhip_ctx_sort_limit_form(self._h).decode()
 
+    def join_key_form(self):
+        """the table form of the hash-join build side most recently built or probed: "narrow" (integer key, unique build side),
+        "packed" (general table over 16-byte packed keys), "wide" (table over row hashes that compares the key columns: keys of
+        any width, or BHIP_JOIN_WIDE=1), "" before the first build"""
+        return L.lib().bhip_ctx_join_key_form(self._h).decode()
+
     def device_cus(self):
         """compute units of the device (the kernels size their grids by it)"""
         return int(L.lib().bhip_ctx_device_cus(self._h))

@@ -535,6 +535,11 @@ const char* bhip_ctx_lean_key_form(bhip_ctx* ctx);
  * too many candidates, a small batch, a first key it does not image — and the plain sort was cut to k), "sort" (the full-sort
  * route: the limit is not below the row count, or BHIP_NO_TOPK is set); "" before the first such execution; valid until the next call */
 const char* bhip_ctx_sort_limit_form(bhip_ctx* ctx);
+/* the table form of the HashJoinExec build side most recently built or probed on the context: "narrow" (one integer key or a pair
+ * of 4-byte integer keys, unique build side), "packed" (the general table over 16-byte packed keys), "wide" (the table over row
+ * hashes whose equality test reads the key columns: keys of any width; also reported when a probe batch whose keys outgrew the
+ * packed key went through the wide table built beside a packed one); "" before the first build; valid until the next call */
+const char* bhip_ctx_join_key_form(bhip_ctx* ctx);
 /* compute units of the context's device (what the kernels size their grids by) */
 int32_t bhip_ctx_device_cus(bhip_ctx* ctx);
 
