@@ -201,7 +201,23 @@ hipError_t launch_pack_key_pair(const LaunchCfg& cfg, const void* a, const void*
                                 uint64_t* validity_out);
 hipError_t launch_join_compact_staged(const LaunchCfg& cfg, const uint32_t* staging, const uint64_t* tile_off, uint64_t total,
                                       int64_t n_tiles, uint32_t* out, const uint32_t* staging2 = nullptr, uint32_t* out2 = nullptr);
-hipError_t launch_join_unmatched_flags(const LaunchCfg& cfg, const uint32_t* matched, uint32_t n_left, uint32_t* flags);
+// existence joins (kernels_hash.hip "existence joins"): the probe reads owner[] and the owner's key only, on any JoinTable.
+// matched != nullptr: the MARK form (Semi / Anti) — a hit sets the bit of the key's representative build row; bitmap / tile_counts
+// / anti are not used.  matched == nullptr: the SELECT form (RightSemi / RightAnti) — the selection bitmap of the probe rows with
+// (hit != anti) and its counts per SEL_TILE rows, the inputs of launch_select_indices; bits at and beyond n_right are 0.
+hipError_t launch_join_probe_exists(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right,
+                                    bool anti, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched);
+hipError_t launch_join_probe_exists_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                         const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool anti, uint64_t* bitmap,
+                                         uint32_t* tile_counts, uint32_t* matched);
+// flags[row] = (the bit of build row `row`'s representative in `matched`) ^ anti, `anti` for a row that `sel` deselects: what the scan
+// and launch_compact_flags turn into build rows.  direct: every row stands for itself (a unique build side; Left / Full, whose probes
+// mark every matched row) and T is not read; otherwise the row finds the slot of its own key.  merge: OR with what flags[] holds
+// (0 / 1 from an earlier launch with anti = false over another table of the same build rows) before `anti` applies.
+hipError_t launch_join_exists_flags(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* sel, const uint32_t* matched, uint32_t n_left, bool direct,
+                                    bool anti, bool merge, uint32_t* flags);
+hipError_t launch_join_exists_flags_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
+                                         const uint32_t* matched, uint32_t n_left, bool anti, bool merge, uint32_t* flags);
 hipError_t launch_compact_flags(const LaunchCfg& cfg, const uint32_t* flags, const uint64_t* offsets, uint32_t n, uint32_t* out);
 
 }  // namespace bhip

@@ -1,4 +1,4 @@
-// ops_join.cpp — HashJoinExec (Inner / Left / Right), left = build side.
+// ops_join.cpp — HashJoinExec (Inner / Left / Right / Full, and the existence joins Semi / Anti / RightSemi / RightAnti), left = build side.
 //
 // Reference: HashJoinExec::try_new(left, right, on: &[(String, String)], join_type) built at
 // rust/core/src/serde/physical_plan/from_proto.rs:253-276 (join types :268-272, key pairs by
@@ -6,6 +6,8 @@
 // collect-left mode: every task drains the whole left child and probes it with one right
 // partition.  Output schema = left fields then right fields, a right key column
 // dropped when it has the same name as its left partner (Appendix A).  Row order unspecified.
+// The existence joins put ONE side in the output, unchanged: Semi / Anti the build rows with / without a partner, RightSemi /
+// RightAnti the probe rows.  NULL keys never match, so Anti and RightAnti emit the rows that have one (NOT EXISTS semantics).
 #include <mutex>
 
 #include "../util_kernels.h"
@@ -31,12 +33,23 @@ struct JoinBuildSide {
     bool resid = false;             // two-column join by the first key; the second is compared on every match (ntable.resid_build)
 };
 
-static const char* join_name(int t) { return t == BHIP_JOIN_INNER ? "Inner" : (t == BHIP_JOIN_LEFT ? "Left" : "Right"); }
+static const char* join_name(int t) {
+    static const char* const names[] = {"Inner", "Left", "Right", "Full", "Semi", "Anti", "RightSemi", "RightAnti"};
+    return names[t];
+}
+// the answer is per BUILD row (the output holds left columns only) / per PROBE row (right columns only)
+static bool build_existence(int t) { return t == BHIP_JOIN_SEMI || t == BHIP_JOIN_ANTI; }
+static bool probe_existence(int t) { return t == BHIP_JOIN_RIGHT_SEMI || t == BHIP_JOIN_RIGHT_ANTI; }
 
 HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type)
     : left_(std::move(left)), right_(std::move(right)), on_(std::move(on)), join_type_(join_type) {
     ctx_ = left_->context();
-    if (join_type < BHIP_JOIN_INNER || join_type > BHIP_JOIN_RIGHT) fail(BHIP_ENOTIMPL, "Unsupported join type");
+    if (join_type < BHIP_JOIN_INNER || join_type > BHIP_JOIN_RIGHT_ANTI) fail(BHIP_ENOTIMPL, "Unsupported join type");
+    // a build row's fate depends on every probe row, and a stream sees one right partition (Left emits its unmatched rows once
+    // per task and stays that way; the types added after it do not inherit that)
+    if ((join_type == BHIP_JOIN_FULL || build_existence(join_type)) && right_->output_partitioning().count > 1)
+        fail(BHIP_ENOTIMPL, std::string(join_name(join_type)) + " join over a right child of " + std::to_string(right_->output_partitioning().count) +
+                                " partitions: put a MergeExec under the right child");
     const Schema& ls = *left_->schema();
     const Schema& rs = *right_->schema();
     for (auto& p : on_) {
@@ -48,17 +61,21 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
                                   dtype_name(ls.fields[li].dtype) + " vs " + dtype_name(rs.fields[ri].dtype) + ")");
     }
     auto s = std::make_shared<Schema>();
+    const bool left_nullable = join_type == BHIP_JOIN_RIGHT || join_type == BHIP_JOIN_FULL;
+    const bool right_nullable = join_type == BHIP_JOIN_LEFT || join_type == BHIP_JOIN_FULL;
     for (auto f : ls.fields) {
-        if (join_type == BHIP_JOIN_RIGHT) f.nullable = true;
+        if (probe_existence(join_type)) break;
+        if (left_nullable) f.nullable = true;
         s->fields.push_back(f);
     }
     for (size_t i = 0; i < rs.fields.size(); ++i) {
+        if (build_existence(join_type)) break;
         bool drop = false;
         for (auto& p : on_)
-            if (p.second == rs.fields[i].name && p.first == p.second) drop = true;
+            if (p.second == rs.fields[i].name && p.first == p.second && !probe_existence(join_type)) drop = true;
         if (drop) continue;
         Field f = rs.fields[i];
-        if (join_type == BHIP_JOIN_LEFT) f.nullable = true;
+        if (right_nullable) f.nullable = true;
         if (s->index_of(f.name) >= 0) fail(BHIP_EINVAL, "join output would have two columns named '" + f.name + "'");
         s->fields.push_back(f);
         right_cols_.push_back((int)i);
@@ -487,7 +504,9 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
     if (n > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "hash join build side of more than 2^31 rows per partition");
     const uint64_t cap = table_capacity((uint64_t)n);
     static const bool narrow_disabled = env_flag("BHIP_NO_NARROW_JOIN");
-    const int nkw = narrow_disabled ? 0 : narrow_key_width();
+    // the existence probes read the general table's owner words: no narrow structures for them
+    const bool existence = build_existence(join_type_) || probe_existence(join_type_);
+    const int nkw = narrow_disabled || existence ? 0 : narrow_key_width();
     bool narrow = false;
     if (nkw && n > 0) {
         const Schema& lsch = *bs->batch->schema;
@@ -614,7 +633,8 @@ struct ProbeOut {
 // what a tiled probe kernel leaves behind, in scratch: the selection bitmap of the emitting rows and their count per SEL_TILE rows,
 // and their partners.  The general table's kernel writes a partner per probe row.  The fused kernel owns whole tiles (it writes
 // every bitmap word of one) and, where a build column is read, stages each tile's emitting rows and their partners, so that one
-// compaction yields both index vectors with no pass over the bitmap (a semi-join stages nothing: it has only the bitmap to compact)
+// compaction yields both index vectors with no pass over the bitmap (a semi-join stages nothing: it has only the bitmap to compact).
+// The existence probe of the general table (RightSemi / RightAnti) writes the bitmap and the counts and no partners.
 struct TileSelection {
     const bool fused;
     const int64_t n, n_tiles;
@@ -624,13 +644,14 @@ struct TileSelection {
     uint64_t* total;
     void* scan_tmp;
     uint32_t *partner = nullptr, *staging = nullptr, *staging_rows = nullptr;
-    TileSelection(Temp& tmp, int64_t rows, bool fused_probe, bool stage) : fused(fused_probe), n(rows), n_tiles((rows + SEL_TILE - 1) / SEL_TILE) {
+    TileSelection(Temp& tmp, int64_t rows, bool fused_probe, bool stage, bool partners = true)
+        : fused(fused_probe), n(rows), n_tiles((rows + SEL_TILE - 1) / SEL_TILE) {
         bitmap = tmp.get<uint64_t>(fused ? (size_t)n_tiles * (SEL_TILE / 64) + 1 : (size_t)(n + 63) / 64 + 1);
         tile_counts = tmp.get<uint32_t>((size_t)n_tiles + 1);
         tile_off = tmp.get<uint64_t>((size_t)n_tiles + 1);
         total = tmp.get<uint64_t>(1);
         scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_tiles));
-        if (!fused) partner = tmp.get<uint32_t>((size_t)n + 1);
+        if (!fused && partners) partner = tmp.get<uint32_t>((size_t)n + 1);
         else if (stage) { staging = tmp.get<uint32_t>((size_t)n_tiles * SEL_TILE); staging_rows = tmp.get<uint32_t>((size_t)n_tiles * SEL_TILE); }
     }
 };
@@ -655,17 +676,24 @@ struct HashJoinExec::Probe {
     const Batch& L;
     const size_t n_lcols;
     const bool right_outer, left_outer, pair;
+    // Semi / Anti: the probe only marks (no output before the end of the stream); RightSemi / RightAnti: it only selects probe rows
+    const bool mark_only, select_only, anti;
+    const size_t n_lout;                 // left columns in the output (right output column k is column n_lout + k of the schema)
     bool need_left = false;
-    BufferPtr matched;                   // left join: one bit per build row some probe row matched
+    BufferPtr matched;                   // Left / Full: one bit per build row some probe row matched; Semi / Anti: per key, on its representative row
+    std::shared_ptr<const JoinBuildSide> sibling;   // the wide table beside a packed `bs`, once a batch of this stream went through it
     std::vector<std::string> rcols;
     SchemaPtr key_schema;                // the probe-side key columns alone, under their names
     std::vector<BatchPtr> out;
 
     Probe(const HashJoinExec& j, int part, const Exec& e, const std::vector<bool>& need, const std::vector<bool>& defer)
         : J(j), partition(part), ex(e), needed(need), deferrable(defer), cfg(e.cfg()), bs(j.build_side(e)), L(*bs->batch), n_lcols(L.cols.size()),
-          right_outer(j.join_type_ == BHIP_JOIN_RIGHT), left_outer(j.join_type_ == BHIP_JOIN_LEFT), pair(j.pair_keys()) {
-        for (size_t i = 0; i < n_lcols; ++i) need_left = need_left || needed[i];
-        if (left_outer) {
+          right_outer(j.join_type_ == BHIP_JOIN_RIGHT || j.join_type_ == BHIP_JOIN_FULL),
+          left_outer(j.join_type_ == BHIP_JOIN_LEFT || j.join_type_ == BHIP_JOIN_FULL), pair(j.pair_keys()),
+          mark_only(build_existence(j.join_type_)), select_only(probe_existence(j.join_type_)),
+          anti(j.join_type_ == BHIP_JOIN_ANTI || j.join_type_ == BHIP_JOIN_RIGHT_ANTI), n_lout(select_only ? 0 : n_lcols) {
+        for (size_t i = 0; i < n_lout; ++i) need_left = need_left || needed[i];
+        if (left_outer || mark_only) {
             matched = make_buffer(ex, (size_t)(L.n_rows / 32 + 2) * 4);
             HIP_CHECK(hipMemsetAsync(matched->ptr(), 0, (size_t)(L.n_rows / 32 + 2) * 4, ex.stream));
         }
@@ -677,10 +705,11 @@ struct HashJoinExec::Probe {
         }
         key_schema = ks;
     }
-    uint32_t* matched_bits() const { return left_outer ? matched->as<uint32_t>() : nullptr; }
+    uint32_t* matched_bits() const { return matched ? matched->as<uint32_t>() : nullptr; }
 
     // output batch from index pairs; o.src: the batch the right columns are gathered from (nullptr: they are NULL).  Columns no
-    // parent reads stay placeholders.
+    // parent reads stay placeholders.  The schema holds the left columns (n_lout of them: none for RightSemi / RightAnti, whose
+    // lidx is null) and then the right columns J.right_cols_ (none for Semi / Anti).
     // (lbuf / rbuf: the buffers that own lidx / ridx, when the caller has them — view columns keep them instead of a copy)
     void emit(const ProbeOut& o, const uint32_t* lidx, const uint32_t* ridx, int64_t n_out, const BufferPtr& lbuf = nullptr, const BufferPtr& rbuf = nullptr) {
         const Schema& os = *J.schema_;
@@ -694,7 +723,7 @@ struct HashJoinExec::Probe {
         // composed with this join's indices either way)
         std::vector<const Column*> lc[2], rc[2];
         std::vector<size_t> lpos[2], rpos[2];
-        for (size_t i = 0; i < n_lcols; ++i)
+        for (size_t i = 0; i < n_lout; ++i)
             if (needed[i]) { lc[deferrable[i] ? 1 : 0].push_back(&L.cols[i]); lpos[deferrable[i] ? 1 : 0].push_back(i); }
         for (int v = 0; v < 2; ++v) {
             if (lc[v].empty()) continue;
@@ -706,7 +735,7 @@ struct HashJoinExec::Probe {
             }
         }
         for (size_t k = 0; k < J.right_cols_.size(); ++k) {
-            const size_t oi = n_lcols + k;
+            const size_t oi = n_lout + k;
             if (!needed[oi]) continue;
             if (!o.src) { b->cols[oi] = null_column(ex, os.fields[oi].dtype, n_out); continue; }
             rc[deferrable[oi] ? 1 : 0].push_back(&o.src->cols[o.rmap ? (*o.rmap)[k] : J.right_cols_[k]]);
@@ -772,12 +801,30 @@ struct HashJoinExec::Probe {
                 side_keys(ex, probe, rcols, rkeys, rsel, has_rsel);
             } catch (const Error& e) {
                 if (!key_width_error(e)) throw;
-                t = J.wide_sibling(ex, *bs);
+                t = sibling = J.wide_sibling(ex, *bs);
             }
         }
         if (t->wide) side_hashes(ex, probe, rcols, rkeys, rsel, has_rsel, K);
         Temp tmp(ex);
         const uint64_t* rselp = has_rsel ? rsel->as<uint64_t>() : nullptr;
+        if (mark_only || select_only) {
+            // existence: one probe per row whatever the duplication (the slot's owner stands for its key).  Semi / Anti leave bits
+            // for emit_build_rows; RightSemi / RightAnti a selection of the probe rows, compacted as the unique build side's is
+            auto exists = [&](uint64_t* bitmap, uint32_t* tile_counts, uint32_t* mark) {
+                if (t->wide)
+                    TIMED_LAUNCH_N(ex, "join_probe_exists_wide", n_right,
+                                   launch_join_probe_exists_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, anti, bitmap,
+                                                                 tile_counts, mark));
+                else
+                    TIMED_LAUNCH_N(ex, "join_probe_exists", n_right,
+                                   launch_join_probe_exists(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, anti, bitmap, tile_counts, mark));
+            };
+            if (mark_only) { exists(nullptr, nullptr, matched_bits()); return; }
+            TileSelection s(tmp, n_right, false, false, false);
+            exists(s.bitmap, s.tile_counts, nullptr);
+            compact(tmp, s, o);
+            return;
+        }
         if (t->unique) {
             // one probe per row -> selection bitmap -> indices (the index pass of FilterExec)
             TileSelection s(tmp, n_right, false, false);
@@ -887,7 +934,7 @@ struct HashJoinExec::Probe {
         if (src_hj && !chain.pred && !join_views_disabled()) {
             std::vector<bool> need(chain.src->schema()->fields.size(), false);
             for (size_t k = 0; k < J.right_cols_.size(); ++k)
-                if (needed[n_lcols + k]) need[rmap[k]] = true;
+                if (needed[n_lout + k]) need[rmap[k]] = true;
             ss = open_join_below(*src_hj, partition, ex, need, key_src);
         } else {
             ss = chain.src->execute(partition, ex);
@@ -911,22 +958,44 @@ struct HashJoinExec::Probe {
         }
     }
 
-    // left join: the left rows no probe row matched, right columns NULL
-    void emit_unmatched_left() {
+    // the end of the stream, from the `matched` bits: the build rows without a partner (anti: Left / Full, with NULL right columns,
+    // and Anti) or with one (Semi), as one batch.  Left / Full marked every matched row; Semi / Anti marked the representative of
+    // every matched key, in `bs`'s table and — where a batch went through it — in the sibling's, whose representatives differ
+    void emit_build_rows() {
         const int64_t n_left = L.n_rows;
-        if (!left_outer || n_left == 0) return;
+        if (!(left_outer || mark_only) || n_left == 0) return;
         Temp tmp(ex);
         uint32_t* flags = tmp.get<uint32_t>((size_t)n_left + 1);
         uint64_t* offsets = tmp.get<uint64_t>((size_t)n_left + 1);
         uint64_t* total = tmp.get<uint64_t>(1);
         void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_left));
-        TIMED_LAUNCH(ex, "join_unmatched_flags", launch_join_unmatched_flags(cfg, matched->as<uint32_t>(), (uint32_t)n_left, flags));
+        const bool direct = left_outer || bs->unique;
+        const bool want_unmatched = left_outer || anti;
+        auto flags_of = [&](const JoinBuildSide& t, bool anti_now, bool merge) {
+            const uint64_t* sel = t.has_sel ? t.sel->as<uint64_t>() : nullptr;
+            if (direct || !t.wide) {
+                TIMED_LAUNCH_N(ex, "join_exists_flags", n_left,
+                               launch_join_exists_flags(cfg, t.table, sel, matched->as<uint32_t>(), (uint32_t)n_left, direct, anti_now, merge, flags));
+                return;
+            }
+            BufferPtr hashes, hsel;                 // the build rows' hashes are not kept after the build: once more, for this one pass
+            bool has_hsel;
+            WideKeyCols K;
+            std::vector<std::string> lcols;
+            for (auto& p : J.on_) lcols.push_back(p.first);
+            side_hashes(ex, L, lcols, hashes, hsel, has_hsel, K);
+            TIMED_LAUNCH_N(ex, "join_exists_flags_wide", n_left,
+                           launch_join_exists_flags_wide(cfg, t.table, t.wkeys, hashes->as<uint64_t>(), sel, matched->as<uint32_t>(), (uint32_t)n_left,
+                                                         anti_now, merge, flags));
+        };
+        if (sibling && !direct) flags_of(*sibling, false, false);
+        flags_of(*bs, want_unmatched, sibling && !direct);
         HIP_CHECK(exclusive_scan_u32_u64(ex.stream, flags, n_left, offsets, false, total, scan_tmp));
-        const uint64_t n_un = read_device(ex, total);
-        if (n_un) {
-            uint32_t* lidx = tmp.get<uint32_t>((size_t)n_un);
+        const uint64_t n_rows = read_device(ex, total);
+        if (n_rows) {
+            uint32_t* lidx = tmp.get<uint32_t>((size_t)n_rows);
             TIMED_LAUNCH(ex, "compact_flags", launch_compact_flags(cfg, flags, offsets, (uint32_t)n_left, lidx));
-            emit(ProbeOut{nullptr, nullptr, nullptr}, lidx, nullptr, (int64_t)n_un);
+            emit(ProbeOut{nullptr, nullptr, nullptr}, lidx, nullptr, (int64_t)n_rows);
         }
     }
 };
@@ -944,7 +1013,7 @@ StreamPtr HashJoinExec::execute_needed(int partition, const Exec& ex, const std:
     return StreamPtr(new LazyStream(schema_, [self, partition, ex, needed, deferrable]() {
         Probe p(*self, partition, ex, needed, deferrable);
         p.probe_right_side();
-        p.emit_unmatched_left();
+        p.emit_build_rows();
         return std::move(p.out);
     }));
 }

@@ -803,7 +803,7 @@ struct Decoder {
                     }
                     need_input(left, "HashJoinExecNode");
                     need_input(right, "HashJoinExecNode");
-                    if (jt > 2) fail(BHIP_EINVAL, "Received a HashJoinNode message with unknown JoinType " + std::to_string(jt));
+                    if (jt > BHIP_JOIN_ANTI) fail(BHIP_EINVAL, "Received a HashJoinNode message with unknown JoinType " + std::to_string(jt));
                     if (on.empty()) fail(BHIP_EINVAL, "HashJoinExec needs at least one key pair");
                     out = std::make_shared<HashJoinExec>(left, right, on, (int)jt);
                 } break;

@@ -436,6 +436,104 @@ join_probe_match_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* r
     }
 }
 
+// set bit `row` of `matched` — read first: within a stream bits only go 0 -> 1, so a stale read costs one redundant atomic and never
+// a wrong answer, while a hot key would otherwise send every one of its probe rows to the memory side for the same word
+__device__ inline void mark_once(uint32_t* matched, uint32_t row) {
+    const uint32_t bit = 1u << (row & 31);
+    if (!(matched[row >> 5] & bit)) atomicOr(&matched[row >> 5], bit);
+}
+
+// ---- existence joins: "is there a partner", never "which partners".  The slot's owner row is the representative of its key
+// whether or not the build side is unique, so only owner[] and the owner's key are read — never head[] or next[] — on any JoinTable.
+//   MARK   (Semi / Anti: the answer is per BUILD row) a hit sets the representative's bit in `matched`; nothing else is written
+//          (join_exists_flags_kernel turns the bits into build rows at the end of the stream)
+//   SELECT (RightSemi / RightAnti: per PROBE row) the bitmap word of every 64 rows = rows with (hit != anti), and the counts per
+//          SEL_TILE rows: the inputs of launch_select_indices.  A row deselected by rsel (NULL key) is a miss, so Anti emits it.
+// Four rows per lane and pass, as join_probe_match_kernel: keys, slot owners, then the owners' keys of all four in flight together.
+template <bool SELECT>
+__global__ void __launch_bounds__(BLOCK)
+join_probe_exists_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right, int anti, uint64_t* bitmap,
+                         uint32_t* tile_counts, uint32_t* matched) {
+    constexpr int PROBE_ROWS = 4;
+    static_assert(SEL_TILE % (64 * PROBE_ROWS) == 0, "the rows of one pass of a wave lie in one selection tile");
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_round = ((uint64_t)n_right + 63u) & ~(uint64_t)63;
+    const uint64_t wave_rows = 64ull * PROBE_ROWS;
+    const uint64_t wave_id = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (BLOCK / 64);
+    const ulonglong2* rk = reinterpret_cast<const ulonglong2*>(rkeys128);
+    const ulonglong2* lk = reinterpret_cast<const ulonglong2*>(T.keys128);
+    for (uint64_t wbase = wave_id * wave_rows; wbase < n_round; wbase += n_waves * wave_rows) {
+        ulonglong2 key[PROBE_ROWS];
+        uint64_t slot[PROBE_ROWS], tag[PROBE_ROWS], owner[PROBE_ROWS];
+        bool in[PROBE_ROWS], live[PROBE_ROWS], hit[PROBE_ROWS];
+#pragma unroll
+        for (int k = 0; k < PROBE_ROWS; ++k) {
+            const uint64_t row64 = wbase + 64ull * k + lane;
+            in[k] = row64 < n_right;
+            live[k] = in[k] && bit_at(rsel, (uint32_t)row64);
+            key[k] = live[k] ? rk[row64] : ulonglong2{0ull, 0ull};
+            hit[k] = false;
+        }
+#pragma unroll
+        for (int k = 0; k < PROBE_ROWS; ++k) {
+            const uint64_t h = hash_key(Key128{key[k].x, key[k].y});
+            slot[k] = h & T.mask;
+            tag[k] = h >> 32;
+            owner[k] = live[k] ? T.owner[slot[k]] : 0ull;
+        }
+#pragma unroll
+        for (int k = 0; k < PROBE_ROWS; ++k) {
+            while (owner[k] != 0) {
+                if ((owner[k] >> 32) == tag[k]) {
+                    const ulonglong2 ok = lk[(uint32_t)owner[k] - 1u];
+                    if (ok.x == key[k].x && ok.y == key[k].y) { hit[k] = true; break; }
+                }
+                slot[k] = (slot[k] + 1) & T.mask;
+                owner[k] = T.owner[slot[k]];
+            }
+            if (!SELECT && hit[k]) mark_once(matched, (uint32_t)owner[k] - 1u);
+        }
+        if (SELECT) {
+            uint32_t emitted = 0;
+#pragma unroll
+            for (int k = 0; k < PROBE_ROWS; ++k) {
+                const uint64_t word = __ballot(in[k] && (hit[k] != (anti != 0)));
+                if (lane == 0 && wbase + 64ull * k < n_round) bitmap[(wbase >> 6) + k] = word;
+                emitted += (uint32_t)__popcll(word);
+            }
+            if (lane == 0 && emitted) atomicAdd(&tile_counts[wbase / SEL_TILE], emitted);
+        }
+    }
+}
+
+// the build rows of a Semi (anti = 0) / Anti (anti = 1) join from the bits the MARK probe left: flags[row] = 0 / 1, for the scan and
+// compact_flags.  A row deselected by `sel` (NULL key) has no partner.  direct: every row is its own representative (a unique build
+// side; or bits that the pair-enumerating kernels set on every matched row: Left / Full).  Otherwise the row finds the slot of its
+// own key again and reads the owner's bit — O(build rows) whatever the duplication; walking head / next from the owner would be one
+// thread's chain of dependent loads per key.  merge: flags[] already holds the answers of another table over the same build rows
+// (the wide sibling of a packed table: their representatives differ), OR-ed in before `anti` applies.
+__device__ inline uint32_t exists_flag(const uint32_t* matched, uint32_t rep, const uint32_t* flags, uint32_t row, int merge, int anti) {
+    uint32_t e = rep != 0xFFFFFFFFu ? (matched[rep >> 5] >> (rep & 31)) & 1u : 0u;
+    if (merge) e |= flags[row];
+    return e ^ (uint32_t)anti;
+}
+__global__ void __launch_bounds__(BLOCK)
+join_exists_flags_kernel(JoinTable T, const uint64_t* sel, const uint32_t* matched, uint32_t n_left, int direct, int anti, int merge,
+                         uint32_t* flags) {
+    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK) {
+        uint32_t rep = 0xFFFFFFFFu;
+        if (bit_at(sel, row)) {
+            rep = row;
+            if (!direct) {
+                const uint32_t slot = table_find(T, Key128{T.keys128[2ull * row], T.keys128[2ull * row + 1]});
+                rep = slot != 0xFFFFFFFFu ? (uint32_t)T.owner[slot] - 1u : 0xFFFFFFFFu;
+            }
+        }
+        flags[row] = exists_flag(matched, rep, flags, row, merge, anti);
+    }
+}
+
 // ---- narrow keys: ONE Int32 / Date32 key column and a unique build side (the primary-key joins of TPC-H).
 // The slot holds the key and the build row together (key | (row + 1) << 32), so a probe step is ONE random
 // 8-byte read instead of a slot read followed by a dependent read of the 16-byte packed key; no packed keys are
@@ -665,6 +763,46 @@ join_probe_match_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols
     }
 }
 
+// the existence probe (join_probe_exists_kernel: MARK / SELECT) over keys of any width; one row per lane and pass, as the kernel above
+template <bool SELECT>
+__global__ void __launch_bounds__(BLOCK)
+join_probe_exists_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
+                              uint32_t n_right, int anti, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
+    static_assert(SEL_TILE % 64 == 0, "the rows of one pass of a wave lie in one selection tile");
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_round = ((uint64_t)n_right + 63u) & ~(uint64_t)63;
+    const uint64_t wave_id = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (BLOCK / 64);
+    for (uint64_t wbase = wave_id * 64ull; wbase < n_round; wbase += n_waves * 64ull) {
+        const uint64_t row64 = wbase + lane;
+        const bool in = row64 < n_right;
+        const uint32_t row = (uint32_t)row64;
+        uint32_t m = 0xFFFFFFFFu;
+        if (in && bit_at(rsel, row)) wide_table_find(T, B, P, rhashes[row], row, &m);
+        const bool hit = m != 0xFFFFFFFFu;
+        if (!SELECT) {
+            if (hit) mark_once(matched, m);
+        } else {
+            const uint64_t word = __ballot(in && (hit != (anti != 0)));
+            if (lane == 0) {
+                bitmap[wbase >> 6] = word;
+                if (word) atomicAdd(&tile_counts[wbase / SEL_TILE], (uint32_t)__popcll(word));
+            }
+        }
+    }
+}
+
+// join_exists_flags_kernel for a wide table that is not unique: the row's hash finds the slot, the key columns confirm it
+__global__ void __launch_bounds__(BLOCK)
+join_exists_flags_wide_kernel(JoinTable T, const WideKeyCols B, const uint64_t* hashes, const uint64_t* sel, const uint32_t* matched,
+                              uint32_t n_left, int anti, int merge, uint32_t* flags) {
+    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK) {
+        uint32_t rep = 0xFFFFFFFFu;
+        if (bit_at(sel, row)) wide_table_find(T, B, B, hashes[row], row, &rep);
+        flags[row] = exists_flag(matched, rep, flags, row, merge, anti);
+    }
+}
+
 // ---- the same for ONE Int64 / UInt64 key (TPC-H at SF1000: l_orderkey / o_orderkey are Int64): 16-byte slots
 // {key, build row + 1}.  The build claims a slot with a 32-bit CAS on the row word and compares against the key
 // COLUMN of the claiming row (immutable input), so no reader ever depends on a half-written slot; the key word is
@@ -688,12 +826,6 @@ join_build_narrow64_kernel(NarrowJoinTable T, const uint64_t* keys, const uint64
             slot = (slot + 1) & T.mask;
         }
     }
-}
-
-__global__ void __launch_bounds__(BLOCK)
-join_unmatched_flags_kernel(const uint32_t* matched, uint32_t n_left, uint32_t* flags) {
-    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK)
-        flags[row] = ((matched[row >> 5] >> (row & 31)) & 1u) ? 0u : 1u;
 }
 
 __global__ void __launch_bounds__(BLOCK)
@@ -800,9 +932,47 @@ hipError_t launch_join_key_present(const LaunchCfg& cfg, const uint32_t* keys, c
     hipLaunchKernelGGL(join_key_present_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, keys, sel, n, kmin, present);
     return hipGetLastError();
 }
-hipError_t launch_join_unmatched_flags(const LaunchCfg& cfg, const uint32_t* matched, uint32_t n_left, uint32_t* flags) {
+hipError_t launch_join_probe_exists(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right,
+                                    bool anti, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
+    if (n_right == 0) return hipSuccess;
+    const dim3 grid(grid_rows(cfg, n_right));
+    if (matched) {
+        hipLaunchKernelGGL(join_probe_exists_kernel<false>, grid, dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel, n_right, 0, nullptr, nullptr, matched);
+        return hipGetLastError();
+    }
+    hipError_t e = hipMemsetAsync(tile_counts, 0, (((size_t)n_right + SEL_TILE - 1) / SEL_TILE) * 4, cfg.stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(join_probe_exists_kernel<true>, grid, dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel, n_right, anti ? 1 : 0, bitmap, tile_counts, nullptr);
+    return hipGetLastError();
+}
+hipError_t launch_join_probe_exists_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
+                                         const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool anti, uint64_t* bitmap,
+                                         uint32_t* tile_counts, uint32_t* matched) {
+    if (n_right == 0) return hipSuccess;
+    const dim3 grid(grid_rows(cfg, n_right));
+    if (matched) {
+        hipLaunchKernelGGL(join_probe_exists_wide_kernel<false>, grid, dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel, n_right, 0, nullptr,
+                           nullptr, matched);
+        return hipGetLastError();
+    }
+    hipError_t e = hipMemsetAsync(tile_counts, 0, (((size_t)n_right + SEL_TILE - 1) / SEL_TILE) * 4, cfg.stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(join_probe_exists_wide_kernel<true>, grid, dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel, n_right, anti ? 1 : 0,
+                       bitmap, tile_counts, nullptr);
+    return hipGetLastError();
+}
+hipError_t launch_join_exists_flags(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* sel, const uint32_t* matched, uint32_t n_left, bool direct,
+                                    bool anti, bool merge, uint32_t* flags) {
     if (n_left == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_unmatched_flags_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, matched, n_left, flags);
+    hipLaunchKernelGGL(join_exists_flags_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, sel, matched, n_left, direct ? 1 : 0,
+                       anti ? 1 : 0, merge ? 1 : 0, flags);
+    return hipGetLastError();
+}
+hipError_t launch_join_exists_flags_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
+                                         const uint32_t* matched, uint32_t n_left, bool anti, bool merge, uint32_t* flags) {
+    if (n_left == 0) return hipSuccess;
+    hipLaunchKernelGGL(join_exists_flags_wide_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, build, hashes, sel, matched, n_left,
+                       anti ? 1 : 0, merge ? 1 : 0, flags);
     return hipGetLastError();
 }
 hipError_t launch_compact_flags(const LaunchCfg& cfg, const uint32_t* flags, const uint64_t* offsets, uint32_t n, uint32_t* out) {

@@ -32,6 +32,7 @@ NP_DTYPE = {E.INT32: np.int32, E.INT64: np.int64, E.UINT8: np.uint8, E.UINT64: n
 
 PARTIAL, FINAL = "Partial", "Final"
 INNER, LEFT, RIGHT = "Inner", "Left", "Right"
+FULL, SEMI, ANTI, RIGHT_SEMI, RIGHT_ANTI = "Full", "Semi", "Anti", "RightSemi", "RightAnti"
 
 
 class Partitioning:
@@ -844,9 +845,10 @@ class HashAggregateExec(ExecutionPlan):
 
 class HashJoinExec(ExecutionPlan):
     """HashJoinExec::try_new(left, right, on: &[(String, String)], join_type)  (from_proto.rs:253-276);
-    left is the build side."""
+    left is the build side.  SEMI / ANTI: the left rows with / without a partner (left fields only); RIGHT_SEMI / RIGHT_ANTI:
+    the right rows (right fields only).  FULL, SEMI and ANTI need a right child of one partition (MergeExec)."""
 
-    _JT = {INNER: 0, LEFT: 1, RIGHT: 2}
+    _JT = {INNER: 0, LEFT: 1, RIGHT: 2, FULL: 3, SEMI: 4, ANTI: 5, RIGHT_SEMI: 6, RIGHT_ANTI: 7}
 
     def __init__(self, left: ExecutionPlan, right: ExecutionPlan, on: Sequence[Tuple[str, str]], join_type: str = INNER):
         if join_type not in self._JT:

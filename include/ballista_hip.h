@@ -243,7 +243,14 @@ typedef struct {
 } bhip_sort_expr;
 
 typedef enum { BHIP_AGG_PARTIAL = 0, BHIP_AGG_FINAL = 1 } bhip_agg_mode;       /* from_proto.rs:181-184 */
-typedef enum { BHIP_JOIN_INNER = 0, BHIP_JOIN_LEFT = 1, BHIP_JOIN_RIGHT = 2 } bhip_join_type; /* :268-272 */
+/* HashJoinExec join types; left is the build side.  0-2 are the wire values of from_proto.rs:268-272; FULL / SEMI / ANTI carry the
+   wire values of the JoinType enum that followed it (3, 4, 5) and decode from a plan; RIGHT_SEMI / RIGHT_ANTI have no wire value
+   and are reached through bhip_plan_hash_join only.  SEMI / ANTI: the left rows with / without a partner, left fields only;
+   RIGHT_SEMI / RIGHT_ANTI: the right rows, right fields only.  NULL keys never match (ANTI emits the rows that have one). */
+typedef enum {
+    BHIP_JOIN_INNER = 0, BHIP_JOIN_LEFT = 1, BHIP_JOIN_RIGHT = 2, BHIP_JOIN_FULL = 3, BHIP_JOIN_SEMI = 4, BHIP_JOIN_ANTI = 5,
+    BHIP_JOIN_RIGHT_SEMI = 6, BHIP_JOIN_RIGHT_ANTI = 7
+} bhip_join_type;
 typedef enum {                                                                /* from_proto.rs:143-158 */
     BHIP_PART_UNKNOWN = 0, BHIP_PART_ROUND_ROBIN = 1, BHIP_PART_HASH = 2
 } bhip_partitioning;
