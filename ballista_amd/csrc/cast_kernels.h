@@ -1,0 +1,20 @@
+// cast_kernels.h — launchers of kernels_cast.hip (internal C++ interface): CAST between Utf8 and the fixed-width types.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kernels.h"
+
+namespace bhip {
+
+constexpr uint32_t CAST_STATUS_DECLINED = 1u;       // a float string outside the exactly rounded path (cast_text.h)
+
+// CAST(<Utf8 column> AS to): n values at `out` (a Boolean target: the bitmap) and n validity bits.  Both bitmaps are written as
+// whole 64-bit words, (n + 63) / 64 of them.  *status gets CAST_STATUS_DECLINED OR-ed in; only a float target can set it.
+hipError_t launch_cast_parse(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int to, void* out, uint64_t* validity, uint32_t* status);
+
+// CAST(<fixed-width column> AS Utf8): lengths first, then — after a scan — the bytes.  validity_out (may be null): the result's
+// validity in whole 64-bit words, for the one source type whose values can have no text (a Date32 outside 0000 .. 9999).
+hipError_t launch_cast_format_lengths(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, uint32_t* lengths, uint64_t* validity_out);
+hipError_t launch_cast_format_write(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, const int32_t* out_offsets, uint8_t* out);
+
+}  // namespace bhip

@@ -1,6 +1,8 @@
 // expr.cpp — expression parsing, typing and lowering to VM programs (see expr.hpp).
 #include "expr.hpp"
 
+#include "../cast_text.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -398,6 +400,8 @@ bool expr_nullable(const ExprPtr& e, const Schema& schema) {
         case BHIP_EXPR_CAST: {
             // a cast that can fall outside the target's range yields NULLs (float -> integer, integer -> narrower integer)
             const int from = expr_type(e->args[0], schema);
+            if (from == DT_UTF8 && e->dtype != DT_UTF8) return true;                // a string that is no value of the type
+            if (from == DT_DATE32 && e->dtype == DT_UTF8) return true;              // a day outside 0000-01-01 .. 9999-12-31
             if (dt_is_float(from) && !dt_is_float(e->dtype)) return true;
             if (dtype_width(e->dtype) && dtype_width(from) && !dt_is_float(e->dtype) && from != e->dtype) return true;
             return expr_nullable(e->args[0], schema);
@@ -550,18 +554,6 @@ Operand ProgramBuilder::compile(const ExprPtr& e) {
 
 static int class_of(int dtype) { return dt_is_float(dtype) ? VC_F64 : (dtype == DT_BOOLEAN ? VC_BOOL : VC_I64); }
 
-static int64_t parse_date(const std::string& s) {
-    int y, m, d;
-    if (sscanf(s.c_str(), "%d-%d-%d", &y, &m, &d) != 3) fail(BHIP_EEXEC, "Cannot cast string '" + s + "' to Date32");
-    // days from civil (proleptic Gregorian)
-    y -= m <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const unsigned yoe = (unsigned)(y - era * 400);
-    const unsigned doy = (153u * (unsigned)(m + (m > 2 ? -3 : 9)) + 2u) / 5u + (unsigned)d - 1u;
-    const unsigned doe = yoe * 365u + yoe / 4u - yoe / 100u + doy;
-    return era * 146097 + (int64_t)doe - 719468;
-}
-
 // multiplier between two temporal types with a common epoch (Date32 days, Date64 ms, Timestamp s/ms/us/ns); 0 = no such cast
 static int64_t temporal_units_per_day(int t) {
     switch (t) {
@@ -579,6 +571,8 @@ static int64_t temporal_units_per_day(int t) {
 Operand ProgramBuilder::compile_cast(const Operand& x, int to) {
     const int from = x.dtype;
     if (from == to) return x;
+    // a cast with Utf8 on one side never reaches the VM: it is evaluated as a column (host/utf8_exprs.cpp), a literal is folded in
+    // compile_uncached.  What arrives here all the same is an internal error, reported like the refusal it used to be.
     if (x.is_utf8_col || from == DT_UTF8 || to == DT_UTF8) fail(BHIP_ENOTIMPL, std::string("cast ") + dtype_name(from) + " -> " + dtype_name(to));
     // constant folding of numeric literals (what DataFusion's planner-inserted casts amount to)
     if (x.is_lit) {
@@ -790,13 +784,21 @@ Operand ProgramBuilder::compile_uncached(const ExprPtr& ep) {
         case BHIP_EXPR_BINARY: return compile_binary(e);
         case BHIP_EXPR_CAST: {
             const ExprPtr& x = e.args[0];
-            if (x->kind == BHIP_EXPR_LITERAL && x->dtype == DT_UTF8 && e.dtype == DT_DATE32 && !x->is_null) {
-                Operand o;
-                o.is_lit = true;
-                o.dtype = DT_DATE32;
-                o.vclass = VC_I64;
-                o.index = literal_index((uint64_t)parse_date(x->name));
-                return o;
+            if (x->kind == BHIP_EXPR_LITERAL && x->dtype == DT_UTF8 && !x->is_null && cast_parse_supported(e.dtype)) {
+                // CAST('1994-01-01' AS Date32), CAST('42' AS Int64): folded here, by the routine the cast kernels run (cast_text.h)
+                auto l = std::make_shared<Expr>();
+                l->kind = BHIP_EXPR_LITERAL;
+                l->dtype = e.dtype;
+                uint64_t bits = 0;
+                const CastPtrReader rd{reinterpret_cast<const uint8_t*>(x->name.data())};
+                const int r = cast_parse(rd, 0, (int64_t)x->name.size(), e.dtype, bits);
+                if (r == CAST_DECLINED)
+                    fail(BHIP_ENOTIMPL, std::string("cast Utf8 -> ") + dtype_name(e.dtype) + ": '" + x->name + "' is outside the exactly rounded range");
+                l->is_null = r != CAST_VALUE;                   // arrow: a string that is no value of the type is NULL
+                if (e.dtype == DT_FLOAT64) l->f64 = cast_bits_f64(bits);
+                else if (e.dtype == DT_FLOAT32) l->f64 = (double)cast_bits_f32((uint32_t)bits);
+                else l->i64 = (int64_t)bits;
+                return compile(l);
             }
             return compile_cast(compile(x), e.dtype);
         }

@@ -97,11 +97,11 @@ HashAggregateExec::HashAggregateExec(int mode, std::vector<std::pair<ExprPtr, st
     }
     schema_ = s;
     // string nodes in the expressions, MIN / MAX over Utf8: run_strings (ops_agg_wide.cpp)
-    for (auto& g : group_) strings_ = strings_ || has_utf8_node(g.first, in) || (g.first->kind == BHIP_EXPR_LITERAL && g.first->dtype == DT_UTF8);
+    for (auto& g : group_) strings_ = strings_ || has_lowered_node(g.first, in) || (g.first->kind == BHIP_EXPR_LITERAL && g.first->dtype == DT_UTF8);
     size_t sp = group_.size();
     for (auto& a : aggr_) {
         if (mode == BHIP_AGG_PARTIAL) {
-            strings_ = strings_ || has_utf8_node(a.arg, in);
+            strings_ = strings_ || has_lowered_node(a.arg, in);
             if ((a.fn == BHIP_AGG_MIN || a.fn == BHIP_AGG_MAX) && expr_type(a.arg, in) == DT_UTF8) strings_ = true;
         } else {
             if ((a.fn == BHIP_AGG_MIN || a.fn == BHIP_AGG_MAX) && in.fields[sp].dtype == DT_UTF8) strings_ = true;
@@ -146,14 +146,14 @@ FusedInput fuse_below(const PlanPtr& input, std::vector<ExprPtr> group, std::vec
     f.args = std::move(args);
     for (;;) {
         if (auto* flt = dynamic_cast<const FilterExec*>(f.source.get())) {
-            if (has_utf8_node(flt->predicate(), *flt->input()->schema())) break;      // string nodes: the filter runs on its own (utf8_exprs.cpp)
+            if (has_lowered_node(flt->predicate(), *flt->input()->schema())) break;      // string nodes: the filter runs on its own (utf8_exprs.cpp)
             f.predicate = f.predicate ? make_binary(flt->predicate(), "And", f.predicate) : flt->predicate();
             f.source = flt->input();
         } else if (auto* co = dynamic_cast<const CoalesceBatchesExec*>(f.source.get())) {
             f.source = co->input();
         } else if (auto* pr = dynamic_cast<const ProjectionExec*>(f.source.get())) {
             bool strings = false;
-            for (auto& en : pr->exprs()) strings = strings || has_utf8_node(en.first, *pr->input()->schema()) || (en.first->kind == BHIP_EXPR_LITERAL && en.first->dtype == DT_UTF8);
+            for (auto& en : pr->exprs()) strings = strings || has_lowered_node(en.first, *pr->input()->schema()) || (en.first->kind == BHIP_EXPR_LITERAL && en.first->dtype == DT_UTF8);
             if (strings) break;
             std::map<std::string, ExprPtr> subst;
             for (auto& en : pr->exprs()) subst[en.second] = en.first;

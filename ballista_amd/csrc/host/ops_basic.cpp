@@ -328,7 +328,7 @@ BatchPtr slice_head(const Exec& ex, const Batch& in, int64_t n) {
 
 // ---- filter ------------------------------------------------------------------------------------------
 int64_t filter_indices(const Exec& ex, const Batch& in, const ExprPtr& predicate, BufferPtr& indices_out) {
-    if (has_utf8_node(predicate, *in.schema)) {
+    if (has_lowered_node(predicate, *in.schema)) {
         // lower(s) = 'x', CASE ... THEN 'a' ... : the string nodes become columns first
         Utf8Lowering low(*in.schema);
         const ExprPtr p2 = low.rewrite(predicate);
@@ -490,7 +490,7 @@ BatchPtr project_batch(const Exec& ex, const Batch& in, const std::vector<std::p
                        const SchemaPtr& schema) {
     {
         bool strings = false;
-        for (auto& en : exprs) strings = strings || has_utf8_node(en.first, *in.schema) || (en.first->kind == BHIP_EXPR_LITERAL && en.first->dtype == DT_UTF8);
+        for (auto& en : exprs) strings = strings || has_lowered_node(en.first, *in.schema) || (en.first->kind == BHIP_EXPR_LITERAL && en.first->dtype == DT_UTF8);
         if (strings) {
             Utf8Lowering low(*in.schema);
             std::vector<std::pair<ExprPtr, std::string>> e2;

@@ -318,14 +318,15 @@ int64_t filter_indices(const Exec& ex, const Batch& in, const ExprPtr& predicate
 
 // expressions that produce Utf8 values (lower / upper / trim / ltrim / rtrim, CASE with string branches, string literals as
 // output columns) are evaluated as extra Utf8 columns of the input batch; the rest of the expression goes to the VM with those
-// nodes replaced by column references (utf8_exprs.cpp)
-bool has_utf8_node(const ExprPtr& e, const Schema& schema);
+// nodes replaced by column references (utf8_exprs.cpp).  CAST to and from Utf8 goes the same way: CAST(x AS Utf8) is one more
+// string-producing node, CAST(<Utf8 expression> AS T) an extra column of type T — "lowered" = evaluated as an extra column.
+bool has_lowered_node(const ExprPtr& e, const Schema& schema);
 class Utf8Lowering {
 public:
     explicit Utf8Lowering(const Schema& in);
     ExprPtr rewrite(const ExprPtr& e, bool output = false);       // output: `e` is a whole output column (a bare string literal counts)
     bool any() const { return !nodes_.empty(); }
-    SchemaPtr schema() const;                                     // the input's fields + one Utf8 field per node
+    SchemaPtr schema() const;                                     // the input's fields + one field per node, of the node's type
     void validate() const;                                        // BHIP_ENOTIMPL for a node this layer cannot evaluate (plan time)
     BatchPtr apply(const Exec& ex, const Batch& in) const;        // the input's columns + the evaluated nodes
 private:

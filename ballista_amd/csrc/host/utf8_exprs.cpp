@@ -5,30 +5,49 @@
 // each as an arrow kernel producing a StringArray; here each such node becomes ONE extra Utf8 column of the input batch
 // (kernels_str.hip: lengths -> scan -> bytes), and the expression around it — comparisons, LIKE, group / sort keys, the other
 // output columns — goes to the expression VM with the node replaced by a reference to that column.
+//
+// CAST to and from Utf8 (kernels_cast.hip; the grammar: cast_text.h) takes the same road in both directions:
+// CAST(x AS Utf8) of a fixed-width x is one more string-producing node, and CAST(<Utf8 expression> AS T) is an extra column too —
+// of type T.  So a lowered node is "an expression evaluated as an extra column of its own type".
+#include "../cast_kernels.h"
+#include "../cast_text.h"
 #include "../str_kernels.h"
 #include "../util_kernels.h"
 #include "plan.hpp"
 
 namespace bhip {
 
+// CAST(x AS Utf8), x of another type
+static bool cast_to_utf8(const ExprPtr& e, const Schema& schema) {
+    return e->kind == BHIP_EXPR_CAST && e->dtype == DT_UTF8 && expr_type(e->args[0], schema) != DT_UTF8;
+}
+// CAST(<Utf8 expression> AS T), T another type.  (A Utf8 literal folds in the VM's compiler instead: host/expr.cpp.)
+static bool cast_from_utf8(const ExprPtr& e, const Schema& schema) {
+    if (e->kind != BHIP_EXPR_CAST || e->dtype == DT_UTF8 || expr_type(e->args[0], schema) != DT_UTF8) return false;
+    const Expr& x = *e->args[0];
+    return !(x.kind == BHIP_EXPR_LITERAL && !x.is_null);
+}
+
 static bool produces_utf8(const ExprPtr& e, const Schema& schema) {
     if (e->kind == BHIP_EXPR_SCALAR_FN) return str_fn(e->name) >= 0 || sha_fn(e->name) != 0;
     if (e->kind == BHIP_EXPR_CASE) return expr_type(e, schema) == DT_UTF8;
+    return cast_to_utf8(e, schema);
+}
+
+bool has_lowered_node(const ExprPtr& e, const Schema& schema) {
+    if (produces_utf8(e, schema) || cast_from_utf8(e, schema)) return true;
+    for (auto& a : e->args)
+        if (has_lowered_node(a, schema)) return true;
     return false;
 }
 
-bool has_utf8_node(const ExprPtr& e, const Schema& schema) {
-    if (produces_utf8(e, schema)) return true;
-    for (auto& a : e->args)
-        if (has_utf8_node(a, schema)) return true;
-    return false;
-}
+static std::string cast_name(int from, int to) { return std::string("cast ") + dtype_name(from) + " -> " + dtype_name(to); }
 
 Utf8Lowering::Utf8Lowering(const Schema& in) : in_(in) {}
 
 ExprPtr Utf8Lowering::rewrite(const ExprPtr& e, bool output) {
     const bool lit = output && e->kind == BHIP_EXPR_LITERAL && e->dtype == DT_UTF8;
-    if (lit || produces_utf8(e, in_)) {
+    if (lit || produces_utf8(e, in_) || cast_from_utf8(e, in_)) {
         const std::string text = e->to_string();
         for (size_t i = 0; i < nodes_.size(); ++i)
             if (nodes_[i]->to_string() == text) return make_column(names_[i]);
@@ -45,7 +64,7 @@ ExprPtr Utf8Lowering::rewrite(const ExprPtr& e, bool output) {
 
 SchemaPtr Utf8Lowering::schema() const {
     auto s = std::make_shared<Schema>(in_);
-    for (size_t i = 0; i < nodes_.size(); ++i) s->fields.push_back(Field{names_[i], DT_UTF8, expr_nullable(nodes_[i], in_)});
+    for (size_t i = 0; i < nodes_.size(); ++i) s->fields.push_back(Field{names_[i], expr_type(nodes_[i], in_), expr_nullable(nodes_[i], in_)});
     return s;
 }
 
@@ -177,6 +196,66 @@ Column eval_case(const Exec& ex, const Batch& in, const Expr& e) {
     return out;
 }
 
+// CAST(x AS Utf8): x as a temporary fixed-width column (any expression the VM evaluates, lowered nodes of its own included),
+// then lengths -> scan -> bytes.  A literal is written on the host, by the same cast_format.
+Column eval_cast_format(const Exec& ex, const Batch& in, const Expr& e) {
+    const ExprPtr& x = e.args[0];
+    const int from = expr_type(x, *in.schema);
+    if (!cast_format_supported(from)) fail(BHIP_ENOTIMPL, cast_name(from, DT_UTF8));
+    const int64_t n = in.n_rows;
+    if (x->kind == BHIP_EXPR_LITERAL) {
+        Expr lit;
+        lit.kind = BHIP_EXPR_LITERAL;
+        lit.dtype = DT_UTF8;
+        uint8_t buf[CAST_TEXT_MAX];
+        const int len = x->is_null ? -1 : cast_format(from, (uint64_t)x->i64, buf);
+        lit.is_null = len < 0;
+        if (len > 0) lit.name.assign(reinterpret_cast<const char*>(buf), (size_t)len);
+        return eval_literal(ex, lit, n);
+    }
+    const Column arg = materialize_column(ex, evaluate_column(ex, in, x));
+    const ColumnRef cr = arg.ref();
+    Temp tmp(ex);
+    uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
+    // only a Date32 can have no text (outside 0000 .. 9999): every other result is NULL exactly where its argument is
+    BufferPtr validity = from == DT_DATE32 ? make_buffer(ex, bitmap_bytes(n) + 8) : nullptr;
+    TIMED_LAUNCH_N(ex, "cast_format_lengths", n, launch_cast_format_lengths(ex.cfg(), cr, n, lengths, validity ? validity->as<uint64_t>() : nullptr));
+    uint64_t* total;
+    Column out = utf8_from_lengths(ex, tmp, lengths, n, &total);
+    // the longest text of the type bounds the result when that is small; else read the total first
+    int64_t bound = n * cast_format_max(from);
+    if (bound > (64 << 20)) bound = (int64_t)read_device(ex, total);
+    if ((uint64_t)bound > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
+    out.data = make_buffer(ex, (size_t)bound + 8);
+    TIMED_LAUNCH_N(ex, "cast_format_write", n, launch_cast_format_write(ex.cfg(), cr, n, out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
+    out.data_bytes = (int64_t)read_device(ex, total);
+    out.validity = validity ? validity : arg.validity;
+    return out;
+}
+
+// CAST(<Utf8 expression> AS T): one thread per row parses its value; the result is nullable whatever the argument is
+Column eval_cast_parse(const Exec& ex, const Batch& in, const Expr& e) {
+    const int to = e.dtype;
+    if (!cast_parse_supported(to)) fail(BHIP_ENOTIMPL, cast_name(DT_UTF8, to));
+    const Column arg = eval_utf8(ex, in, e.args[0]);
+    const int64_t n = in.n_rows;
+    Column out;
+    out.dtype = to;
+    out.length = n;
+    out.data = make_buffer(ex, (to == DT_BOOLEAN ? bitmap_bytes(n) : (size_t)n * dtype_width(to)) + 8);
+    out.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+    Temp tmp(ex);
+    uint32_t* status = tmp.get<uint32_t>(1);
+    const bool can_decline = dt_is_float(to);
+    if (can_decline) HIP_CHECK(hipMemsetAsync(status, 0, 4, ex.stream));
+    TIMED_LAUNCH_N(ex, "cast_parse", n, launch_cast_parse(ex.cfg(), arg.ref(), n, to, out.data->ptr(), out.validity->as<uint64_t>(), status));
+    // integer, Boolean and Date32 targets cannot decline: handed on in stream order, no host wait
+    if (can_decline && (read_device(ex, status) & CAST_STATUS_DECLINED))
+        fail(BHIP_ENOTIMPL, cast_name(DT_UTF8, to) + ": a value outside the exactly rounded range (more than 15 significant digits, or a "
+                            "power of ten beyond 10^22) is not converted on the GPU path");
+    return out;
+}
+
 Column eval_utf8(const Exec& ex, const Batch& in, const ExprPtr& e) {
     switch (e->kind) {
         case BHIP_EXPR_COLUMN: {
@@ -193,6 +272,10 @@ Column eval_utf8(const Exec& ex, const Batch& in, const ExprPtr& e) {
             if (sha_fn(e->name)) return eval_sha(ex, in, *e);
             break;
         case BHIP_EXPR_CASE: return eval_case(ex, in, *e);
+        case BHIP_EXPR_CAST:
+            if (e->dtype != DT_UTF8) break;
+            if (expr_type(e->args[0], *in.schema) == DT_UTF8) return eval_utf8(ex, in, e->args[0]);
+            return eval_cast_format(ex, in, *e);
         default: break;
     }
     fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e->to_string());
@@ -204,15 +287,18 @@ BatchPtr Utf8Lowering::apply(const Exec& ex, const Batch& in) const {
     auto out = std::make_shared<Batch>(in);
     out->schema = schema();
     for (auto& node : nodes_) {
+        const int t = expr_type(node, in_);
         if (in.n_rows == 0) {
             Column c;
-            c.dtype = DT_UTF8;
-            c.offsets = make_buffer(ex, 8);
-            HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream));
+            c.dtype = t;
+            if (t == DT_UTF8) {
+                c.offsets = make_buffer(ex, 8);
+                HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream));
+            }
             c.data = make_buffer(ex, 8);
             out->cols.push_back(c);
         } else {
-            out->cols.push_back(eval_utf8(ex, in, node));
+            out->cols.push_back(t == DT_UTF8 ? eval_utf8(ex, in, node) : eval_cast_parse(ex, in, *node));
         }
     }
     return out;
@@ -241,10 +327,28 @@ void Utf8Lowering::validate() const {
                 for (size_t i = 0; i < np; ++i) walk(e->args[fw + 2 * i + 1]);
                 if (e->has_else) walk(e->args.back());
             } break;
+            case BHIP_EXPR_CAST: {
+                if (e->dtype != DT_UTF8) fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e->to_string());
+                const ExprPtr& x = e->args[0];
+                const int from = expr_type(x, in_);
+                if (from == DT_UTF8) { walk(x); break; }
+                if (!cast_format_supported(from)) fail(BHIP_ENOTIMPL, cast_name(from, DT_UTF8));
+                // the argument is a projection of its own: its string nodes and its VM program are checked as ProjectionExec does
+                Utf8Lowering inner(in_);
+                const ExprPtr lowered = inner.rewrite(x, true);
+                inner.validate();
+                const SchemaPtr aug = inner.schema();
+                ProgramBuilder pb(*aug);
+                if (lowered->kind != BHIP_EXPR_COLUMN) pb.add_output(lowered);
+            } break;
             default: fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e->to_string());
         }
     };
-    for (auto& n : nodes_) walk(n);
+    for (auto& n : nodes_) {
+        if (expr_type(n, in_) == DT_UTF8) { walk(n); continue; }
+        if (!cast_parse_supported(n->dtype)) fail(BHIP_ENOTIMPL, cast_name(DT_UTF8, n->dtype));
+        walk(n->args[0]);
+    }
 }
 
 }  // namespace bhip

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cast_text.h"
 #include "kernels.h"
 #include "tbl_kernels.h"
 #include "vm_device.h"
@@ -69,14 +70,7 @@ struct TextLdsReader {
     __device__ uint8_t operator()(int64_t pos) const { return buf[pos - origin]; }
 };
 
-__device__ inline int64_t days_from_civil(int64_t y, unsigned m, unsigned d) {
-    y -= m <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const unsigned yoe = (unsigned)(y - era * 400);
-    const unsigned doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
-    const unsigned doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + (int64_t)doe - 719468;
-}
+// days_from_civil: cast_text.h (the host folds date literals with the same function)
 
 static __constant__ double TEXT_POW10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
                                              1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
