@@ -160,6 +160,7 @@ SYMBOLS = {
     "bhip_plan_hash_aggregate": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(Expr), C.POINTER(C.c_char_p),
                                              C.c_int32, C.POINTER(Aggregate), _PP]),
     "bhip_plan_hash_join": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, _PP]),
+    "bhip_plan_hash_join_filter": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.POINTER(Expr), _PP]),
     "bhip_plan_sort": (C.c_int32, [_P, C.c_int32, C.POINTER(SortExprC), _PP]),
     "bhip_plan_repartition": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(Expr), C.c_int32, _PP]),
     "bhip_plan_coalesce_batches": (C.c_int32, [_P, C.c_int64, _PP]),

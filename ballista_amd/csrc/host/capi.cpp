@@ -309,6 +309,18 @@ bhip_status bhip_plan_hash_join(bhip_plan* left, bhip_plan* right, int32_t n_on,
     BHIP_API_END
 }
 
+bhip_status bhip_plan_hash_join_filter(bhip_plan* left, bhip_plan* right, int32_t n_on, const char* const* left_keys,
+                                       const char* const* right_keys, int32_t join_type, const bhip_expr* filter, bhip_plan** out) {
+    if (!filter) return bhip_plan_hash_join(left, right, n_on, left_keys, right_keys, join_type, out);
+    BHIP_API_BEGIN
+    need(out, "out");
+    if (n_on < 1) fail(BHIP_EINVAL, "HashJoinExec needs at least one key pair");
+    std::vector<std::pair<std::string, std::string>> on;
+    for (int i = 0; i < n_on; ++i) { need(left_keys[i], "left key"); need(right_keys[i], "right key"); on.push_back({left_keys[i], right_keys[i]}); }
+    *out = wrap_plan(std::make_shared<HashJoinExec>(plan_of(left, "left"), plan_of(right, "right"), on, join_type, parse_expr(*filter)));
+    BHIP_API_END
+}
+
 bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* exprs, bhip_plan** out) {
     BHIP_API_BEGIN
     need(out, "out");

@@ -219,5 +219,15 @@ hipError_t launch_join_exists_flags(const LaunchCfg& cfg, const JoinTable& T, co
 hipError_t launch_join_exists_flags_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
                                          const uint32_t* matched, uint32_t n_left, bool anti, bool merge, uint32_t* flags);
 hipError_t launch_compact_flags(const LaunchCfg& cfg, const uint32_t* flags, const uint64_t* offsets, uint32_t n, uint32_t* out);
+// residual join filter (kernels_hash.hip "residual join filter").  The candidates lidx / ridx are what launch_join_probe_emit[_wide]
+// wrote with right_outer = false (a probe row's candidates consecutive), sel[0 .. n_keep) the ascending positions the filter kept
+// (null: every candidate, n_keep of them).  out_l / out_r [n_keep]: the kept pairs (both null: not wanted).  matched: one bit per
+// build row, as the emit kernels set it (null: none).  hit: one bit per probe row of the batch in 64-bit words, zeroed by the caller
+// (null: none).
+hipError_t launch_join_pairs_resolve(const LaunchCfg& cfg, const uint32_t* sel, const uint32_t* lidx, const uint32_t* ridx, uint64_t n_keep, uint32_t* out_l,
+                                     uint32_t* out_r, uint32_t* matched, uint64_t* hit);
+// the `hit` words of a batch of n probe rows, in place -> the selection bitmap of the rows whose bit is set (anti: clear), bits at and
+// beyond n zero, and its counts per SEL_TILE rows (plain stores: no memset): the inputs of launch_select_indices
+hipError_t launch_join_hit_select(const LaunchCfg& cfg, uint64_t* bitmap, uint32_t n, bool anti, uint32_t* tile_counts);
 
 }  // namespace bhip

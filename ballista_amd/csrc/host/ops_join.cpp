@@ -41,8 +41,8 @@ static const char* join_name(int t) {
 static bool build_existence(int t) { return t == BHIP_JOIN_SEMI || t == BHIP_JOIN_ANTI; }
 static bool probe_existence(int t) { return t == BHIP_JOIN_RIGHT_SEMI || t == BHIP_JOIN_RIGHT_ANTI; }
 
-HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type)
-    : left_(std::move(left)), right_(std::move(right)), on_(std::move(on)), join_type_(join_type) {
+HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type, ExprPtr filter)
+    : left_(std::move(left)), right_(std::move(right)), on_(std::move(on)), join_type_(join_type), filter_(std::move(filter)) {
     ctx_ = left_->context();
     if (join_type < BHIP_JOIN_INNER || join_type > BHIP_JOIN_RIGHT_ANTI) fail(BHIP_ENOTIMPL, "Unsupported join type");
     // a build row's fate depends on every probe row, and a stream sees one right partition (Left emits its unmatched rows once
@@ -81,6 +81,7 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
         right_cols_.push_back((int)i);
     }
     schema_ = s;
+    if (filter_) check_filter();
     // key layout must be valid (surfaces BHIP_ENOTIMPL at plan time); one the packed key cannot hold goes to the wide-key table,
     // whose row-hash program has to be valid instead
     ScanParams P;
@@ -99,15 +100,58 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
     cache_ = std::make_shared<BuildCache>();
 }
 
+// The residual filter is typed against the Inner join's output schema whatever the join type: the left fields, then the right fields
+// minus a right key column named like its left partner (the name then means the left column).  The checks are FilterExec's.
+void HashJoinExec::check_filter() {
+    const Schema &ls = *left_->schema(), &rs = *right_->schema();
+    Schema fs;
+    std::vector<FilterCol> origin;
+    for (size_t i = 0; i < ls.fields.size(); ++i) {
+        fs.fields.push_back(ls.fields[i]);
+        origin.push_back(FilterCol{true, (int)i, ls.fields[i]});
+    }
+    for (size_t i = 0; i < rs.fields.size(); ++i) {
+        bool drop = false;
+        for (auto& p : on_)
+            if (p.second == rs.fields[i].name && p.first == p.second) drop = true;
+        if (drop) continue;
+        // (the existence types' outputs would not clash, but the filter's schema does: a ProjectionExec renames)
+        if (fs.index_of(rs.fields[i].name) >= 0) fail(BHIP_EINVAL, "join output would have two columns named '" + rs.fields[i].name + "'");
+        fs.fields.push_back(rs.fields[i]);
+        origin.push_back(FilterCol{false, (int)i, rs.fields[i]});
+    }
+    std::vector<std::string> used;
+    collect_columns(filter_, used);
+    for (auto& u : used) {
+        const int i = fs.index_of(u);
+        if (i < 0) fail(BHIP_EINVAL, "No field named '" + u + "'");
+        bool seen = false;
+        for (auto& fc : filter_cols_) seen = seen || fc.field.name == u;
+        if (!seen) filter_cols_.push_back(origin[i]);
+    }
+    // (a constant filter would run over a batch without columns; TRUE is the unfiltered join, FALSE / NULL a plan without partners)
+    if (filter_cols_.empty()) fail(BHIP_ENOTIMPL, "Join filter that reads no column of either side: " + filter_->to_string());
+    if (expr_type(filter_, fs) != DT_BOOLEAN)
+        fail(BHIP_EINVAL, "Join filter must return boolean values, not " + std::string(dtype_name(expr_type(filter_, fs))));
+    Utf8Lowering low(fs);
+    const ExprPtr lowered = low.rewrite(filter_);
+    low.validate();
+    const SchemaPtr aug = low.schema();
+    ProgramBuilder pb(*aug);
+    pb.set_predicate(lowered);      // surfaces BHIP_ENOTIMPL at plan time
+}
+
 PlanPtr HashJoinExec::with_new_children(const std::vector<PlanPtr>& c) const {
     if (c.size() != 2) fail(BHIP_EINVAL, "HashJoinExec wrong number of children");
-    return std::make_shared<HashJoinExec>(c[0], c[1], on_, join_type_);
+    return std::make_shared<HashJoinExec>(c[0], c[1], on_, join_type_, filter_);
 }
 
 std::string HashJoinExec::describe() const {
     std::string s = std::string("HashJoinExec: mode=CollectLeft, join_type=") + join_name(join_type_) + ", on=[";
     for (size_t i = 0; i < on_.size(); ++i) s += (i ? ", " : "") + std::string("(") + on_[i].first + ", " + on_[i].second + ")";
-    return s + "]";
+    s += "]";
+    if (filter_) s += ", filter=" + filter_->to_string();
+    return s;
 }
 
 // the integer key columns that need no packed 16-byte image: 4 (Int32 / Date32), 8 (Int64 / UInt64) bytes wide, else 0
@@ -504,9 +548,10 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
     if (n > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "hash join build side of more than 2^31 rows per partition");
     const uint64_t cap = table_capacity((uint64_t)n);
     static const bool narrow_disabled = env_flag("BHIP_NO_NARROW_JOIN");
-    // the existence probes read the general table's owner words: no narrow structures for them
+    // the existence probes read the general table's owner words, a residual filter enumerates candidates through its chains: no
+    // narrow structures for them
     const bool existence = build_existence(join_type_) || probe_existence(join_type_);
-    const int nkw = narrow_disabled || existence ? 0 : narrow_key_width();
+    const int nkw = narrow_disabled || existence || filter_ ? 0 : narrow_key_width();
     bool narrow = false;
     if (nkw && n > 0) {
         const Schema& lsch = *bs->batch->schema;
@@ -624,10 +669,12 @@ bool int_ranges_of(const ExprPtr& pred, const Batch& b, ProbeFilter& F) {
 
 // where the output columns of probed rows are gathered from: the batch `src`, whose column for right output column k is rmap[k]
 // (nullptr: right_cols_[k]) and whose row of probe row i is remap[i] (nullptr: row i)
+// (fmap: the same for the right columns the residual filter reads, J.filter_cols_ in their order; nullptr: the column's own index)
 struct ProbeOut {
     const Batch* src;
     const std::vector<int>* rmap;
     const uint32_t* remap;
+    const std::vector<int>* fmap = nullptr;
 };
 
 // what a tiled probe kernel leaves behind, in scratch: the selection bitmap of the emitting rows and their count per SEL_TILE rows,
@@ -681,6 +728,7 @@ struct HashJoinExec::Probe {
     const size_t n_lout;                 // left columns in the output (right output column k is column n_lout + k of the schema)
     bool need_left = false;
     BufferPtr matched;                   // Left / Full: one bit per build row some probe row matched; Semi / Anti: per key, on its representative row
+                                         // (under a residual filter: per build row for all four — two rows of one key can differ under it)
     std::shared_ptr<const JoinBuildSide> sibling;   // the wide table beside a packed `bs`, once a batch of this stream went through it
     std::vector<std::string> rcols;
     SchemaPtr key_schema;                // the probe-side key columns alone, under their names
@@ -805,8 +853,9 @@ struct HashJoinExec::Probe {
             }
         }
         if (t->wide) side_hashes(ex, probe, rcols, rkeys, rsel, has_rsel, K);
-        Temp tmp(ex);
         const uint64_t* rselp = has_rsel ? rsel->as<uint64_t>() : nullptr;
+        if (J.filter_) { probe_filtered(*t, o, rkeys->as<uint64_t>(), rselp, K, n_right); return; }
+        Temp tmp(ex);
         if (mark_only || select_only) {
             // existence: one probe per row whatever the duplication (the slot's owner stands for its key).  Semi / Anti leave bits
             // for emit_build_rows; RightSemi / RightAnti a selection of the probe rows, compacted as the unique build side's is
@@ -865,6 +914,103 @@ struct HashJoinExec::Probe {
                            launch_join_probe_emit(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, offsets,
                                                   ix.lidx, ix.ridx, matched_bits()));
         finish(tmp, o, ix, n_out);
+    }
+
+    // ---- residual filter: candidates (the key-equal pairs, enumerated as an Inner join whatever the join type and the build side's
+    // duplication) -> the filter over the gathered columns it reads -> join_pairs_resolve: the kept pairs, the build rows' `matched`
+    // bits and the probe rows' `hit` bits -> the output of the join type.  A row all of whose candidates fail has no partner.
+    // the filter over the candidates: the ascending positions it keeps
+    int64_t filter_candidates(Temp& tmp, const ProbeOut& o, const uint32_t* lidx, const uint32_t* ridx, uint64_t n_cand, BufferPtr& sel) {
+        if (o.remap) {
+            uint32_t* orig = tmp.get<uint32_t>((size_t)n_cand);
+            TIMED_LAUNCH_N(ex, "take_fixed", n_cand, launch_take_fixed(cfg, o.remap, 4, ridx, (int64_t)n_cand, orig));
+            ridx = orig;
+        }
+        std::vector<const Column*> lc, rc;
+        std::vector<size_t> lpos, rpos;
+        for (size_t k = 0; k < J.filter_cols_.size(); ++k) {
+            const auto& fc = J.filter_cols_[k];
+            if (fc.left) { lc.push_back(&L.cols[fc.index]); lpos.push_back(k); }
+            else { rc.push_back(&o.src->cols[o.fmap ? (*o.fmap)[k] : fc.index]); rpos.push_back(k); }
+        }
+        auto fb = std::make_shared<Batch>();
+        auto fs = std::make_shared<Schema>();
+        fb->ctx = ex.ctx;
+        fb->n_rows = (int64_t)n_cand;
+        fb->cols.resize(J.filter_cols_.size());
+        if (!lc.empty()) {
+            auto got = take_columns(ex, lc, lidx, (int64_t)n_cand, false);
+            for (size_t k = 0; k < got.size(); ++k) fb->cols[lpos[k]] = std::move(got[k]);
+        }
+        if (!rc.empty()) {
+            auto got = take_columns(ex, rc, ridx, (int64_t)n_cand, false);
+            for (size_t k = 0; k < got.size(); ++k) fb->cols[rpos[k]] = std::move(got[k]);
+        }
+        for (size_t k = 0; k < J.filter_cols_.size(); ++k) {
+            Field f = J.filter_cols_[k].field;
+            f.nullable = f.nullable || (bool)fb->cols[k].validity;
+            fs->fields.push_back(f);
+        }
+        fb->schema = fs;
+        return filter_indices(ex, *fb, J.filter_, sel);
+    }
+
+    void probe_filtered(const JoinBuildSide& t, const ProbeOut& o, const uint64_t* rkeys, const uint64_t* rselp, const WideKeyCols& K, int64_t n_right) {
+        Temp tmp(ex);
+        uint64_t* total = tmp.get<uint64_t>(1);
+        uint32_t* counts = tmp.get<uint32_t>((size_t)n_right + 1);
+        uint64_t* offsets = tmp.get<uint64_t>((size_t)n_right + 1);
+        void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_right));
+        if (t.wide)
+            TIMED_LAUNCH_N(ex, "join_probe_count_wide", n_right,
+                           launch_join_probe_count_wide(cfg, t.table, t.wkeys, K, rkeys, rselp, (uint32_t)n_right, false, counts));
+        else
+            TIMED_LAUNCH_N(ex, "join_probe_count", n_right, launch_join_probe_count(cfg, t.table, rkeys, rselp, (uint32_t)n_right, false, counts));
+        HIP_CHECK(exclusive_scan_u32_u64(ex.stream, counts, n_right, offsets, false, total, scan_tmp));
+        const uint64_t n_cand = read_device(ex, total);
+        if (n_cand > 0xFFFFFFF0ull) fail(BHIP_EEXEC, "join filter: the key-equal candidate pairs of one probe batch exceed 2^32");
+        // Right / Full / RightSemi / RightAnti answer per probe row of this batch
+        const bool need_hit = right_outer || select_only;
+        TileSelection s(tmp, need_hit ? n_right : 0, false, false, false);
+        if (need_hit) HIP_CHECK(hipMemsetAsync(s.bitmap, 0, ((size_t)(n_right + 63) / 64) * 8, ex.stream));
+        if (n_cand) {
+            uint32_t* lidx = tmp.get<uint32_t>((size_t)n_cand);
+            uint32_t* ridx = tmp.get<uint32_t>((size_t)n_cand);
+            if (t.wide)
+                TIMED_LAUNCH_N(ex, "join_probe_emit_wide", n_right,
+                               launch_join_probe_emit_wide(cfg, t.table, t.wkeys, K, rkeys, rselp, (uint32_t)n_right, false, offsets, lidx, ridx, nullptr));
+            else
+                TIMED_LAUNCH_N(ex, "join_probe_emit", n_right,
+                               launch_join_probe_emit(cfg, t.table, rkeys, rselp, (uint32_t)n_right, false, offsets, lidx, ridx, nullptr));
+            BufferPtr sel;
+            const uint64_t n_keep = (uint64_t)filter_candidates(tmp, o, lidx, ridx, n_cand, sel);
+            if (n_keep) {
+                // all kept: the candidates are the pairs, and only the bits are left to set
+                const bool all = n_keep == n_cand, pairs = !mark_only && !select_only;
+                JoinIndices ix;
+                ix.lidx = lidx;
+                ix.ridx = ridx;
+                if (pairs && !all) {
+                    ix.lidx = tmp.get<uint32_t>((size_t)n_keep);
+                    ix.ridx = tmp.get<uint32_t>((size_t)n_keep);
+                }
+                if ((pairs && !all) || matched || need_hit)
+                    TIMED_LAUNCH_N(ex, "join_pairs_resolve", n_keep,
+                                   launch_join_pairs_resolve(cfg, all ? nullptr : sel->as<uint32_t>(), lidx, ridx, n_keep, pairs && !all ? ix.lidx : nullptr,
+                                                             pairs && !all ? ix.ridx : nullptr, matched_bits(), need_hit ? s.bitmap : nullptr));
+                if (pairs) finish(tmp, o, ix, n_keep);
+            }
+        }
+        if (!need_hit) return;
+        // the probe rows with (RightSemi) / without (Right / Full: with NULL left columns; RightAnti) a partner
+        TIMED_LAUNCH_N(ex, "join_hit_select", n_right, launch_join_hit_select(cfg, s.bitmap, (uint32_t)n_right, right_outer || anti, s.tile_counts));
+        HIP_CHECK(exclusive_scan_u32_u64(ex.stream, s.tile_counts, s.n_tiles, s.tile_off, false, s.total, s.scan_tmp));
+        const uint64_t n_sel = read_device(ex, s.total);
+        if (n_sel == 0) return;
+        JoinIndices ix;
+        ix.ridx = tmp.get<uint32_t>((size_t)n_sel);
+        TIMED_LAUNCH_N(ex, "select_indices", n_right, launch_select_indices(cfg, s.bitmap, s.tile_off, n_right, ix.ridx));
+        finish(tmp, o, ix, n_sel);
     }
 
     // ---- narrow build side: one pass over the probe rows: ranges -> key-set bit -> rank map / table (kernels_join.hip) -----
@@ -928,6 +1074,8 @@ struct HashJoinExec::Probe {
         std::vector<int> rmap, key_src;                    // right OUTPUT column k / key k -> source column
         for (int ci : J.right_cols_) rmap.push_back(chain.src_of[ci]);
         for (auto& rc : rcols) key_src.push_back(chain.src_of[rsch.index_of(rc)]);
+        std::vector<int> fmap;                             // column k of the residual filter (a right one) -> source column
+        for (auto& fc : J.filter_cols_) fmap.push_back(fc.left ? -1 : chain.src_of[fc.index]);
         // a join below (no filter in between): only the columns read here, and everything but the keys may arrive as views
         StreamPtr ss;
         auto src_hj = dynamic_cast<const HashJoinExec*>(chain.src.get());
@@ -935,6 +1083,8 @@ struct HashJoinExec::Probe {
             std::vector<bool> need(chain.src->schema()->fields.size(), false);
             for (size_t k = 0; k < J.right_cols_.size(); ++k)
                 if (needed[n_lout + k]) need[rmap[k]] = true;
+            for (int c : fmap)
+                if (c >= 0) need[c] = true;
             ss = open_join_below(*src_hj, partition, ex, need, key_src);
         } else {
             ss = chain.src->execute(partition, ex);
@@ -954,7 +1104,7 @@ struct HashJoinExec::Probe {
                     for (auto& kc : keys) kc = take_batch_column(ex, kc, sel->as<uint32_t>(), n);
                 }
             }
-            probe_rows(n, keys, F, ProbeOut{b.get(), &rmap, sel ? sel->as<uint32_t>() : nullptr});
+            probe_rows(n, keys, F, ProbeOut{b.get(), &rmap, sel ? sel->as<uint32_t>() : nullptr, &fmap});
         }
     }
 
@@ -969,7 +1119,7 @@ struct HashJoinExec::Probe {
         uint64_t* offsets = tmp.get<uint64_t>((size_t)n_left + 1);
         uint64_t* total = tmp.get<uint64_t>(1);
         void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_left));
-        const bool direct = left_outer || bs->unique;
+        const bool direct = left_outer || bs->unique || J.filter_;          // (a residual filter marks the very rows that passed it)
         const bool want_unmatched = left_outer || anti;
         auto flags_of = [&](const JoinBuildSide& t, bool anti_now, bool merge) {
             const uint64_t* sel = t.has_sel ? t.sel->as<uint64_t>() : nullptr;

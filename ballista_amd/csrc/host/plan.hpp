@@ -233,7 +233,9 @@ HashAggResult hash_aggregate(const Exec& ex, Temp& tmp, const ScanParams& P0, co
 struct JoinBuildSide;
 class HashJoinExec : public ExecutionPlan {
 public:
-    HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type);
+    // filter (may be null): the residual predicate over the Inner join's output schema of the two children — a build row and a probe
+    // row are partners when their keys are equal AND it is TRUE (ops_join.cpp "residual filter")
+    HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type, ExprPtr filter = nullptr);
     const char* name() const override { return "HashJoinExec"; }
     SchemaPtr schema() const override { return schema_; }
     Partitioning output_partitioning() const override { return right_->output_partitioning(); }
@@ -255,6 +257,12 @@ private:
     int join_type_;
     SchemaPtr schema_;
     std::vector<int> right_cols_;   // right columns kept in the output
+    ExprPtr filter_;
+    // the columns filter_ reads, each once, in the order the expression first names them (the schema of the batch the filter runs
+    // over at run time is built from this list): column `index` of the left / right child's schema
+    struct FilterCol { bool left; int index; Field field; };
+    std::vector<FilterCol> filter_cols_;
+    void check_filter();             // the plan-time checks of filter_ (FilterExec's), and filter_cols_
     int narrow_key_width() const;
     bool pair_keys() const;          // TWO 4-byte integer key pairs: packed into one 8-byte key per side, then the single-key machinery
     // the build side (hash table over the whole left child) is built once and shared by every

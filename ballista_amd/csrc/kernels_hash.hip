@@ -534,6 +534,59 @@ join_exists_flags_kernel(JoinTable T, const uint64_t* sel, const uint32_t* match
     }
 }
 
+// ---- residual join filter: the probe enumerated CANDIDATES (key-equal pairs, lidx / ridx, a probe row's candidates consecutive) and
+// the filter kept the ascending positions sel[0 .. n_keep) of them (sel == nullptr: all).  One lane per kept candidate: the pair goes
+// to out_l / out_r (null: the join emits no pairs, or the candidates are the pairs), its build row's bit into `matched` (32-bit words;
+// null: the join type has none) and its probe row's bit into `hit` (64-bit words over the batch, zeroed by the caller; null likewise).
+// ridx[sel[.]] is non-decreasing, so only the first kept candidate of a probe row touches `hit`: lane k compares with lane k - 1's row.
+// A streaming pass over the two gathers; the bit sets are read before they are written (mark_once) with the intent of keeping a hot
+// key's candidates off the memory side — no counter run has confirmed that; no per-wave merge of the bits.
+__global__ void __launch_bounds__(BLOCK)
+join_pairs_resolve_kernel(const uint32_t* sel, const uint32_t* lidx, const uint32_t* ridx, uint64_t n_keep, uint32_t* out_l, uint32_t* out_r,
+                          uint32_t* matched, unsigned long long* hit) {
+    const int lane = threadIdx.x & 63;
+    for (uint64_t k = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; k < n_keep; k += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t p = sel ? sel[k] : k;
+        const uint32_t l = lidx[p], r = ridx[p];
+        if (out_l) { out_l[k] = l; out_r[k] = r; }
+        if (matched) mark_once(matched, l);
+        if (hit) {
+            // (lane k - 1 of this wave is active whenever lane k is: k - 1 < k < n_keep in the same pass)
+            uint32_t prev = __shfl_up(r, 1, 64);
+            if (lane == 0) prev = k ? ridx[sel ? sel[k - 1] : k - 1] : 0xFFFFFFFFu;
+            if (prev != r || k == 0) {
+                const unsigned long long bit = 1ull << (r & 63);
+                if (!(hit[r >> 6] & bit)) atomicOr(&hit[r >> 6], bit);
+            }
+        }
+    }
+}
+
+// the `hit` words of a batch of n probe rows -> the selection of the rows whose bit is set (anti = 0) or clear (anti = 1), in place:
+// the bitmap (the last word's tail masked) and its counts per SEL_TILE rows, the inputs of launch_select_indices.  One wave per tile:
+// its 16 words on 16 lanes, the count a plain store.
+__global__ void __launch_bounds__(BLOCK)
+join_hit_select_kernel(uint64_t* bitmap, uint32_t n, int anti, uint32_t* tile_counts) {
+    constexpr int TILE_WORDS = SEL_TILE / 64;
+    static_assert(TILE_WORDS == 16, "a tile's words on the first 16 lanes");
+    const int lane = threadIdx.x & 63;
+    const uint32_t n_words = (n + 63u) / 64u, n_tiles = (n + SEL_TILE - 1u) / SEL_TILE;
+    const uint32_t n_waves = gridDim.x * (BLOCK / 64);
+    for (uint32_t t = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); t < n_tiles; t += n_waves) {
+        const uint32_t w = t * TILE_WORDS + (uint32_t)lane;
+        uint64_t word = 0;
+        if (lane < TILE_WORDS && w < n_words) {
+            word = anti ? ~bitmap[w] : bitmap[w];
+            if (w == n_words - 1u && (n & 63u)) word &= (1ull << (n & 63u)) - 1ull;
+            bitmap[w] = word;
+        }
+        uint32_t c = (uint32_t)__popcll(word);
+#pragma unroll
+        for (int d = TILE_WORDS / 2; d >= 1; d >>= 1) c += __shfl_down(c, d, 64);
+        if (lane == 0) tile_counts[t] = c;
+    }
+}
+
 // ---- narrow keys: ONE Int32 / Date32 key column and a unique build side (the primary-key joins of TPC-H).
 // The slot holds the key and the build row together (key | (row + 1) << 32), so a probe step is ONE random
 // 8-byte read instead of a slot read followed by a dependent read of the 16-byte packed key; no packed keys are
@@ -973,6 +1026,19 @@ hipError_t launch_join_exists_flags_wide(const LaunchCfg& cfg, const JoinTable& 
     if (n_left == 0) return hipSuccess;
     hipLaunchKernelGGL(join_exists_flags_wide_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, build, hashes, sel, matched, n_left,
                        anti ? 1 : 0, merge ? 1 : 0, flags);
+    return hipGetLastError();
+}
+hipError_t launch_join_pairs_resolve(const LaunchCfg& cfg, const uint32_t* sel, const uint32_t* lidx, const uint32_t* ridx, uint64_t n_keep, uint32_t* out_l,
+                                     uint32_t* out_r, uint32_t* matched, uint64_t* hit) {
+    if (n_keep == 0) return hipSuccess;
+    hipLaunchKernelGGL(join_pairs_resolve_kernel, dim3(grid_rows(cfg, n_keep)), dim3(BLOCK), 0, cfg.stream, sel, lidx, ridx, n_keep, out_l, out_r, matched,
+                       reinterpret_cast<unsigned long long*>(hit));
+    return hipGetLastError();
+}
+hipError_t launch_join_hit_select(const LaunchCfg& cfg, uint64_t* bitmap, uint32_t n, bool anti, uint32_t* tile_counts) {
+    if (n == 0) return hipSuccess;
+    const size_t n_tiles = ((size_t)n + SEL_TILE - 1) / SEL_TILE;
+    hipLaunchKernelGGL(join_hit_select_kernel, dim3(grid_rows(cfg, n_tiles * 64)), dim3(BLOCK), 0, cfg.stream, bitmap, n, anti ? 1 : 0, tile_counts);
     return hipGetLastError();
 }
 hipError_t launch_compact_flags(const LaunchCfg& cfg, const uint32_t* flags, const uint64_t* offsets, uint32_t n, uint32_t* out) {

@@ -846,19 +846,27 @@ class HashAggregateExec(ExecutionPlan):
 class HashJoinExec(ExecutionPlan):
     """HashJoinExec::try_new(left, right, on: &[(String, String)], join_type)  (from_proto.rs:253-276);
     left is the build side.  SEMI / ANTI: the left rows with / without a partner (left fields only); RIGHT_SEMI / RIGHT_ANTI:
-    the right rows (right fields only).  FULL, SEMI and ANTI need a right child of one partition (MergeExec)."""
+    the right rows (right fields only).  FULL, SEMI and ANTI need a right child of one partition (MergeExec).
+    filter: a residual predicate over the Inner join's output schema of the two children (whatever the join type): rows are partners
+    when their keys are equal AND it is TRUE.  It has no wire form: the C ABI only."""
 
     _JT = {INNER: 0, LEFT: 1, RIGHT: 2, FULL: 3, SEMI: 4, ANTI: 5, RIGHT_SEMI: 6, RIGHT_ANTI: 7}
 
-    def __init__(self, left: ExecutionPlan, right: ExecutionPlan, on: Sequence[Tuple[str, str]], join_type: str = INNER):
+    def __init__(self, left: ExecutionPlan, right: ExecutionPlan, on: Sequence[Tuple[str, str]], join_type: str = INNER,
+                 filter: Optional[E.PhysicalExpr] = None):
         if join_type not in self._JT:
             raise L.PlanError(L.EINVAL, f"Unsupported join type {join_type}")
         lw = _Lowered()
         h = C.c_void_p()
-        L.check(L.lib().bhip_plan_hash_join(left._h, right._h, len(on), lw.strings([a for a, _ in on]),
-                                            lw.strings([b for _, b in on]), self._JT[join_type], C.byref(h)))
+        if filter is None:
+            L.check(L.lib().bhip_plan_hash_join(left._h, right._h, len(on), lw.strings([a for a, _ in on]),
+                                                lw.strings([b for _, b in on]), self._JT[join_type], C.byref(h)))
+        else:
+            ex = lw.expr(filter)
+            L.check(L.lib().bhip_plan_hash_join_filter(left._h, right._h, len(on), lw.strings([a for a, _ in on]),
+                                                       lw.strings([b for _, b in on]), self._JT[join_type], C.byref(ex), C.byref(h)))
         super().__init__(h, left.ctx, [left, right])
-        self.left, self.right, self.on, self.join_type = left, right, list(on), join_type
+        self.left, self.right, self.on, self.join_type, self.filter = left, right, list(on), join_type, filter
 
 
 class SortExec(ExecutionPlan):

@@ -308,6 +308,14 @@ bhip_status bhip_plan_hash_aggregate(bhip_plan* input, int32_t mode, int32_t n_g
                                      bhip_plan** out);                                               /* :173-252 */
 bhip_status bhip_plan_hash_join(bhip_plan* left, bhip_plan* right, int32_t n_on, const char* const* left_keys,
                                 const char* const* right_keys, int32_t join_type, bhip_plan** out);  /* :253-276 */
+/* the same with a residual join filter: a left and a right row are partners when their keys are equal AND `filter` is TRUE (NULL
+ * is not a match), for every join type — a row all of whose key-equal candidates fail it is a row without a partner.  The filter is
+ * typed against the INNER join's output schema of the two children whatever the join type (left fields, then right fields minus a
+ * right key column named like its left partner); with a filter, a non-key name on both sides is BHIP_EINVAL for SEMI / ANTI /
+ * RIGHT_SEMI / RIGHT_ANTI as well; a filter that reads no column is BHIP_ENOTIMPL.  Output schema and nullability are those of bhip_plan_hash_join.  filter NULL: exactly
+ * bhip_plan_hash_join.  No wire form (HashJoinExecNode has no field for it). */
+bhip_status bhip_plan_hash_join_filter(bhip_plan* left, bhip_plan* right, int32_t n_on, const char* const* left_keys,
+                                       const char* const* right_keys, int32_t join_type, const bhip_expr* filter, bhip_plan** out);
 bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* exprs, bhip_plan** out); /* :291-331 */
 bhip_status bhip_plan_repartition(bhip_plan* input, int32_t scheme, int32_t n_exprs, const bhip_expr* hash_exprs,
                                   int32_t partition_count, bhip_plan** out);                         /* :133-164 */
