@@ -104,36 +104,32 @@ struct JoinTable {
     uint32_t* head;           // [capacity] id+1 of the most recently inserted build row of the slot's key
     uint32_t* next;           // [n_left]   id+1 of the next build row with the same key
     uint64_t mask;
-    const uint64_t* keys128;  // packed keys of the build rows (null: the wide form below, whose keys are the build side's columns)
+    const uint64_t* keys128;  // packed keys of the build rows (null: the wide form below)
     uint32_t* dup_flag;       // set by the build when two build rows share a key (may be null)
+    const WideKeyCols* cols;  // the wide form: the key columns of the build rows.  HOST memory, for the launchers (they pass the
+                              // columns to the kernel by value); no kernel reads this member
 };
-hipError_t launch_join_build(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* sel, uint32_t n_left);
-hipError_t launch_join_probe_count(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel,
-                                   uint32_t n_right, bool right_outer, uint32_t* counts);
-hipError_t launch_join_probe_emit(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel,
-                                  uint32_t n_right, bool right_outer, const uint64_t* offsets, uint32_t* left_idx,
-                                  uint32_t* right_idx, uint32_t* matched);
+// The keys of one side's rows (the build side's for launch_join_build and launch_join_exists_flags, else the probe side's), in the
+// form of the table they meet: the launcher picks the kernel instantiation from it.
+// Keys of any width (cols != nullptr): the slot word is claimed with the high half of the 64-bit ROW HASH (scan_keys in hash-only
+// mode) as its tag, and a tag hit is confirmed on the key columns themselves — build row (owner) against build row in the build
+// kernel, probe row against build row (owner) in the probes.  Rows with a NULL key part are deselected by sel and never reach a
+// compare.  Fixed-width parts compare by their 64-bit image (dt_load: floats by bits, as the packed key does), Utf8 parts by
+// length, then bytes.  Everything else a launcher takes means the same for both forms.
+struct JoinSideKeys {
+    const uint64_t* keys;     // packed: 2 x u64 per row; wide: one 64-bit row hash per row
+    const uint64_t* sel;      // the rows without a NULL key part (null: all)
+    const WideKeyCols* cols;  // wide: the side's key columns (host memory); null: packed
+};
+hipError_t launch_join_build(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& build, uint32_t n_left);
+hipError_t launch_join_probe_count(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool right_outer,
+                                   uint32_t* counts);
+hipError_t launch_join_probe_emit(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool right_outer,
+                                  const uint64_t* offsets, uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched);
 // unique build keys: one table probe per row -> partner[] (build row id, 0xFFFFFFFF = none) + the selection bitmap of
 // emitting rows and its counts per SEL_TILE rows (the inputs of launch_select_indices)
-hipError_t launch_join_probe_match(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel,
-                                   uint32_t n_right, bool right_outer, uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts,
-                                   uint32_t* matched);
-// keys of any width (T.keys128 == nullptr): the slot word is claimed with the high half of the 64-bit ROW HASH (scan_keys in
-// hash-only mode) as its tag, and a tag hit is confirmed on the key columns themselves — `build` row (owner) against `build` row
-// in the build kernel, `probe` row against `build` row (owner) in the probes.  Rows with a NULL key part are deselected by
-// sel / rsel and never reach a compare.  Fixed-width parts compare by their 64-bit image (dt_load: floats by bits, as the packed
-// key does), Utf8 parts by length, then bytes.  partner / bitmap / tile_counts / counts / offsets / left_idx / right_idx / matched
-// and right_outer mean what they mean for the packed launchers above.
-hipError_t launch_join_build_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
-                                  uint32_t n_left);
-hipError_t launch_join_probe_match_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* partner,
-                                        uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched);
-hipError_t launch_join_probe_count_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* counts);
-hipError_t launch_join_probe_emit_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                       const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, const uint64_t* offsets,
-                                       uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched);
+hipError_t launch_join_probe_match(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool right_outer,
+                                   uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched);
 // one Int32 / Date32 key column, unique build side: key and build row share the slot (kernels_hash.hip)
 struct NarrowJoinTable {
     // CAS table (sparse keys): key width 4: [capacity] key | (build row + 1) << 32, 0 = empty;
@@ -205,21 +201,17 @@ hipError_t launch_join_compact_staged(const LaunchCfg& cfg, const uint32_t* stag
 // matched != nullptr: the MARK form (Semi / Anti) — a hit sets the bit of the key's representative build row; bitmap / tile_counts
 // / anti are not used.  matched == nullptr: the SELECT form (RightSemi / RightAnti) — the selection bitmap of the probe rows with
 // (hit != anti) and its counts per SEL_TILE rows, the inputs of launch_select_indices; bits at and beyond n_right are 0.
-hipError_t launch_join_probe_exists(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right,
-                                    bool anti, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched);
-hipError_t launch_join_probe_exists_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                         const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool anti, uint64_t* bitmap,
-                                         uint32_t* tile_counts, uint32_t* matched);
-// flags[row] = (the bit of build row `row`'s representative in `matched`) ^ anti, `anti` for a row that `sel` deselects: what the scan
-// and launch_compact_flags turn into build rows.  direct: every row stands for itself (a unique build side; Left / Full, whose probes
-// mark every matched row) and T is not read; otherwise the row finds the slot of its own key.  merge: OR with what flags[] holds
-// (0 / 1 from an earlier launch with anti = false over another table of the same build rows) before `anti` applies.
-hipError_t launch_join_exists_flags(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* sel, const uint32_t* matched, uint32_t n_left, bool direct,
-                                    bool anti, bool merge, uint32_t* flags);
-hipError_t launch_join_exists_flags_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
-                                         const uint32_t* matched, uint32_t n_left, bool anti, bool merge, uint32_t* flags);
+hipError_t launch_join_probe_exists(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool anti, uint64_t* bitmap,
+                                    uint32_t* tile_counts, uint32_t* matched);
+// flags[row] = (the bit of build row `row`'s representative in `matched`) ^ anti, `anti` for a row that build.sel deselects: what the
+// scan and launch_compact_flags turn into build rows.  direct: every row stands for itself (a unique build side; Left / Full, whose
+// probes mark every matched row) and neither T nor build.keys is read; otherwise the row finds the slot of its own key.  merge: OR
+// with what flags[] holds (0 / 1 from an earlier launch with anti = false over another table of the same build rows) before `anti`
+// applies.
+hipError_t launch_join_exists_flags(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& build, const uint32_t* matched, uint32_t n_left,
+                                    bool direct, bool anti, bool merge, uint32_t* flags);
 hipError_t launch_compact_flags(const LaunchCfg& cfg, const uint32_t* flags, const uint64_t* offsets, uint32_t n, uint32_t* out);
-// residual join filter (kernels_hash.hip "residual join filter").  The candidates lidx / ridx are what launch_join_probe_emit[_wide]
+// residual join filter (kernels_hash.hip "residual join filter").  The candidates lidx / ridx are what launch_join_probe_emit
 // wrote with right_outer = false (a probe row's candidates consecutive), sel[0 .. n_keep) the ascending positions the filter kept
 // (null: every candidate, n_keep of them).  out_l / out_r [n_keep]: the kept pairs (both null: not wanted).  matched: one bit per
 // build row, as the emit kernels set it (null: none).  hit: one bit per probe row of the batch in 64-bit words, zeroed by the caller

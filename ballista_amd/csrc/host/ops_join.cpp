@@ -17,14 +17,37 @@
 
 namespace bhip {
 
+// the keys of one side's rows in the form of a general table (side_keys): packed 16-byte keys, or (wide) 64-bit row hashes and the
+// key columns themselves; and the selection of the rows without a NULL key part
+struct SideKeys {
+    BufferPtr keys, sel;            // 2 x u64 per row (packed) / one row hash per row (wide); sel: only with has_sel
+    bool has_sel = false;
+    WideKeyCols cols = {};          // wide: the key columns (n = 0: the packed form)
+    JoinSideKeys view() const {
+        return JoinSideKeys{keys ? keys->as<uint64_t>() : nullptr, has_sel ? sel->as<uint64_t>() : nullptr, cols.n ? &cols : nullptr};
+    }
+};
+
+// the general table's kernels under the names profiles, DESIGN.md and the tests know them by: the packed form's, "_wide" for the other
+enum JoinKernel { K_BUILD, K_PROBE_COUNT, K_PROBE_EMIT, K_PROBE_MATCH, K_PROBE_EXISTS, K_EXISTS_FLAGS };
+static const char* kernel_name(JoinKernel k, bool wide) {
+    static const char* const names[][2] = {{"join_build", "join_build_wide"},
+                                           {"join_probe_count", "join_probe_count_wide"},
+                                           {"join_probe_emit", "join_probe_emit_wide"},
+                                           {"join_probe_match", "join_probe_match_wide"},
+                                           {"join_probe_exists", "join_probe_exists_wide"},
+                                           {"join_exists_flags", "join_exists_flags_wide"}};
+    return names[k][wide ? 1 : 0];
+}
+
 struct JoinBuildSide {
     BatchPtr batch;                 // all left rows
-    BufferPtr keys, sel, owner, head, next, dup;
+    SideKeys keys;                  // general table: the build rows' keys in its form (table.keys128 / table.cols point into it; a wide
+                                    // table's row hashes are dropped after the build)
+    BufferPtr owner, head, next, dup;
     JoinTable table;
-    bool has_sel = false;
     bool unique = false;            // no two build rows share a key: probe rows have at most one partner
-    bool wide = false;              // keys of any width: `table` over row hashes (no `keys`), equality on the key columns `wkeys` of `batch`
-    WideKeyCols wkeys;
+    bool wide = false;              // keys of any width: `table` over row hashes, equality on the key columns keys.cols of `batch`
     bool narrow = false;            // ONE integer key, unique: NarrowJoinTable instead of JoinTable
     int narrow_width = 0;           // its key bytes (4: Int32 / Date32, 8: Int64 / UInt64)
     BufferPtr slots, present, rpack, rbits, rperm;
@@ -40,6 +63,12 @@ static const char* join_name(int t) {
 // the answer is per BUILD row (the output holds left columns only) / per PROBE row (right columns only)
 static bool build_existence(int t) { return t == BHIP_JOIN_SEMI || t == BHIP_JOIN_ANTI; }
 static bool probe_existence(int t) { return t == BHIP_JOIN_RIGHT_SEMI || t == BHIP_JOIN_RIGHT_ANTI; }
+// a right key column named like its left partner: the Inner join's output schema keeps the left one only
+static bool named_like_left_key(const std::vector<std::pair<std::string, std::string>>& on, const std::string& right_name) {
+    for (auto& p : on)
+        if (p.second == right_name && p.first == p.second) return true;
+    return false;
+}
 
 HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type, ExprPtr filter)
     : left_(std::move(left)), right_(std::move(right)), on_(std::move(on)), join_type_(join_type), filter_(std::move(filter)) {
@@ -59,6 +88,7 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
         if (ls.fields[li].dtype != rs.fields[ri].dtype)
             fail(BHIP_EINVAL, "join keys " + p.first + " / " + p.second + " have different types (" +
                                   dtype_name(ls.fields[li].dtype) + " vs " + dtype_name(rs.fields[ri].dtype) + ")");
+        left_keys_.push_back(p.first);
     }
     auto s = std::make_shared<Schema>();
     const bool left_nullable = join_type == BHIP_JOIN_RIGHT || join_type == BHIP_JOIN_FULL;
@@ -70,10 +100,7 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
     }
     for (size_t i = 0; i < rs.fields.size(); ++i) {
         if (build_existence(join_type)) break;
-        bool drop = false;
-        for (auto& p : on_)
-            if (p.second == rs.fields[i].name && p.first == p.second && !probe_existence(join_type)) drop = true;
-        if (drop) continue;
+        if (!probe_existence(join_type) && named_like_left_key(on_, rs.fields[i].name)) continue;
         Field f = rs.fields[i];
         if (right_nullable) f.nullable = true;
         if (s->index_of(f.name) >= 0) fail(BHIP_EINVAL, "join output would have two columns named '" + f.name + "'");
@@ -87,14 +114,14 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
     ScanParams P;
     try {
         ProgramBuilder pb(ls);
-        for (auto& p : on_) pb.add_key(make_column(p.first), true);
+        for (auto& k : left_keys_) pb.add_key(make_column(k), true);
         pb.finish(P);
     } catch (const Error& e) {
         if (!key_width_error(e)) throw;
         static_wide_ = true;
         ProgramBuilder hb(ls);
         hb.set_hash_only();
-        for (auto& p : on_) hb.add_key(make_column(p.first), true);
+        for (auto& k : left_keys_) hb.add_key(make_column(k), true);
         hb.finish(P);
     }
     cache_ = std::make_shared<BuildCache>();
@@ -111,10 +138,7 @@ void HashJoinExec::check_filter() {
         origin.push_back(FilterCol{true, (int)i, ls.fields[i]});
     }
     for (size_t i = 0; i < rs.fields.size(); ++i) {
-        bool drop = false;
-        for (auto& p : on_)
-            if (p.second == rs.fields[i].name && p.first == p.second) drop = true;
-        if (drop) continue;
+        if (named_like_left_key(on_, rs.fields[i].name)) continue;
         // (the existence types' outputs would not clash, but the filter's schema does: a ProjectionExec renames)
         if (fs.index_of(rs.fields[i].name) >= 0) fail(BHIP_EINVAL, "join output would have two columns named '" + rs.fields[i].name + "'");
         fs.fields.push_back(rs.fields[i]);
@@ -157,22 +181,23 @@ std::string HashJoinExec::describe() const {
 // the integer key columns that need no packed 16-byte image: 4 (Int32 / Date32), 8 (Int64 / UInt64) bytes wide, else 0
 static int int_key_width(int t) { return (t == DT_INT32 || t == DT_DATE32) ? 4 : (t == DT_INT64 || t == DT_UINT64) ? 8 : 0; }
 
-// packed keys (+ "no NULL key" selection) of one side
-static void side_keys(const Exec& ex, const Batch& b, const std::vector<std::string>& cols, BufferPtr& keys, BufferPtr& sel,
-                      bool& has_sel) {
+// the keys of the rows of `b` (key columns `cols`) in a general table's form: packed keys, or (wide) row hashes and the key columns;
+// and the "no NULL key part" selection
+static SideKeys side_keys(const Exec& ex, const Batch& b, const std::vector<std::string>& cols, bool wide) {
+    SideKeys k;
     // one NULL-free integer key column (every TPC-H join): the image is a widening copy, no expression program
-    if (cols.size() == 1) {
+    if (!wide && cols.size() == 1) {
         const int ci = b.schema->index_of(cols[0]);
         const Column& c = b.cols[ci];
         const int w = int_key_width(c.dtype);
         if (w && !c.validity) {
-            keys = make_buffer(ex, (size_t)b.n_rows * 16 + 16);
-            has_sel = false;
-            TIMED_LAUNCH_N(ex, "widen_key", b.n_rows, launch_widen_key(ex.cfg(), c.data->ptr(), w, b.n_rows, keys->as<uint64_t>()));
-            return;
+            k.keys = make_buffer(ex, (size_t)b.n_rows * 16 + 16);
+            TIMED_LAUNCH_N(ex, "widen_key", b.n_rows, launch_widen_key(ex.cfg(), c.data->ptr(), w, b.n_rows, k.keys->as<uint64_t>()));
+            return k;
         }
     }
     ProgramBuilder pb(*b.schema);
+    if (wide) pb.set_hash_only();
     ExprPtr pred;
     for (auto& c : cols) {
         const int ci = b.schema->index_of(c);
@@ -182,54 +207,25 @@ static void side_keys(const Exec& ex, const Batch& b, const std::vector<std::str
             e->args = {make_column(c)};
             pred = pred ? make_binary(pred, "And", e) : ExprPtr(e);
         }
+        if (wide) k.cols.col[k.cols.n++] = b.cols[ci].ref();
     }
     if (pred) pb.set_predicate(pred);
     for (auto& c : cols) pb.add_key(make_column(c), true);
     ScanParams P;
     pb.finish(P);
     ProgramBuilder::bind(P, pb.columns(), b, pb.creates_nulls());
-    keys = make_buffer(ex, (size_t)b.n_rows * 16 + 16);
-    has_sel = (bool)pred;
-    if (has_sel) sel = make_buffer(ex, bitmap_bytes(b.n_rows) + 8);
-    if (b.n_rows == 0) return;
+    k.keys = make_buffer(ex, (size_t)b.n_rows * (wide ? 8 : 16) + 16);
+    k.has_sel = (bool)pred;
+    if (k.has_sel) k.sel = make_buffer(ex, bitmap_bytes(b.n_rows) + 8);
+    if (b.n_rows == 0) return k;
     Temp tmp(ex);
     ScanStatus* st = tmp.get<ScanStatus>(1);
     HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
-    TIMED_LAUNCH_N(ex, "scan_keys", b.n_rows, launch_scan_keys(ex.cfg(), P, keys->as<uint64_t>(), nullptr, has_sel ? sel->as<uint64_t>() : nullptr, st));
+    uint64_t* out = k.keys->as<uint64_t>();
+    TIMED_LAUNCH_N(ex, "scan_keys", b.n_rows,
+                   launch_scan_keys(ex.cfg(), P, wide ? nullptr : out, wide ? out : nullptr, k.has_sel ? k.sel->as<uint64_t>() : nullptr, st));
     check_scan_status(ex, st);
-}
-
-// the wide-key form of one side: 64-bit row hashes (+ "no NULL key" selection) and the key columns themselves
-static void side_hashes(const Exec& ex, const Batch& b, const std::vector<std::string>& cols, BufferPtr& hashes, BufferPtr& sel, bool& has_sel,
-                        WideKeyCols& K) {
-    ProgramBuilder pb(*b.schema);
-    pb.set_hash_only();
-    ExprPtr pred;
-    memset(&K, 0, sizeof(K));
-    for (auto& c : cols) {
-        const int ci = b.schema->index_of(c);
-        if (b.schema->fields[ci].nullable || b.cols[ci].validity) {
-            auto e = std::make_shared<Expr>();
-            e->kind = BHIP_EXPR_IS_NOT_NULL;
-            e->args = {make_column(c)};
-            pred = pred ? make_binary(pred, "And", e) : ExprPtr(e);
-        }
-        K.col[K.n++] = b.cols[ci].ref();
-    }
-    if (pred) pb.set_predicate(pred);
-    for (auto& c : cols) pb.add_key(make_column(c), true);
-    ScanParams P;
-    pb.finish(P);
-    ProgramBuilder::bind(P, pb.columns(), b, pb.creates_nulls());
-    hashes = make_buffer(ex, (size_t)b.n_rows * 8 + 16);
-    has_sel = (bool)pred;
-    if (has_sel) sel = make_buffer(ex, bitmap_bytes(b.n_rows) + 8);
-    if (b.n_rows == 0) return;
-    Temp tmp(ex);
-    ScanStatus* st = tmp.get<ScanStatus>(1);
-    HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
-    TIMED_LAUNCH_N(ex, "scan_keys", b.n_rows, launch_scan_keys(ex.cfg(), P, nullptr, hashes->as<uint64_t>(), has_sel ? sel->as<uint64_t>() : nullptr, st));
-    check_scan_status(ex, st);
+    return k;
 }
 
 // TWO key pairs of 4-byte integer columns, the same type on both sides (UInt32 counts here, and not for a single key below)
@@ -482,9 +478,7 @@ static BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema) {
 // row hashes with the key columns of the build batch as the keys — any width
 static void build_general_table(const Exec& ex, JoinBuildSide* bs, const std::vector<std::string>& key_names, uint64_t cap, bool wide) {
     const int64_t n = bs->batch->n_rows;
-    BufferPtr hashes;
-    if (wide) side_hashes(ex, *bs->batch, key_names, hashes, bs->sel, bs->has_sel, bs->wkeys);
-    else side_keys(ex, *bs->batch, key_names, bs->keys, bs->sel, bs->has_sel);
+    bs->keys = side_keys(ex, *bs->batch, key_names, wide);
     bs->wide = wide;
     bs->owner = make_buffer(ex, cap * 8);
     bs->head = make_buffer(ex, cap * 4);
@@ -495,16 +489,16 @@ static void build_general_table(const Exec& ex, JoinBuildSide* bs, const std::ve
     bs->table.head = bs->head->as<uint32_t>();
     bs->table.next = bs->next->as<uint32_t>();
     bs->table.mask = cap - 1;
-    bs->table.keys128 = wide ? nullptr : bs->keys->as<uint64_t>();
+    bs->table.keys128 = wide ? nullptr : bs->keys.keys->as<uint64_t>();
+    bs->table.cols = wide ? &bs->keys.cols : nullptr;
     bs->dup = make_buffer(ex, 8);
     HIP_CHECK(hipMemsetAsync(bs->dup->ptr(), 0, 8, ex.stream));
     bs->table.dup_flag = bs->dup->as<uint32_t>();
-    const uint64_t* sel = bs->has_sel ? bs->sel->as<uint64_t>() : nullptr;
-    if (wide) TIMED_LAUNCH_N(ex, "join_build_wide", n, launch_join_build_wide(ex.cfg(), bs->table, bs->wkeys, hashes->as<uint64_t>(), sel, (uint32_t)n));
-    else TIMED_LAUNCH_N(ex, "join_build", n, launch_join_build(ex.cfg(), bs->table, sel, (uint32_t)n));
+    TIMED_LAUNCH_N(ex, kernel_name(K_BUILD, wide), n, launch_join_build(ex.cfg(), bs->table, bs->keys.view(), (uint32_t)n));
     // other tasks (other HIP streams) will read the table: it must be complete before it is published
     bs->unique = read_device(ex, bs->dup->as<uint32_t>()) == 0;
     bs->table.dup_flag = nullptr;
+    if (wide) bs->keys.keys.reset();        // the row hashes: only the build read them (emit_build_rows computes them again for its one pass)
 }
 
 // the wide-key table over the build batch of `packed`, beside it in the cache: for the probe batches whose keys outgrow the packed key
@@ -513,9 +507,7 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::wide_sibling(const Exec& ex, 
     if (!cache_->wide) {
         auto w = std::make_shared<JoinBuildSide>();
         w->batch = packed.batch;
-        std::vector<std::string> left_keys;
-        for (auto& p : on_) left_keys.push_back(p.first);
-        build_general_table(ex, w.get(), left_keys, table_capacity((uint64_t)w->batch->n_rows), true);
+        build_general_table(ex, w.get(), left_keys_, table_capacity((uint64_t)w->batch->n_rows), true);
         cache_->wide = w;
     }
     ex.ctx->set_join_key_form("wide");
@@ -531,10 +523,8 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
     auto bs = std::make_shared<JoinBuildSide>();
     std::vector<BatchPtr> parts;
     const int np = left_->output_partitioning().count;
-    std::vector<std::string> left_keys;
-    for (auto& p : on_) left_keys.push_back(p.first);
     for (int p = 0; p < np; ++p) {
-        auto s = open_join_child(left_, p, ex, left_keys);
+        auto s = open_join_child(left_, p, ex, left_keys_);
         while (BatchPtr b = s->next())
             if (b->n_rows > 0) parts.push_back(b);
     }
@@ -555,9 +545,9 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
     bool narrow = false;
     if (nkw && n > 0) {
         const Schema& lsch = *bs->batch->schema;
-        const Column& c0 = bs->batch->cols[lsch.index_of(left_keys[0])];
+        const Column& c0 = bs->batch->cols[lsch.index_of(left_keys_[0])];
         if (pair_keys()) {
-            const Column& c1 = bs->batch->cols[lsch.index_of(left_keys[1])];
+            const Column& c1 = bs->batch->cols[lsch.index_of(left_keys_[1])];
             // ON (a, b) = (c, d), 4-byte integers.  First choice: the build side unique on `a` alone (a key and an attribute it determines:
             // TPC-H Q5's s_suppkey, s_nationkey) — the join goes by `a` (rank map where the keys are dense) and a match stands only if
             // the second columns agree (join_filter_probe_kernel<RESID>).  Second: both columns packed into one 8-byte key.
@@ -584,15 +574,14 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
         bool wide = static_wide_ || wide_keys_.load() || env_flag("BHIP_JOIN_WIDE");
         if (!wide) {
             try {
-                build_general_table(ex, bs.get(), left_keys, cap, false);
+                build_general_table(ex, bs.get(), left_keys_, cap, false);
             } catch (const Error& e) {
                 if (!key_width_error(e)) throw;                 // a build value longer than its share of the packed key
                 wide_keys_.store(true);
-                bs->keys.reset();
                 wide = true;
             }
         }
-        if (wide) build_general_table(ex, bs.get(), left_keys, cap, true);
+        if (wide) build_general_table(ex, bs.get(), left_keys_, cap, true);
     }
     cache_->built = bs;
     report(*bs);
@@ -834,39 +823,53 @@ struct HashJoinExec::Probe {
         finish(tmp, o, ix, n_out);
     }
 
+    // the key-equal pairs of one probe batch through the chains of `t`: count -> scan -> read -> emit.  -> their number; ix.lidx /
+    // ix.ridx: scratch of `tmp` (a probe row's pairs consecutive).  outer: a probe row without a pair yields (none, row); mark: the
+    // build rows' bits (null: none)
+    uint64_t enumerate_pairs(Temp& tmp, const JoinBuildSide& t, const JoinSideKeys& keys, int64_t n_right, bool outer, uint32_t* mark,
+                             const char* too_many, JoinIndices& ix) {
+        uint64_t* total = tmp.get<uint64_t>(1);
+        uint32_t* counts = tmp.get<uint32_t>((size_t)n_right + 1);
+        uint64_t* offsets = tmp.get<uint64_t>((size_t)n_right + 1);
+        void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_right));
+        TIMED_LAUNCH_N(ex, kernel_name(K_PROBE_COUNT, t.wide), n_right, launch_join_probe_count(cfg, t.table, keys, (uint32_t)n_right, outer, counts));
+        HIP_CHECK(exclusive_scan_u32_u64(ex.stream, counts, n_right, offsets, false, total, scan_tmp));
+        const uint64_t n = read_device(ex, total);
+        if (n > 0xFFFFFFF0ull) fail(BHIP_EEXEC, too_many);
+        if (n == 0) return 0;
+        ix.lidx = tmp.get<uint32_t>((size_t)n);
+        ix.ridx = tmp.get<uint32_t>((size_t)n);
+        TIMED_LAUNCH_N(ex, kernel_name(K_PROBE_EMIT, t.wide), n_right,
+                       launch_join_probe_emit(cfg, t.table, keys, (uint32_t)n_right, outer, offsets, ix.lidx, ix.ridx, mark));
+        return n;
+    }
+
     // ---- general table: `probe` holds the key columns of the probe rows under their names -----------------------------------------
     // (a packed build side whose keys this batch's values outgrow: the batch goes through the wide table over the same build rows,
-    // HashJoinExec::wide_sibling; the wide kernels read row hashes `rkeys` and the key columns `K` where the packed ones read packed keys)
+    // HashJoinExec::wide_sibling.  Below this point the form only names the kernels: the launchers pick it from the keys.)
     void probe_general(const Batch& probe, const ProbeOut& o) {
         const int64_t n_right = probe.n_rows;
         if (n_right == 0) return;
         std::shared_ptr<const JoinBuildSide> t = bs;
-        BufferPtr rkeys, rsel;
-        bool has_rsel = false;
-        WideKeyCols K;
+        SideKeys pk;
         if (!t->wide) {
             try {
-                side_keys(ex, probe, rcols, rkeys, rsel, has_rsel);
+                pk = side_keys(ex, probe, rcols, false);
             } catch (const Error& e) {
                 if (!key_width_error(e)) throw;
                 t = sibling = J.wide_sibling(ex, *bs);
             }
         }
-        if (t->wide) side_hashes(ex, probe, rcols, rkeys, rsel, has_rsel, K);
-        const uint64_t* rselp = has_rsel ? rsel->as<uint64_t>() : nullptr;
-        if (J.filter_) { probe_filtered(*t, o, rkeys->as<uint64_t>(), rselp, K, n_right); return; }
+        if (t->wide) pk = side_keys(ex, probe, rcols, true);
+        const JoinSideKeys keys = pk.view();
+        if (J.filter_) { probe_filtered(*t, o, keys, n_right); return; }
         Temp tmp(ex);
         if (mark_only || select_only) {
             // existence: one probe per row whatever the duplication (the slot's owner stands for its key).  Semi / Anti leave bits
             // for emit_build_rows; RightSemi / RightAnti a selection of the probe rows, compacted as the unique build side's is
             auto exists = [&](uint64_t* bitmap, uint32_t* tile_counts, uint32_t* mark) {
-                if (t->wide)
-                    TIMED_LAUNCH_N(ex, "join_probe_exists_wide", n_right,
-                                   launch_join_probe_exists_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, anti, bitmap,
-                                                                 tile_counts, mark));
-                else
-                    TIMED_LAUNCH_N(ex, "join_probe_exists", n_right,
-                                   launch_join_probe_exists(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, anti, bitmap, tile_counts, mark));
+                TIMED_LAUNCH_N(ex, kernel_name(K_PROBE_EXISTS, t->wide), n_right,
+                               launch_join_probe_exists(cfg, t->table, keys, (uint32_t)n_right, anti, bitmap, tile_counts, mark));
             };
             if (mark_only) { exists(nullptr, nullptr, matched_bits()); return; }
             TileSelection s(tmp, n_right, false, false, false);
@@ -877,43 +880,14 @@ struct HashJoinExec::Probe {
         if (t->unique) {
             // one probe per row -> selection bitmap -> indices (the index pass of FilterExec)
             TileSelection s(tmp, n_right, false, false);
-            if (t->wide)
-                TIMED_LAUNCH_N(ex, "join_probe_match_wide", n_right,
-                               launch_join_probe_match_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer,
-                                                            s.partner, s.bitmap, s.tile_counts, matched_bits()));
-            else
-                TIMED_LAUNCH_N(ex, "join_probe_match", n_right,
-                               launch_join_probe_match(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, s.partner,
-                                                       s.bitmap, s.tile_counts, matched_bits()));
+            TIMED_LAUNCH_N(ex, kernel_name(K_PROBE_MATCH, t->wide), n_right,
+                           launch_join_probe_match(cfg, t->table, keys, (uint32_t)n_right, right_outer, s.partner, s.bitmap, s.tile_counts, matched_bits()));
             compact(tmp, s, o);
             return;
         }
-        uint64_t* total = tmp.get<uint64_t>(1);
-        uint32_t* counts = tmp.get<uint32_t>((size_t)n_right + 1);
-        uint64_t* offsets = tmp.get<uint64_t>((size_t)n_right + 1);
-        void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_right));
-        if (t->wide)
-            TIMED_LAUNCH_N(ex, "join_probe_count_wide", n_right,
-                           launch_join_probe_count_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, counts));
-        else
-            TIMED_LAUNCH_N(ex, "join_probe_count", n_right,
-                           launch_join_probe_count(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, counts));
-        HIP_CHECK(exclusive_scan_u32_u64(ex.stream, counts, n_right, offsets, false, total, scan_tmp));
-        const uint64_t n_out = read_device(ex, total);
-        if (n_out > 0xFFFFFFF0ull) fail(BHIP_EEXEC, "join output of one probe batch exceeds 2^32 rows");
-        if (n_out == 0) return;
         JoinIndices ix;
-        ix.lidx = tmp.get<uint32_t>((size_t)n_out);
-        ix.ridx = tmp.get<uint32_t>((size_t)n_out);
-        if (t->wide)
-            TIMED_LAUNCH_N(ex, "join_probe_emit_wide", n_right,
-                           launch_join_probe_emit_wide(cfg, t->table, t->wkeys, K, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer,
-                                                       offsets, ix.lidx, ix.ridx, matched_bits()));
-        else
-            TIMED_LAUNCH_N(ex, "join_probe_emit", n_right,
-                           launch_join_probe_emit(cfg, t->table, rkeys->as<uint64_t>(), rselp, (uint32_t)n_right, right_outer, offsets,
-                                                  ix.lidx, ix.ridx, matched_bits()));
-        finish(tmp, o, ix, n_out);
+        const uint64_t n_out = enumerate_pairs(tmp, *t, keys, n_right, right_outer, matched_bits(), "join output of one probe batch exceeds 2^32 rows", ix);
+        if (n_out) finish(tmp, o, ix, n_out);
     }
 
     // ---- residual filter: candidates (the key-equal pairs, enumerated as an Inner join whatever the join type and the build side's
@@ -955,41 +929,22 @@ struct HashJoinExec::Probe {
         return filter_indices(ex, *fb, J.filter_, sel);
     }
 
-    void probe_filtered(const JoinBuildSide& t, const ProbeOut& o, const uint64_t* rkeys, const uint64_t* rselp, const WideKeyCols& K, int64_t n_right) {
+    void probe_filtered(const JoinBuildSide& t, const ProbeOut& o, const JoinSideKeys& keys, int64_t n_right) {
         Temp tmp(ex);
-        uint64_t* total = tmp.get<uint64_t>(1);
-        uint32_t* counts = tmp.get<uint32_t>((size_t)n_right + 1);
-        uint64_t* offsets = tmp.get<uint64_t>((size_t)n_right + 1);
-        void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_right));
-        if (t.wide)
-            TIMED_LAUNCH_N(ex, "join_probe_count_wide", n_right,
-                           launch_join_probe_count_wide(cfg, t.table, t.wkeys, K, rkeys, rselp, (uint32_t)n_right, false, counts));
-        else
-            TIMED_LAUNCH_N(ex, "join_probe_count", n_right, launch_join_probe_count(cfg, t.table, rkeys, rselp, (uint32_t)n_right, false, counts));
-        HIP_CHECK(exclusive_scan_u32_u64(ex.stream, counts, n_right, offsets, false, total, scan_tmp));
-        const uint64_t n_cand = read_device(ex, total);
-        if (n_cand > 0xFFFFFFF0ull) fail(BHIP_EEXEC, "join filter: the key-equal candidate pairs of one probe batch exceed 2^32");
+        JoinIndices cand;
+        const uint64_t n_cand = enumerate_pairs(tmp, t, keys, n_right, false, nullptr, "join filter: the key-equal candidate pairs of one probe batch exceed 2^32", cand);
         // Right / Full / RightSemi / RightAnti answer per probe row of this batch
         const bool need_hit = right_outer || select_only;
         TileSelection s(tmp, need_hit ? n_right : 0, false, false, false);
         if (need_hit) HIP_CHECK(hipMemsetAsync(s.bitmap, 0, ((size_t)(n_right + 63) / 64) * 8, ex.stream));
         if (n_cand) {
-            uint32_t* lidx = tmp.get<uint32_t>((size_t)n_cand);
-            uint32_t* ridx = tmp.get<uint32_t>((size_t)n_cand);
-            if (t.wide)
-                TIMED_LAUNCH_N(ex, "join_probe_emit_wide", n_right,
-                               launch_join_probe_emit_wide(cfg, t.table, t.wkeys, K, rkeys, rselp, (uint32_t)n_right, false, offsets, lidx, ridx, nullptr));
-            else
-                TIMED_LAUNCH_N(ex, "join_probe_emit", n_right,
-                               launch_join_probe_emit(cfg, t.table, rkeys, rselp, (uint32_t)n_right, false, offsets, lidx, ridx, nullptr));
+            const uint32_t *lidx = cand.lidx, *ridx = cand.ridx;
             BufferPtr sel;
             const uint64_t n_keep = (uint64_t)filter_candidates(tmp, o, lidx, ridx, n_cand, sel);
             if (n_keep) {
                 // all kept: the candidates are the pairs, and only the bits are left to set
                 const bool all = n_keep == n_cand, pairs = !mark_only && !select_only;
-                JoinIndices ix;
-                ix.lidx = lidx;
-                ix.ridx = ridx;
+                JoinIndices ix = cand;
                 if (pairs && !all) {
                     ix.lidx = tmp.get<uint32_t>((size_t)n_keep);
                     ix.ridx = tmp.get<uint32_t>((size_t)n_keep);
@@ -1122,21 +1077,16 @@ struct HashJoinExec::Probe {
         const bool direct = left_outer || bs->unique || J.filter_;          // (a residual filter marks the very rows that passed it)
         const bool want_unmatched = left_outer || anti;
         auto flags_of = [&](const JoinBuildSide& t, bool anti_now, bool merge) {
-            const uint64_t* sel = t.has_sel ? t.sel->as<uint64_t>() : nullptr;
-            if (direct || !t.wide) {
-                TIMED_LAUNCH_N(ex, "join_exists_flags", n_left,
-                               launch_join_exists_flags(cfg, t.table, sel, matched->as<uint32_t>(), (uint32_t)n_left, direct, anti_now, merge, flags));
-                return;
+            // a wide table's rows find their slots by their hashes, which are not kept after the build: once more, for this one pass
+            const bool rehash = t.wide && !direct;
+            JoinSideKeys keys = t.keys.view();
+            SideKeys again;
+            if (rehash) {
+                again = side_keys(ex, L, J.left_keys_, true);
+                keys.keys = again.keys->as<uint64_t>();
             }
-            BufferPtr hashes, hsel;                 // the build rows' hashes are not kept after the build: once more, for this one pass
-            bool has_hsel;
-            WideKeyCols K;
-            std::vector<std::string> lcols;
-            for (auto& p : J.on_) lcols.push_back(p.first);
-            side_hashes(ex, L, lcols, hashes, hsel, has_hsel, K);
-            TIMED_LAUNCH_N(ex, "join_exists_flags_wide", n_left,
-                           launch_join_exists_flags_wide(cfg, t.table, t.wkeys, hashes->as<uint64_t>(), sel, matched->as<uint32_t>(), (uint32_t)n_left,
-                                                         anti_now, merge, flags));
+            TIMED_LAUNCH_N(ex, kernel_name(K_EXISTS_FLAGS, rehash), n_left,
+                           launch_join_exists_flags(cfg, t.table, keys, matched->as<uint32_t>(), (uint32_t)n_left, direct, anti_now, merge, flags));
         };
         if (sibling && !direct) flags_of(*sibling, false, false);
         flags_of(*bs, want_unmatched, sibling && !direct);

@@ -254,6 +254,7 @@ private:
     struct Probe;                    // the probe of one partition against the build side (ops_join.cpp)
     PlanPtr left_, right_;
     std::vector<std::pair<std::string, std::string>> on_;
+    std::vector<std::string> left_keys_;   // on_[i].first
     int join_type_;
     SchemaPtr schema_;
     std::vector<int> right_cols_;   // right columns kept in the output

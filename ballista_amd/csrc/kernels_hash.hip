@@ -284,11 +284,86 @@ hash_agg_compact_kernel(HashAggTable T, const uint64_t* dense_index, int nulls, 
 // =============================================================================================
 __device__ inline bool bit_at(const uint64_t* bm, uint32_t i) { return bm == nullptr || ((bm[i >> 6] >> (i & 63)) & 1ull); }
 
+// ---- join keys of any width: the JoinTable over 64-bit row hashes, equality on the key columns ---------------------------
+// (HashJoinExec on c_name, a phone number, three Int64 columns ...: what the 16-byte packed key cannot hold.)  Slot word, chain
+// (head / next) and dup_flag are those of the packed form; the tag is the high half of the row hash, so the columns are read
+// for true matches and about one in 2^32 others.  Row `a` of A against row `b` of B, column by column; both rows are known to
+// have no NULL key part (sel / rsel), so no validity is read.  Fixed-width parts: the 64-bit image the packed key holds (floats by
+// bits: -0.0 != +0.0, a NaN equals the NaN of the same bits).  Utf8: lengths, then 8 bytes at a time where 8 remain, then the
+// tail byte by byte — only bytes of the two values are read, nothing behind offsets[n].
+__device__ inline bool wide_rows_equal(const WideKeyCols& A, uint32_t a, const WideKeyCols& B, uint32_t b) {
+    for (int c = 0; c < A.n; ++c) {
+        const ColumnRef& ra = A.col[c];
+        const ColumnRef& rb = B.col[c];
+        switch (ra.dtype) {
+            case DT_UTF8: {
+                const int32_t a0 = ra.offsets[a], b0 = rb.offsets[b];
+                const int32_t len = ra.offsets[a + 1] - a0;
+                if (len != rb.offsets[b + 1] - b0) return false;
+                const uint8_t* x = static_cast<const uint8_t*>(ra.data) + a0;
+                const uint8_t* y = static_cast<const uint8_t*>(rb.data) + b0;
+                int32_t i = 0;
+                for (; i + 8 <= len; i += 8) {
+                    uint64_t u, v;
+                    __builtin_memcpy(&u, x + i, 8);
+                    __builtin_memcpy(&v, y + i, 8);
+                    if (u != v) return false;
+                }
+                for (; i < len; ++i)
+                    if (x[i] != y[i]) return false;
+            } break;
+            case DT_BOOLEAN: {
+                const uint8_t* x = static_cast<const uint8_t*>(ra.data);
+                const uint8_t* y = static_cast<const uint8_t*>(rb.data);
+                if (((x[a >> 3] >> (a & 7)) & 1) != ((y[b >> 3] >> (b & 7)) & 1)) return false;
+            } break;
+            default:
+                if (dt_load(ra.dtype, ra.data, a) != dt_load(rb.dtype, rb.data, b)) return false;
+                break;
+        }
+    }
+    return true;
+}
+
+// ---- the two key forms of a JoinTable.  Every kernel below is written once, over a policy K that it takes BY VALUE as a kernel
+// argument and that answers three questions about the rows that probe the table:
+//   key(row)           the handle of row `row`'s key — what a lane holds while it walks the slots; none() for a row that is not probed
+//   hash(key)          its 64-bit hash (slot = the low bits, tag = the high half)
+//   equal(T, o, key)   build row `o` (the owner of a slot of T) has an equal key
+// The build side probes with its own rows (join_build_kernel, join_exists_flags_kernel): the same policy with probe = build.
+// PROBE_ROWS: the rows per lane and pass of join_owner_walk.
+struct PackedKeys {                 // 16-byte packed keys (scan_keys / widen_key): the probing rows' here, the build rows' in T.keys128
+                                    // (a copy of that pointer here took join_probe_match from 73 to 82 SGPRs: one block per CU fewer)
+    const ulonglong2* probe;
+    using Key = ulonglong2;
+    static constexpr int PROBE_ROWS = 4;
+    __device__ Key key(uint64_t row) const { return probe[row]; }
+    __device__ static Key none() { return ulonglong2{0ull, 0ull}; }
+    __device__ uint64_t hash(const Key& k) const { return hash_key(Key128{k.x, k.y}); }
+    __device__ bool equal(const JoinTable& T, uint32_t o, const Key& k) const {
+        const ulonglong2 b = reinterpret_cast<const ulonglong2*>(T.keys128)[o];
+        return b.x == k.x && b.y == k.y;
+    }
+};
+struct WideKeys {                   // the key columns of the build rows (B) and of the probing rows (P), and the latter's row hashes
+    WideKeyCols B, P;
+    const uint64_t* hashes;
+    struct Key { uint64_t hash; uint32_t row; };
+    static constexpr int PROBE_ROWS = 1;    // (four, as the packed form: a change of speed that nobody has measured)
+    __device__ Key key(uint64_t row) const { return Key{hashes[row], (uint32_t)row}; }
+    __device__ static Key none() { return Key{0ull, 0u}; }
+    __device__ uint64_t hash(const Key& k) const { return k.hash; }
+    __device__ bool equal(const JoinTable&, uint32_t o, const Key& k) const { return wide_rows_equal(B, o, P, k.row); }
+};
+
 // JoinTable slot word = (claiming row + 1) | (high half of the key's hash) << 32, claimed by ONE 64-bit CAS.  The tag lets
-// a prober pass a slot of another key without touching that key in keys128: the probe is bound by the number of cache
-// lines it pulls out of L2 / MALL (Q5: 18 M probes, 96 % of them misses walking ~2.5 slots, two lines per slot before).
-__device__ inline uint32_t join_table_upsert(const JoinTable& T, const Key128& key, uint32_t row) {
-    const uint64_t h = hash_key(key);
+// a prober pass a slot of another key without touching that key (keys128, or the key columns): the probe is bound by the number of
+// cache lines it pulls out of L2 / MALL (Q5: 18 M probes, 96 % of them misses walking ~2.5 slots, two lines per slot before).
+// find (or claim) the slot of build row `row`'s key `key`
+// (ends: the table has more slots than build rows, and an empty slot is claimed or turns out to be taken)
+template <class K>
+__device__ inline uint32_t join_upsert(const JoinTable& T, const K& keys, const typename K::Key& key, uint32_t row) {
+    const uint64_t h = keys.hash(key);
     const uint64_t tag = h >> 32;
     const unsigned long long want = (unsigned long long)(row + 1u) | (tag << 32);
     uint64_t slot = h & T.mask;
@@ -298,50 +373,46 @@ __device__ inline uint32_t join_table_upsert(const JoinTable& T, const Key128& k
             o = atomicCAS(reinterpret_cast<unsigned long long*>(&T.owner[slot]), 0ull, want);
             if (o == 0) return (uint32_t)slot;       // claimed: this row's key defines the slot
         }
-        if ((o >> 32) == tag) {
-            const uint64_t* k = T.keys128 + 2ull * ((uint32_t)o - 1u);
-            if (k[0] == key.k0 && k[1] == key.k1) return (uint32_t)slot;
-        }
+        if ((o >> 32) == tag && keys.equal(T, (uint32_t)o - 1u, key)) return (uint32_t)slot;
         slot = (slot + 1) & T.mask;
     }
 }
 
+// slot whose owner's key equals `key`, or 0xFFFFFFFF; *owner_row = that owner (read-only: the table was finished by the build kernel).
+// Ends at the first empty slot, and table_capacity() leaves at least half of the slots empty.
+template <class K>
+__device__ inline uint32_t join_find(const JoinTable& T, const K& keys, const typename K::Key& key, uint32_t* owner_row) {
+    const uint64_t h = keys.hash(key);
+    const uint64_t tag = h >> 32;
+    uint64_t slot = h & T.mask;
+    for (;;) {
+        const uint64_t o = T.owner[slot];
+        if (o == 0) return 0xFFFFFFFFu;
+        if ((o >> 32) == tag && keys.equal(T, (uint32_t)o - 1u, key)) { *owner_row = (uint32_t)o - 1u; return (uint32_t)slot; }
+        slot = (slot + 1) & T.mask;
+    }
+}
+
+template <class K>
 __global__ void __launch_bounds__(BLOCK)
-join_build_kernel(JoinTable T, const uint64_t* sel, uint32_t n_left) {
+join_build_kernel(JoinTable T, const K keys, const uint64_t* sel, uint32_t n_left) {
     for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK) {
         if (!bit_at(sel, row)) continue;                       // NULL keys never match
-        const Key128 key{T.keys128[2ull * row], T.keys128[2ull * row + 1]};
-        const uint32_t slot = join_table_upsert(T, key, row);
+        const uint32_t slot = join_upsert(T, keys, keys.key(row), row);
         const uint32_t prev = atomicExch(&T.head[slot], row + 1u);     // push on the slot's chain
         T.next[row] = prev;
         if (prev != 0 && T.dup_flag) *T.dup_flag = 1u;                 // a second row with this key: not a unique build side
     }
 }
 
-// slot holding `key`, or 0xFFFFFFFF (read-only: the table was finished by the build kernel)
-__device__ inline uint32_t table_find(const JoinTable& T, const Key128& key) {
-    const uint64_t h = hash_key(key);
-    const uint64_t tag = h >> 32;
-    uint64_t slot = h & T.mask;
-    for (;;) {
-        const uint64_t o = T.owner[slot];
-        if (o == 0) return 0xFFFFFFFFu;
-        if ((o >> 32) == tag) {
-            const uint64_t* k = T.keys128 + 2ull * ((uint32_t)o - 1u);
-            if (k[0] == key.k0 && k[1] == key.k1) return (uint32_t)slot;
-        }
-        slot = (slot + 1) & T.mask;
-    }
-}
-
+template <class K>
 __global__ void __launch_bounds__(BLOCK)
-join_probe_count_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right, int right_outer,
-                        uint32_t* counts) {
+join_probe_count_kernel(JoinTable T, const K keys, const uint64_t* rsel, uint32_t n_right, int right_outer, uint32_t* counts) {
     for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_right; row += gridDim.x * BLOCK) {
         uint32_t c = 0;
         if (bit_at(rsel, row)) {
-            const Key128 key{rkeys128[2ull * row], rkeys128[2ull * row + 1]};
-            const uint32_t slot = table_find(T, key);
+            uint32_t owner;
+            const uint32_t slot = join_find(T, keys, keys.key(row), &owner);
             if (slot != 0xFFFFFFFFu)
                 for (uint32_t l = T.head[slot]; l != 0; l = T.next[l - 1u]) ++c;
         }
@@ -349,15 +420,16 @@ join_probe_count_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* r
     }
 }
 
+template <class K>
 __global__ void __launch_bounds__(BLOCK)
-join_probe_emit_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right, int right_outer,
-                       const uint64_t* offsets, uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched) {
+join_probe_emit_kernel(JoinTable T, const K keys, const uint64_t* rsel, uint32_t n_right, int right_outer, const uint64_t* offsets,
+                       uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched) {
     for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_right; row += gridDim.x * BLOCK) {
         uint64_t pos = offsets[row];
         uint32_t c = 0;
         if (bit_at(rsel, row)) {
-            const Key128 key{rkeys128[2ull * row], rkeys128[2ull * row + 1]};
-            const uint32_t slot = table_find(T, key);
+            uint32_t owner;
+            const uint32_t slot = join_find(T, keys, keys.key(row), &owner);
             if (slot != 0xFFFFFFFFu)
                 for (uint32_t l = T.head[slot]; l != 0; l = T.next[l - 1u]) {
                     left_idx[pos] = l - 1u;
@@ -371,69 +443,87 @@ join_probe_emit_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* rs
     }
 }
 
-// ---- unique build keys (primary-key side: every TPC-H join): a probe row has at most one partner, so the
-// table is probed ONCE and the result is a selection: partner[row] (build row id, 0xFFFFFFFF = none), the bitmap
-// of emitting rows and its per-1024-row counts — the index pass of FilterExec (select_indices) then yields the
-// probe-side indices in row order and one gather of partner[] the build-side indices.  With unique keys the
-// slot's owner IS its only row: the chain head is never read (two random reads per probe instead of three).
-__global__ void __launch_bounds__(BLOCK)
-join_probe_match_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right, int right_outer,
-                        uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
-    // four rows per lane and pass, as the narrow probe: the packed keys, then the slot owners, then the owners' keys of all
-    // four are in flight together (the chain key -> owner -> owner's key is latency; Q5: 18 M probes took 0.72 ms one by one)
-    constexpr int PROBE_ROWS = 4;
-    static_assert(SEL_TILE % (64 * PROBE_ROWS) == 0, "the rows of one pass of a wave lie in one selection tile");
+// ---- one probe per row: the slot's OWNER row of every probe row (0xFFFFFFFF: no build row has its key), ROWS = K::PROBE_ROWS rows
+// per lane and pass.  tail(wbase, n_round, lane, in, m) then sees, for k < ROWS, probe row wbase + 64 k + lane: in[k] = it exists
+// (< n_right), m[k] = its owner row; every lane of a wave makes the same number of passes, so a ballot in the tail sees all 64.
+// Packed keys, four rows, as the narrow probe: the packed keys, then the slot owners, then the owners' keys of all four are in
+// flight together (the chain key -> owner -> owner's key is latency; Q5: 18 M probes took 0.72 ms one by one).
+template <class K, class Tail>
+__device__ inline void join_owner_walk(const JoinTable& T, const K& keys, const uint64_t* rsel, uint32_t n_right, Tail tail) {
+    constexpr int ROWS = K::PROBE_ROWS;
+    static_assert(SEL_TILE % (64 * ROWS) == 0, "the rows of one pass of a wave lie in one selection tile");
     const int lane = threadIdx.x & 63;
     const uint64_t n_round = ((uint64_t)n_right + 63u) & ~(uint64_t)63;
-    const uint64_t wave_rows = 64ull * PROBE_ROWS;
+    const uint64_t wave_rows = 64ull * ROWS;
     const uint64_t wave_id = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (BLOCK / 64);
-    const ulonglong2* rk = reinterpret_cast<const ulonglong2*>(rkeys128);
-    const ulonglong2* lk = reinterpret_cast<const ulonglong2*>(T.keys128);
     for (uint64_t wbase = wave_id * wave_rows; wbase < n_round; wbase += n_waves * wave_rows) {
-        ulonglong2 key[PROBE_ROWS];
-        uint64_t slot[PROBE_ROWS], tag[PROBE_ROWS], owner[PROBE_ROWS];
-        uint32_t m[PROBE_ROWS];
-        bool in[PROBE_ROWS], live[PROBE_ROWS];
+        typename K::Key key[ROWS];
+        uint64_t slot[ROWS], tag[ROWS], owner[ROWS];
+        uint32_t m[ROWS];
+        bool in[ROWS], live[ROWS];
 #pragma unroll
-        for (int k = 0; k < PROBE_ROWS; ++k) {
+        for (int k = 0; k < ROWS; ++k) {
             const uint64_t row64 = wbase + 64ull * k + lane;
             in[k] = row64 < n_right;
             live[k] = in[k] && bit_at(rsel, (uint32_t)row64);
-            key[k] = live[k] ? rk[row64] : ulonglong2{0ull, 0ull};
+            key[k] = live[k] ? keys.key(row64) : K::none();
             m[k] = 0xFFFFFFFFu;
         }
 #pragma unroll
-        for (int k = 0; k < PROBE_ROWS; ++k) {
-            const uint64_t h = hash_key(Key128{key[k].x, key[k].y});
+        for (int k = 0; k < ROWS; ++k) {
+            const uint64_t h = keys.hash(key[k]);
             slot[k] = h & T.mask;
             tag[k] = h >> 32;
             owner[k] = live[k] ? T.owner[slot[k]] : 0ull;
         }
 #pragma unroll
-        for (int k = 0; k < PROBE_ROWS; ++k) {
+        for (int k = 0; k < ROWS; ++k) {
             while (owner[k] != 0) {
-                if ((owner[k] >> 32) == tag[k]) {
-                    const ulonglong2 ok = lk[(uint32_t)owner[k] - 1u];
-                    if (ok.x == key[k].x && ok.y == key[k].y) { m[k] = (uint32_t)owner[k] - 1u; break; }
-                }
+                if ((owner[k] >> 32) == tag[k] && keys.equal(T, (uint32_t)owner[k] - 1u, key[k])) { m[k] = (uint32_t)owner[k] - 1u; break; }
                 slot[k] = (slot[k] + 1) & T.mask;
                 owner[k] = T.owner[slot[k]];
             }
-            if (matched && m[k] != 0xFFFFFFFFu) atomicOr(&matched[m[k] >> 5], 1u << (m[k] & 31));
         }
-        uint32_t emitted = 0;
-#pragma unroll
-        for (int k = 0; k < PROBE_ROWS; ++k) {
-            const uint64_t row64 = wbase + 64ull * k + lane;
-            const bool emit = in[k] && (right_outer || m[k] != 0xFFFFFFFFu);
-            if (emit) partner[(uint32_t)row64] = m[k];
-            const uint64_t word = __ballot(emit);
-            if (lane == 0 && wbase + 64ull * k < n_round) bitmap[(wbase >> 6) + k] = word;
-            emitted += (uint32_t)__popcll(word);
-        }
-        if (lane == 0 && emitted) atomicAdd(&tile_counts[wbase / SEL_TILE], emitted);
+        tail(wbase, n_round, lane, in, m);
     }
+}
+
+// the selection a pass of join_owner_walk leaves: the bitmap word of every 64 rows = the rows that emit, and the count of the pass
+// added to its SEL_TILE rows' (zeroed by the launcher) — the inputs of launch_select_indices
+template <int ROWS>
+__device__ inline void store_selection(const bool (&emit)[ROWS], uint64_t wbase, uint64_t n_round, int lane, uint64_t* bitmap,
+                                       uint32_t* tile_counts) {
+    uint32_t emitted = 0;
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) {
+        const uint64_t word = __ballot(emit[k]);
+        if (lane == 0 && wbase + 64ull * k < n_round) bitmap[(wbase >> 6) + k] = word;
+        emitted += (uint32_t)__popcll(word);
+    }
+    if (lane == 0 && emitted) atomicAdd(&tile_counts[wbase / SEL_TILE], emitted);
+}
+
+// ---- unique build keys (primary-key side: every TPC-H join): a probe row has at most one partner, so the
+// table is probed ONCE and the result is a selection: partner[row] (build row id, 0xFFFFFFFF = none), the bitmap
+// of emitting rows and its per-1024-row counts — the index pass of FilterExec (select_indices) then yields the
+// probe-side indices in row order and one gather of partner[] the build-side indices.  With unique keys the
+// slot's owner IS its only row: the chain head is never read (two random reads per probe instead of three).
+template <class K>
+__global__ void __launch_bounds__(BLOCK)
+join_probe_match_kernel(JoinTable T, const K keys, const uint64_t* rsel, uint32_t n_right, int right_outer, uint32_t* partner,
+                        uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
+    constexpr int ROWS = K::PROBE_ROWS;
+    join_owner_walk(T, keys, rsel, n_right, [&](uint64_t wbase, uint64_t n_round, int lane, const bool (&in)[ROWS], const uint32_t (&m)[ROWS]) {
+        bool emit[ROWS];
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) {
+            if (matched && m[k] != 0xFFFFFFFFu) atomicOr(&matched[m[k] >> 5], 1u << (m[k] & 31));
+            emit[k] = in[k] && (right_outer || m[k] != 0xFFFFFFFFu);
+            if (emit[k]) partner[(uint32_t)(wbase + 64ull * k + lane)] = m[k];
+        }
+        store_selection(emit, wbase, n_round, lane, bitmap, tile_counts);
+    });
 }
 
 // set bit `row` of `matched` — read first: within a stream bits only go 0 -> 1, so a stale read costs one redundant atomic and never
@@ -449,62 +539,21 @@ __device__ inline void mark_once(uint32_t* matched, uint32_t row) {
 //          (join_exists_flags_kernel turns the bits into build rows at the end of the stream)
 //   SELECT (RightSemi / RightAnti: per PROBE row) the bitmap word of every 64 rows = rows with (hit != anti), and the counts per
 //          SEL_TILE rows: the inputs of launch_select_indices.  A row deselected by rsel (NULL key) is a miss, so Anti emits it.
-// Four rows per lane and pass, as join_probe_match_kernel: keys, slot owners, then the owners' keys of all four in flight together.
-template <bool SELECT>
+template <class K, bool SELECT>
 __global__ void __launch_bounds__(BLOCK)
-join_probe_exists_kernel(JoinTable T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right, int anti, uint64_t* bitmap,
-                         uint32_t* tile_counts, uint32_t* matched) {
-    constexpr int PROBE_ROWS = 4;
-    static_assert(SEL_TILE % (64 * PROBE_ROWS) == 0, "the rows of one pass of a wave lie in one selection tile");
-    const int lane = threadIdx.x & 63;
-    const uint64_t n_round = ((uint64_t)n_right + 63u) & ~(uint64_t)63;
-    const uint64_t wave_rows = 64ull * PROBE_ROWS;
-    const uint64_t wave_id = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * (BLOCK / 64);
-    const ulonglong2* rk = reinterpret_cast<const ulonglong2*>(rkeys128);
-    const ulonglong2* lk = reinterpret_cast<const ulonglong2*>(T.keys128);
-    for (uint64_t wbase = wave_id * wave_rows; wbase < n_round; wbase += n_waves * wave_rows) {
-        ulonglong2 key[PROBE_ROWS];
-        uint64_t slot[PROBE_ROWS], tag[PROBE_ROWS], owner[PROBE_ROWS];
-        bool in[PROBE_ROWS], live[PROBE_ROWS], hit[PROBE_ROWS];
+join_probe_exists_kernel(JoinTable T, const K keys, const uint64_t* rsel, uint32_t n_right, int anti, uint64_t* bitmap, uint32_t* tile_counts,
+                         uint32_t* matched) {
+    constexpr int ROWS = K::PROBE_ROWS;
+    join_owner_walk(T, keys, rsel, n_right, [&](uint64_t wbase, uint64_t n_round, int lane, const bool (&in)[ROWS], const uint32_t (&m)[ROWS]) {
+        bool emit[ROWS];
 #pragma unroll
-        for (int k = 0; k < PROBE_ROWS; ++k) {
-            const uint64_t row64 = wbase + 64ull * k + lane;
-            in[k] = row64 < n_right;
-            live[k] = in[k] && bit_at(rsel, (uint32_t)row64);
-            key[k] = live[k] ? rk[row64] : ulonglong2{0ull, 0ull};
-            hit[k] = false;
+        for (int k = 0; k < ROWS; ++k) {
+            const bool hit = m[k] != 0xFFFFFFFFu;
+            if (!SELECT && hit) mark_once(matched, m[k]);
+            emit[k] = in[k] && (hit != (anti != 0));
         }
-#pragma unroll
-        for (int k = 0; k < PROBE_ROWS; ++k) {
-            const uint64_t h = hash_key(Key128{key[k].x, key[k].y});
-            slot[k] = h & T.mask;
-            tag[k] = h >> 32;
-            owner[k] = live[k] ? T.owner[slot[k]] : 0ull;
-        }
-#pragma unroll
-        for (int k = 0; k < PROBE_ROWS; ++k) {
-            while (owner[k] != 0) {
-                if ((owner[k] >> 32) == tag[k]) {
-                    const ulonglong2 ok = lk[(uint32_t)owner[k] - 1u];
-                    if (ok.x == key[k].x && ok.y == key[k].y) { hit[k] = true; break; }
-                }
-                slot[k] = (slot[k] + 1) & T.mask;
-                owner[k] = T.owner[slot[k]];
-            }
-            if (!SELECT && hit[k]) mark_once(matched, (uint32_t)owner[k] - 1u);
-        }
-        if (SELECT) {
-            uint32_t emitted = 0;
-#pragma unroll
-            for (int k = 0; k < PROBE_ROWS; ++k) {
-                const uint64_t word = __ballot(in[k] && (hit[k] != (anti != 0)));
-                if (lane == 0 && wbase + 64ull * k < n_round) bitmap[(wbase >> 6) + k] = word;
-                emitted += (uint32_t)__popcll(word);
-            }
-            if (lane == 0 && emitted) atomicAdd(&tile_counts[wbase / SEL_TILE], emitted);
-        }
-    }
+        if (SELECT) store_selection(emit, wbase, n_round, lane, bitmap, tile_counts);
+    });
 }
 
 // the build rows of a Semi (anti = 0) / Anti (anti = 1) join from the bits the MARK probe left: flags[row] = 0 / 1, for the scan and
@@ -518,17 +567,15 @@ __device__ inline uint32_t exists_flag(const uint32_t* matched, uint32_t rep, co
     if (merge) e |= flags[row];
     return e ^ (uint32_t)anti;
 }
+template <class K>
 __global__ void __launch_bounds__(BLOCK)
-join_exists_flags_kernel(JoinTable T, const uint64_t* sel, const uint32_t* matched, uint32_t n_left, int direct, int anti, int merge,
+join_exists_flags_kernel(JoinTable T, const K keys, const uint64_t* sel, const uint32_t* matched, uint32_t n_left, int direct, int anti, int merge,
                          uint32_t* flags) {
     for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK) {
         uint32_t rep = 0xFFFFFFFFu;
         if (bit_at(sel, row)) {
-            rep = row;
-            if (!direct) {
-                const uint32_t slot = table_find(T, Key128{T.keys128[2ull * row], T.keys128[2ull * row + 1]});
-                rep = slot != 0xFFFFFFFFu ? (uint32_t)T.owner[slot] - 1u : 0xFFFFFFFFu;
-            }
+            if (direct) rep = row;
+            else join_find(T, keys, keys.key(row), &rep);
         }
         flags[row] = exists_flag(matched, rep, flags, row, merge, anti);
     }
@@ -672,190 +719,6 @@ wide_key_assign_kernel(const WideKeyCols K, const uint64_t* hashes, uint32_t* ta
     }
 }
 
-// ---- join keys of any width: the JoinTable over 64-bit row hashes, equality on the key columns ---------------------------
-// (HashJoinExec on c_name, a phone number, three Int64 columns ...: what the 16-byte packed key cannot hold.)  Slot word, chain
-// (head / next) and dup_flag are those of join_build_kernel; the tag is the high half of the row hash, so the columns are read
-// for true matches and about one in 2^32 others.  Row `a` of A against row `b` of B, column by column; both rows are known to
-// have no NULL key part (sel / rsel), so no validity is read.  Fixed-width parts: the 64-bit image the packed key holds (floats by
-// bits: -0.0 != +0.0, a NaN equals the NaN of the same bits).  Utf8: lengths, then 8 bytes at a time where 8 remain, then the
-// tail byte by byte — only bytes of the two values are read, nothing behind offsets[n].
-__device__ inline bool wide_rows_equal(const WideKeyCols& A, uint32_t a, const WideKeyCols& B, uint32_t b) {
-    for (int c = 0; c < A.n; ++c) {
-        const ColumnRef& ra = A.col[c];
-        const ColumnRef& rb = B.col[c];
-        switch (ra.dtype) {
-            case DT_UTF8: {
-                const int32_t a0 = ra.offsets[a], b0 = rb.offsets[b];
-                const int32_t len = ra.offsets[a + 1] - a0;
-                if (len != rb.offsets[b + 1] - b0) return false;
-                const uint8_t* x = static_cast<const uint8_t*>(ra.data) + a0;
-                const uint8_t* y = static_cast<const uint8_t*>(rb.data) + b0;
-                int32_t i = 0;
-                for (; i + 8 <= len; i += 8) {
-                    uint64_t u, v;
-                    __builtin_memcpy(&u, x + i, 8);
-                    __builtin_memcpy(&v, y + i, 8);
-                    if (u != v) return false;
-                }
-                for (; i < len; ++i)
-                    if (x[i] != y[i]) return false;
-            } break;
-            case DT_BOOLEAN: {
-                const uint8_t* x = static_cast<const uint8_t*>(ra.data);
-                const uint8_t* y = static_cast<const uint8_t*>(rb.data);
-                if (((x[a >> 3] >> (a & 7)) & 1) != ((y[b >> 3] >> (b & 7)) & 1)) return false;
-            } break;
-            default:
-                if (dt_load(ra.dtype, ra.data, a) != dt_load(rb.dtype, rb.data, b)) return false;
-                break;
-        }
-    }
-    return true;
-}
-
-__global__ void __launch_bounds__(BLOCK)
-join_build_wide_kernel(JoinTable T, const WideKeyCols K, const uint64_t* hashes, const uint64_t* sel, uint32_t n_left) {
-    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK) {
-        if (!bit_at(sel, row)) continue;                       // NULL keys never match
-        const uint64_t h = hashes[row];
-        const uint64_t tag = h >> 32;
-        const unsigned long long want = (unsigned long long)(row + 1u) | (tag << 32);
-        uint64_t slot = h & T.mask;
-        // (ends: the table has more slots than build rows, and an empty slot is claimed or turns out to be taken)
-        for (;;) {
-            unsigned long long o = T.owner[slot];
-            if (o == 0) {
-                o = atomicCAS(reinterpret_cast<unsigned long long*>(&T.owner[slot]), 0ull, want);
-                if (o == 0) break;                             // claimed: this row's key defines the slot
-            }
-            if ((o >> 32) == tag && wide_rows_equal(K, (uint32_t)o - 1u, K, row)) break;
-            slot = (slot + 1) & T.mask;
-        }
-        const uint32_t prev = atomicExch(&T.head[slot], row + 1u);     // push on the slot's chain
-        T.next[row] = prev;
-        if (prev != 0 && T.dup_flag) *T.dup_flag = 1u;                 // a second row with this key: not a unique build side
-    }
-}
-
-// slot whose owner's key equals probe row `row`'s, or 0xFFFFFFFF; *owner_row = that owner (read-only: the table is finished).
-// Ends at the first empty slot, and table_capacity() leaves at least half of the slots empty.
-__device__ inline uint32_t wide_table_find(const JoinTable& T, const WideKeyCols& B, const WideKeyCols& P, uint64_t h, uint32_t row,
-                                           uint32_t* owner_row) {
-    const uint64_t tag = h >> 32;
-    uint64_t slot = h & T.mask;
-    for (;;) {
-        const uint64_t o = T.owner[slot];
-        if (o == 0) return 0xFFFFFFFFu;
-        if ((o >> 32) == tag && wide_rows_equal(B, (uint32_t)o - 1u, P, row)) { *owner_row = (uint32_t)o - 1u; return (uint32_t)slot; }
-        slot = (slot + 1) & T.mask;
-    }
-}
-
-__global__ void __launch_bounds__(BLOCK)
-join_probe_count_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
-                             uint32_t n_right, int right_outer, uint32_t* counts) {
-    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_right; row += gridDim.x * BLOCK) {
-        uint32_t c = 0;
-        if (bit_at(rsel, row)) {
-            uint32_t owner;
-            const uint32_t slot = wide_table_find(T, B, P, rhashes[row], row, &owner);
-            if (slot != 0xFFFFFFFFu)
-                for (uint32_t l = T.head[slot]; l != 0; l = T.next[l - 1u]) ++c;
-        }
-        counts[row] = (right_outer && c == 0) ? 1u : c;
-    }
-}
-
-__global__ void __launch_bounds__(BLOCK)
-join_probe_emit_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
-                            uint32_t n_right, int right_outer, const uint64_t* offsets, uint32_t* left_idx, uint32_t* right_idx,
-                            uint32_t* matched) {
-    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_right; row += gridDim.x * BLOCK) {
-        uint64_t pos = offsets[row];
-        uint32_t c = 0;
-        if (bit_at(rsel, row)) {
-            uint32_t owner;
-            const uint32_t slot = wide_table_find(T, B, P, rhashes[row], row, &owner);
-            if (slot != 0xFFFFFFFFu)
-                for (uint32_t l = T.head[slot]; l != 0; l = T.next[l - 1u]) {
-                    left_idx[pos] = l - 1u;
-                    right_idx[pos] = row;
-                    if (matched) atomicOr(&matched[(l - 1u) >> 5], 1u << ((l - 1u) & 31));
-                    ++pos;
-                    ++c;
-                }
-        }
-        if (right_outer && c == 0) { left_idx[pos] = 0xFFFFFFFFu; right_idx[pos] = row; }
-    }
-}
-
-// unique build keys: partner[] + selection bitmap + tile counts, as join_probe_match_kernel leaves them; one row per lane and pass
-// (every lane of a wave makes the same number of passes, so the ballot sees all 64)
-__global__ void __launch_bounds__(BLOCK)
-join_probe_match_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
-                             uint32_t n_right, int right_outer, uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
-    static_assert(SEL_TILE % 64 == 0, "the rows of one pass of a wave lie in one selection tile");
-    const int lane = threadIdx.x & 63;
-    const uint64_t n_round = ((uint64_t)n_right + 63u) & ~(uint64_t)63;
-    const uint64_t wave_id = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * (BLOCK / 64);
-    for (uint64_t wbase = wave_id * 64ull; wbase < n_round; wbase += n_waves * 64ull) {
-        const uint64_t row64 = wbase + lane;
-        const bool in = row64 < n_right;
-        const uint32_t row = (uint32_t)row64;
-        uint32_t m = 0xFFFFFFFFu;
-        if (in && bit_at(rsel, row)) wide_table_find(T, B, P, rhashes[row], row, &m);
-        if (matched && m != 0xFFFFFFFFu) atomicOr(&matched[m >> 5], 1u << (m & 31));
-        const bool emit = in && (right_outer || m != 0xFFFFFFFFu);
-        if (emit) partner[row] = m;
-        const uint64_t word = __ballot(emit);
-        if (lane == 0) {
-            bitmap[wbase >> 6] = word;
-            if (word) atomicAdd(&tile_counts[wbase / SEL_TILE], (uint32_t)__popcll(word));
-        }
-    }
-}
-
-// the existence probe (join_probe_exists_kernel: MARK / SELECT) over keys of any width; one row per lane and pass, as the kernel above
-template <bool SELECT>
-__global__ void __launch_bounds__(BLOCK)
-join_probe_exists_wide_kernel(JoinTable T, const WideKeyCols B, const WideKeyCols P, const uint64_t* rhashes, const uint64_t* rsel,
-                              uint32_t n_right, int anti, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
-    static_assert(SEL_TILE % 64 == 0, "the rows of one pass of a wave lie in one selection tile");
-    const int lane = threadIdx.x & 63;
-    const uint64_t n_round = ((uint64_t)n_right + 63u) & ~(uint64_t)63;
-    const uint64_t wave_id = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * (BLOCK / 64);
-    for (uint64_t wbase = wave_id * 64ull; wbase < n_round; wbase += n_waves * 64ull) {
-        const uint64_t row64 = wbase + lane;
-        const bool in = row64 < n_right;
-        const uint32_t row = (uint32_t)row64;
-        uint32_t m = 0xFFFFFFFFu;
-        if (in && bit_at(rsel, row)) wide_table_find(T, B, P, rhashes[row], row, &m);
-        const bool hit = m != 0xFFFFFFFFu;
-        if (!SELECT) {
-            if (hit) mark_once(matched, m);
-        } else {
-            const uint64_t word = __ballot(in && (hit != (anti != 0)));
-            if (lane == 0) {
-                bitmap[wbase >> 6] = word;
-                if (word) atomicAdd(&tile_counts[wbase / SEL_TILE], (uint32_t)__popcll(word));
-            }
-        }
-    }
-}
-
-// join_exists_flags_kernel for a wide table that is not unique: the row's hash finds the slot, the key columns confirm it
-__global__ void __launch_bounds__(BLOCK)
-join_exists_flags_wide_kernel(JoinTable T, const WideKeyCols B, const uint64_t* hashes, const uint64_t* sel, const uint32_t* matched,
-                              uint32_t n_left, int anti, int merge, uint32_t* flags) {
-    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n_left; row += gridDim.x * BLOCK) {
-        uint32_t rep = 0xFFFFFFFFu;
-        if (bit_at(sel, row)) wide_table_find(T, B, B, hashes[row], row, &rep);
-        flags[row] = exists_flag(matched, rep, flags, row, merge, anti);
-    }
-}
-
 // ---- the same for ONE Int64 / UInt64 key (TPC-H at SF1000: l_orderkey / o_orderkey are Int64): 16-byte slots
 // {key, build row + 1}.  The build claims a slot with a 32-bit CAS on the row word and compares against the key
 // COLUMN of the claiming row (immutable input), so no reader ever depends on a half-written slot; the key word is
@@ -895,68 +758,46 @@ static int grid_rows(const LaunchCfg& cfg, size_t n) {
     return (int)g;
 }
 
-hipError_t launch_join_build(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* sel, uint32_t n_left) {
+// the key form of `side` against table T as the policy the kernels take: launch(PackedKeys) or launch(WideKeys)
+template <class F>
+static hipError_t with_key_form(const JoinTable& T, const JoinSideKeys& side, F launch) {
+    if (side.cols) launch(WideKeys{*T.cols, *side.cols, side.keys});
+    else launch(PackedKeys{reinterpret_cast<const ulonglong2*>(side.keys)});
+    return hipGetLastError();
+}
+
+hipError_t launch_join_build(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& build, uint32_t n_left) {
     if (n_left == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_build_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, sel, n_left);
-    return hipGetLastError();
+    return with_key_form(T, build, [&](auto keys) {
+        hipLaunchKernelGGL(join_build_kernel<decltype(keys)>, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, keys, build.sel, n_left);
+    });
 }
-hipError_t launch_join_probe_count(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel,
-                                   uint32_t n_right, bool right_outer, uint32_t* counts) {
+hipError_t launch_join_probe_count(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool right_outer,
+                                   uint32_t* counts) {
     if (n_right == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_probe_count_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel,
-                       n_right, right_outer ? 1 : 0, counts);
-    return hipGetLastError();
+    return with_key_form(T, probe, [&](auto keys) {
+        hipLaunchKernelGGL(join_probe_count_kernel<decltype(keys)>, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, keys, probe.sel,
+                           n_right, right_outer ? 1 : 0, counts);
+    });
 }
-hipError_t launch_join_probe_emit(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel,
-                                  uint32_t n_right, bool right_outer, const uint64_t* offsets, uint32_t* left_idx,
-                                  uint32_t* right_idx, uint32_t* matched) {
+hipError_t launch_join_probe_emit(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool right_outer,
+                                  const uint64_t* offsets, uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched) {
     if (n_right == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_probe_emit_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel,
-                       n_right, right_outer ? 1 : 0, offsets, left_idx, right_idx, matched);
-    return hipGetLastError();
+    return with_key_form(T, probe, [&](auto keys) {
+        hipLaunchKernelGGL(join_probe_emit_kernel<decltype(keys)>, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, keys, probe.sel,
+                           n_right, right_outer ? 1 : 0, offsets, left_idx, right_idx, matched);
+    });
 }
-hipError_t launch_join_probe_match(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel,
-                                   uint32_t n_right, bool right_outer, uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts,
-                                   uint32_t* matched) {
+hipError_t launch_join_probe_match(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool right_outer,
+                                   uint32_t* partner, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
     if (n_right == 0) return hipSuccess;
     const size_t n_tiles = ((size_t)n_right + SEL_TILE - 1) / SEL_TILE;
     hipError_t e = hipMemsetAsync(tile_counts, 0, n_tiles * 4, cfg.stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(join_probe_match_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel,
-                       n_right, right_outer ? 1 : 0, partner, bitmap, tile_counts, matched);
-    return hipGetLastError();
-}
-hipError_t launch_join_build_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
-                                  uint32_t n_left) {
-    if (n_left == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_build_wide_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, build, hashes, sel, n_left);
-    return hipGetLastError();
-}
-hipError_t launch_join_probe_count_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* counts) {
-    if (n_right == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_probe_count_wide_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel,
-                       n_right, right_outer ? 1 : 0, counts);
-    return hipGetLastError();
-}
-hipError_t launch_join_probe_emit_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                       const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, const uint64_t* offsets,
-                                       uint32_t* left_idx, uint32_t* right_idx, uint32_t* matched) {
-    if (n_right == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_probe_emit_wide_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel,
-                       n_right, right_outer ? 1 : 0, offsets, left_idx, right_idx, matched);
-    return hipGetLastError();
-}
-hipError_t launch_join_probe_match_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                        const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool right_outer, uint32_t* partner,
-                                        uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
-    if (n_right == 0) return hipSuccess;
-    const size_t n_tiles = ((size_t)n_right + SEL_TILE - 1) / SEL_TILE;
-    hipError_t e = hipMemsetAsync(tile_counts, 0, n_tiles * 4, cfg.stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(join_probe_match_wide_kernel, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel,
-                       n_right, right_outer ? 1 : 0, partner, bitmap, tile_counts, matched);
-    return hipGetLastError();
+    return with_key_form(T, probe, [&](auto keys) {
+        hipLaunchKernelGGL(join_probe_match_kernel<decltype(keys)>, dim3(grid_rows(cfg, n_right)), dim3(BLOCK), 0, cfg.stream, T, keys, probe.sel,
+                           n_right, right_outer ? 1 : 0, partner, bitmap, tile_counts, matched);
+    });
 }
 hipError_t launch_join_build_narrow(const LaunchCfg& cfg, const NarrowJoinTable& T, const void* keys, int key_width,
                                     const uint64_t* sel, uint32_t n_left) {
@@ -985,48 +826,30 @@ hipError_t launch_join_key_present(const LaunchCfg& cfg, const uint32_t* keys, c
     hipLaunchKernelGGL(join_key_present_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, keys, sel, n, kmin, present);
     return hipGetLastError();
 }
-hipError_t launch_join_probe_exists(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* rkeys128, const uint64_t* rsel, uint32_t n_right,
-                                    bool anti, uint64_t* bitmap, uint32_t* tile_counts, uint32_t* matched) {
+hipError_t launch_join_probe_exists(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& probe, uint32_t n_right, bool anti, uint64_t* bitmap,
+                                    uint32_t* tile_counts, uint32_t* matched) {
     if (n_right == 0) return hipSuccess;
     const dim3 grid(grid_rows(cfg, n_right));
-    if (matched) {
-        hipLaunchKernelGGL(join_probe_exists_kernel<false>, grid, dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel, n_right, 0, nullptr, nullptr, matched);
-        return hipGetLastError();
-    }
+    if (matched)
+        return with_key_form(T, probe, [&](auto keys) {
+            auto mark = join_probe_exists_kernel<decltype(keys), false>;
+            hipLaunchKernelGGL(mark, grid, dim3(BLOCK), 0, cfg.stream, T, keys, probe.sel, n_right, 0, nullptr, nullptr, matched);
+        });
     hipError_t e = hipMemsetAsync(tile_counts, 0, (((size_t)n_right + SEL_TILE - 1) / SEL_TILE) * 4, cfg.stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(join_probe_exists_kernel<true>, grid, dim3(BLOCK), 0, cfg.stream, T, rkeys128, rsel, n_right, anti ? 1 : 0, bitmap, tile_counts, nullptr);
-    return hipGetLastError();
+    return with_key_form(T, probe, [&](auto keys) {
+        auto select = join_probe_exists_kernel<decltype(keys), true>;
+        hipLaunchKernelGGL(select, grid, dim3(BLOCK), 0, cfg.stream, T, keys, probe.sel, n_right, anti ? 1 : 0, bitmap, tile_counts, nullptr);
+    });
 }
-hipError_t launch_join_probe_exists_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const WideKeyCols& probe,
-                                         const uint64_t* rhashes, const uint64_t* rsel, uint32_t n_right, bool anti, uint64_t* bitmap,
-                                         uint32_t* tile_counts, uint32_t* matched) {
-    if (n_right == 0) return hipSuccess;
-    const dim3 grid(grid_rows(cfg, n_right));
-    if (matched) {
-        hipLaunchKernelGGL(join_probe_exists_wide_kernel<false>, grid, dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel, n_right, 0, nullptr,
-                           nullptr, matched);
-        return hipGetLastError();
-    }
-    hipError_t e = hipMemsetAsync(tile_counts, 0, (((size_t)n_right + SEL_TILE - 1) / SEL_TILE) * 4, cfg.stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(join_probe_exists_wide_kernel<true>, grid, dim3(BLOCK), 0, cfg.stream, T, build, probe, rhashes, rsel, n_right, anti ? 1 : 0,
-                       bitmap, tile_counts, nullptr);
-    return hipGetLastError();
-}
-hipError_t launch_join_exists_flags(const LaunchCfg& cfg, const JoinTable& T, const uint64_t* sel, const uint32_t* matched, uint32_t n_left, bool direct,
-                                    bool anti, bool merge, uint32_t* flags) {
+hipError_t launch_join_exists_flags(const LaunchCfg& cfg, const JoinTable& T, const JoinSideKeys& build, const uint32_t* matched, uint32_t n_left,
+                                    bool direct, bool anti, bool merge, uint32_t* flags) {
     if (n_left == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_exists_flags_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, sel, matched, n_left, direct ? 1 : 0,
-                       anti ? 1 : 0, merge ? 1 : 0, flags);
-    return hipGetLastError();
-}
-hipError_t launch_join_exists_flags_wide(const LaunchCfg& cfg, const JoinTable& T, const WideKeyCols& build, const uint64_t* hashes, const uint64_t* sel,
-                                         const uint32_t* matched, uint32_t n_left, bool anti, bool merge, uint32_t* flags) {
-    if (n_left == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_exists_flags_wide_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, build, hashes, sel, matched, n_left,
-                       anti ? 1 : 0, merge ? 1 : 0, flags);
-    return hipGetLastError();
+    // (direct: no key is read, and a wide build side's row hashes need not exist: the packed instantiation for both forms)
+    return with_key_form(T, direct ? JoinSideKeys{nullptr, build.sel, nullptr} : build, [&](auto keys) {
+        hipLaunchKernelGGL(join_exists_flags_kernel<decltype(keys)>, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, keys, build.sel, matched,
+                           n_left, direct ? 1 : 0, anti ? 1 : 0, merge ? 1 : 0, flags);
+    });
 }
 hipError_t launch_join_pairs_resolve(const LaunchCfg& cfg, const uint32_t* sel, const uint32_t* lidx, const uint32_t* ridx, uint64_t n_keep, uint32_t* out_l,
                                      uint32_t* out_r, uint32_t* matched, uint64_t* hit) {

@@ -5,6 +5,7 @@ Expected rows: join_types_cases.expected, derived from the CPU oracle's Inner / 
 against pyarrow in test_join_types_plan.py.  Rows compare as multisets keyed by the row ids li / ri.  Sizes: 900 build rows in two
 partitions; 5000 probe rows as batches of 1025 (one past the 1024-row selection tile), 1975 and 2000 rows — two partitions for
 RightSemi / RightAnti, one partition (or two under a MergeExec) for the types that answer for the build side."""
+import functools
 from collections import OrderedDict
 
 import numpy as np
@@ -115,6 +116,43 @@ def test_probe_batch_sizes(ctx, n, jt):
     left, right, on = JT.sides("int64_dup", True, 3, JT.NL, n)
     plan = ba.HashJoinExec(build_exec(ctx, left), helpers.memory_exec(ctx, [[right]]), on, jt)
     JT.assert_same_rows(rows(plan), JT.expected(jt, left, right, on))
+
+
+EDGE_NL = 300
+
+
+@functools.lru_cache(maxsize=None)
+def edge_sides(unique, n):
+    """300 build rows with short Utf8 keys (the general table: no narrow structures), unique or 100 values three times over; ONE probe
+    batch of n rows whose last row has a NULL key and, from two rows on, whose first row finds no partner"""
+    rng = np.random.default_rng(100 * n + unique)
+    pool = ["k%03d" % i + "-" * (i % 8) for i in range(400)]                     # 4 .. 11 bytes; the build side knows the first 300 / 100
+    lk = [pool[int(i)] for i in (rng.permutation(EDGE_NL) if unique else rng.integers(0, 100, EDGE_NL))]
+    rk = [pool[int(i)] for i in rng.integers(0, 400 if unique else 130, n)]
+    rk[0] = "no-partner"
+    valid = np.ones(n, dtype=bool)
+    valid[-1] = False
+    left = JT.with_ids("l", EDGE_NL, [("lk", OCol("Utf8", lk)), ("lx", OCol("Float64", rng.integers(0, 1000, EDGE_NL) / 8.0))])
+    right = JT.with_ids("r", n, [("rk", OCol("Utf8", rk, valid)), ("ry", OCol("Int64", rng.integers(0, 10 ** 6, n)))])
+    return left, right, [("lk", "rk")]
+
+
+@pytest.mark.parametrize("jt", ["Inner", "Right", JT.FULL, JT.SEMI, JT.RIGHT_SEMI, JT.RIGHT_ANTI])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025])
+@pytest.mark.parametrize("unique", [True, False])
+@pytest.mark.parametrize("form", ["packed", "wide"])
+def test_probe_batch_sizes_in_both_key_forms(ctx, form, unique, n, jt, monkeypatch):
+    """the one walk under join_probe_match and join_probe_exists (kernels_hash.hip join_owner_walk: four rows per lane and pass over
+    packed keys, one over wide keys) at the edges of the bitmap word (64), of one four-row pass of a wave (256) and of the selection
+    tile (1024): the match tail with and without right_outer (Right, Full / Inner; a duplicated build side enumerates pairs instead),
+    the mark tail (Semi) and the select tail with and without anti (RightAnti / RightSemi)"""
+    if form == "wide":
+        monkeypatch.setenv("BHIP_JOIN_WIDE", "1")
+    left, right, on = edge_sides(unique, n)
+    plan = ba.HashJoinExec(helpers.memory_exec(ctx, [[left]]), helpers.memory_exec(ctx, [[right]]), on, jt)
+    want = JT.oracle_join(left, right, on, jt) if jt in ("Inner", "Right") else JT.expected(jt, left, right, on)
+    JT.assert_same_rows(rows(plan), want)
+    assert ctx.join_key_form() == form
 
 
 # ---- 3. degenerate sides ------------------------------------------------------------------------------------------------------------
