@@ -17,4 +17,13 @@ hipError_t launch_cast_parse(const LaunchCfg& cfg, const ColumnRef& c, int64_t n
 hipError_t launch_cast_format_lengths(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, uint32_t* lengths, uint64_t* validity_out);
 hipError_t launch_cast_format_write(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, const int32_t* out_offsets, uint8_t* out);
 
+// to_timestamp(<Utf8 column>): n Timestamp(Nanosecond) values at `out` (0 for a NULL row; the result's validity is the argument's).
+// *status gets TO_TIMESTAMP_STATUS_INVALID OR-ed in when a non-NULL value is outside the grammar of temporal_text.h.
+constexpr uint32_t TO_TIMESTAMP_STATUS_INVALID = 1u;
+hipError_t launch_to_timestamp_parse(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int64_t* out, uint32_t* status);
+
+// date_trunc(granularity, <Timestamp column>): n values of the column's own type at `out` and n validity bits, written as whole
+// 64-bit words: NULL where the argument is, or where the floor does not fit int64 in the unit.  granularity: TruncGranularity.
+hipError_t launch_date_trunc(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int granularity, int64_t* out, uint64_t* validity);
+
 }  // namespace bhip

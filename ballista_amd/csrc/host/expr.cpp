@@ -2,6 +2,8 @@
 #include "expr.hpp"
 
 #include "../cast_text.h"
+#include "../str_kernels.h"
+#include "../temporal_text.h"
 
 #include <algorithm>
 #include <cmath>
@@ -59,9 +61,60 @@ int sha_fn(const std::string& name) {
 }
 
 void check_scalar_function(const std::string& name, int n_args) {
-    if (math_fn(name) < 0 && str_fn(name) < 0 && sha_fn(name) == 0 && name != "octet_length")
+    if (name == "concat") {
+        if (n_args < 1) fail(BHIP_EINVAL, "concat takes at least one argument");
+        if (n_args > STR_CONCAT_MAX) fail(BHIP_ENOTIMPL, "concat with more than 8 arguments");
+        return;
+    }
+    if (name == "nullif" || name == "date_trunc") {
+        if (n_args != 2) fail(BHIP_EINVAL, "scalar function '" + name + "' takes two arguments");
+        return;
+    }
+    if (math_fn(name) < 0 && str_fn(name) < 0 && sha_fn(name) == 0 && name != "octet_length" && name != "to_timestamp")
         fail(BHIP_ENOTIMPL, "scalar function '" + name + "' is not supported");
     if (n_args != 1) fail(BHIP_EINVAL, "scalar function takes one argument");
+}
+
+static ExprPtr make_literal(int dtype, bool is_null, int64_t i64) {
+    auto l = std::make_shared<Expr>();
+    l->kind = BHIP_EXPR_LITERAL;
+    l->dtype = dtype;
+    l->is_null = is_null;
+    l->i64 = i64;
+    return l;
+}
+
+int date_trunc_granularity(const Expr& e, const Schema& schema) {
+    const Expr& g = *e.args[0];
+    if (g.kind != BHIP_EXPR_LITERAL || g.dtype != DT_UTF8 || g.is_null)
+        fail(BHIP_ENOTIMPL, "date_trunc granularity must be a non-NULL Utf8 literal: " + e.to_string());
+    const int gran = trunc_granularity(g.name.data(), (int64_t)g.name.size());
+    if (gran < 0) fail(BHIP_EINVAL, "Unsupported date_trunc granularity '" + g.name + "'");
+    const int t = expr_type(e.args[1], schema);
+    if (timestamp_units_per_second(t) == 0) fail(BHIP_EINVAL, std::string("date_trunc requires a Timestamp argument, not ") + dtype_name(t));
+    return gran;
+}
+
+ExprPtr fold_temporal_literal(const ExprPtr& e, const Schema& schema) {
+    if (e->kind != BHIP_EXPR_SCALAR_FN) return nullptr;
+    if (e->name == "to_timestamp") {
+        const Expr& x = *e->args[0];
+        if (x.kind != BHIP_EXPR_LITERAL || x.dtype != DT_UTF8 || x.is_null) return nullptr;         // (a NULL literal: a column of NULLs, utf8_exprs.cpp)
+        int64_t ns = 0;
+        const CastPtrReader rd{reinterpret_cast<const uint8_t*>(x.name.data())};
+        if (!to_timestamp_parse(rd, 0, (int64_t)x.name.size(), ns)) fail(BHIP_EEXEC, "to_timestamp: '" + x.name + "' is not a timestamp");
+        return make_literal(DT_TIMESTAMP_NS, false, ns);
+    }
+    if (e->name == "date_trunc") {
+        ExprPtr x = e->args[1];
+        if (x->kind != BHIP_EXPR_LITERAL) x = fold_temporal_literal(x, schema);
+        if (!x) return nullptr;
+        const int gran = date_trunc_granularity(*e, schema);
+        int64_t v = 0;
+        const bool ok = !x->is_null && temporal_trunc(x->dtype, gran, x->i64, v);
+        return make_literal(x->dtype, !ok, v);
+    }
+    return nullptr;
 }
 
 ExprPtr make_column(const std::string& name) {
@@ -147,7 +200,8 @@ ExprPtr parse_expr(const bhip_expr& pe) {
             case BHIP_EXPR_SCALAR_FN: {
                 check_scalar_function(n.name ? n.name : "", n.n_args);
                 e->name = n.name;
-                e->args = {pop()};
+                e->args.resize((size_t)n.n_args);
+                for (int k = n.n_args - 1; k >= 0; --k) e->args[(size_t)k] = pop();
             } break;
             default: fail(BHIP_ENOTIMPL, "unsupported expression kind " + std::to_string(n.kind));
         }
@@ -190,7 +244,11 @@ std::string Expr::to_string() const {
             if (has_else) o << "ELSE " << args.back()->to_string() << " ";
             o << "END";
         } break;
-        case BHIP_EXPR_SCALAR_FN: o << name << "(" << args[0]->to_string() << ")"; break;
+        case BHIP_EXPR_SCALAR_FN:
+            o << name << "(";
+            for (size_t i = 0; i < args.size(); ++i) o << (i ? ", " : "") << args[i]->to_string();
+            o << ")";
+            break;
         default: o << "?";
     }
     return o.str();
@@ -241,7 +299,11 @@ int expr_type(const ExprPtr& e, const Schema& schema) {
             case_layout(*e, fw, np);
             return expr_type(e->args[fw + 1], schema);
         }
-        case BHIP_EXPR_SCALAR_FN: return (str_fn(e->name) >= 0 || sha_fn(e->name)) ? DT_UTF8 : (e->name == "octet_length" ? DT_INT32 : DT_FLOAT64);
+        case BHIP_EXPR_SCALAR_FN:
+            if (e->name == "nullif") return expr_type(e->args[0], schema);
+            if (e->name == "date_trunc") return expr_type(e->args[1], schema);
+            if (e->name == "to_timestamp") return DT_TIMESTAMP_NS;
+            return (str_fn(e->name) >= 0 || sha_fn(e->name) || e->name == "concat") ? DT_UTF8 : (e->name == "octet_length" ? DT_INT32 : DT_FLOAT64);
         default: fail(BHIP_ENOTIMPL, "unsupported expression kind");
     }
 }
@@ -252,7 +314,13 @@ bool expr_large(const ExprPtr& e, const Schema& schema) {
             const int i = schema.index_of(e->name);
             return i >= 0 && schema.fields[i].large;
         }
-        case BHIP_EXPR_SCALAR_FN: return str_fn(e->name) >= 0 && expr_large(e->args[0], schema);
+        case BHIP_EXPR_SCALAR_FN:
+            if (e->name == "concat") {
+                for (auto& a : e->args)
+                    if (expr_large(a, schema)) return true;
+                return false;
+            }
+            return str_fn(e->name) >= 0 && expr_large(e->args[0], schema);
         case BHIP_EXPR_CASE: {
             size_t fw, np;
             case_layout(*e, fw, np);
@@ -377,6 +445,15 @@ ExprPtr coerce_expr(const ExprPtr& e, const Schema& schema) {
             auto c = std::make_shared<Expr>(*e);
             const bool math = math_fn(e->name) >= 0;        // Signature::Uniform(1, [Float64, Float32]): the first type the argument coerces to
             for (auto& a : c->args) a = math ? cast_to(coerce_expr(a, schema), DT_FLOAT64, schema) : coerce_expr(a, schema);
+            if (e->name == "nullif" && c->args.size() == 2) {
+                // the two sides of `a = b`: one common type, which is the result's (a Utf8 `a` is refused when it is compiled)
+                const int ta = expr_type(c->args[0], schema), tb = expr_type(c->args[1], schema);
+                if (ta != DT_UTF8 && tb != DT_UTF8) {
+                    const int t = common_type(ta, tb);
+                    c->args[0] = cast_to(c->args[0], t, schema);
+                    c->args[1] = cast_to(c->args[1], t, schema);
+                }
+            }
             return c;
         }
         default: {
@@ -406,8 +483,12 @@ bool expr_nullable(const ExprPtr& e, const Schema& schema) {
             if (dtype_width(e->dtype) && dtype_width(from) && !dt_is_float(e->dtype) && from != e->dtype) return true;
             return expr_nullable(e->args[0], schema);
         }
+        case BHIP_EXPR_SCALAR_FN:
+            // nullif makes NULLs of its own; a date_trunc floor may not fit int64.  (concat, to_timestamp: nullable iff an argument is)
+            if (e->name == "nullif" || e->name == "date_trunc") return true;
+            [[fallthrough]];
         case BHIP_EXPR_CASE:
-            if (!e->has_else) return true;
+            if (e->kind == BHIP_EXPR_CASE && !e->has_else) return true;
             [[fallthrough]];
         default:
             for (auto& a : e->args)
@@ -881,7 +962,25 @@ Operand ProgramBuilder::compile_uncached(const ExprPtr& ep) {
                 instrs_.back().ins.c = (uint8_t)a.col;
                 return o;
             }
-            if (str_fn(e.name) >= 0 || sha_fn(e.name)) fail(BHIP_ENOTIMPL, "expression producing Utf8 / Binary: " + e.name + "() (evaluated as a column, host/utf8_exprs.cpp)");
+            if (e.name == "nullif") {
+                // CASE WHEN a = b THEN NULL ELSE a END: `a = b` is the library's own Eq, no VM instruction of its own
+                const int t = expr_type(e.args[0], schema_);
+                if (t == DT_UTF8) fail(BHIP_ENOTIMPL, "nullif over Utf8 values");
+                if (expr_type(e.args[1], schema_) != t)
+                    fail(BHIP_EINVAL, std::string("nullif arguments have different types: ") + dtype_name(t) + " and " + dtype_name(expr_type(e.args[1], schema_)));
+                auto c = std::make_shared<Expr>();
+                c->kind = BHIP_EXPR_CASE;
+                c->has_else = true;
+                c->args = {make_binary(e.args[0], "Eq", e.args[1]), make_literal(t, true, 0), e.args[0]};
+                return compile(c);
+            }
+            if (e.name == "to_timestamp" || e.name == "date_trunc") {
+                if (e.name == "date_trunc") (void)date_trunc_granularity(e, schema_);
+                else if (expr_type(e.args[0], schema_) != DT_UTF8) fail(BHIP_EINVAL, "to_timestamp requires a Utf8 argument");
+                if (const ExprPtr l = fold_temporal_literal(ep, schema_)) return compile(l);
+                fail(BHIP_ENOTIMPL, "expression " + e.name + "() outside the lowering (evaluated as a column, host/utf8_exprs.cpp)");
+            }
+            if (str_fn(e.name) >= 0 || sha_fn(e.name) || e.name == "concat") fail(BHIP_ENOTIMPL, "expression producing Utf8 / Binary: " + e.name + "() (evaluated as a column, host/utf8_exprs.cpp)");
             if (expr_type(e.args[0], schema_) != DT_FLOAT64) fail(BHIP_EINVAL, e.name + " requires a Float64 argument");
             Operand a = materialize(compile(e.args[0]));
             return emit(OP_MATH_F64, &a, nullptr, false, VC_F64, DT_FLOAT64, (uint16_t)math_fn(e.name));

@@ -77,6 +77,12 @@ bool expr_binary(const ExprPtr& e, const Schema& schema);         // ... is Bina
 int sha_fn(const std::string& name);                              // digest bits of sha224 / sha256 / sha384 / sha512, 0 otherwise
 // index of a string-valued scalar function (lower, upper, trim, ltrim, rtrim; evaluated as columns, utf8_exprs.cpp), -1 otherwise
 int str_fn(const std::string& name);
+// date_trunc(g, t): every plan-time check of the call (BHIP_ENOTIMPL for a granularity that is no literal, BHIP_EINVAL for an unknown
+// one or a `t` that is no Timestamp); returns the TruncGranularity (temporal_text.h)
+int date_trunc_granularity(const Expr& e, const Schema& schema);
+// to_timestamp / date_trunc over literals alone: the literal they fold to (by temporal_text.h, what the kernels run), else null.
+// A to_timestamp literal outside the grammar fails here with BHIP_EEXEC, as the same text in a column would when the query runs.
+ExprPtr fold_temporal_literal(const ExprPtr& e, const Schema& schema);
 
 class ProgramBuilder {
 public:

@@ -9,8 +9,12 @@
 // CAST to and from Utf8 (kernels_cast.hip; the grammar: cast_text.h) takes the same road in both directions:
 // CAST(x AS Utf8) of a fixed-width x is one more string-producing node, and CAST(<Utf8 expression> AS T) is an extra column too —
 // of type T.  So a lowered node is "an expression evaluated as an extra column of its own type".
+//
+// concat is one more string-producing node; to_timestamp (Utf8 -> Timestamp(Nanosecond)) and date_trunc (Timestamp -> Timestamp)
+// are lowered nodes of a fixed-width type, like CAST(<Utf8> AS T).  Over literals alone the two fold in the VM's compiler instead.
 #include "../cast_kernels.h"
 #include "../cast_text.h"
+#include "../temporal_text.h"
 #include "../str_kernels.h"
 #include "../util_kernels.h"
 #include "plan.hpp"
@@ -28,14 +32,20 @@ static bool cast_from_utf8(const ExprPtr& e, const Schema& schema) {
     return !(x.kind == BHIP_EXPR_LITERAL && !x.is_null);
 }
 
+// to_timestamp(<Utf8 expression>) / date_trunc(g, <Timestamp expression>) that does not fold to a literal
+static bool temporal_fn(const ExprPtr& e, const Schema& schema) {
+    if (e->kind != BHIP_EXPR_SCALAR_FN || (e->name != "to_timestamp" && e->name != "date_trunc")) return false;
+    return fold_temporal_literal(e, schema) == nullptr;
+}
+
 static bool produces_utf8(const ExprPtr& e, const Schema& schema) {
-    if (e->kind == BHIP_EXPR_SCALAR_FN) return str_fn(e->name) >= 0 || sha_fn(e->name) != 0;
+    if (e->kind == BHIP_EXPR_SCALAR_FN) return str_fn(e->name) >= 0 || sha_fn(e->name) != 0 || e->name == "concat";
     if (e->kind == BHIP_EXPR_CASE) return expr_type(e, schema) == DT_UTF8;
     return cast_to_utf8(e, schema);
 }
 
 bool has_lowered_node(const ExprPtr& e, const Schema& schema) {
-    if (produces_utf8(e, schema) || cast_from_utf8(e, schema)) return true;
+    if (produces_utf8(e, schema) || cast_from_utf8(e, schema) || temporal_fn(e, schema)) return true;
     for (auto& a : e->args)
         if (has_lowered_node(a, schema)) return true;
     return false;
@@ -47,7 +57,7 @@ Utf8Lowering::Utf8Lowering(const Schema& in) : in_(in) {}
 
 ExprPtr Utf8Lowering::rewrite(const ExprPtr& e, bool output) {
     const bool lit = output && e->kind == BHIP_EXPR_LITERAL && e->dtype == DT_UTF8;
-    if (lit || produces_utf8(e, in_) || cast_from_utf8(e, in_)) {
+    if (lit || produces_utf8(e, in_) || cast_from_utf8(e, in_) || temporal_fn(e, in_)) {
         const std::string text = e->to_string();
         for (size_t i = 0; i < nodes_.size(); ++i)
             if (nodes_[i]->to_string() == text) return make_column(names_[i]);
@@ -256,6 +266,87 @@ Column eval_cast_parse(const Exec& ex, const Batch& in, const Expr& e) {
     return out;
 }
 
+// concat(a1, ..., ak): lengths -> scan -> bytes.  Short literal arguments travel in the kernels' argument struct; a literal that does
+// not fit there becomes a column first, and a NULL literal makes every row NULL.
+Column eval_concat(const Exec& ex, const Batch& in, const Expr& e) {
+    const int64_t n = in.n_rows;
+    if (e.args.size() > (size_t)STR_CONCAT_MAX) fail(BHIP_ENOTIMPL, "concat with more than 8 arguments");
+    for (auto& a : e.args)
+        if (a->kind == BHIP_EXPR_LITERAL && a->is_null) return eval_literal(ex, *a, n);
+    StrConcatArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_args = (int32_t)e.args.size();
+    std::vector<Column> cols(e.args.size());
+    int64_t bound = 0;
+    int32_t lit_used = 0;
+    bool any_validity = false;
+    for (size_t j = 0; j < e.args.size(); ++j) {
+        const Expr& a = *e.args[j];
+        if (a.kind == BHIP_EXPR_LITERAL && a.dtype == DT_UTF8 && lit_used + (int64_t)a.name.size() <= STR_CONCAT_LIT_BYTES) {
+            A.is_lit[j] = 1;
+            A.lit_off[j] = lit_used;
+            A.lit_len[j] = (int32_t)a.name.size();
+            memcpy(A.lit_bytes + lit_used, a.name.data(), a.name.size());
+            lit_used += A.lit_len[j];
+            bound += n * A.lit_len[j];
+            continue;
+        }
+        cols[j] = eval_utf8(ex, in, e.args[j]);
+        A.col[j] = cols[j].ref();
+        bound += cols[j].data_bytes;
+        any_validity = any_validity || (bool)cols[j].validity;
+    }
+    Temp tmp(ex);
+    uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
+    BufferPtr validity = any_validity ? make_buffer(ex, bitmap_bytes(n) + 8) : nullptr;
+    TIMED_LAUNCH_N(ex, "concat_lengths", n, launch_concat_lengths(ex.cfg(), A, n, lengths, validity ? validity->as<uint64_t>() : nullptr));
+    uint64_t* total;
+    Column out = utf8_from_lengths(ex, tmp, lengths, n, &total);
+    // a row holds every argument's bytes: the sum of their byte counts bounds the result when it is small; else read the total
+    int64_t total_bytes = -1;
+    if (bound > (64 << 20)) bound = total_bytes = (int64_t)read_device(ex, total);
+    if ((uint64_t)bound > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
+    out.data = make_buffer(ex, (size_t)bound + 8);
+    TIMED_LAUNCH_N(ex, "concat_write", n, launch_concat_write(ex.cfg(), A, n, out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
+    out.data_bytes = total_bytes >= 0 ? total_bytes : (int64_t)read_device(ex, total);
+    out.validity = validity;
+    return out;
+}
+
+// to_timestamp(<Utf8 expression>): one thread per row parses its value; NULL exactly where the argument is, and a non-NULL value
+// that is no timestamp fails the batch
+Column eval_to_timestamp(const Exec& ex, const Batch& in, const Expr& e) {
+    const Column arg = eval_utf8(ex, in, e.args[0]);
+    const int64_t n = in.n_rows;
+    Column out;
+    out.dtype = DT_TIMESTAMP_NS;
+    out.length = n;
+    out.data = make_buffer(ex, (size_t)n * 8 + 8);
+    out.validity = arg.validity;
+    Temp tmp(ex);
+    uint32_t* status = tmp.get<uint32_t>(1);
+    HIP_CHECK(hipMemsetAsync(status, 0, 4, ex.stream));
+    TIMED_LAUNCH_N(ex, "to_timestamp_parse", n, launch_to_timestamp_parse(ex.cfg(), arg.ref(), n, out.data->as<int64_t>(), status));
+    if (read_device(ex, status) & TO_TIMESTAMP_STATUS_INVALID)
+        fail(BHIP_EEXEC, "to_timestamp: a value is not a timestamp (YYYY-MM-DD[T ]hh:mm:ss[.fraction][Z|+hh:mm] within the range of "
+                         "Timestamp(Nanosecond))");
+    return out;
+}
+
+// date_trunc(g, t): t as a temporary column (any expression the VM evaluates, lowered nodes of its own included), then one streaming kernel
+Column eval_date_trunc(const Exec& ex, const Batch& in, const Expr& e) {
+    const int gran = date_trunc_granularity(e, *in.schema);
+    const Column arg = materialize_column(ex, evaluate_column(ex, in, e.args[1]));
+    const int64_t n = in.n_rows;
+    Column out;
+    out.dtype = arg.dtype;
+    out.length = n;
+    out.data = make_buffer(ex, (size_t)n * 8 + 8);
+    out.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+    TIMED_LAUNCH_N(ex, "date_trunc", n, launch_date_trunc(ex.cfg(), arg.ref(), n, gran, out.data->as<int64_t>(), out.validity->as<uint64_t>()));
+    return out;
+}
+
 Column eval_utf8(const Exec& ex, const Batch& in, const ExprPtr& e) {
     switch (e->kind) {
         case BHIP_EXPR_COLUMN: {
@@ -270,6 +361,7 @@ Column eval_utf8(const Exec& ex, const Batch& in, const ExprPtr& e) {
         case BHIP_EXPR_SCALAR_FN:
             if (str_fn(e->name) >= 0) return eval_transform(ex, in, *e);
             if (sha_fn(e->name)) return eval_sha(ex, in, *e);
+            if (e->name == "concat") return eval_concat(ex, in, *e);
             break;
         case BHIP_EXPR_CASE: return eval_case(ex, in, *e);
         case BHIP_EXPR_CAST:
@@ -298,7 +390,10 @@ BatchPtr Utf8Lowering::apply(const Exec& ex, const Batch& in) const {
             c.data = make_buffer(ex, 8);
             out->cols.push_back(c);
         } else {
-            out->cols.push_back(t == DT_UTF8 ? eval_utf8(ex, in, node) : eval_cast_parse(ex, in, *node));
+            if (t == DT_UTF8) out->cols.push_back(eval_utf8(ex, in, node));
+            else if (node->kind == BHIP_EXPR_CAST) out->cols.push_back(eval_cast_parse(ex, in, *node));
+            else if (node->name == "to_timestamp") out->cols.push_back(eval_to_timestamp(ex, in, *node));
+            else out->cols.push_back(eval_date_trunc(ex, in, *node));
         }
     }
     return out;
@@ -306,6 +401,15 @@ BatchPtr Utf8Lowering::apply(const Exec& ex, const Batch& in) const {
 
 // plan-time check: every string node is one this file evaluates (BHIP_ENOTIMPL otherwise, before anything runs)
 void Utf8Lowering::validate() const {
+    // an argument that is a projection of its own (evaluate_column): its lowered nodes and its VM program are checked as ProjectionExec does
+    auto check_projected = [&](const ExprPtr& x) {
+        Utf8Lowering inner(in_);
+        const ExprPtr lowered = inner.rewrite(x, true);
+        inner.validate();
+        const SchemaPtr aug = inner.schema();
+        ProgramBuilder pb(*aug);
+        if (lowered->kind != BHIP_EXPR_COLUMN) pb.add_output(lowered);
+    };
     std::function<void(const ExprPtr&)> walk = [&](const ExprPtr& e) {
         switch (e->kind) {
             case BHIP_EXPR_COLUMN: {
@@ -317,6 +421,15 @@ void Utf8Lowering::validate() const {
                 if (e->dtype != DT_UTF8) fail(BHIP_EINVAL, "expected a Utf8 literal");
                 break;
             case BHIP_EXPR_SCALAR_FN:
+                if (e->name == "concat") {
+                    if (e->args.size() > (size_t)STR_CONCAT_MAX) fail(BHIP_ENOTIMPL, "concat with more than 8 arguments");
+                    for (auto& a : e->args) {
+                        const int t = expr_type(a, in_);
+                        if (t != DT_UTF8) fail(BHIP_EINVAL, std::string("concat requires Utf8 arguments, not ") + dtype_name(t));
+                        walk(a);
+                    }
+                    break;
+                }
                 if (str_fn(e->name) < 0 && !sha_fn(e->name)) fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e->to_string());
                 walk(e->args[0]);
                 break;
@@ -333,19 +446,23 @@ void Utf8Lowering::validate() const {
                 const int from = expr_type(x, in_);
                 if (from == DT_UTF8) { walk(x); break; }
                 if (!cast_format_supported(from)) fail(BHIP_ENOTIMPL, cast_name(from, DT_UTF8));
-                // the argument is a projection of its own: its string nodes and its VM program are checked as ProjectionExec does
-                Utf8Lowering inner(in_);
-                const ExprPtr lowered = inner.rewrite(x, true);
-                inner.validate();
-                const SchemaPtr aug = inner.schema();
-                ProgramBuilder pb(*aug);
-                if (lowered->kind != BHIP_EXPR_COLUMN) pb.add_output(lowered);
+                check_projected(x);
             } break;
             default: fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e->to_string());
         }
     };
     for (auto& n : nodes_) {
         if (expr_type(n, in_) == DT_UTF8) { walk(n); continue; }
+        if (n->kind == BHIP_EXPR_SCALAR_FN && n->name == "date_trunc") {
+            (void)date_trunc_granularity(*n, in_);
+            check_projected(n->args[1]);
+            continue;
+        }
+        if (n->kind == BHIP_EXPR_SCALAR_FN) {          // to_timestamp
+            if (expr_type(n->args[0], in_) != DT_UTF8) fail(BHIP_EINVAL, std::string("to_timestamp requires a Utf8 argument, not ") + dtype_name(expr_type(n->args[0], in_)));
+            walk(n->args[0]);
+            continue;
+        }
         if (!cast_parse_supported(n->dtype)) fail(BHIP_ENOTIMPL, cast_name(DT_UTF8, n->dtype));
         walk(n->args[0]);
     }

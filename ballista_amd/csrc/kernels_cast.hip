@@ -7,10 +7,14 @@
 //
 //   Utf8 -> T     one thread per row walks its bytes in HBM; value, and the validity as one ballot word per wave64
 //   T -> Utf8     lengths -> exclusive scan (offsets) -> bytes, the shape of str_transform_*
+//
+// to_timestamp (Utf8 -> Timestamp(Nanosecond)) and date_trunc (Timestamp -> Timestamp) are lowered the same way and live here;
+// their grammar and calendar arithmetic are temporal_text.h.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "cast_kernels.h"
 #include "cast_text.h"
+#include "temporal_text.h"
 
 namespace bhip {
 
@@ -99,6 +103,40 @@ cast_format_write_kernel(ColumnRef c, int64_t n, const int32_t* out_offsets, uin
     }
 }
 
+// to_timestamp: one thread per row walks its bytes, as cast_parse_kernel does.  A NULL row stays NULL (the result shares the
+// argument's validity) and gets a defined 0; a non-NULL text outside the grammar raises the status bit — the query fails.
+__global__ void __launch_bounds__(BLOCK)
+to_timestamp_parse_kernel(ColumnRef c, int64_t n, int64_t* out, uint32_t* status) {
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        int64_t v = 0;
+        if (bit_at(c.validity, i)) {
+            const CastPtrReader rd{reinterpret_cast<const uint8_t*>(c.data)};
+            bad |= !to_timestamp_parse(rd, (int64_t)c.offsets[i], (int64_t)c.offsets[i + 1], v);
+        }
+        out[i] = v;
+    }
+    if (bad) atomicOr(status, TO_TIMESTAMP_STATUS_INVALID);
+}
+
+// date_trunc: a streaming kernel, 8 bytes in and 8 bytes out per row plus the validity — one ballot word per wave64, the lanes
+// past n voting `false` (the loop runs to n rounded up)
+__global__ void __launch_bounds__(BLOCK)
+date_trunc_kernel(ColumnRef c, int64_t n, int g, int64_t* out, uint64_t* validity) {
+    const int64_t n_round = (n + 63) & ~(int64_t)63;
+    const int64_t* in = reinterpret_cast<const int64_t*>(c.data);
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * BLOCK) {
+        bool valid = false;
+        if (i < n) {
+            int64_t v = 0;
+            valid = bit_at(c.validity, i) && temporal_trunc(c.dtype, g, in[i], v);
+            out[i] = valid ? v : 0;                     // 0 for a NULL: the bytes stay defined
+        }
+        const uint64_t vw = __ballot(valid);
+        if ((threadIdx.x & 63) == 0) validity[i >> 6] = vw;
+    }
+}
+
 inline int grid_of(const LaunchCfg& cfg, int64_t n) {
     const int64_t want = (n + BLOCK - 1) / BLOCK, cap = (int64_t)cfg.device_cus * 8;
     return (int)(want < 1 ? 1 : (want > cap ? cap : want));
@@ -124,6 +162,20 @@ hipError_t launch_cast_parse(const LaunchCfg& cfg, const ColumnRef& c, int64_t n
         case 4: return parse_as<uint32_t>(cfg, c, n, to, out, validity, status);
         default: return parse_as<uint64_t>(cfg, c, n, to, out, validity, status);
     }
+}
+
+hipError_t launch_to_timestamp_parse(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int64_t* out, uint32_t* status) {
+    if (c.dtype != DT_UTF8) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(to_timestamp_parse_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, c, n, out, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_date_trunc(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int granularity, int64_t* out, uint64_t* validity) {
+    if (timestamp_units_per_second(c.dtype) == 0 || granularity < 0 || granularity >= TRUNC_COUNT) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(date_trunc_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, c, n, granularity, out, validity);
+    return hipGetLastError();
 }
 
 hipError_t launch_cast_format_lengths(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, uint32_t* lengths, uint64_t* validity_out) {

@@ -1,5 +1,5 @@
 // kernels_str.hip — expressions that PRODUCE Utf8 values: lower / upper / trim / ltrim / rtrim
-// (rust/core/src/serde/logical_plan/from_proto.rs:910-918 ships them), CASE ... THEN <string>, string literals as columns.
+// (rust/core/src/serde/logical_plan/from_proto.rs:910-918 ships them), CASE ... THEN <string>, string literals as columns, concat.
 //
 // The expression VM (vm_device.h) keeps 64-bit values per row; a string result is a new Arrow column instead: every kernel
 // here runs as lengths -> exclusive scan (offsets) -> bytes, one thread per row, over the offsets / bytes / validity buffers
@@ -132,6 +132,81 @@ str_select_write_kernel(StrSelectArgs A, int64_t n, const int32_t* out_offsets, 
         const ColumnRef& v = A.val[case_branch(A, i)];
         const uint8_t* s = reinterpret_cast<const uint8_t*>(v.data) + v.offsets[i];
         for (int k = 0; k < len; ++k) out[d0 + k] = s[k];
+    }
+}
+
+// ---- concat(a1, ..., ak) ---------------------------------------------------------------------------------------------------------
+// lengths: the sum of the arguments' lengths, 0 and a cleared validity bit where any argument is NULL.  Rows are taken 64 at a
+// time by whole waves (the loop runs to n rounded up), so every validity word is one ballot, the last partial one included.
+__global__ void __launch_bounds__(BLOCK)
+concat_lengths_kernel(StrConcatArgs A, int64_t n, uint32_t* lengths, uint64_t* validity) {
+    const int64_t n_round = (n + 63) & ~(int64_t)63;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * BLOCK) {
+        bool valid = false;
+        if (i < n) {
+            valid = true;
+            uint64_t len = 0;
+            for (int j = 0; j < A.n_args; ++j) {
+                if (A.is_lit[j]) { len += (uint64_t)A.lit_len[j]; continue; }
+                const ColumnRef& c = A.col[j];
+                valid = valid && bit_at(c.validity, i);
+                len += (uint64_t)(c.offsets[i + 1] - c.offsets[i]);
+            }
+            lengths[i] = !valid ? 0u : (len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)len);
+        }
+        const uint64_t w = __ballot(valid);
+        if (validity != nullptr && (threadIdx.x & 63) == 0) validity[i >> 6] = w;
+    }
+}
+
+// bytes: one thread per row copies every argument to the row's offset — right for TPC-H-sized values.  A row whose result is
+// longer than STR_CONCAT_WAVE_BYTES would keep its one lane busy while the other 63 wait for it: such rows are left out of the
+// per-lane pass and copied afterwards by the whole wave, 64 consecutive bytes per step.  (The loop runs to n rounded up, so all
+// 64 lanes of a wave are there for the second pass.)
+__global__ void __launch_bounds__(BLOCK)
+concat_write_kernel(StrConcatArgs A, int64_t n, const int32_t* out_offsets, uint8_t* out) {
+    const int64_t n_round = (n + 63) & ~(int64_t)63;
+    const int lane = threadIdx.x & 63;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * BLOCK) {
+        int len = 0;
+        int32_t d0 = 0;
+        if (i < n) {
+            d0 = out_offsets[i];
+            len = out_offsets[i + 1] - d0;
+        }
+        if (len > 0 && len <= STR_CONCAT_WAVE_BYTES) {           // (len == 0: a NULL row, or every argument empty)
+            uint8_t* d = out + d0;
+            for (int j = 0; j < A.n_args; ++j) {
+                const uint8_t* s;
+                int l;
+                if (A.is_lit[j]) { s = A.lit_bytes + A.lit_off[j]; l = A.lit_len[j]; }
+                else {
+                    const ColumnRef& c = A.col[j];
+                    const int32_t o0 = c.offsets[i];
+                    s = reinterpret_cast<const uint8_t*>(c.data) + o0;
+                    l = c.offsets[i + 1] - o0;
+                }
+                for (int k = 0; k < l; ++k) d[k] = s[k];
+                d += l;
+            }
+        }
+        for (uint64_t todo = __ballot(len > STR_CONCAT_WAVE_BYTES); todo != 0; todo &= todo - 1) {
+            const int64_t row = i - lane + (__ffsll((unsigned long long)todo) - 1);      // wave-uniform, < n
+            uint8_t* d = out + out_offsets[row];
+            for (int j = 0; j < A.n_args; ++j) {
+                const uint8_t* s;
+                int l;
+                if (A.is_lit[j]) { s = A.lit_bytes + A.lit_off[j]; l = A.lit_len[j]; }
+                else {
+                    const ColumnRef& c = A.col[j];
+                    const int32_t o0 = c.offsets[row];
+                    s = reinterpret_cast<const uint8_t*>(c.data) + o0;
+                    l = c.offsets[row + 1] - o0;
+                }
+                for (int k = lane; k < l; k += 64) d[k] = s[k];
+                d += l;
+            }
+        }
     }
 }
 
@@ -300,6 +375,26 @@ hipError_t launch_str_select_lengths(const LaunchCfg& cfg, const StrSelectArgs& 
 hipError_t launch_str_select_write(const LaunchCfg& cfg, const StrSelectArgs& A, int64_t n, const int32_t* out_offsets, uint8_t* out) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(str_select_write_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, out_offsets, out);
+    return hipGetLastError();
+}
+static bool concat_args_ok(const StrConcatArgs& A) {
+    if (A.n_args < 1 || A.n_args > STR_CONCAT_MAX) return false;
+    for (int j = 0; j < A.n_args; ++j) {
+        if (!A.is_lit[j]) { if (A.col[j].dtype != DT_UTF8 || A.col[j].offsets == nullptr) return false; continue; }
+        if (A.lit_off[j] < 0 || A.lit_len[j] < 0 || A.lit_off[j] + A.lit_len[j] > STR_CONCAT_LIT_BYTES) return false;
+    }
+    return true;
+}
+hipError_t launch_concat_lengths(const LaunchCfg& cfg, const StrConcatArgs& A, int64_t n, uint32_t* lengths, uint64_t* validity) {
+    if (!concat_args_ok(A)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(concat_lengths_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, lengths, validity);
+    return hipGetLastError();
+}
+hipError_t launch_concat_write(const LaunchCfg& cfg, const StrConcatArgs& A, int64_t n, const int32_t* out_offsets, uint8_t* out) {
+    if (!concat_args_ok(A)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(concat_write_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, out_offsets, out);
     return hipGetLastError();
 }
 hipError_t launch_sha2(const LaunchCfg& cfg, int bits, const ColumnRef& c, int64_t n, int32_t* out_offsets, uint8_t* out) {

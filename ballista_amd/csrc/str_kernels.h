@@ -29,6 +29,22 @@ struct StrSelectArgs {
 hipError_t launch_str_select_lengths(const LaunchCfg& cfg, const StrSelectArgs& A, int64_t n, uint32_t* lengths, uint64_t* validity);
 hipError_t launch_str_select_write(const LaunchCfg& cfg, const StrSelectArgs& A, int64_t n, const int32_t* out_offsets, uint8_t* out);
 
+// concat(a1, ..., ak): NULL where any argument is (SQL ||).  An argument is a Utf8 column, or a literal carried in the struct
+// (is_lit[j] != 0: lit_len[j] bytes at lit_bytes + lit_off[j]; its ColumnRef is unused).
+constexpr int STR_CONCAT_MAX = 8;
+constexpr int STR_CONCAT_LIT_BYTES = 256;        // all literal arguments together
+constexpr int STR_CONCAT_WAVE_BYTES = 1024;      // a row whose result is longer is copied by its whole wave, not by one lane
+struct StrConcatArgs {
+    int32_t n_args;
+    int32_t is_lit[STR_CONCAT_MAX], lit_off[STR_CONCAT_MAX], lit_len[STR_CONCAT_MAX];
+    ColumnRef col[STR_CONCAT_MAX];
+    uint8_t lit_bytes[STR_CONCAT_LIT_BYTES];
+};
+// lengths[i] = the sum of the arguments' lengths (0 for a NULL row; saturated at 2^32 - 1, which the 2 GiB check of the caller
+// catches).  validity (may be null when no argument has a validity buffer): written as whole 64-bit words, (n + 63) / 64 of them.
+hipError_t launch_concat_lengths(const LaunchCfg& cfg, const StrConcatArgs& A, int64_t n, uint32_t* lengths, uint64_t* validity);
+hipError_t launch_concat_write(const LaunchCfg& cfg, const StrConcatArgs& A, int64_t n, const int32_t* out_offsets, uint8_t* out);
+
 // sha224 / sha256 / sha384 / sha512 of every string: n digests of bits / 8 bytes at out + row * (bits / 8), offsets written too
 hipError_t launch_sha2(const LaunchCfg& cfg, int bits, const ColumnRef& c, int64_t n, int32_t* out_offsets, uint8_t* out);
 

@@ -208,7 +208,10 @@ typedef enum {
     BHIP_EXPR_IN_LIST = 9,     /* n_args list items + 1 ; negated       pops n_args+1       */
     BHIP_EXPR_CASE = 10,       /* n_args = #when/then pairs; flags bit0: has base expr,
                                   bit1: has else.  Stack order: [base] w1 t1 ... wn tn [else] */
-    BHIP_EXPR_SCALAR_FN = 11   /* name = function ("sqrt", "abs", ...) ; n_args             */
+    BHIP_EXPR_SCALAR_FN = 11   /* name = function ; pops n_args, pushed in order.  One argument: sqrt abs floor ceil round
+                                  trunc signum exp ln log2 log10 sin cos tan asin acos atan, lower upper trim ltrim rtrim,
+                                  octet_length, sha224 sha256 sha384 sha512, to_timestamp.  Two: nullif(a, b),
+                                  date_trunc('granularity', t).  One to eight: concat.  md5 and array: BHIP_ENOTIMPL */
 } bhip_expr_kind;
 
 typedef struct {
