@@ -4,8 +4,8 @@
 // records (quote-aware in CSV), fields, values and NULLs are found on the device.  Every value the device needs arrives as a
 // kernel argument or is written by a kernel: no hipMemcpyAsync reads a host variable here.
 //
-// `.tbl` is the '|', quote-free, NULL-free, header-free case with kernels of its own.  Where the CSV scan does more, it says so
-// at that point: the count pass, the starts kernel, the header, three more per-slot buffers, the flags, the copy launcher.
+// `.tbl` is the '|', quote-free, NULL-free, header-free case with count, starts and parse kernels of its own.  Where the CSV scan
+// does more, it says so at that point: the count pass, the starts kernel, the header, three more per-slot buffers, the flags.
 #include <cstring>
 
 #include "../util_kernels.h"
@@ -83,19 +83,15 @@ TextScanSpec make_text_spec(int format, int n_fields, const bhip_column_desc* fi
     }
     spec.schema = schema;
 
-    // the field walk of the format's parse kernel; fields behind the last projected one are never walked
-    auto walk = [&](auto& plan) {
-        memset(&plan, 0, sizeof(plan));
-        plan.n_fields = last_needed + 1;
-        for (int f = 0; f < n_fields; ++f) {
-            plan.dtype[f] = fields[f].dtype;
-            plan.out[f] = out[f];
-        }
-    };
-    walk(spec.tbl);
-    walk(spec.csv);
-    spec.csv.delimiter = csv_opts.delimiter;
-    for (int f = 0; f < n_fields; ++f) spec.csv.nullable[f] = fields[f].nullable != 0;
+    // the field walk of the parse kernel; fields behind the last projected one are never walked
+    memset(&spec.plan, 0, sizeof(spec.plan));
+    spec.plan.n_fields = last_needed + 1;
+    spec.plan.delimiter = csv_opts.delimiter;
+    for (int f = 0; f < n_fields; ++f) {
+        spec.plan.dtype[f] = fields[f].dtype;
+        spec.plan.out[f] = out[f];
+        spec.plan.nullable[f] = fields[f].nullable != 0;
+    }
     return spec;
 }
 
@@ -198,8 +194,7 @@ TextParsed parse_text_slab(const Exec& ex, const TextScanSpec& spec, const TextS
     // ---- columns.  CSV: a mark per row whose string holds "" pairs, a validity bitmap per nullable column, Boolean as a bitmap
     uint32_t* flags = tmp.get<uint32_t>(2);
     HIP_CHECK(hipMemsetAsync(flags, 0, 8, ex.stream));
-    TblPlan tbl = spec.tbl;
-    CsvPlan plan = spec.csv;
+    TextPlan plan = spec.plan;
     for (size_t s = 0; s < n_slots; ++s) {
         const int dt = spec.dtype[s];
         Column c;
@@ -218,15 +213,12 @@ TextParsed parse_text_slab(const Exec& ex, const TextScanSpec& spec, const TextS
                 plan.validity[s] = c.validity->as<uint64_t>();
             }
         }
-        tbl.data[s] = plan.data[s];
-        tbl.str_start[s] = plan.str_start[s];
-        tbl.str_len[s] = plan.str_len[s];
         batch->cols.push_back(std::move(c));
     }
 
     // ---- parse
     if (csv) HIP_CHECK(launch_csv_parse(cfg, text, starts + header, n_rows, n_bytes, plan, quoted, flags));
-    else HIP_CHECK(launch_tbl_parse(cfg, text, starts, n_rows, n_bytes, tbl, flags));
+    else HIP_CHECK(launch_tbl_parse(cfg, text, starts, n_rows, n_bytes, plan, flags));
 
     // ---- strings: lengths -> offsets -> bytes
     uint64_t* totals_str = tmp.get<uint64_t>(n_slots + 1);
@@ -256,8 +248,7 @@ TextParsed parse_text_slab(const Exec& ex, const TextScanSpec& spec, const TextS
         c.data_bytes = (int64_t)host_totals[s];
         c.data = make_buffer(ex, (size_t)c.data_bytes + 8);
         const int32_t* offsets = c.offsets->as<int32_t>();
-        if (csv) HIP_CHECK(launch_csv_copy_strings(cfg, text, plan.str_start[s], plan.str_len[s], plan.str_esc[s], offsets, n_rows, c.data->as<uint8_t>()));
-        else HIP_CHECK(launch_tbl_copy_strings(cfg, text, plan.str_start[s], plan.str_len[s], offsets, n_rows, c.data->as<uint8_t>()));
+        HIP_CHECK(launch_text_copy_strings(cfg, text, plan.str_start[s], plan.str_len[s], plan.str_esc[s], offsets, n_rows, c.data->as<uint8_t>()));
     }
     HIP_CHECK(hipStreamSynchronize(ex.stream));
     return TextParsed{batch, (int64_t)cut};

@@ -29,12 +29,11 @@ struct TextParsed {
     int64_t cut = 0;
 };
 
-// what one scan reads: the schema and the projection, validated once.  The plan structs are the kernels' own arguments (both are
-// filled, the format's own is used); their per-slot pointers are filled per slab.
+// what one scan reads: the schema and the projection, validated once.  The plan is the parse kernels' own argument; its per-slot
+// pointers are filled per slab.
 struct TextScanSpec {
     int format = BHIP_TEXT_TBL;     // BHIP_TEXT_TBL | BHIP_TEXT_CSV
-    TblPlan tbl;                    // field walk
-    CsvPlan csv;                    // ... with the delimiter and which fields may be NULL
+    TextPlan plan;                  // field walk; CSV: with the delimiter and which fields may be NULL
     SchemaPtr schema;
     std::vector<int> dtype;         // [slot]
     std::vector<char> nullable;     // [slot]

@@ -11,9 +11,10 @@
 //              wave by a ballot + masked popcount, across the waves through LDS; '\n' outside quotes are ranked and written.
 //   3. parse   one thread per record, fields found quote-aware; validity, Boolean and ""-mark bits leave as one ballot word per
 //              wave.
-//   4. copy    Utf8 bytes behind an exclusive scan of the lengths, "" collapsed where marked.
-// The value grammar is the `.tbl` scan's (kernels_tbl.hip) plus Boolean.  The LDS staging, the byte readers and the helpers of
-// the conversions are shared with that scan: text_device.h.  What two CSV readers would read differently (a '"' inside an
+//   4. copy    Utf8 bytes behind an exclusive scan of the lengths, "" collapsed where marked (text_copy_strings_kernel,
+//              kernels_tbl.hip).
+// The value grammar is the `.tbl` scan's plus Boolean.  The LDS staging, the byte readers and the conversion of a fixed-width
+// value (text_convert) are shared with that scan: text_device.h.  What two CSV readers would read differently (a '"' inside an
 // unquoted field, bytes behind a closing quote, a bare '\r') raises CSV_ERR_STRAY_QUOTE: the caller keeps its CPU reader.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
@@ -128,16 +129,9 @@ csv_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_b
     if (in) pm = ~pm;
     uint64_t ends = nm & ~pm;                                   // '\n' outside quotes
     const uint32_t c = (uint32_t)__popcll(ends);
-    s_scan[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < BLOCK; d <<= 1) {                       // inclusive Hillis-Steele scan of the thread counts
-        const uint32_t v = tid >= d ? s_scan[tid - d] : 0;
-        __syncthreads();
-        s_scan[tid] += v;
-        __syncthreads();
-    }
+    const uint32_t before = block_rank_base(c, s_scan, tid);
     if (c == 0) return;
-    uint64_t rank = chunk_base[blockIdx.x] + (s_scan[tid] - c);
+    uint64_t rank = chunk_base[blockIdx.x] + before;
     const int64_t base = chunk0 + (int64_t)tid * TEXT_THREAD_BYTES;
     while (ends) {
         const int b = __ffsll((unsigned long long)ends) - 1;
@@ -146,84 +140,20 @@ csv_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* quotes_b
     }
 }
 
-// a non-empty value [a, b) of a fixed-width column -> row i of `data`; returns the error flags.  Int32 / Int64 / Float64 / Date32
-// as in kernels_tbl.hip (one exact division for decimals).  A Boolean comes back in `truth`.
-// Everything below the Boolean case is a second copy of the conversion in tbl_parse_line (kernels_tbl.hip) and has to change with
-// it: sharing it changes the code of tbl_parse_kernel, and that version has not been timed on the device (see there).
+// a non-empty Boolean value [a, b): "true" / "false" in any letter case.  The value comes back in `truth` and leaves as a ballot bit.
 template <class R>
-__device__ inline uint32_t csv_convert(const R& rd, int64_t a, int64_t b, int dt, void* data, int64_t i, bool& truth) {
-    uint32_t err = 0;
-    if (dt == DT_BOOLEAN) {
-        const char* word = (b - a) == 4 ? "true" : "false";
-        bool ok = (b - a) == 4 || (b - a) == 5;
-        for (int k = 0; ok && k < (int)(b - a); ++k) ok = (rd(a + k) | 0x20) == (uint8_t)word[k];
-        truth = ok && (b - a) == 4;
-        return ok ? 0u : (uint32_t)TBL_ERR_BAD_VALUE;
-    }
-    if (dt == DT_DATE32) {
-        // YYYY-MM-DD
-        bool ok = (b - a) == 10 && rd(a + 4) == '-' && rd(a + 7) == '-';
-        int v[8];
-        const int pos[8] = {0, 1, 2, 3, 5, 6, 8, 9};
-        for (int k = 0; k < 8 && ok; ++k) {
-            const int c = (int)rd(a + pos[k]) - '0';
-            ok = c >= 0 && c <= 9;
-            v[k] = c;
-        }
-        int32_t days = 0;
-        if (ok) {
-            const int y = v[0] * 1000 + v[1] * 100 + v[2] * 10 + v[3], m = v[4] * 10 + v[5], d = v[6] * 10 + v[7];
-            ok = m >= 1 && m <= 12 && d >= 1 && d <= 31;
-            days = (int32_t)days_from_civil(y, (unsigned)m, (unsigned)d);
-        }
-        if (!ok) err |= TBL_ERR_BAD_VALUE;
-        reinterpret_cast<int32_t*>(data)[i] = days;
-        return err;
-    }
-    int64_t r = a;
-    bool neg = false;
-    if (rd(r) == '-' || rd(r) == '+') { neg = rd(r) == '-'; ++r; }
-    uint64_t m = 0;
-    int digits = 0, frac = 0;
-    bool seen_dot = false, ok = r < b;
-    for (; r < b; ++r) {
-        const uint8_t ch = rd(r);
-        if (ch >= '0' && ch <= '9') {
-            if (digits >= 19) {                                  // 19 digits still fit 64 bits
-                if (dt == DT_FLOAT64) { err |= TBL_ERR_PRECISION; m = 0; frac = 0; r = b; break; }
-                ok = false;
-                break;
-            }
-            m = m * 10 + (uint64_t)(ch - '0');
-            if (m != 0 || seen_dot) ++digits;             // leading zeros of the integer part are free
-            if (seen_dot) ++frac;
-        } else if (ch == '.' && !seen_dot && dt == DT_FLOAT64) {
-            seen_dot = true;
-        } else { ok = false; break; }
-    }
-    if (dt == DT_FLOAT64) {
-        if (!ok) err |= TBL_ERR_BAD_VALUE;
-        else if (m >= (1ull << 53) || frac > 22) { err |= TBL_ERR_PRECISION; ok = false; }
-        const double v = ok ? (double)m / TEXT_POW10[frac] : 0.0;
-        reinterpret_cast<double*>(data)[i] = neg ? -v : v;
-    } else {
-        if (!ok || seen_dot) err |= TBL_ERR_BAD_VALUE;
-        if (m > (neg ? (1ull << 63) : (1ull << 63) - 1ull)) err |= TBL_ERR_BAD_VALUE;      // beyond Int64
-        const int64_t v = neg ? (int64_t)(0ull - m) : (int64_t)m;
-        if (dt == DT_INT32) {
-            if (v > 2147483647ll || v < -2147483648ll) err |= TBL_ERR_BAD_VALUE;
-            reinterpret_cast<int32_t*>(data)[i] = (int32_t)v;
-        } else {
-            reinterpret_cast<int64_t*>(data)[i] = v;
-        }
-    }
-    return err;
+__device__ inline uint32_t csv_convert_bool(const R& rd, int64_t a, int64_t b, bool& truth) {
+    const char* word = (b - a) == 4 ? "true" : "false";
+    bool ok = (b - a) == 4 || (b - a) == 5;
+    for (int k = 0; ok && k < (int)(b - a); ++k) ok = (rd(a + k) | 0x20) == (uint8_t)word[k];
+    truth = ok && (b - a) == 4;
+    return ok ? 0u : (uint32_t)TBL_ERR_BAD_VALUE;
 }
 
 // one record [p, e) per lane.  Every lane of the wave walks all the fields, with or without a record (`active`), because the bits
 // of a column leave as one ballot word per wave: `word` is the wave's word in every bitmap, or -1 when the wave has no record.
 template <bool QUOTED, class R>
-__device__ inline uint32_t csv_parse_record(const R& rd, bool active, int64_t p, int64_t e, int64_t i, int64_t word, const CsvPlan& plan,
+__device__ inline uint32_t csv_parse_record(const R& rd, bool active, int64_t p, int64_t e, int64_t i, int64_t word, const TextPlan& plan,
                                             uint32_t& null_slots) {
     uint32_t err = 0;
     const bool writer = (threadIdx.x & 63) == 0 && word >= 0;
@@ -285,7 +215,15 @@ __device__ inline uint32_t csv_parse_record(const R& rd, bool active, int64_t p,
             } else {
                 valid = true;
                 if (pairs) err |= TBL_ERR_BAD_VALUE;
-                err |= csv_convert(rd, a, b, dt, plan.data[out], i, truth);
+                // a constant type per call, so one instance of the conversion per type: 0.16 ms per GiB of text faster than one
+                // call with `dt` passed through (profiles/text_convert_shared.txt).  The host admits no other type.
+                switch (dt) {
+                    case DT_BOOLEAN: err |= csv_convert_bool(rd, a, b, truth); break;
+                    case DT_DATE32: err |= text_convert(rd, a, b, DT_DATE32, plan.data[out], i); break;
+                    case DT_FLOAT64: err |= text_convert(rd, a, b, DT_FLOAT64, plan.data[out], i); break;
+                    case DT_INT64: err |= text_convert(rd, a, b, DT_INT64, plan.data[out], i); break;
+                    default: err |= text_convert(rd, a, b, DT_INT32, plan.data[out], i); break;
+                }
             }
         }
         if (plan.validity[out]) {
@@ -305,7 +243,7 @@ __device__ inline uint32_t csv_parse_record(const R& rd, bool active, int64_t p,
 // Record i0 is a multiple of 256, so wave w of the workgroup owns bitmap word i0 / 64 + w of every column.
 template <bool QUOTED>
 __global__ void __launch_bounds__(BLOCK)
-csv_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_records, int64_t n_bytes, CsvPlan plan, uint32_t* flags) {
+csv_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_records, int64_t n_bytes, TextPlan plan, uint32_t* flags) {
     __shared__ __align__(16) uint8_t s_buf[TEXT_STAGE];
     uint32_t err = 0, null_slots = 0;
     const int tid = threadIdx.x;
@@ -325,26 +263,6 @@ csv_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_records,
     }
     if (err) atomicOr(flags, err);
     if (null_slots && (tid & 63) == 0) atomicOr(flags + 1, null_slots);
-}
-
-// pass 4: one thread per row.  Inside a quoted field every '"' is the first of a "" pair: the second is skipped.
-__global__ void __launch_bounds__(BLOCK)
-csv_copy_strings_kernel(const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len, const uint64_t* str_esc,
-                        const int32_t* offsets, int64_t n, uint8_t* out) {
-    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
-        const uint8_t* s = text + str_start[i];
-        uint8_t* d = out + offsets[i];
-        const uint32_t len = str_len[i];
-        if (str_esc && ((str_esc[i >> 6] >> (i & 63)) & 1ull)) {
-            for (uint32_t b = 0; b < len; ++b) {
-                const uint8_t ch = *s;
-                d[b] = ch;
-                s += ch == '"' ? 2 : 1;
-            }
-        } else {
-            for (uint32_t b = 0; b < len; ++b) d[b] = s[b];
-        }
-    }
 }
 
 hipError_t launch_csv_count(const LaunchCfg& cfg, const uint8_t* text, int64_t n_bytes, uint32_t* quotes, uint32_t* newlines) {
@@ -367,18 +285,11 @@ hipError_t launch_csv_starts(const LaunchCfg& cfg, const uint8_t* text, int64_t 
     return hipGetLastError();
 }
 hipError_t launch_csv_parse(const LaunchCfg& cfg, const uint8_t* text, const uint64_t* starts, int64_t n_records, int64_t n_bytes,
-                            const CsvPlan& plan, bool quoted, uint32_t* flags) {
+                            const TextPlan& plan, bool quoted, uint32_t* flags) {
     if (n_records == 0) return hipSuccess;
     const dim3 grid(grid_rows(cfg, n_records));
     if (quoted) hipLaunchKernelGGL(csv_parse_kernel<true>, grid, dim3(BLOCK), 0, cfg.stream, text, starts, n_records, n_bytes, plan, flags);
     else hipLaunchKernelGGL(csv_parse_kernel<false>, grid, dim3(BLOCK), 0, cfg.stream, text, starts, n_records, n_bytes, plan, flags);
-    return hipGetLastError();
-}
-hipError_t launch_csv_copy_strings(const LaunchCfg& cfg, const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len,
-                                   const uint64_t* str_esc, const int32_t* offsets, int64_t n, uint8_t* out) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(csv_copy_strings_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, text, str_start, str_len, str_esc,
-                       offsets, n, out);
     return hipGetLastError();
 }
 

@@ -6,13 +6,9 @@
 // Byte work, three passes over the text:
 //   1. newlines per 16 KiB chunk                          (count)  -> exclusive scan
 //   2. start offset of every line                          (stable ranks inside a chunk: thread-local counts + LDS scan)
-//   3. one thread per line walks its fields; projected fields are converted in place:
-//        Int32 / Int64   [-]digits
-//        Float64         [-]digits[.digits]  =  M / 10^k with M < 2^53 and k <= 22: both exact in double, so the one
-//                        division is the correctly rounded value of the decimal text (what str::parse::<f64> returns)
-//        Date32          YYYY-MM-DD -> days since 1970-01-01 (proleptic Gregorian)
-//        Utf8            (offset, length) of the field; a second pass copies the bytes behind an exclusive scan
-// The LDS staging, the byte readers and the helpers of the conversions are shared with the CSV scan: text_device.h.
+//   3. one thread per line walks its fields; projected fields are converted in place (text_convert), a Utf8 field leaves as
+//      (offset, length); a second pass copies the bytes behind an exclusive scan of the lengths
+// The LDS staging, the byte readers and the conversion with its grammar are shared with the CSV scan: text_device.h.
 // Anything else in the text (exponents, > 15 significant digits, missing fields, blank lines) raises a flag and the
 // host reports BHIP_EEXEC / BHIP_ENOTIMPL: the caller keeps its CPU reader for that file.
 #include <hip/hip_runtime.h>
@@ -71,16 +67,9 @@ tbl_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* chunk_ba
     uint32_t c = 0;
 #pragma unroll
     for (int d = 0; d < 16; ++d) c += newlines_exact(s_text[tid * 17 + d]);
-    s_scan[tid] = c;
-    __syncthreads();
-    for (int d = 1; d < BLOCK; d <<= 1) {                 // inclusive Hillis-Steele scan of the thread counts
-        const uint32_t v = tid >= d ? s_scan[tid - d] : 0;
-        __syncthreads();
-        s_scan[tid] += v;
-        __syncthreads();
-    }
+    const uint32_t before = block_rank_base(c, s_scan, tid);
     if (c == 0) return;
-    uint64_t rank = chunk_base[blockIdx.x] + (s_scan[tid] - c);
+    uint64_t rank = chunk_base[blockIdx.x] + before;
     const int64_t base = chunk0 + (int64_t)tid * TEXT_THREAD_BYTES;
     for (int d = 0; d < 16; ++d) {
         const uint32_t w = s_text[tid * 17 + d];
@@ -91,12 +80,8 @@ tbl_starts_kernel(const uint8_t* text, int64_t n_bytes, const uint64_t* chunk_ba
 }
 
 // one line [p, e): walk the fields, convert the projected ones.  Returns the error flags.
-// The Date32 / Int32 / Int64 / Float64 conversion below is a second copy of csv_convert (kernels_csv.hip) and has to change with
-// it.  It is not shared yet because routing this walk through one conversion function, even with Boolean compiled out, changes
-// the code of tbl_parse_kernel (61 -> 52 VGPRs, most of its instructions reordered), the hottest kernel of the scan, and that
-// version has not been timed on the device (profiles/text_scan_unified.txt).
 template <class R>
-__device__ inline uint32_t tbl_parse_line(const R& rd, int64_t p, int64_t e, int64_t i, const TblPlan& plan) {
+__device__ inline uint32_t tbl_parse_line(const R& rd, int64_t p, int64_t e, int64_t i, const TextPlan& plan) {
     uint32_t err = 0;
     if (e > p && rd(e - 1) == '\r') --e;
     if (e <= p) return TBL_ERR_BLANK_LINE;
@@ -110,62 +95,8 @@ __device__ inline uint32_t tbl_parse_line(const R& rd, int64_t p, int64_t e, int
             if (dt == DT_UTF8) {
                 plan.str_start[out][i] = (uint32_t)p;
                 plan.str_len[out][i] = (uint32_t)(q - p);
-            } else if (dt == DT_DATE32) {
-                // YYYY-MM-DD
-                bool ok = (q - p) == 10 && rd(p + 4) == '-' && rd(p + 7) == '-';
-                int v[8];
-                const int pos[8] = {0, 1, 2, 3, 5, 6, 8, 9};
-                for (int k = 0; k < 8 && ok; ++k) {
-                    const int c = (int)rd(p + pos[k]) - '0';
-                    ok = c >= 0 && c <= 9;
-                    v[k] = c;
-                }
-                int32_t days = 0;
-                if (ok) {
-                    const int y = v[0] * 1000 + v[1] * 100 + v[2] * 10 + v[3], m = v[4] * 10 + v[5], d = v[6] * 10 + v[7];
-                    ok = m >= 1 && m <= 12 && d >= 1 && d <= 31;
-                    days = (int32_t)days_from_civil(y, (unsigned)m, (unsigned)d);
-                }
-                if (!ok) err |= TBL_ERR_BAD_VALUE;
-                reinterpret_cast<int32_t*>(plan.data[out])[i] = days;
             } else {
-                int64_t r = p;
-                bool neg = false;
-                if (r < q && (rd(r) == '-' || rd(r) == '+')) { neg = rd(r) == '-'; ++r; }
-                uint64_t m = 0;
-                int digits = 0, frac = 0;
-                bool seen_dot = false, ok = r < q;
-                for (; r < q; ++r) {
-                    const uint8_t ch = rd(r);
-                    if (ch >= '0' && ch <= '9') {
-                        if (digits >= 19) {                                  // 19 digits still fit 64 bits
-                            if (dt == DT_FLOAT64) { err |= TBL_ERR_PRECISION; m = 0; frac = 0; r = q; break; }
-                            ok = false;
-                            break;
-                        }
-                        m = m * 10 + (uint64_t)(ch - '0');
-                        if (m != 0 || seen_dot) ++digits;             // leading zeros of the integer part are free
-                        if (seen_dot) ++frac;
-                    } else if (ch == '.' && !seen_dot && dt == DT_FLOAT64) {
-                        seen_dot = true;
-                    } else { ok = false; break; }
-                }
-                if (dt == DT_FLOAT64) {
-                    if (!ok) err |= TBL_ERR_BAD_VALUE;
-                    else if (m >= (1ull << 53) || frac > 22) { err |= TBL_ERR_PRECISION; ok = false; }
-                    double v = ok ? (double)m / TEXT_POW10[frac] : 0.0;
-                    reinterpret_cast<double*>(plan.data[out])[i] = neg ? -v : v;
-                } else {
-                    if (!ok || seen_dot) err |= TBL_ERR_BAD_VALUE;
-                    if (m > (neg ? (1ull << 63) : (1ull << 63) - 1ull)) err |= TBL_ERR_BAD_VALUE;      // beyond Int64
-                    const int64_t v = neg ? (int64_t)(0ull - m) : (int64_t)m;
-                    if (dt == DT_INT32) {
-                        if (v > 2147483647ll || v < -2147483648ll) err |= TBL_ERR_BAD_VALUE;
-                        reinterpret_cast<int32_t*>(plan.data[out])[i] = (int32_t)v;
-                    } else {
-                        reinterpret_cast<int64_t*>(plan.data[out])[i] = v;
-                    }
-                }
+                err |= text_convert(rd, p, q, dt, plan.data[out], i);
             }
         }
         p = q + 1;
@@ -175,7 +106,7 @@ __device__ inline uint32_t tbl_parse_line(const R& rd, int64_t p, int64_t e, int
 
 // pass 3: a workgroup takes 256 consecutive lines and walks them in LDS (stage_span), or in HBM when they do not fit.
 __global__ void __launch_bounds__(BLOCK)
-tbl_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_lines, int64_t n_bytes, TblPlan plan, uint32_t* flags) {
+tbl_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_lines, int64_t n_bytes, TextPlan plan, uint32_t* flags) {
     __shared__ __align__(16) uint8_t s_buf[TEXT_STAGE];
     uint32_t err = 0;
     const int tid = threadIdx.x;
@@ -196,14 +127,24 @@ tbl_parse_kernel(const uint8_t* text, const uint64_t* starts, int64_t n_lines, i
     if (err) atomicOr(flags, err);
 }
 
+// pass 4, both formats: one thread per row.  A set bit of str_esc (CSV; null: no row has any) marks a quoted field with "" pairs:
+// every '"' inside it is the first of a pair, and the second is skipped.
 __global__ void __launch_bounds__(BLOCK)
-tbl_copy_strings_kernel(const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len, const int32_t* offsets, int64_t n,
-                        uint8_t* out) {
+text_copy_strings_kernel(const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len, const uint64_t* str_esc,
+                         const int32_t* offsets, int64_t n, uint8_t* out) {
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
         const uint8_t* s = text + str_start[i];
         uint8_t* d = out + offsets[i];
         const uint32_t len = str_len[i];
-        for (uint32_t b = 0; b < len; ++b) d[b] = s[b];
+        if (str_esc && ((str_esc[i >> 6] >> (i & 63)) & 1ull)) {
+            for (uint32_t b = 0; b < len; ++b) {
+                const uint8_t ch = *s;
+                d[b] = ch;
+                s += ch == '"' ? 2 : 1;
+            }
+        } else {
+            for (uint32_t b = 0; b < len; ++b) d[b] = s[b];
+        }
     }
 }
 
@@ -220,16 +161,17 @@ hipError_t launch_tbl_starts(const LaunchCfg& cfg, const uint8_t* text, int64_t 
     return hipGetLastError();
 }
 hipError_t launch_tbl_parse(const LaunchCfg& cfg, const uint8_t* text, const uint64_t* starts, int64_t n_lines, int64_t n_bytes,
-                            const TblPlan& plan, uint32_t* flags) {
+                            const TextPlan& plan, uint32_t* flags) {
     if (n_lines == 0) return hipSuccess;
     hipLaunchKernelGGL(tbl_parse_kernel, dim3(grid_rows(cfg, n_lines)), dim3(BLOCK), 0, cfg.stream, text, starts, n_lines, n_bytes, plan,
                        flags);
     return hipGetLastError();
 }
-hipError_t launch_tbl_copy_strings(const LaunchCfg& cfg, const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len,
-                                   const int32_t* offsets, int64_t n, uint8_t* out) {
+hipError_t launch_text_copy_strings(const LaunchCfg& cfg, const uint8_t* text, const uint32_t* str_start, const uint32_t* str_len,
+                                    const uint64_t* str_esc, const int32_t* offsets, int64_t n, uint8_t* out) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(tbl_copy_strings_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, text, str_start, str_len, offsets, n, out);
+    hipLaunchKernelGGL(text_copy_strings_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, text, str_start, str_len, str_esc,
+                       offsets, n, out);
     return hipGetLastError();
 }
 

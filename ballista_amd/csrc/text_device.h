@@ -1,7 +1,7 @@
 // text_device.h — what the `.tbl` scan (kernels_tbl.hip) and the CSV scan (kernels_csv.hip) have in common on the device, once:
-// the staging of a chunk and of a span of records in LDS, the byte readers of the field walk, the date and power-of-ten helpers of
-// the value grammar.  The count, starts, record-walk and copy kernels are each format's own, and so is, for now, the conversion
-// of a fixed-width value (see tbl_parse_line in kernels_tbl.hip).
+// the staging of a chunk and of a span of records in LDS, the rank scan of the starts passes, the byte readers of the field walk
+// and the conversion of a fixed-width value (text_convert).  The count, starts and record-walk kernels are each format's own; the
+// string copy is one kernel for both (kernels_tbl.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,10 +70,89 @@ struct TextLdsReader {
     __device__ uint8_t operator()(int64_t pos) const { return buf[pos - origin]; }
 };
 
-// days_from_civil: cast_text.h (the host folds date literals with the same function)
+// starts passes: inclusive Hillis-Steele scan of the per-thread counts `c` in s_scan[BLOCK]; returns the count of the threads before
+// this one.  Every thread of the workgroup calls it.
+__device__ inline uint32_t block_rank_base(uint32_t c, uint32_t* s_scan, int tid) {
+    s_scan[tid] = c;
+    __syncthreads();
+    for (int d = 1; d < BLOCK; d <<= 1) {
+        const uint32_t v = tid >= d ? s_scan[tid - d] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    return s_scan[tid] - c;
+}
 
-static __constant__ double TEXT_POW10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
-                                             1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+// the value [a, b) of a fixed-width column -> row i of `data`; returns the TBL_ERR_* bits.  The grammar of both scans:
+//   Int32 / Int64   [-]digits
+//   Float64         [-]digits[.digits]  =  M / 10^k with M < 2^53 and k <= 22: both exact in double, so the one
+//                   division is the correctly rounded value of the decimal text (what str::parse::<f64> returns)
+//   Date32          YYYY-MM-DD -> days since 1970-01-01 (proleptic Gregorian; days_from_civil is cast_text.h's, the host folds
+//                   date literals with it)
+// A '+' is read like no sign.  An empty value is TBL_ERR_BAD_VALUE.  A value is stored even when a flag is raised: 0 days, +-0.0
+// or the wrapped integer.
+template <class R>
+__device__ inline uint32_t text_convert(const R& rd, int64_t a, int64_t b, int dt, void* data, int64_t i) {
+    uint32_t err = 0;
+    if (dt == DT_DATE32) {
+        bool ok = (b - a) == 10 && rd(a + 4) == '-' && rd(a + 7) == '-';
+        int v[8];
+        const int pos[8] = {0, 1, 2, 3, 5, 6, 8, 9};
+        for (int k = 0; k < 8 && ok; ++k) {
+            const int c = (int)rd(a + pos[k]) - '0';
+            ok = c >= 0 && c <= 9;
+            v[k] = c;
+        }
+        int32_t days = 0;
+        if (ok) {
+            const int y = v[0] * 1000 + v[1] * 100 + v[2] * 10 + v[3], m = v[4] * 10 + v[5], d = v[6] * 10 + v[7];
+            ok = m >= 1 && m <= 12 && d >= 1 && d <= 31;
+            days = (int32_t)days_from_civil(y, (unsigned)m, (unsigned)d);
+        }
+        if (!ok) err |= TBL_ERR_BAD_VALUE;
+        reinterpret_cast<int32_t*>(data)[i] = days;
+        return err;
+    }
+    int64_t r = a;
+    bool neg = false;
+    if (r < b && (rd(r) == '-' || rd(r) == '+')) { neg = rd(r) == '-'; ++r; }
+    uint64_t m = 0;
+    int digits = 0, frac = 0;
+    bool seen_dot = false, ok = r < b;
+    for (; r < b; ++r) {
+        const uint8_t ch = rd(r);
+        if (ch >= '0' && ch <= '9') {
+            if (digits >= 19) {                                  // 19 digits still fit 64 bits
+                if (dt == DT_FLOAT64) { err |= TBL_ERR_PRECISION; m = 0; frac = 0; r = b; break; }
+                ok = false;
+                break;
+            }
+            m = m * 10 + (uint64_t)(ch - '0');
+            if (m != 0 || seen_dot) ++digits;             // leading zeros of the integer part are free
+            if (seen_dot) ++frac;
+        } else if (ch == '.' && !seen_dot && dt == DT_FLOAT64) {
+            seen_dot = true;
+        } else { ok = false; break; }
+    }
+    if (dt == DT_FLOAT64) {
+        if (!ok) err |= TBL_ERR_BAD_VALUE;
+        else if (m >= (1ull << 53) || frac > 22) { err |= TBL_ERR_PRECISION; ok = false; }
+        const double v = ok ? (double)m / cast_pow10(frac) : 0.0;
+        reinterpret_cast<double*>(data)[i] = neg ? -v : v;
+    } else {
+        if (!ok || seen_dot) err |= TBL_ERR_BAD_VALUE;
+        if (m > (neg ? (1ull << 63) : (1ull << 63) - 1ull)) err |= TBL_ERR_BAD_VALUE;      // beyond Int64
+        const int64_t v = neg ? (int64_t)(0ull - m) : (int64_t)m;
+        if (dt == DT_INT32) {
+            if (v > 2147483647ll || v < -2147483648ll) err |= TBL_ERR_BAD_VALUE;
+            reinterpret_cast<int32_t*>(data)[i] = (int32_t)v;
+        } else {
+            reinterpret_cast<int64_t*>(data)[i] = v;
+        }
+    }
+    return err;
+}
 
 // workgroups of a pass with one thread per row
 static inline int grid_rows(const LaunchCfg& cfg, int64_t n) {

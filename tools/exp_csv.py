@@ -100,7 +100,8 @@ def kernel_times(out, label, fmt, env=None):
     for f in sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True))[-1:]:
         for r in csv.DictReader(open(f)):
             name = r["Name"].split("(")[0].replace("bhip::", "").replace("void ", "")
-            if name.startswith(("tbl_", "csv_")):
+            name = name.replace("tbl_copy_strings", "text_copy_strings").replace("csv_copy_strings", "text_copy_strings")  # a checkout with two copy kernels
+            if name.startswith(("tbl_", "csv_", "text_")):
                 out[name] = float(r["AverageNs"]) / 1e6
     return out
 
@@ -128,7 +129,7 @@ def main():
     sa, sb, sc = (sum(med(p, n) for n in names(p)) for p in ("a", "b", "c"))
     print(f"b / a = {sb / sa:.3f} ({sb - sa:+.3f} ms against a spread of {spread:.3f} ms);  c / a = {sc / sa:.3f}")
     for ta, tb in (("tbl_count_kernel", "csv_count_kernel"), ("tbl_starts_kernel", "tbl_starts_kernel"), ("tbl_parse_kernel", "csv_parse_kernel<false>"),
-                   ("tbl_copy_strings_kernel", "csv_copy_strings_kernel")):
+                   ("text_copy_strings_kernel", "text_copy_strings_kernel")):
         print(f"  pass {ta:24s} a {med('a', ta):.3f} ms   b {tb:24s} {med('b', tb):.3f} ms")
     for fmt in "abc" if other else "":                   # the yardstick is the other checkout's own spread, measured in this run
         sums = [sum(runs[f"{fmt}{k}"].values()) for k in range(3)]

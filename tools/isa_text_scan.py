@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """ISA comparison of the text scan kernels (kernels_tbl.hip, kernels_csv.hip) between this checkout and another one (e.g. the
 parent commit), CPU only: compiles both files of both trees for gfx950 with the Makefile's flags (--cuda-device-only -S) and
-prints, per kernel, "identical" when the instruction streams are equal line for line (comments dropped, the names of the POW10
-table and of the byte readers normalised) and the resources are the same, or the resources of both sides and the number of instruction lines that differ.
+prints, per kernel, "identical" when the instruction streams are equal line for line (comments dropped, the names of the power-of-ten
+table, of the byte readers, of the plan type and of the string-copy kernel normalised: another checkout may still have TEXT_POW10,
+TblPlan / CsvPlan and csv_copy_strings_kernel) and the resources are the same, or the resources of both sides and the number of instruction lines that differ.
 
     python tools/isa_text_scan.py OTHER_TREE [--keep DIR]
 
@@ -31,7 +32,9 @@ def compile_tree(tree, tmp, tag):
         asm = os.path.join(tmp, f"{tag}_{f}.s")
         subprocess.run([HIPCC] + FLAGS + [os.path.join(tree, "ballista_amd", "csrc", f), "-o", asm], check=True)
         text = open(asm).read()
-        text = re.sub(r"\b_ZN4bhip\w*POW10E\b", "POW10", text)
+        text = re.sub(r"(?:__const\.)?_ZN4bhip\w*(?:POW10E|pow10Ei\.t)\b", "POW10", text)
+        text = re.sub(r"7(?:Tbl|Csv)Plan", "8TextPlan", text)                            # the plan type inside mangled kernel names
+        text = text.replace("23csv_copy_strings_kernel", "24text_copy_strings_kernel")  # the one copy kernel was CSV's
         text = re.sub(r"\d+(Tbl|Csv|Text)(Global|Lds)Reader", r"\2Reader", text)       # the readers' names inside mangled symbols
         bodies, cur = {}, None
         for line in text.splitlines():
