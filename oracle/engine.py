@@ -575,31 +575,48 @@ def hash_join(left, right, on, join_type="Inner"):
     return out
 
 
+def _order_key(c: OCol):
+    """an integer array whose ascending order is the order of the column's values (NULL rows: any value).
+    Floats: IEEE-754 totalOrder, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, NaNs by magnitude bits (DESIGN.md "Sort order of
+    floating-point keys"), written from sign and magnitude: a clear sign orders by magnitude, a set sign by falling magnitude
+    below every clear one.  Utf8: dense ranks of the byte strings."""
+    v = c.values
+    if c.dtype == "Utf8":
+        enc = np.empty(len(v), dtype=object)
+        enc[:] = [s.encode() for s in v]
+        if len(enc) == 0:
+            return np.zeros(0, np.int64)
+        return np.unique(enc, return_inverse=True)[1].astype(np.int64).reshape(-1)
+    if c.dtype in FLOAT_TYPES:
+        wide = c.dtype == "Float64"
+        bits = np.ascontiguousarray(v).view(np.uint64 if wide else np.uint32)
+        mag = (bits & (bits.dtype.type(0x7FFFFFFFFFFFFFFF if wide else 0x7FFFFFFF))).astype(np.int64)
+        negative = (bits >> bits.dtype.type(63 if wide else 31)).astype(np.bool_)
+        return np.where(negative, -mag - 1, mag)
+    if c.dtype == "Boolean":
+        return v.astype(np.int64)
+    if c.dtype == "UInt64":
+        return v
+    return v.astype(np.int64)
+
+
 def sort_batch(batch, sort_exprs):
-    """SortExec (from_proto.rs:291-331): lexicographic, per key descending / nulls_first.
-    Stable here; the reference leaves tie order unspecified."""
+    """SortExec (from_proto.rs:291-331): lexicographic, per key descending / nulls_first; ties keep input order (the reference
+    leaves tie order unspecified: stability is this project's choice, and the device sorts the same way).
+    Every sort key gives a NULL-rank column and a value column of integers (_order_key; descending = the complement, which is
+    exact at INT64_MIN and for UInt64; NULL rows share one value); one stable lexsort over all of them is the order."""
     n = batch_len(batch)
-    order = np.arange(n)
-    for se in reversed(list(sort_exprs)):
+    cols = []                                   # most significant first
+    for se in sort_exprs:
         c = evaluate(se.expr, batch)
-        vals = c.values[order]
-        ok = c.is_valid()[order]
-        if c.dtype == "Utf8":
-            keys = np.array([s.encode() for s in vals], dtype=object)
-        else:
-            keys = vals
-        idx = np.argsort(keys[ok] if True else keys, kind="stable")
-        valid_pos = np.nonzero(ok)[0][idx]
+        key = _order_key(c)
         if se.descending:
-            # stable descending: reverse groups of equal keys, not the rows inside them
-            kv = keys[valid_pos]
-            if len(kv):
-                change = np.nonzero(np.array([kv[i] != kv[i - 1] for i in range(1, len(kv))], dtype=bool))[0] + 1
-                groups = np.split(valid_pos, change)
-                valid_pos = np.concatenate(groups[::-1]) if groups else valid_pos
-        null_pos = np.nonzero(~ok)[0]
-        new = np.concatenate([null_pos, valid_pos]) if se.nulls_first else np.concatenate([valid_pos, null_pos])
-        order = order[new.astype(np.int64)]
+            key = ~key
+        if c.valid is not None:
+            key = np.where(c.valid, key, key.dtype.type(0))
+            cols.append(np.where(c.valid, 1, 0).astype(np.int8) if se.nulls_first else np.where(c.valid, 0, 1).astype(np.int8))
+        cols.append(key)
+    order = np.lexsort(tuple(reversed(cols))) if cols and n else np.arange(n)
     return OrderedDict((k, c.take(order)) for k, c in batch.items())
 
 

@@ -12,7 +12,7 @@ from collections import OrderedDict
 import numpy as np
 
 import ballista_amd as ba
-from oracle.engine import OCol
+from oracle.engine import OCol, batch_len
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,6 +122,28 @@ def assert_rows_equal(got, want, ordered=False, float_rtol=0.0, key_cols=None, z
                     f"row {ri} col {names[ci]}: {x!r} vs {y!r} (bit exact expected)"
             else:
                 assert x == y, f"row {ri} col {names[ci]}: {x!r} vs {y!r}"
+
+
+def assert_bit_exact(got, want):
+    """two oracle-style batches are the same rows in the same order, bit for bit: validity, and under it the values compared as
+    unsigned integers of their width — a NaN's payload and a zero's sign count (assert_rows_equal lets any NaN match any NaN).
+    numpy only for fixed-width columns, so it serves at millions of rows."""
+    if not want or batch_len(want) == 0:
+        assert not got or batch_len(got) == 0
+        return
+    assert_same_schema(got, want)
+    for name in want:
+        g, w = got[name], want[name]
+        assert len(g) == len(w), (name, len(g), len(w))
+        gv, wv = g.is_valid(), w.is_valid()
+        assert np.array_equal(gv, wv), f"{name}: validity differs at {np.nonzero(gv != wv)[0][:5]}"
+        if w.dtype == "Utf8":
+            a, b = list(g.values[wv]), list(w.values[wv])
+        else:
+            bits = {8: np.uint64, 4: np.uint32, 2: np.uint16, 1: np.uint8}[w.values.dtype.itemsize]
+            a, b = np.ascontiguousarray(g.values[wv]).view(bits), np.ascontiguousarray(w.values[wv]).view(bits)
+        bad = [i for i, (x, y) in enumerate(zip(a, b)) if x != y][:5] if w.dtype == "Utf8" else np.nonzero(a != b)[0][:5]
+        assert len(bad) == 0, f"{name}: rows {list(bad)} differ: {[a[i] for i in bad]} vs {[b[i] for i in bad]}"
 
 
 # ---- the reference's .tbl fixtures (rust/scheduler/testdata/*, copied as data under tests/golden/tbl)

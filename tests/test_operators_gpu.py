@@ -438,7 +438,7 @@ def test_sort_few_rows_edge_values(ctx):
     """strings that are prefixes of each other with trailing NUL bytes, empty strings, NaN / infinities"""
     from collections import OrderedDict
     svals = ["ab", "ab\0", "a", "", "ab\0c", "abc", "a\0", "b", "", "ab"]
-    fvals = np.array([0.0, 2.5, np.nan, np.inf, -np.inf, 1.5, -1.5, 2.5, 0.0, -3.0])     # (one NaN, no -0.0: their tie order is unspecified)
+    fvals = np.array([0.0, 2.5, np.nan, np.inf, -np.inf, 1.5, -1.5, 2.5, 0.0, -3.0])     # (one NaN, no -0.0: test_sort_edges_gpu.py has signed NaNs and both zeros)
     b = OrderedDict([("s", OCol("Utf8", svals, np.array([1, 1, 1, 1, 1, 1, 1, 0, 1, 1], bool))), ("f", OCol("Float64", fvals)),
                      ("i", OCol("Int64", np.arange(10)))])
     m = helpers.memory_exec(ctx, [[b]])
@@ -454,7 +454,7 @@ def test_sort_mid_size(ctx, n):
     input position — the same stable order as the oracle's sort"""
     from collections import OrderedDict
     rng = np.random.default_rng(n)
-    b = OrderedDict([("f", OCol("Float64", np.round(rng.normal(0, 1000, n), 1) + 0.0, rng.random(n) > 0.05)),     # (+ 0.0: no -0.0, whose tie with 0.0 is unspecified)
+    b = OrderedDict([("f", OCol("Float64", np.round(rng.normal(0, 1000, n), 1) + 0.0, rng.random(n) > 0.05)),     # (+ 0.0: no -0.0 here; it sorts before 0.0, test_sort_edges_gpu.py)
                      ("d", OCol("Date32", rng.integers(8000, 10400, n))), ("i", OCol("Int64", rng.integers(-2**40, 2**40, n))),
                      ("s", OCol("Utf8", [f"k{v % 97}" for v in range(n)]))])
     m = helpers.memory_exec(ctx, [[b]])

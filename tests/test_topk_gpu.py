@@ -2,11 +2,10 @@
 first k rows of the stable sort — same rows, same order, same tie order, one batch — and Context.sort_limit_form() tells which
 route ran ("topk", "topk_fallback", "sort").
 
-Expected values come from oracle/plan_eval.py on the same plan.  Two kinds of case compare instead with a plain SortExec plan
-collected on the GPU and cut to k in numpy (the route every limit over a sort took before the selection existed, never the
-selection itself): Float64 keys with NaNs and signed zeros, whose place the oracle's numpy sort does not define, and the
-2^20-row shapes, where the oracle's descending sort walks the rows in Python.  Every comparison is bit exact: row order, every
-column, validity."""
+Expected values come from oracle/plan_eval.py on the same plan; its sort orders Float64 keys by the same total order as the device
+(NaNs by sign and payload, -0.0 before +0.0: DESIGN.md "Sort order of floating-point keys").  The 2^20-row cases cut a plain
+SortExec plan's output to k in numpy, so that the three of them share one sort per key list; that output is itself checked against
+the oracle before it is used.  Every comparison is bit exact: row order, every column, validity."""
 from collections import OrderedDict
 
 import numpy as np
@@ -32,23 +31,7 @@ def S(name, desc=False, nulls_first=True):
     return E.PhysicalSortExpr(col(name), descending=desc, nulls_first=nulls_first)
 
 
-def assert_bit_exact(got, want):
-    if not want or og.batch_len(want) == 0:
-        assert not got or og.batch_len(got) == 0
-        return
-    helpers.assert_same_schema(got, want)
-    for name in want:
-        g, w = got[name], want[name]
-        assert len(g) == len(w), (name, len(g), len(w))
-        gv, wv = g.is_valid(), w.is_valid()
-        assert np.array_equal(gv, wv), f"{name}: validity differs at {np.nonzero(gv != wv)[0][:5]}"
-        if w.dtype == "Utf8":
-            a, b = list(g.values[wv]), list(w.values[wv])
-        else:
-            bits = {8: np.uint64, 4: np.uint32, 2: np.uint16, 1: np.uint8}[w.values.dtype.itemsize]
-            a, b = np.ascontiguousarray(g.values[wv]).view(bits), np.ascontiguousarray(w.values[wv]).view(bits)
-        bad = [i for i, (x, y) in enumerate(zip(a, b)) if x != y][:5] if w.dtype == "Utf8" else np.nonzero(a != b)[0][:5]
-        assert len(bad) == 0, f"{name}: rows {list(bad)} differ: {[a[i] for i in bad]} vs {[b[i] for i in bad]}"
+assert_bit_exact = helpers.assert_bit_exact
 
 
 def head(batch, k):
@@ -70,7 +53,7 @@ def run_limit(ctx, limit_plan, form, want):
     return got
 
 
-def check(ctx, batches, keys, k, form, reference="oracle", limit=ba.GlobalLimitExec, coalesce=None):
+def check(ctx, batches, keys, k, form, limit=ba.GlobalLimitExec, coalesce=None):
     m = helpers.memory_exec(ctx, [batches])
     if coalesce == "below":
         m2 = ba.CoalesceBatchesExec(m, 2048)
@@ -80,8 +63,7 @@ def check(ctx, batches, keys, k, form, reference="oracle", limit=ba.GlobalLimitE
         srt = ba.SortExec(keys, m)
     node = ba.CoalesceBatchesExec(srt, 4096) if coalesce == "above" else srt
     plan = limit(node, k)
-    want = plan_eval.collect(plan) if reference == "oracle" else head(gpu_sorted(srt), k)
-    return run_limit(ctx, plan, form, want)
+    return run_limit(ctx, plan, form, plan_eval.collect(plan))
 
 
 # ---- tails: the smallest selectable batch, one past 64 Ki, one past 1 Mi --------------------------------------------------------
@@ -96,14 +78,17 @@ def tail_batch(n):
 
 @pytest.fixture(scope="module")
 def big(ctx):
-    """the 2^20 + 37 rows shared by the big cases: the device MemoryExec and, per key list, the plain sort's output"""
+    """the 2^20 + 37 rows shared by the big cases: the device MemoryExec and, per key list, the plain sort's output (checked
+    against the oracle's sort of the same plan when it is first made)"""
     b = tail_batch(BIG)
     m = helpers.memory_exec(ctx, [[b]])
     cache = {}
 
     def sorted_by(keys, tag):
         if tag not in cache:
-            cache[tag] = gpu_sorted(ba.SortExec(keys, m))
+            srt = ba.SortExec(keys, m)
+            cache[tag] = gpu_sorted(srt)
+            assert_bit_exact(cache[tag], plan_eval.collect(srt))
         return cache[tag]
     return m, sorted_by
 
@@ -168,7 +153,7 @@ def test_first_key_types(ctx, kind, desc):
     keys = [S("key", desc=desc), S("t", desc=True)]
     ks = [37, 1200] if kind == "Utf8" else [37]       # Utf8 ascending, k = 1200: the threshold falls among the values that share 8 bytes
     for k in ks:
-        check(ctx, [b], keys, k, "topk", reference="gpu_sort" if kind == "Float64" else "oracle")
+        check(ctx, [b], keys, k, "topk")
 
 
 # ---- nullable first key -----------------------------------------------------------------------------------------------------
