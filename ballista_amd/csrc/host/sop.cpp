@@ -33,7 +33,8 @@ struct Builder {
 
     // ---- predicate: AND of  column <op> literal  over Float64 / Int32 / Date32 columns, folded into one
     // [lo, hi] range per column.  Strict bounds move to the neighbouring representable value, which is
-    // exact: x < L  <=>  x <= pred(L) for doubles (NaN fails both), x <= L - 1 for integers.
+    // exact: x < L  <=>  x <= pred(L) for doubles (NaN fails both), x <= L - 1 for integers (kept as doubles, so
+    // INT32_MIN - 1 and INT32_MAX + 1 are exact and simply match no Int32 value).
     bool predicate(const ExprPtr& e) {
         if (e->kind == BHIP_EXPR_BINARY && e->name == "And") return predicate(e->args[0]) && predicate(e->args[1]);
         if (e->kind != BHIP_EXPR_BINARY) return false;
@@ -64,6 +65,9 @@ struct Builder {
             case 3: lo = is_int ? lit + 1.0 : std::nextafter(lit, inf); break;      // x >  L
             default: lo = lit; break;                                               // x >= L
         }
+        // x < -inf and x > +inf hold for no x, but -inf and +inf have no neighbour beyond them (nextafter returns them
+        // unchanged, which would keep the rows equal to them): an empty range, which build_sop leaves to the VM
+        if (!is_int && ((k == 1 && lit == -inf) || (k == 3 && lit == inf))) { lo = inf; hi = -inf; }
         const int c = column(ci);
         if (c < 0) return false;
         for (int i = 0; i < out.prog.n_ranges; ++i)

@@ -14,6 +14,7 @@ import ballista_amd as ba
 from ballista_amd import expr as E
 from ballista_amd.expr import col, lit
 from oracle import engine as og
+from oracle import plan_eval
 from oracle.engine import OCol
 
 import helpers
@@ -257,3 +258,44 @@ def test_full_semi_and_anti_still_need_one_right_partition(ctx):
     for jt in (JT.FULL, JT.SEMI, JT.ANTI):
         with pytest.raises(ba.NotImplementedOnGpu, match="MergeExec"):
             ba.HashJoinExec(build_exec(ctx, left), probe_exec(ctx, right, 2), on, jt, filter=flt)
+
+
+# ---- 9. the probe's fused range filter at the Int32 extremes -----------------------------------------------------------------------------------
+
+I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+@pytest.mark.parametrize("jt", [JF.INNER, JF.RIGHT])
+@pytest.mark.parametrize("name,pred", [
+    ("gt_max", col("ry") > lit(I32_MAX, E.INT32)), ("lt_min", col("ry") < lit(I32_MIN, E.INT32)),
+    ("ge_min", col("ry") >= lit(I32_MIN, E.INT32)), ("le_max", col("ry") <= lit(I32_MAX, E.INT32)),
+    ("eq_max", col("ry").eq(lit(I32_MAX, E.INT32))), ("max_lt", lit(I32_MAX, E.INT32) < col("ry")),
+    ("min_ge", lit(I32_MIN, E.INT32) >= col("ry")),
+])
+def test_probe_side_int32_predicates_at_the_extremes(ctx, name, pred, jt):
+    """a FilterExec over the probe side of a join on a unique Int32 key runs inside the probe kernel as integer ranges
+    (ops_join.cpp::int_ranges_of, the integer image of build_sop's double ranges).  Bounds one past either end of Int32 select
+    nothing, bounds AT the ends select everything; probe rows at both extremes, on keys with and without a build row"""
+    rng = np.random.default_rng(11)
+    nl, nr = 200, 1025 + 70
+    left = OrderedDict([("lk", OCol("Int32", rng.permutation(400)[:nl].astype(np.int32))), ("lx", OCol("Float64", rng.random(nl)))])
+    ry = rng.integers(-5, 5, nr).astype(np.int64)
+    ry[rng.random(nr) < 0.25] = I32_MAX
+    ry[rng.random(nr) < 0.25] = I32_MIN
+    ry[[0, 1, 63, 64, 1023, 1024, nr - 1]] = [I32_MAX, I32_MIN, I32_MAX, I32_MIN, I32_MIN, I32_MAX, I32_MAX]
+    rk = rng.integers(0, 400, nr).astype(np.int32)
+    rk[[0, 1, 63, 64, 1023, 1024, nr - 1]] = left["lk"].values[:7]              # the rows at the extremes have partners
+    right = OrderedDict([("rk", OCol("Int32", rk)), ("ry", OCol("Int32", ry.astype(np.int32))), ("ri", OCol("Int32", np.arange(nr, dtype=np.int32)))])
+    flt = ba.FilterExec(pred, helpers.memory_exec(ctx, [[helpers.slice_batch(right, 0, 1025), helpers.slice_batch(right, 1025, nr)]]))
+    plan = ba.HashJoinExec(helpers.memory_exec(ctx, [[left]]), flt, [("lk", "rk")], jt)
+    got = helpers.concat(helpers.collect_product(plan))
+    want = plan_eval.collect(plan)
+    helpers.assert_rows_equal(got, want, ordered=False, key_cols=["ri", "lk"])
+    assert ctx.join_key_form() == "narrow"
+    n_rows = len(helpers.rows_of(got))
+    if name in ("gt_max", "lt_min", "max_lt"):
+        assert n_rows == 0
+    elif name in ("ge_min", "le_max"):
+        assert n_rows == (nr if jt == JF.RIGHT else int(np.isin(rk, left["lk"].values).sum()))
+    else:
+        assert 0 < n_rows < nr

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/ab_switch_check.txt
 : > $O
 J="tests/test_join_paths_gpu.py tests/test_goldens.py tests/test_operators_gpu.py tests/test_q12_gpu.py"
-A="tests/test_operators_gpu.py tests/test_goldens.py tests/test_q1_q6_gpu.py tests/test_lean_gpu.py tests/test_types_gpu.py tests/test_strings_gpu.py"
+A="tests/test_operators_gpu.py tests/test_goldens.py tests/test_q1_q6_gpu.py tests/test_lean_gpu.py tests/test_fastpath_edges_gpu.py tests/test_types_gpu.py tests/test_strings_gpu.py"
 run() { # name=value, test list
   local out; out=$(env "$1" python -m pytest $2 -m gpu -q 2>&1 | tail -1); echo "$1 : $out" | tee -a $O
 }
