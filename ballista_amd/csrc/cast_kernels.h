@@ -26,4 +26,8 @@ hipError_t launch_to_timestamp_parse(const LaunchCfg& cfg, const ColumnRef& c, i
 // 64-bit words: NULL where the argument is, or where the floor does not fit int64 in the unit.  granularity: TruncGranularity.
 hipError_t launch_date_trunc(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int granularity, int64_t* out, uint64_t* validity);
 
+// date_part(part, <Date32 / Date64 / Timestamp column>): n Int32 values at `out` and n validity bits, written as whole 64-bit words:
+// NULL where the argument is, or where the field does not fit Int32.  part: DatePart (temporal_text.h).
+hipError_t launch_date_part(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int part, int32_t* out, uint64_t* validity);
+
 }  // namespace bhip

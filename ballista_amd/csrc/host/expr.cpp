@@ -3,6 +3,7 @@
 
 #include "../cast_text.h"
 #include "../str_kernels.h"
+#include "../str_text.h"
 #include "../temporal_text.h"
 
 #include <algorithm>
@@ -60,7 +61,26 @@ int sha_fn(const std::string& name) {
     return name == "sha224" ? 224 : name == "sha256" ? 256 : name == "sha384" ? 384 : name == "sha512" ? 512 : 0;
 }
 
-void check_scalar_function(const std::string& name, int n_args) {
+int str_range_fn(const std::string& name) { return name == "substr" ? STR_SUBSTR : name == "left" ? STR_LEFT : name == "right" ? STR_RIGHT : -1; }
+bool str_typed_fn(const std::string& name) { return name == "char_length" || name == "strpos" || name == "starts_with"; }
+
+// substring -> substr; length, character_length -> char_length: one name per function from here on
+static std::string canonical_fn(const std::string& name) {
+    if (name == "substring") return "substr";
+    if (name == "length" || name == "character_length") return "char_length";
+    return name;
+}
+
+void check_scalar_function(const std::string& alias, int n_args) {
+    const std::string name = canonical_fn(alias);
+    if (name == "substr") {
+        if (n_args != 2 && n_args != 3) fail(BHIP_EINVAL, "scalar function 'substr' takes two or three arguments");
+        return;
+    }
+    if (str_range_fn(name) >= 0 || name == "strpos" || name == "starts_with" || name == "date_part") {
+        if (n_args != 2) fail(BHIP_EINVAL, "scalar function '" + name + "' takes two arguments");
+        return;
+    }
     if (name == "concat") {
         if (n_args < 1) fail(BHIP_EINVAL, "concat takes at least one argument");
         if (n_args > STR_CONCAT_MAX) fail(BHIP_ENOTIMPL, "concat with more than 8 arguments");
@@ -70,7 +90,7 @@ void check_scalar_function(const std::string& name, int n_args) {
         if (n_args != 2) fail(BHIP_EINVAL, "scalar function '" + name + "' takes two arguments");
         return;
     }
-    if (math_fn(name) < 0 && str_fn(name) < 0 && sha_fn(name) == 0 && name != "octet_length" && name != "to_timestamp")
+    if (math_fn(name) < 0 && str_fn(name) < 0 && sha_fn(name) == 0 && name != "octet_length" && name != "to_timestamp" && name != "char_length")
         fail(BHIP_ENOTIMPL, "scalar function '" + name + "' is not supported");
     if (n_args != 1) fail(BHIP_EINVAL, "scalar function takes one argument");
 }
@@ -114,7 +134,80 @@ ExprPtr fold_temporal_literal(const ExprPtr& e, const Schema& schema) {
         const bool ok = !x->is_null && temporal_trunc(x->dtype, gran, x->i64, v);
         return make_literal(x->dtype, !ok, v);
     }
+    if (e->name == "date_part") {
+        ExprPtr x = e->args[1];
+        if (x->kind != BHIP_EXPR_LITERAL) x = fold_temporal_literal(x, schema);
+        if (!x) return nullptr;
+        const int part = date_part_of(*e, schema);
+        int32_t v = 0;
+        const bool ok = !x->is_null && temporal_part(x->dtype, part, x->i64, v);
+        return make_literal(DT_INT32, !ok, v);
+    }
     return nullptr;
+}
+
+int date_part_of(const Expr& e, const Schema& schema) {
+    const Expr& p = *e.args[0];
+    if (p.kind != BHIP_EXPR_LITERAL || p.dtype != DT_UTF8 || p.is_null)
+        fail(BHIP_ENOTIMPL, "date_part part must be a non-NULL Utf8 literal: " + e.to_string());
+    const int part = date_part_name(p.name.data(), (int64_t)p.name.size());
+    if (part < 0) fail(BHIP_EINVAL, "Unsupported date_part part '" + p.name + "'");
+    const int t = expr_type(e.args[1], schema);
+    if (temporal_units_per_day(t) == 0) fail(BHIP_EINVAL, std::string("date_part requires a Date32, Date64 or Timestamp argument, not ") + dtype_name(t));
+    return part;
+}
+
+void check_string_fn(const Expr& e, const Schema& schema) {
+    const int t0 = expr_type(e.args[0], schema);
+    if (t0 != DT_UTF8) fail(BHIP_EINVAL, e.name + " requires a Utf8 first argument, not " + dtype_name(t0));
+    if (str_range_fn(e.name) >= 0) {
+        for (size_t k = 1; k < e.args.size(); ++k) {
+            const int t = expr_type(e.args[k], schema);
+            if (t != DT_INT64) fail(BHIP_EINVAL, e.name + " requires Int64 arguments after the first, not " + dtype_name(t));
+        }
+        if (e.args.size() == 3 && e.args[2]->kind == BHIP_EXPR_LITERAL && !e.args[2]->is_null && e.args[2]->i64 < 0)
+            fail(BHIP_EINVAL, "negative substring length not allowed: " + e.to_string());
+    } else if (e.args.size() == 2) {
+        const int t = expr_type(e.args[1], schema);
+        if (t != DT_UTF8) fail(BHIP_EINVAL, e.name + " requires Utf8 arguments, not " + dtype_name(t));
+        if (e.args[1]->kind == BHIP_EXPR_LITERAL && e.args[1]->name.size() > (size_t)STR_LITERAL_MAX)
+            fail(BHIP_ENOTIMPL, e.name + " with a literal longer than 240 bytes");
+    }
+}
+
+static ExprPtr make_utf8_literal(const std::string& text) {
+    auto l = std::make_shared<Expr>();
+    l->kind = BHIP_EXPR_LITERAL;
+    l->dtype = DT_UTF8;
+    l->name = text;
+    return l;
+}
+
+ExprPtr fold_string_literal(const ExprPtr& e, const Schema& schema) {
+    if (e->kind != BHIP_EXPR_SCALAR_FN || (str_range_fn(e->name) < 0 && !str_typed_fn(e->name))) return nullptr;
+    check_string_fn(*e, schema);
+    bool all_literals = true, any_null = false;
+    for (auto& a : e->args) {
+        all_literals = all_literals && a->kind == BHIP_EXPR_LITERAL;
+        any_null = any_null || (a->kind == BHIP_EXPR_LITERAL && a->is_null);
+    }
+    const int rt = expr_type(e, schema);
+    if (any_null) return make_literal(rt, true, 0);     // a NULL in any argument gives NULL, whatever the other arguments hold
+    if (!all_literals) return nullptr;
+    const std::string& s = e->args[0]->name;
+    const CastPtrReader rd{reinterpret_cast<const uint8_t*>(s.data())};
+    const int64_t end = (int64_t)s.size();
+    const int fn = str_range_fn(e->name);
+    if (fn >= 0) {
+        int64_t b = 0, q = 0;
+        str_range(fn, rd, 0, end, e->args[1]->i64, e->args.size() == 3, e->args.size() == 3 ? e->args[2]->i64 : 0, b, q);      // (count < 0: refused above)
+        return make_utf8_literal(s.substr((size_t)b, (size_t)(q - b)));
+    }
+    if (e->name == "char_length") return make_literal(DT_INT32, false, str_char_count(rd, 0, end));
+    const std::string& sub = e->args[1]->name;
+    const CastPtrReader sr{reinterpret_cast<const uint8_t*>(sub.data())};
+    if (e->name == "strpos") return make_literal(DT_INT32, false, str_strpos(rd, 0, end, sr, 0, (int64_t)sub.size()));
+    return make_literal(DT_BOOLEAN, false, str_starts_with(rd, 0, end, sr, 0, (int64_t)sub.size()) ? 1 : 0);
 }
 
 ExprPtr make_column(const std::string& name) {
@@ -199,7 +292,7 @@ ExprPtr parse_expr(const bhip_expr& pe) {
             } break;
             case BHIP_EXPR_SCALAR_FN: {
                 check_scalar_function(n.name ? n.name : "", n.n_args);
-                e->name = n.name;
+                e->name = canonical_fn(n.name);
                 e->args.resize((size_t)n.n_args);
                 for (int k = n.n_args - 1; k >= 0; --k) e->args[(size_t)k] = pop();
             } break;
@@ -303,6 +396,9 @@ int expr_type(const ExprPtr& e, const Schema& schema) {
             if (e->name == "nullif") return expr_type(e->args[0], schema);
             if (e->name == "date_trunc") return expr_type(e->args[1], schema);
             if (e->name == "to_timestamp") return DT_TIMESTAMP_NS;
+            if (str_range_fn(e->name) >= 0) return DT_UTF8;
+            if (e->name == "char_length" || e->name == "strpos" || e->name == "date_part") return DT_INT32;
+            if (e->name == "starts_with") return DT_BOOLEAN;
             return (str_fn(e->name) >= 0 || sha_fn(e->name) || e->name == "concat") ? DT_UTF8 : (e->name == "octet_length" ? DT_INT32 : DT_FLOAT64);
         default: fail(BHIP_ENOTIMPL, "unsupported expression kind");
     }
@@ -320,7 +416,7 @@ bool expr_large(const ExprPtr& e, const Schema& schema) {
                     if (expr_large(a, schema)) return true;
                 return false;
             }
-            return str_fn(e->name) >= 0 && expr_large(e->args[0], schema);
+            return (str_fn(e->name) >= 0 || str_range_fn(e->name) >= 0) && expr_large(e->args[0], schema);
         case BHIP_EXPR_CASE: {
             size_t fw, np;
             case_layout(*e, fw, np);
@@ -445,6 +541,9 @@ ExprPtr coerce_expr(const ExprPtr& e, const Schema& schema) {
             auto c = std::make_shared<Expr>(*e);
             const bool math = math_fn(e->name) >= 0;        // Signature::Uniform(1, [Float64, Float32]): the first type the argument coerces to
             for (auto& a : c->args) a = math ? cast_to(coerce_expr(a, schema), DT_FLOAT64, schema) : coerce_expr(a, schema);
+            if (str_range_fn(e->name) >= 0)             // start, count, n: integers of any width, brought to Int64 like a side of a comparison
+                for (size_t k = 1; k < c->args.size(); ++k)
+                    if (numeric_rank(expr_type(c->args[k], schema)) && !dt_is_float(expr_type(c->args[k], schema))) c->args[k] = cast_to(c->args[k], DT_INT64, schema);
             if (e->name == "nullif" && c->args.size() == 2) {
                 // the two sides of `a = b`: one common type, which is the result's (a Utf8 `a` is refused when it is compiled)
                 const int ta = expr_type(c->args[0], schema), tb = expr_type(c->args[1], schema);
@@ -485,7 +584,8 @@ bool expr_nullable(const ExprPtr& e, const Schema& schema) {
         }
         case BHIP_EXPR_SCALAR_FN:
             // nullif makes NULLs of its own; a date_trunc floor may not fit int64.  (concat, to_timestamp: nullable iff an argument is)
-            if (e->name == "nullif" || e->name == "date_trunc") return true;
+            // a date_part field may not fit Int32
+            if (e->name == "nullif" || e->name == "date_trunc" || e->name == "date_part") return true;
             [[fallthrough]];
         case BHIP_EXPR_CASE:
             if (e->kind == BHIP_EXPR_CASE && !e->has_else) return true;
@@ -635,18 +735,8 @@ Operand ProgramBuilder::compile(const ExprPtr& e) {
 
 static int class_of(int dtype) { return dt_is_float(dtype) ? VC_F64 : (dtype == DT_BOOLEAN ? VC_BOOL : VC_I64); }
 
-// multiplier between two temporal types with a common epoch (Date32 days, Date64 ms, Timestamp s/ms/us/ns); 0 = no such cast
-static int64_t temporal_units_per_day(int t) {
-    switch (t) {
-        case DT_DATE32: return 1;
-        case DT_TIMESTAMP_S: return 86400ll;
-        case DT_DATE64:
-        case DT_TIMESTAMP_MS: return 86400000ll;
-        case DT_TIMESTAMP_US: return 86400000000ll;
-        case DT_TIMESTAMP_NS: return 86400000000000ll;
-        default: return 0;
-    }
-}
+// (temporal_units_per_day, temporal_text.h: the multiplier between two temporal types with a common epoch — Date32 days, Date64 ms,
+// Timestamp s/ms/us/ns; 0 = no such cast)
 
 // CAST (arrow's cast kernel, non-"safe=false": a value the target cannot hold becomes NULL)
 Operand ProgramBuilder::compile_cast(const Operand& x, int to) {
@@ -980,6 +1070,16 @@ Operand ProgramBuilder::compile_uncached(const ExprPtr& ep) {
                 if (const ExprPtr l = fold_temporal_literal(ep, schema_)) return compile(l);
                 fail(BHIP_ENOTIMPL, "expression " + e.name + "() outside the lowering (evaluated as a column, host/utf8_exprs.cpp)");
             }
+            if (e.name == "date_part") {
+                (void)date_part_of(e, schema_);
+                if (const ExprPtr l = fold_temporal_literal(ep, schema_)) return compile(l);
+                fail(BHIP_ENOTIMPL, "expression " + e.name + "() outside the lowering (evaluated as a column, host/utf8_exprs.cpp)");
+            }
+            if (str_typed_fn(e.name)) {
+                if (const ExprPtr l = fold_string_literal(ep, schema_)) return compile(l);
+                fail(BHIP_ENOTIMPL, "expression " + e.name + "() outside the lowering (evaluated as a column, host/utf8_exprs.cpp)");
+            }
+            if (str_range_fn(e.name) >= 0) fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e.name + "() (evaluated as a column, host/utf8_exprs.cpp)");
             if (str_fn(e.name) >= 0 || sha_fn(e.name) || e.name == "concat") fail(BHIP_ENOTIMPL, "expression producing Utf8 / Binary: " + e.name + "() (evaluated as a column, host/utf8_exprs.cpp)");
             if (expr_type(e.args[0], schema_) != DT_FLOAT64) fail(BHIP_EINVAL, e.name + " requires a Float64 argument");
             Operand a = materialize(compile(e.args[0]));

@@ -83,6 +83,17 @@ int date_trunc_granularity(const Expr& e, const Schema& schema);
 // to_timestamp / date_trunc over literals alone: the literal they fold to (by temporal_text.h, what the kernels run), else null.
 // A to_timestamp literal outside the grammar fails here with BHIP_EEXEC, as the same text in a column would when the query runs.
 ExprPtr fold_temporal_literal(const ExprPtr& e, const Schema& schema);
+// date_part('part', x): every plan-time check of the call (BHIP_ENOTIMPL for a part that is no literal, BHIP_EINVAL for an unknown one
+// or an `x` that is no Date32 / Date64 / Timestamp); returns the DatePart (temporal_text.h)
+int date_part_of(const Expr& e, const Schema& schema);
+// the code-point string functions (str_text.h): StrRangeFn of substr / left / right, -1 otherwise; char_length / strpos / starts_with
+int str_range_fn(const std::string& name);
+bool str_typed_fn(const std::string& name);
+// ... their plan-time checks (BHIP_EINVAL: an argument of the wrong type, a literal count < 0) ...
+void check_string_fn(const Expr& e, const Schema& schema);
+// ... and what a call folds to: a NULL literal when any argument is a NULL literal, the value (by str_text.h, what the kernels run)
+// when every argument is a literal, else null
+ExprPtr fold_string_literal(const ExprPtr& e, const Schema& schema);
 
 class ProgramBuilder {
 public:

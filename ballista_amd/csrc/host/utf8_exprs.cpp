@@ -12,10 +12,14 @@
 //
 // concat is one more string-producing node; to_timestamp (Utf8 -> Timestamp(Nanosecond)) and date_trunc (Timestamp -> Timestamp)
 // are lowered nodes of a fixed-width type, like CAST(<Utf8> AS T).  Over literals alone the two fold in the VM's compiler instead.
+//
+// substr / left / right are string-producing nodes too; char_length, strpos, starts_with and date_part are lowered nodes of type
+// Int32 / Boolean.  Their rules are str_text.h and temporal_text.h; a call over literals alone folds by the same functions.
 #include "../cast_kernels.h"
 #include "../cast_text.h"
 #include "../temporal_text.h"
 #include "../str_kernels.h"
+#include "../str_text.h"
 #include "../util_kernels.h"
 #include "plan.hpp"
 
@@ -32,20 +36,22 @@ static bool cast_from_utf8(const ExprPtr& e, const Schema& schema) {
     return !(x.kind == BHIP_EXPR_LITERAL && !x.is_null);
 }
 
-// to_timestamp(<Utf8 expression>) / date_trunc(g, <Timestamp expression>) that does not fold to a literal
-static bool temporal_fn(const ExprPtr& e, const Schema& schema) {
-    if (e->kind != BHIP_EXPR_SCALAR_FN || (e->name != "to_timestamp" && e->name != "date_trunc")) return false;
-    return fold_temporal_literal(e, schema) == nullptr;
+// to_timestamp(<Utf8 expression>) / date_trunc(g, <Timestamp expression>) / date_part(p, <temporal expression>) and
+// char_length / strpos / starts_with: a fixed-width result evaluated as a column, unless the call folds to a literal
+static bool typed_fn(const ExprPtr& e, const Schema& schema) {
+    if (e->kind != BHIP_EXPR_SCALAR_FN) return false;
+    if (e->name == "to_timestamp" || e->name == "date_trunc" || e->name == "date_part") return fold_temporal_literal(e, schema) == nullptr;
+    return str_typed_fn(e->name) && fold_string_literal(e, schema) == nullptr;
 }
 
 static bool produces_utf8(const ExprPtr& e, const Schema& schema) {
-    if (e->kind == BHIP_EXPR_SCALAR_FN) return str_fn(e->name) >= 0 || sha_fn(e->name) != 0 || e->name == "concat";
+    if (e->kind == BHIP_EXPR_SCALAR_FN) return str_fn(e->name) >= 0 || sha_fn(e->name) != 0 || e->name == "concat" || str_range_fn(e->name) >= 0;
     if (e->kind == BHIP_EXPR_CASE) return expr_type(e, schema) == DT_UTF8;
     return cast_to_utf8(e, schema);
 }
 
 bool has_lowered_node(const ExprPtr& e, const Schema& schema) {
-    if (produces_utf8(e, schema) || cast_from_utf8(e, schema) || temporal_fn(e, schema)) return true;
+    if (produces_utf8(e, schema) || cast_from_utf8(e, schema) || typed_fn(e, schema)) return true;
     for (auto& a : e->args)
         if (has_lowered_node(a, schema)) return true;
     return false;
@@ -57,7 +63,7 @@ Utf8Lowering::Utf8Lowering(const Schema& in) : in_(in) {}
 
 ExprPtr Utf8Lowering::rewrite(const ExprPtr& e, bool output) {
     const bool lit = output && e->kind == BHIP_EXPR_LITERAL && e->dtype == DT_UTF8;
-    if (lit || produces_utf8(e, in_) || cast_from_utf8(e, in_) || temporal_fn(e, in_)) {
+    if (lit || produces_utf8(e, in_) || cast_from_utf8(e, in_) || typed_fn(e, in_)) {
         const std::string text = e->to_string();
         for (size_t i = 0; i < nodes_.size(); ++i)
             if (nodes_[i]->to_string() == text) return make_column(names_[i]);
@@ -347,6 +353,117 @@ Column eval_date_trunc(const Exec& ex, const Batch& in, const Expr& e) {
     return out;
 }
 
+// an integer argument of substr / left / right: a literal travels in the struct, anything else is evaluated as an Int64 column
+// (kept alive in `keep`)
+StrIntArg int_argument(const Exec& ex, const Batch& in, const ExprPtr& a, std::vector<Column>& keep, bool& any_validity) {
+    StrIntArg r;
+    memset(&r, 0, sizeof(r));
+    if (a->kind == BHIP_EXPR_LITERAL) {
+        r.is_lit = 1;
+        r.lit = a->i64;
+        return r;
+    }
+    keep.push_back(materialize_column(ex, evaluate_column(ex, in, a)));
+    if (keep.back().dtype != DT_INT64) fail(BHIP_EINVAL, "expected an Int64 argument: " + a->to_string());
+    r.col = keep.back().ref();
+    any_validity = any_validity || (bool)keep.back().validity;
+    return r;
+}
+
+// substr(s, start[, count]) / left(s, n) / right(s, n): lengths -> scan -> bytes; the result is a byte range of the argument, so the
+// argument's byte count bounds it.  One status word says that a row asked for a negative count.
+Column eval_str_range(const Exec& ex, const Batch& in, const ExprPtr& ep) {
+    const Expr& e = *ep;
+    const int64_t n = in.n_rows;
+    if (const ExprPtr l = fold_string_literal(ep, *in.schema)) return eval_literal(ex, *l, n);       // (it checks the call as well)
+    const Column arg = eval_utf8(ex, in, e.args[0]);
+    std::vector<Column> ints;
+    bool any_validity = (bool)arg.validity;
+    StrRangeArgs A;
+    memset(&A, 0, sizeof(A));
+    A.fn = str_range_fn(e.name);
+    A.has_count = e.args.size() == 3 ? 1 : 0;
+    A.s = arg.ref();
+    A.a = int_argument(ex, in, e.args[1], ints, any_validity);
+    if (A.has_count) A.b = int_argument(ex, in, e.args[2], ints, any_validity);
+    Temp tmp(ex);
+    uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
+    uint32_t* status = tmp.get<uint32_t>(1);
+    HIP_CHECK(hipMemsetAsync(status, 0, 4, ex.stream));
+    BufferPtr validity = any_validity ? make_buffer(ex, bitmap_bytes(n) + 8) : nullptr;
+    TIMED_LAUNCH_N(ex, "str_range_lengths", n, launch_str_range_lengths(ex.cfg(), A, n, lengths, validity ? validity->as<uint64_t>() : nullptr, status));
+    uint64_t* total;
+    Column out = utf8_from_lengths(ex, tmp, lengths, n, &total);
+    out.data = make_buffer(ex, (size_t)arg.data_bytes + 8);
+    TIMED_LAUNCH_N(ex, "str_range_write", n, launch_str_range_write(ex.cfg(), A, n, out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
+    struct Back { uint64_t total; uint32_t status, pad; };
+    static_assert(sizeof(Back) == 16, "one read");
+    Back* back = tmp.get<Back>(1);
+    HIP_CHECK(hipMemcpyAsync(&back->total, total, 8, hipMemcpyDeviceToDevice, ex.stream));
+    HIP_CHECK(hipMemcpyAsync(&back->status, status, 4, hipMemcpyDeviceToDevice, ex.stream));
+    const Back b = read_device(ex, back);
+    if (b.status & STR_RANGE_STATUS_NEGATIVE) fail(BHIP_EEXEC, "negative substring length not allowed");
+    out.data_bytes = (int64_t)b.total;
+    out.validity = validity;
+    return out;
+}
+
+// char_length(<Utf8 expression>): one thread per row counts its code points; NULL exactly where the argument is
+Column eval_char_length(const Exec& ex, const Batch& in, const Expr& e) {
+    const Column arg = eval_utf8(ex, in, e.args[0]);
+    const int64_t n = in.n_rows;
+    Column out;
+    out.dtype = DT_INT32;
+    out.length = n;
+    out.data = make_buffer(ex, (size_t)n * 4 + 8);
+    out.validity = arg.validity;
+    TIMED_LAUNCH_N(ex, "char_length", n, launch_char_length(ex.cfg(), arg.ref(), n, out.data->as<int32_t>()));
+    return out;
+}
+
+// strpos(s, sub) -> Int32 / starts_with(s, prefix) -> Boolean: the second argument a literal in the struct, or a column
+Column eval_str_search(const Exec& ex, const Batch& in, const Expr& e) {
+    const bool pos = e.name == "strpos";
+    const Column arg = eval_utf8(ex, in, e.args[0]);
+    const int64_t n = in.n_rows;
+    StrSearchArgs A;
+    memset(&A, 0, sizeof(A));
+    A.s = arg.ref();
+    Column sub;
+    const Expr& x = *e.args[1];
+    if (x.kind == BHIP_EXPR_LITERAL) {
+        A.sub_is_lit = 1;
+        A.lit.len = (int32_t)x.name.size();
+        memcpy(A.lit.bytes, x.name.data(), x.name.size());
+    } else {
+        sub = eval_utf8(ex, in, e.args[1]);
+        A.sub = sub.ref();
+    }
+    Column out;
+    out.dtype = pos ? DT_INT32 : DT_BOOLEAN;
+    out.length = n;
+    out.data = make_buffer(ex, (pos ? (size_t)n * 4 : bitmap_bytes(n)) + 8);
+    if (arg.validity || sub.validity) out.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+    uint64_t* validity = out.validity ? out.validity->as<uint64_t>() : nullptr;
+    if (pos) TIMED_LAUNCH_N(ex, "strpos", n, launch_strpos(ex.cfg(), A, n, out.data->as<int32_t>(), validity));
+    else TIMED_LAUNCH_N(ex, "starts_with", n, launch_starts_with(ex.cfg(), A, n, out.data->as<uint64_t>(), validity));
+    return out;
+}
+
+// date_part(p, x): x as a temporary column, then one streaming kernel, as date_trunc
+Column eval_date_part(const Exec& ex, const Batch& in, const Expr& e) {
+    const int part = date_part_of(e, *in.schema);
+    const Column arg = materialize_column(ex, evaluate_column(ex, in, e.args[1]));
+    const int64_t n = in.n_rows;
+    Column out;
+    out.dtype = DT_INT32;
+    out.length = n;
+    out.data = make_buffer(ex, (size_t)n * 4 + 8);
+    out.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+    TIMED_LAUNCH_N(ex, "date_part", n, launch_date_part(ex.cfg(), arg.ref(), n, part, out.data->as<int32_t>(), out.validity->as<uint64_t>()));
+    return out;
+}
+
 Column eval_utf8(const Exec& ex, const Batch& in, const ExprPtr& e) {
     switch (e->kind) {
         case BHIP_EXPR_COLUMN: {
@@ -362,6 +479,7 @@ Column eval_utf8(const Exec& ex, const Batch& in, const ExprPtr& e) {
             if (str_fn(e->name) >= 0) return eval_transform(ex, in, *e);
             if (sha_fn(e->name)) return eval_sha(ex, in, *e);
             if (e->name == "concat") return eval_concat(ex, in, *e);
+            if (str_range_fn(e->name) >= 0) return eval_str_range(ex, in, e);
             break;
         case BHIP_EXPR_CASE: return eval_case(ex, in, *e);
         case BHIP_EXPR_CAST:
@@ -393,7 +511,10 @@ BatchPtr Utf8Lowering::apply(const Exec& ex, const Batch& in) const {
             if (t == DT_UTF8) out->cols.push_back(eval_utf8(ex, in, node));
             else if (node->kind == BHIP_EXPR_CAST) out->cols.push_back(eval_cast_parse(ex, in, *node));
             else if (node->name == "to_timestamp") out->cols.push_back(eval_to_timestamp(ex, in, *node));
-            else out->cols.push_back(eval_date_trunc(ex, in, *node));
+            else if (node->name == "date_trunc") out->cols.push_back(eval_date_trunc(ex, in, *node));
+            else if (node->name == "date_part") out->cols.push_back(eval_date_part(ex, in, *node));
+            else if (node->name == "char_length") out->cols.push_back(eval_char_length(ex, in, *node));
+            else out->cols.push_back(eval_str_search(ex, in, *node));
         }
     }
     return out;
@@ -430,6 +551,13 @@ void Utf8Lowering::validate() const {
                     }
                     break;
                 }
+                if (str_range_fn(e->name) >= 0) {
+                    check_string_fn(*e, in_);
+                    walk(e->args[0]);
+                    for (size_t k = 1; k < e->args.size(); ++k)
+                        if (e->args[k]->kind != BHIP_EXPR_LITERAL) check_projected(e->args[k]);
+                    break;
+                }
                 if (str_fn(e->name) < 0 && !sha_fn(e->name)) fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e->to_string());
                 walk(e->args[0]);
                 break;
@@ -456,6 +584,16 @@ void Utf8Lowering::validate() const {
         if (n->kind == BHIP_EXPR_SCALAR_FN && n->name == "date_trunc") {
             (void)date_trunc_granularity(*n, in_);
             check_projected(n->args[1]);
+            continue;
+        }
+        if (n->kind == BHIP_EXPR_SCALAR_FN && n->name == "date_part") {
+            (void)date_part_of(*n, in_);
+            check_projected(n->args[1]);
+            continue;
+        }
+        if (n->kind == BHIP_EXPR_SCALAR_FN && str_typed_fn(n->name)) {
+            check_string_fn(*n, in_);
+            for (auto& a : n->args) walk(a);
             continue;
         }
         if (n->kind == BHIP_EXPR_SCALAR_FN) {          // to_timestamp

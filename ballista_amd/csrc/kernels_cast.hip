@@ -8,8 +8,8 @@
 //   Utf8 -> T     one thread per row walks its bytes in HBM; value, and the validity as one ballot word per wave64
 //   T -> Utf8     lengths -> exclusive scan (offsets) -> bytes, the shape of str_transform_*
 //
-// to_timestamp (Utf8 -> Timestamp(Nanosecond)) and date_trunc (Timestamp -> Timestamp) are lowered the same way and live here;
-// their grammar and calendar arithmetic are temporal_text.h.
+// to_timestamp (Utf8 -> Timestamp(Nanosecond)), date_trunc (Timestamp -> Timestamp) and date_part (Date32 / Date64 / Timestamp ->
+// Int32) are lowered the same way and live here; their grammar and calendar arithmetic are temporal_text.h.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "cast_kernels.h"
@@ -137,6 +137,23 @@ date_trunc_kernel(ColumnRef c, int64_t n, int g, int64_t* out, uint64_t* validit
     }
 }
 
+// date_part: one Int32 field per row of a Date32 / Date64 / Timestamp column, the validity as date_trunc_kernel writes it: NULL
+// where the argument is, or where the field does not fit Int32
+__global__ void __launch_bounds__(BLOCK)
+date_part_kernel(ColumnRef c, int64_t n, int part, int32_t* out, uint64_t* validity) {
+    const int64_t n_round = (n + 63) & ~(int64_t)63;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * BLOCK) {
+        bool valid = false;
+        if (i < n) {
+            int32_t v = 0;
+            valid = bit_at(c.validity, i) && temporal_part(c.dtype, part, (int64_t)load_value(c, i), v);
+            out[i] = valid ? v : 0;                     // 0 for a NULL: the bytes stay defined
+        }
+        const uint64_t vw = __ballot(valid);
+        if ((threadIdx.x & 63) == 0) validity[i >> 6] = vw;
+    }
+}
+
 inline int grid_of(const LaunchCfg& cfg, int64_t n) {
     const int64_t want = (n + BLOCK - 1) / BLOCK, cap = (int64_t)cfg.device_cus * 8;
     return (int)(want < 1 ? 1 : (want > cap ? cap : want));
@@ -175,6 +192,13 @@ hipError_t launch_date_trunc(const LaunchCfg& cfg, const ColumnRef& c, int64_t n
     if (timestamp_units_per_second(c.dtype) == 0 || granularity < 0 || granularity >= TRUNC_COUNT) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(date_trunc_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, c, n, granularity, out, validity);
+    return hipGetLastError();
+}
+
+hipError_t launch_date_part(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int part, int32_t* out, uint64_t* validity) {
+    if (temporal_units_per_day(c.dtype) == 0 || part < 0 || part >= PART_COUNT) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(date_part_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, c, n, part, out, validity);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // kernels_str.hip — expressions that PRODUCE Utf8 values: lower / upper / trim / ltrim / rtrim
-// (rust/core/src/serde/logical_plan/from_proto.rs:910-918 ships them), CASE ... THEN <string>, string literals as columns, concat.
+// (rust/core/src/serde/logical_plan/from_proto.rs:910-918 ships them), CASE ... THEN <string>, string literals as columns, concat,
+// substr / left / right — and the typed results over strings that count code points: char_length, strpos, starts_with.
 //
 // The expression VM (vm_device.h) keeps 64-bit values per row; a string result is a new Arrow column instead: every kernel
 // here runs as lengths -> exclusive scan (offsets) -> bytes, one thread per row, over the offsets / bytes / validity buffers
@@ -7,6 +8,7 @@
 // expression to the VM, which compares / hashes / LIKEs Utf8 columns in place.
 #include <hip/hip_runtime.h>
 #include "str_kernels.h"
+#include "str_text.h"
 
 namespace bhip {
 
@@ -210,6 +212,118 @@ concat_write_kernel(StrConcatArgs A, int64_t n, const int32_t* out_offsets, uint
     }
 }
 
+// ---- substr / left / right: a byte range of the argument (str_text.h has the rules) ------------------------------------------------
+__device__ inline bool int_arg(const StrIntArg& a, int64_t i, int64_t& v) {
+    if (a.is_lit) { v = a.lit; return true; }
+    v = reinterpret_cast<const int64_t*>(a.col.data)[i];
+    return bit_at(a.col.validity, i);
+}
+
+// row i's result as [begin, stop) of A.s's value bytes; false for a NULL row.  negative: substr with count < 0 in a non-NULL row
+// (an empty range: the batch fails).
+__device__ inline bool range_of_row(const StrRangeArgs& A, int64_t i, int32_t& begin, int32_t& stop, bool& negative) {
+    begin = stop = 0;
+    negative = false;
+    int64_t a = 0, b = 0;
+    bool valid = bit_at(A.s.validity, i);
+    valid = int_arg(A.a, i, a) && valid;
+    if (A.has_count) valid = int_arg(A.b, i, b) && valid;
+    if (!valid) return false;
+    const CastPtrReader rd{reinterpret_cast<const uint8_t*>(A.s.data)};
+    int64_t p, q;
+    negative = !str_range(A.fn, rd, (int64_t)A.s.offsets[i], (int64_t)A.s.offsets[i + 1], a, A.has_count != 0, b, p, q);
+    begin = (int32_t)p;
+    stop = (int32_t)q;
+    return true;
+}
+
+// lengths and validity, rows taken 64 at a time by whole waves as in concat_lengths_kernel
+__global__ void __launch_bounds__(BLOCK)
+str_range_lengths_kernel(StrRangeArgs A, int64_t n, uint32_t* lengths, uint64_t* validity, uint32_t* status) {
+    const int64_t n_round = (n + 63) & ~(int64_t)63;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * BLOCK) {
+        bool valid = false;
+        if (i < n) {
+            int32_t begin, stop;
+            bool negative;
+            valid = range_of_row(A, i, begin, stop, negative);
+            bad |= negative;
+            lengths[i] = (uint32_t)(stop - begin);
+        }
+        const uint64_t w = __ballot(valid);
+        if (validity != nullptr && (threadIdx.x & 63) == 0) validity[i >> 6] = w;
+    }
+    if (bad) atomicOr(status, STR_RANGE_STATUS_NEGATIVE);
+}
+
+// bytes: one lane per row, as concat_write_kernel; a row whose RESULT is longer than STR_CONCAT_WAVE_BYTES is copied by its whole
+// wave afterwards.  (concat's second pass walks an argument list per row; here the owning lane hands its one source range to the
+// wave, so the pass is this kernel's own.)
+__global__ void __launch_bounds__(BLOCK)
+str_range_write_kernel(StrRangeArgs A, int64_t n, const int32_t* out_offsets, uint8_t* out) {
+    const int64_t n_round = (n + 63) & ~(int64_t)63;
+    const int lane = threadIdx.x & 63;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(A.s.data);
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * BLOCK) {
+        int len = 0;
+        int32_t d0 = 0, begin = 0;
+        if (i < n) {
+            d0 = out_offsets[i];
+            len = out_offsets[i + 1] - d0;
+            if (len > 0) {                                       // (len == 0: a NULL row or an empty result)
+                int32_t stop;
+                bool negative;
+                range_of_row(A, i, begin, stop, negative);
+            }
+        }
+        if (len > 0 && len <= STR_CONCAT_WAVE_BYTES)
+            for (int k = 0; k < len; ++k) out[d0 + k] = src[begin + k];
+        for (uint64_t todo = __ballot(len > STR_CONCAT_WAVE_BYTES); todo != 0; todo &= todo - 1) {
+            const int owner = __ffsll((unsigned long long)todo) - 1;
+            const int l = __shfl(len, owner);
+            const int32_t d = __shfl(d0, owner), b = __shfl(begin, owner);
+            for (int k = lane; k < l; k += 64) out[d + k] = src[b + k];
+        }
+    }
+}
+
+// ---- char_length / strpos / starts_with: typed results over Utf8 arguments ------------------------------------------------------------
+__global__ void __launch_bounds__(BLOCK)
+char_length_kernel(ColumnRef c, int64_t n, int32_t* out) {
+    const CastPtrReader rd{reinterpret_cast<const uint8_t*>(c.data)};
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK)
+        out[i] = bit_at(c.validity, i) ? (int32_t)str_char_count(rd, (int64_t)c.offsets[i], (int64_t)c.offsets[i + 1]) : 0;     // 0 for a NULL
+}
+
+// POS: strpos (n Int32 values), else starts_with (n bits, one ballot word per wave64 like the validity)
+template <bool POS>
+__global__ void __launch_bounds__(BLOCK)
+str_search_kernel(StrSearchArgs A, int64_t n, int32_t* out, uint64_t* out_bits, uint64_t* validity) {
+    const int64_t n_round = (n + 63) & ~(int64_t)63;
+    const CastPtrReader rd{reinterpret_cast<const uint8_t*>(A.s.data)};
+    const CastPtrReader sub{A.sub_is_lit ? A.lit.bytes : reinterpret_cast<const uint8_t*>(A.sub.data)};
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * BLOCK) {
+        bool valid = false;
+        int32_t r = 0;
+        if (i < n) {
+            valid = bit_at(A.s.validity, i) && (A.sub_is_lit || bit_at(A.sub.validity, i));
+            if (valid) {
+                const int64_t p0 = A.sub_is_lit ? 0 : (int64_t)A.sub.offsets[i], p1 = A.sub_is_lit ? (int64_t)A.lit.len : (int64_t)A.sub.offsets[i + 1];
+                const int64_t s0 = (int64_t)A.s.offsets[i], s1 = (int64_t)A.s.offsets[i + 1];
+                r = POS ? str_strpos(rd, s0, s1, sub, p0, p1) : (int32_t)str_starts_with(rd, s0, s1, sub, p0, p1);
+            }
+            if (POS) out[i] = r;                                 // 0 for a NULL: the bytes stay defined
+        }
+        const uint64_t vw = __ballot(valid);
+        if (!POS) {
+            const uint64_t bw = __ballot(r != 0);
+            if ((threadIdx.x & 63) == 0) out_bits[i >> 6] = bw;
+        }
+        if (validity != nullptr && (threadIdx.x & 63) == 0) validity[i >> 6] = vw;
+    }
+}
+
 // ---- SHA-2 (FIPS 180-4) of every string: sha224 / sha256 / sha384 / sha512 (rust/core/src/serde/logical_plan/from_proto.rs:924-927) --
 // one thread per row, the message schedule kept as a 16-word ring; the digest (28 / 32 / 48 / 64 bytes, big-endian words) goes to
 // out + row * digest_bytes: fixed-stride Binary values (a NULL row's bytes are never read: validity says so)
@@ -395,6 +509,47 @@ hipError_t launch_concat_write(const LaunchCfg& cfg, const StrConcatArgs& A, int
     if (!concat_args_ok(A)) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(concat_write_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, out_offsets, out);
+    return hipGetLastError();
+}
+static bool int_arg_ok(const StrIntArg& a) { return a.is_lit || (a.col.dtype == DT_INT64 && a.col.data != nullptr); }
+static bool range_args_ok(const StrRangeArgs& A) {
+    if (A.fn < STR_SUBSTR || A.fn > STR_RIGHT || (A.has_count && A.fn != STR_SUBSTR)) return false;
+    if (A.s.dtype != DT_UTF8 || A.s.offsets == nullptr) return false;
+    return int_arg_ok(A.a) && (!A.has_count || int_arg_ok(A.b));
+}
+hipError_t launch_str_range_lengths(const LaunchCfg& cfg, const StrRangeArgs& A, int64_t n, uint32_t* lengths, uint64_t* validity, uint32_t* status) {
+    if (!range_args_ok(A)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(str_range_lengths_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, lengths, validity, status);
+    return hipGetLastError();
+}
+hipError_t launch_str_range_write(const LaunchCfg& cfg, const StrRangeArgs& A, int64_t n, const int32_t* out_offsets, uint8_t* out) {
+    if (!range_args_ok(A)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(str_range_write_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, out_offsets, out);
+    return hipGetLastError();
+}
+hipError_t launch_char_length(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int32_t* out) {
+    if (c.dtype != DT_UTF8 || c.offsets == nullptr) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(char_length_kernel, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, c, n, out);
+    return hipGetLastError();
+}
+static bool search_args_ok(const StrSearchArgs& A) {
+    if (A.s.dtype != DT_UTF8 || A.s.offsets == nullptr) return false;
+    if (A.sub_is_lit) return A.lit.len >= 0 && A.lit.len <= STR_LITERAL_MAX;
+    return A.sub.dtype == DT_UTF8 && A.sub.offsets != nullptr;
+}
+hipError_t launch_strpos(const LaunchCfg& cfg, const StrSearchArgs& A, int64_t n, int32_t* out, uint64_t* validity) {
+    if (!search_args_ok(A)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(str_search_kernel<true>, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, out, (uint64_t*)nullptr, validity);
+    return hipGetLastError();
+}
+hipError_t launch_starts_with(const LaunchCfg& cfg, const StrSearchArgs& A, int64_t n, uint64_t* out_bits, uint64_t* validity) {
+    if (!search_args_ok(A)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(str_search_kernel<false>, dim3(grid_of(cfg, n)), dim3(BLOCK), 0, cfg.stream, A, n, (int32_t*)nullptr, out_bits, validity);
     return hipGetLastError();
 }
 hipError_t launch_sha2(const LaunchCfg& cfg, int bits, const ColumnRef& c, int64_t n, int32_t* out_offsets, uint8_t* out) {

@@ -45,6 +45,33 @@ struct StrConcatArgs {
 hipError_t launch_concat_lengths(const LaunchCfg& cfg, const StrConcatArgs& A, int64_t n, uint32_t* lengths, uint64_t* validity);
 hipError_t launch_concat_write(const LaunchCfg& cfg, const StrConcatArgs& A, int64_t n, const int32_t* out_offsets, uint8_t* out);
 
+// substr(s, start[, count]) / left(s, n) / right(s, n) (str_text.h: StrRangeFn and the rules).  An integer argument is an Int64
+// column or a literal carried in the struct; left / right keep n in `a`.  NULL where any argument is.
+struct StrIntArg { int32_t is_lit, pad; int64_t lit; ColumnRef col; };
+struct StrRangeArgs {
+    int32_t fn, has_count;
+    ColumnRef s;
+    StrIntArg a, b;
+};
+constexpr uint32_t STR_RANGE_STATUS_NEGATIVE = 1u;      // a non-NULL row of substr with count < 0
+// lengths[i] = the result's byte count (0 for a NULL row).  validity (may be null when no argument has a validity buffer): whole
+// 64-bit words, (n + 63) / 64 of them.  *status gets STR_RANGE_STATUS_NEGATIVE OR-ed in.
+hipError_t launch_str_range_lengths(const LaunchCfg& cfg, const StrRangeArgs& A, int64_t n, uint32_t* lengths, uint64_t* validity, uint32_t* status);
+// the bytes: a row whose result is longer than STR_CONCAT_WAVE_BYTES is copied by its whole wave, a shorter one by its lane
+hipError_t launch_str_range_write(const LaunchCfg& cfg, const StrRangeArgs& A, int64_t n, const int32_t* out_offsets, uint8_t* out);
+
+// char_length(s): n Int32 code-point counts (0 for a NULL row; the result's validity is the argument's)
+hipError_t launch_char_length(const LaunchCfg& cfg, const ColumnRef& c, int64_t n, int32_t* out);
+// strpos(s, sub) -> n Int32 values, starts_with(s, prefix) -> n bits.  `sub` is a Utf8 column, or a literal carried in the struct.
+// validity (may be null when neither argument has a validity buffer) and the bits of starts_with: whole 64-bit words.
+struct StrSearchArgs {
+    int32_t sub_is_lit, pad;
+    ColumnRef s, sub;
+    StrLiteral lit;
+};
+hipError_t launch_strpos(const LaunchCfg& cfg, const StrSearchArgs& A, int64_t n, int32_t* out, uint64_t* validity);
+hipError_t launch_starts_with(const LaunchCfg& cfg, const StrSearchArgs& A, int64_t n, uint64_t* out_bits, uint64_t* validity);
+
 // sha224 / sha256 / sha384 / sha512 of every string: n digests of bits / 8 bytes at out + row * (bits / 8), offsets written too
 hipError_t launch_sha2(const LaunchCfg& cfg, int bits, const ColumnRef& c, int64_t n, int32_t* out_offsets, uint8_t* out);
 

@@ -1,4 +1,5 @@
-// temporal_text.h — to_timestamp's text grammar and date_trunc's calendar arithmetic, written once (DESIGN.md §3.2 has the table).
+// temporal_text.h — to_timestamp's text grammar, date_trunc's and date_part's calendar arithmetic, written once (DESIGN.md §3.2 has
+// the table).
 //
 // Plain host / device inline functions like cast_text.h, which this header extends (civil_from_days / days_from_civil live there):
 // the kernels (kernels_cast.hip), the host's folding of literals (host/expr.cpp) and the stand-alone check program
@@ -66,6 +67,60 @@ BHIP_HD inline bool temporal_trunc(int unit, int g, int64_t v, int64_t& out) {
     // days <= v / upd, so only the lower end can be missed; INT64_MIN / upd rounds towards zero: the first day that fits
     if (days < TEMPORAL_I64_MIN / upd) return false;
     out = days * upd;
+    return true;
+}
+
+// ---- date_part('part', x): one calendar field of a Date32, a Date64 or a Timestamp, as Int32 --------------------------------------
+enum DatePart : int { PART_YEAR = 0, PART_QUARTER, PART_MONTH, PART_DAY, PART_DOW, PART_DOY, PART_HOUR, PART_MINUTE, PART_SECOND, PART_COUNT };
+
+// the part named by text[0, len): exactly one of the nine lower-case words, else -1
+BHIP_HD inline int date_part_name(const char* text, int64_t len) {
+    const char* names[PART_COUNT] = {"year", "quarter", "month", "day", "dow", "doy", "hour", "minute", "second"};
+    for (int p = 0; p < PART_COUNT; ++p) {
+        int64_t k = 0;
+        while (k < len && names[p][k] != 0 && names[p][k] == text[k]) ++k;
+        if (k == len && names[p][k] == 0) return p;
+    }
+    return -1;
+}
+
+// units of a temporal type in one day; 0 for every other type.  (Date64 counts milliseconds.)
+BHIP_HD inline int64_t temporal_units_per_day(int t) {
+    if (t == DT_DATE32) return 1ll;
+    if (t == DT_DATE64) return 86400000ll;
+    return timestamp_units_per_second(t) * 86400ll;
+}
+
+// date_part of one value `v` of temporal type `t`: true and the field in `out`, false where it does not fit Int32 (the result is
+// NULL: the year of a value far from 1970).  Instants before 1970 floor; dow: 0 = Sunday; doy: 1 .. 366; whole seconds.
+BHIP_HD inline bool temporal_part(int t, int part, int64_t v, int32_t& out) {
+    out = 0;
+    const int64_t upd = temporal_units_per_day(t);
+    if (upd == 0 || part < 0 || part >= PART_COUNT) return false;
+    int64_t days = v / upd, rem = v % upd;          // C++ rounds towards zero: a negative remainder belongs to the day before
+    if (rem < 0) { rem += upd; --days; }
+    if (part >= PART_HOUR) {
+        const int64_t ups = upd / 86400ll;
+        const int64_t sod = ups ? rem / ups : 0;    // second of the day; a Date32 has none
+        out = (int32_t)(part == PART_HOUR ? sod / 3600 : part == PART_MINUTE ? sod / 60 % 60 : sod % 60);
+        return true;
+    }
+    if (part == PART_DOW) {
+        int64_t dow = (days % 7 + 4) % 7;           // 1970-01-01 is a Thursday
+        if (dow < 0) dow += 7;
+        out = (int32_t)dow;
+        return true;
+    }
+    int64_t y;
+    unsigned m, d;
+    civil_from_days(days, y, m, d);
+    if (part == PART_YEAR) {
+        if (y < -2147483648ll || y > 2147483647ll) return false;
+        out = (int32_t)y;
+    } else if (part == PART_QUARTER) out = (int32_t)((m - 1) / 3 + 1);
+    else if (part == PART_MONTH) out = (int32_t)m;
+    else if (part == PART_DAY) out = (int32_t)d;
+    else out = (int32_t)(days - days_from_civil(y, 1u, 1u) + 1);
     return true;
 }
 

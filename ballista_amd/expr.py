@@ -44,9 +44,16 @@ STRING_FUNCTIONS = ("lower", "upper", "trim", "ltrim", "rtrim")
 SHA_FUNCTIONS = ("sha224", "sha256", "sha384", "sha512")
 # concat(a1 .. a8) -> Utf8, nullif(a, b) -> type of a, date_trunc('granularity', t) -> type of t, to_timestamp(s) ->
 # Timestamp(Nanosecond) (from_proto.rs:913-923 leaves them out; the rules are DESIGN.md §3.2).  md5 and array stay refused.
-MULTI_ARG_FUNCTIONS = {"concat": (1, 8), "nullif": (2, 2), "date_trunc": (2, 2)}
+# The code-point string functions and date_part (no wire form either): substr(s, start[, count]), left(s, n),
+# right(s, n) -> Utf8; char_length(s), strpos(s, sub) -> Int32; starts_with(s, prefix) -> Boolean; date_part('part', x) -> Int32.
+MULTI_ARG_FUNCTIONS = {"concat": (1, 8), "nullif": (2, 2), "date_trunc": (2, 2), "substr": (2, 3), "left": (2, 2), "right": (2, 2),
+                       "strpos": (2, 2), "starts_with": (2, 2), "date_part": (2, 2)}
 DATE_TRUNC_GRANULARITIES = ("second", "minute", "hour", "day", "week", "month", "year")
-SCALAR_FUNCTIONS = MATH_FUNCTIONS + STRING_FUNCTIONS + SHA_FUNCTIONS + ("octet_length", "concat", "nullif", "date_trunc", "to_timestamp")
+DATE_PART_PARTS = ("year", "quarter", "month", "day", "dow", "doy", "hour", "minute", "second")
+SUBSTRING_FUNCTIONS = ("substr", "left", "right")
+FUNCTION_ALIASES = {"substring": "substr", "length": "char_length", "character_length": "char_length"}
+SCALAR_FUNCTIONS = (MATH_FUNCTIONS + STRING_FUNCTIONS + SHA_FUNCTIONS + SUBSTRING_FUNCTIONS +
+                    ("octet_length", "concat", "nullif", "date_trunc", "to_timestamp", "char_length", "strpos", "starts_with", "date_part"))
 
 
 class PhysicalExpr:
@@ -141,6 +148,7 @@ class ScalarFunctionExpr(PhysicalExpr):
     args: Sequence[PhysicalExpr]
 
     def __post_init__(self):
+        self.fun = FUNCTION_ALIASES.get(self.fun, self.fun)
         if self.fun not in SCALAR_FUNCTIONS:
             raise NotImplementedError(f"scalar function '{self.fun}' is not supported")
         lo, hi = MULTI_ARG_FUNCTIONS.get(self.fun, (1, 1))
@@ -245,8 +253,12 @@ def expr_type(e: PhysicalExpr, schema: dict) -> str:
             return expr_type(e.args[1], schema)
         if e.fun == "to_timestamp":
             return TIMESTAMP_NS
-        if e.fun == "concat":
+        if e.fun == "concat" or e.fun in SUBSTRING_FUNCTIONS:
             return UTF8
+        if e.fun in ("char_length", "strpos", "date_part"):
+            return INT32
+        if e.fun == "starts_with":
+            return BOOLEAN
         return UTF8 if e.fun in STRING_FUNCTIONS else BINARY if e.fun in SHA_FUNCTIONS else INT32 if e.fun == "octet_length" else FLOAT64
     raise TypeError(f"not a PhysicalExpr: {e!r}")
 
@@ -321,6 +333,11 @@ def coerce(e: PhysicalExpr, schema: dict) -> PhysicalExpr:
                 t = common(ta, tb)
                 a, b = cast_to(a, t), cast_to(b, t)
             return ScalarFunctionExpr("nullif", [a, b])
+        if e.fun in SUBSTRING_FUNCTIONS:
+            # start, count, n: integers of any width, brought to Int64 like a side of a comparison
+            s, *ints = (coerce(x, schema) for x in e.args)
+            return ScalarFunctionExpr(e.fun, [s] + [cast_to(x, INT64) if expr_type(x, schema) in _NUMERIC_RANK and
+                                                    expr_type(x, schema) not in (FLOAT64, FLOAT32) else x for x in ints])
         if e.fun not in MATH_FUNCTIONS:
             return ScalarFunctionExpr(e.fun, [coerce(a, schema) for a in e.args])
         return ScalarFunctionExpr(e.fun, [cast_to(coerce(a, schema), FLOAT64) for a in e.args])

@@ -211,7 +211,10 @@ typedef enum {
     BHIP_EXPR_SCALAR_FN = 11   /* name = function ; pops n_args, pushed in order.  One argument: sqrt abs floor ceil round
                                   trunc signum exp ln log2 log10 sin cos tan asin acos atan, lower upper trim ltrim rtrim,
                                   octet_length, sha224 sha256 sha384 sha512, to_timestamp.  Two: nullif(a, b),
-                                  date_trunc('granularity', t).  One to eight: concat.  md5 and array: BHIP_ENOTIMPL */
+                                  date_trunc('granularity', t), left(s, n), right(s, n), strpos(s, sub), starts_with(s, prefix),
+                                  date_part('part', x).  Two or three: substr(s, start[, count]) (alias substring).  One to
+                                  eight: concat.  char_length (aliases length, character_length) takes one.  n, start and count
+                                  are Int64.  md5 and array: BHIP_ENOTIMPL */
 } bhip_expr_kind;
 
 typedef struct {
