@@ -90,6 +90,15 @@ def write_fixtures(d, monkeypatch):
                 ("snappy_plain_v2_pages", dict(compression="snappy", use_dictionary=False, data_page_version="2.0", data_page_size=2048))]
     for name, kw in variants:
         pq.write_table(pt, os.path.join(d, name + ".parquet"), row_group_size=700, **kw)
+    # ... and two page shapes of tests/parquet_files.py, small enough (<= 2 KiB) for every bit of them to be flipped: a hand-written page
+    # that alternates bit-packed and RLE runs under NULLs, and pages of 37 rows (Int32, Utf8, RLE Boolean; Snappy, V2) that end inside
+    # a validity word
+    import parquet_files as P
+    P.hand_run_mix(True, "hand_run_mix.parquet")(d)
+    pq.write_table(P.mixed_table(200, 0.3, 7).select(["low", "s", "b"]), os.path.join(d, "unaligned_pages.parquet"), write_batch_size=37, data_page_size=64,
+                   dictionary_pagesize_limit=300, data_page_version="2.0", compression="SNAPPY", write_statistics=False)
+    for name in ("hand_run_mix", "unaligned_pages"):
+        assert os.path.getsize(os.path.join(d, name + ".parquet")) <= 2048, name
 
 
 def test_host_parsers_survive_truncations_and_bit_flips_under_asan(harness, tmp_path, monkeypatch):
@@ -109,5 +118,5 @@ def test_host_parsers_survive_truncations_and_bit_flips_under_asan(harness, tmp_
     assert r.returncode == 0, tail
     assert "host_fuzz OK" in r.stdout and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, tail
     # every fixture kind was exercised
-    for name in ("q5.plan.bin", "case.expr.bin", "pyarrow.arrow", "own.arrow", "snappy_dict_v2.parquet"):
+    for name in ("q5.plan.bin", "case.expr.bin", "pyarrow.arrow", "own.arrow", "snappy_dict_v2.parquet", "hand_run_mix.parquet", "unaligned_pages.parquet"):
         assert name in r.stdout, tail

@@ -52,7 +52,11 @@ def same(got, want):
     for name in want.schema.names:
         g, w = got[name].combine_chunks(), want[name].combine_chunks()
         if pa.types.is_floating(w.type):
-            assert g.to_pylist() == w.to_pylist(), name          # bit exact: values are copied, never recomputed
+            # bit exact: values are copied, never recomputed — compared as bit patterns under the validity mask (NaN payloads, -0.0)
+            valid = w.is_valid().to_numpy(zero_copy_only=False)
+            assert g.type == w.type and np.array_equal(g.is_valid().to_numpy(zero_copy_only=False), valid), name
+            u = np.uint64 if w.type == pa.float64() else np.uint32
+            assert np.array_equal(g.to_numpy(zero_copy_only=False).view(u)[valid], w.to_numpy(zero_copy_only=False).view(u)[valid]), name
         else:
             assert g.cast(w.type).to_pylist() == w.to_pylist(), name
 
