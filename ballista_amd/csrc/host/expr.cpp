@@ -637,9 +637,9 @@ static uint64_t f64_bits(double d) { uint64_t u; memcpy(&u, &d, 8); return u; }
 
 Operand ProgramBuilder::load_column(int schema_idx) {
     const Field& f = schema_.fields[schema_idx];
-    const std::string key = "#col" + std::to_string(schema_idx);
-    auto it = cse_.find(key);
-    if (it != cse_.end()) return it->second;
+    // (a map of its own, keyed by the position: no column NAME can stand for another column's load or for an expression)
+    auto it = col_cse_.find(schema_idx);
+    if (it != col_cse_.end()) return it->second;
     Operand o;
     o.dtype = f.dtype;
     o.col = column_index(schema_idx);
@@ -661,7 +661,7 @@ Operand ProgramBuilder::load_column(int schema_idx) {
         // remember the vreg in a parallel slot: reuse `dst` after allocation; keep vreg in instr-less table
         load_vregs_.push_back(o.index);
     }
-    cse_[key] = o;
+    col_cse_[schema_idx] = o;
     return o;
 }
 
@@ -724,8 +724,45 @@ Operand ProgramBuilder::materialize(const Operand& o) {
     return emit(OP_MOV_V, &o, nullptr, false, o.vclass, o.dtype);
 }
 
+// The CSE key of a subtree: two subtrees share a key only if they are the same computation.  to_string() is not such a key — a
+// Float64 literal prints without its type, so a column NAMED "1" and lit(1.0) both print "1", and a column named "(a Plus b)"
+// prints like the sum.  Here a column is its schema position, a literal its type and bits (-0.0 and 0.0 differ), and every piece of
+// free text (operator and function names, Utf8 literals) carries its length, so no text can imitate the structure around it.
+static void cse_key(const Expr& e, const Schema& schema, std::string& k) {
+    auto text = [&](const std::string& t) { k += std::to_string(t.size()); k += ':'; k += t; };
+    switch (e.kind) {
+        case BHIP_EXPR_COLUMN:
+            k += 'c';
+            k += std::to_string(schema.index_of(e.name));          // (-1: compile_uncached refuses the name)
+            k += ';';
+            return;
+        case BHIP_EXPR_LITERAL:
+            k += e.is_null ? 'n' : 'l';
+            k += std::to_string(e.dtype);
+            k += ':';
+            if (e.is_null) { k += ';'; return; }
+            if (e.dtype == DT_UTF8) text(e.name);
+            else k += std::to_string(dt_is_float(e.dtype) ? f64_bits(e.f64) : (uint64_t)e.i64);
+            k += ';';
+            return;
+        default: break;
+    }
+    k += 'k';
+    k += std::to_string(e.kind);
+    k += '.';
+    k += std::to_string(e.dtype);
+    k += (e.negated ? 'N' : '-');
+    k += (e.has_base ? 'B' : '-');
+    k += (e.has_else ? 'E' : '-');
+    text(e.name);
+    k += '(';
+    for (auto& a : e.args) { cse_key(*a, schema, k); k += ','; }
+    k += ')';
+}
+
 Operand ProgramBuilder::compile(const ExprPtr& e) {
-    const std::string key = e->to_string();
+    std::string key;
+    cse_key(*e, schema_, key);
     auto it = cse_.find(key);
     if (it != cse_.end()) return it->second;
     Operand o = compile_uncached(e);

@@ -29,7 +29,7 @@ struct Expr {
     double f64 = 0;
     std::vector<ExprPtr> args;
 
-    std::string to_string() const;    // Debug-style rendering, also the CSE key
+    std::string to_string() const;    // Debug-style rendering (not a key: two different trees can print alike)
 };
 
 ExprPtr parse_expr(const bhip_expr& e);
@@ -159,7 +159,8 @@ private:
     std::vector<uint64_t> lits_;
     std::string strlits_;
     std::vector<bool> vreg_is_b_;
-    std::map<std::string, Operand> cse_;
+    std::map<std::string, Operand> cse_;       // compiled subtrees by cse_key() (expr.cpp)
+    std::map<int, Operand> col_cse_;           // column loads by schema position
     int pred_vreg_ = -1;
     struct KeyV { int kind; int src; int width; int nullable; };
     std::vector<KeyV> keys_;

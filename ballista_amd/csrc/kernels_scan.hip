@@ -75,31 +75,38 @@ scan_project_kernel(const ScanParams P, const ProjectOut O, ScanStatus* status) 
 template <int R, bool NULLS>
 __global__ void __launch_bounds__(BLOCK)
 scan_pred_bitmap_kernel(const ScanParams P, uint64_t* bitmap, uint32_t* tile_counts, ScanStatus* status) {
+    // A selection tile is always SEL_TILE = 1024 rows (the per-tile counts feed launch_select_indices).  R = 4 interprets it in one
+    // pass; R = 2 — programs whose slots do not fit the LDS at 1024 rows — in two passes of 512 rows over the same slots, with the
+    // same bitmap words (a pass starts on a multiple of 64 rows) and one count per 1024 rows.
     constexpr int TILE = BLOCK * R;
-    static_assert(TILE == SEL_TILE, "selection tiles are 1024 rows");
+    static_assert(SEL_TILE % TILE == 0, "a selection tile (1024 rows) is a whole number of passes");
+    constexpr int PASSES = SEL_TILE / TILE;
     extern __shared__ __align__(16) uint8_t lds_raw[];
     const TileLds L = carve_tile_lds<R, NULLS>(lds_raw, P.prog);
     __shared__ uint32_t s_cnt;
     const int tid = threadIdx.x;
     uint32_t err = 0;
-    const int64_t n_tiles = (P.n_rows + TILE - 1) / TILE;
+    const int64_t n_tiles = (P.n_rows + SEL_TILE - 1) / SEL_TILE;
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const int64_t base = t * TILE;
         if (tid == 0) s_cnt = 0;
         __syncthreads();
-        vm_load_tile<R, NULLS>(P, L, base, err);
-        vm_execute<R, NULLS>(P, L, base, err);
         uint32_t cnt = 0;
+        for (int h = 0; h < PASSES; ++h) {
+            const int64_t base = t * SEL_TILE + (int64_t)h * TILE;
+            if (h > 0 && base >= P.n_rows) break;                  // (wave-uniform; a tile is only loaded when it has rows)
+            vm_load_tile<R, NULLS>(P, L, base, err);
+            vm_execute<R, NULLS>(P, L, base, err);
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int idx = r * BLOCK + tid;
-            const int64_t row = base + idx;
-            bool sel = row < P.n_rows;
-            if (sel && P.pred_slot >= 0) sel = L.bvals[P.pred_slot * TILE + idx] & 1;
-            const uint64_t word = __ballot(sel);
-            if ((tid & 63) == 0) {
-                if ((row) < P.n_rows) gptr_w<uint64_t>(bitmap)[row >> 6] = word;
-                cnt += (uint32_t)__popcll(word);
+            for (int r = 0; r < R; ++r) {
+                const int idx = r * BLOCK + tid;
+                const int64_t row = base + idx;
+                bool sel = row < P.n_rows;
+                if (sel && P.pred_slot >= 0) sel = L.bvals[P.pred_slot * TILE + idx] & 1;
+                const uint64_t word = __ballot(sel);
+                if ((tid & 63) == 0) {
+                    if ((row) < P.n_rows) gptr_w<uint64_t>(bitmap)[row >> 6] = word;
+                    cnt += (uint32_t)__popcll(word);
+                }
             }
         }
         if ((tid & 63) == 0) atomicAdd(&s_cnt, cnt);
@@ -209,23 +216,29 @@ hipError_t launch_scan_project(const LaunchCfg& cfg, const ScanParams& P, const 
     return P.prog.nullable ? launch_project_n<true>(cfg, P, out, status) : launch_project_n<false>(cfg, P, out, status);
 }
 
-hipError_t launch_scan_pred_bitmap(const LaunchCfg& cfg, const ScanParams& P, uint64_t* bitmap, uint32_t* tile_counts,
-                                   ScanStatus* status) {
-    const size_t lds = host_tile_bytes<4>(P.prog);
-    if (lds > LDS_PER_CU) return hipErrorInvalidValue;
+constexpr size_t PRED_STATIC_LDS = 16;           // scan_pred_bitmap_kernel's s_cnt, with the alignment the dynamic array asks for
+
+template <int R, bool NULLS>
+static hipError_t launch_pred_bitmap_t(const LaunchCfg& cfg, const ScanParams& P, uint64_t* bitmap, uint32_t* tile_counts, ScanStatus* status) {
+    const size_t lds = host_tile_bytes<R>(P.prog);
+    if (lds + PRED_STATIC_LDS > LDS_PER_CU) return hipErrorInvalidValue;     // (R = 2: the compiler's 24 value + 16 Boolean slots take 116 KiB)
     const int64_t n_tiles = (P.n_rows + SEL_TILE - 1) / SEL_TILE;
     const int grid = pick_grid(cfg, n_tiles, lds, 4);
-    hipError_t e;
-    if (P.prog.nullable) {
-        auto k = scan_pred_bitmap_kernel<4, true>;
-        if ((e = set_lds(k, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, cfg.stream, P, bitmap, tile_counts, status);
-    } else {
-        auto k = scan_pred_bitmap_kernel<4, false>;
-        if ((e = set_lds(k, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, cfg.stream, P, bitmap, tile_counts, status);
-    }
+    auto k = scan_pred_bitmap_kernel<R, NULLS>;
+    const hipError_t e = set_lds(k, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, cfg.stream, P, bitmap, tile_counts, status);
     return hipGetLastError();
+}
+
+hipError_t launch_scan_pred_bitmap(const LaunchCfg& cfg, const ScanParams& P, uint64_t* bitmap, uint32_t* tile_counts,
+                                   ScanStatus* status) {
+    // R = 4 whenever one workgroup's slots fit the LDS at 1024 rows (as before: the selection tile in one pass); else the same
+    // tile as two passes of R = 2.  (The other sinks go to R = 2 earlier, choose_r: their tile size is free.)
+    // (the kernel's own counter counts: 16 value and 16 Boolean slots over nullable inputs are 160 KiB to the byte, and no launch)
+    const bool r4 = host_tile_bytes<4>(P.prog) + PRED_STATIC_LDS <= LDS_PER_CU;
+    if (P.prog.nullable) return r4 ? launch_pred_bitmap_t<4, true>(cfg, P, bitmap, tile_counts, status) : launch_pred_bitmap_t<2, true>(cfg, P, bitmap, tile_counts, status);
+    return r4 ? launch_pred_bitmap_t<4, false>(cfg, P, bitmap, tile_counts, status) : launch_pred_bitmap_t<2, false>(cfg, P, bitmap, tile_counts, status);
 }
 
 template <bool NULLS>
