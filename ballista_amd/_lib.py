@@ -114,6 +114,10 @@ class SortExprC(C.Structure):
     _fields_ = [("expr", Expr), ("descending", C.c_int32), ("nulls_first", C.c_int32)]
 
 
+class WindowExprC(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("arg", Expr), ("offset", C.c_int64), ("frame", C.c_int32), ("name", C.c_char_p)]
+
+
 # every symbol include/ballista_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
@@ -162,6 +166,7 @@ SYMBOLS = {
     "bhip_plan_hash_join": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, _PP]),
     "bhip_plan_hash_join_filter": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.POINTER(Expr), _PP]),
     "bhip_plan_sort": (C.c_int32, [_P, C.c_int32, C.POINTER(SortExprC), _PP]),
+    "bhip_plan_window": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.c_int32, C.POINTER(SortExprC), C.c_int32, C.POINTER(WindowExprC), _PP]),
     "bhip_plan_repartition": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(Expr), C.c_int32, _PP]),
     "bhip_plan_coalesce_batches": (C.c_int32, [_P, C.c_int64, _PP]),
     "bhip_plan_merge": (C.c_int32, [_P, _PP]),

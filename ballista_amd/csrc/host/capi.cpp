@@ -331,6 +331,28 @@ bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* ex
     BHIP_API_END
 }
 
+bhip_status bhip_plan_window(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
+                             const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns, bhip_plan** out) {
+    BHIP_API_BEGIN
+    need(out, "out");
+    if (n_partition < 0 || n_order < 0 || n_fn < 0) fail(BHIP_EINVAL, "WindowAggExec: negative count");
+    if (n_partition > 0) need(partition_by, "partition_by");
+    if (n_order > 0) need(order_by, "order_by");
+    if (n_fn > 0) need(fns, "fns");
+    std::vector<ExprPtr> part;
+    for (int i = 0; i < n_partition; ++i) part.push_back(parse_expr(partition_by[i]));
+    std::vector<SortDesc> order;
+    for (int i = 0; i < n_order; ++i) order.push_back(SortDesc{parse_expr(order_by[i].expr), order_by[i].descending != 0, order_by[i].nulls_first != 0});
+    std::vector<WindowFnDesc> f;
+    for (int i = 0; i < n_fn; ++i) {
+        need(fns[i].name, "window expression name");
+        const bool has_arg = fns[i].arg.nodes && fns[i].arg.n_nodes > 0;
+        f.push_back(WindowFnDesc{fns[i].fn, has_arg ? parse_expr(fns[i].arg) : nullptr, fns[i].offset, fns[i].frame, fns[i].name});
+    }
+    *out = wrap_plan(std::make_shared<WindowAggExec>(part, order, f, plan_of(input, "input")));
+    BHIP_API_END
+}
+
 bhip_status bhip_plan_repartition(bhip_plan* input, int32_t scheme, int32_t n_exprs, const bhip_expr* hash_exprs,
                                   int32_t partition_count, bhip_plan** out) {
     BHIP_API_BEGIN

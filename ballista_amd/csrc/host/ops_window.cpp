@@ -1,0 +1,261 @@
+// ops_window.cpp — WindowAggExec: ranking, LAG / LEAD / FIRST_VALUE / LAST_VALUE and running aggregates over one window
+// specification (PARTITION BY ... ORDER BY ...), on the device (kernels_window.hip).
+//
+// The reference's serde has no window operator (rust/core/src/serde/physical_plan/from_proto.rs:58-346 builds none), so this one is
+// reached through bhip_plan_window only, like the join filter and the Semi / Anti joins; semantics: DESIGN.md "Window functions".
+//
+// The operator sorts its single input partition itself with SortExec's code (sort_permutation + take_batch; stable, so ties keep input
+// order) by the partition keys ASC NULLS FIRST and then the order keys, and the rows leave in that order.  After the sort every function
+// is a scan or a gather:
+//   flags        rows i - 1 and i compared on the evaluated key columns: "starts a partition", "starts a peer group" (two bitmaps)
+//   bounds       part_start / peer_start / peers_to (forward scan of the flags), part_end / peer_end (backward scan) — each made once, when
+//                a function needs it
+//   ranks        elementwise from the bounds; LAG / LEAD / FIRST_VALUE / LAST_VALUE: an index vector, then the outer-join gather
+//   aggregates   a segmented inclusive scan of the argument (value + non-NULL count per row), then the finish kernel reads the running
+//                state at the frame's last row: the row itself (ROWS), peer_end (RANGE) or part_end (whole partition)
+#include "../window_kernels.h"
+#include "plan.hpp"
+
+namespace bhip {
+
+namespace {
+const char* window_fn_name(int fn) {
+    switch (fn) {
+        case BHIP_WIN_ROW_NUMBER: return "ROW_NUMBER";
+        case BHIP_WIN_RANK: return "RANK";
+        case BHIP_WIN_DENSE_RANK: return "DENSE_RANK";
+        case BHIP_WIN_LAG: return "LAG";
+        case BHIP_WIN_LEAD: return "LEAD";
+        case BHIP_WIN_FIRST_VALUE: return "FIRST_VALUE";
+        case BHIP_WIN_LAST_VALUE: return "LAST_VALUE";
+        case BHIP_WIN_SUM: return "SUM";
+        case BHIP_WIN_AVG: return "AVG";
+        case BHIP_WIN_COUNT: return "COUNT";
+        case BHIP_WIN_MIN: return "MIN";
+        default: return "MAX";
+    }
+}
+const char* frame_name(int frame) {
+    switch (frame) {
+        case BHIP_FRAME_PARTITION: return "PARTITION";
+        case BHIP_FRAME_ROWS_TO_CURRENT: return "ROWS_TO_CURRENT";
+        default: return "RANGE_TO_CURRENT";
+    }
+}
+bool is_ranking(int fn) { return fn == BHIP_WIN_ROW_NUMBER || fn == BHIP_WIN_RANK || fn == BHIP_WIN_DENSE_RANK; }
+bool is_aggregate(int fn) { return fn >= BHIP_WIN_SUM && fn <= BHIP_WIN_MAX; }
+bool has_frame(int fn) { return is_aggregate(fn) || fn == BHIP_WIN_LAST_VALUE; }
+}  // namespace
+
+WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<SortDesc> order_by, std::vector<WindowFnDesc> fns, PlanPtr input)
+    : partition_by_(std::move(partition_by)), order_by_(std::move(order_by)), fns_(std::move(fns)) {
+    input_ = std::move(input);
+    ctx_ = input_->context();
+    const Schema& in = *input_->schema();
+    if (partition_by_.size() > (size_t)WINDOW_MAX_KEYS || order_by_.size() > (size_t)WINDOW_MAX_KEYS)
+        fail(BHIP_ENOTIMPL, "WindowAggExec takes at most " + std::to_string(WINDOW_MAX_KEYS) + " partition keys and " + std::to_string(WINDOW_MAX_KEYS) +
+                                " order keys");
+    if (fns_.empty()) fail(BHIP_EINVAL, "WindowAggExec needs at least one window expression");
+    Utf8Lowering low(in);                  // a key or an argument like lower(s) is evaluated as a column first (utf8_exprs.cpp)
+    for (auto& e : partition_by_) { expr_type(e, in); low.rewrite(e, true); }
+    for (auto& s : order_by_) { expr_type(s.expr, in); low.rewrite(s.expr, true); }
+    auto sch = std::make_shared<Schema>(in);
+    for (auto& f : fns_) {
+        if (f.fn < BHIP_WIN_ROW_NUMBER || f.fn > BHIP_WIN_MAX) fail(BHIP_EINVAL, "Unknown window function " + std::to_string(f.fn));
+        if (f.frame < BHIP_FRAME_DEFAULT || f.frame > BHIP_FRAME_RANGE_TO_CURRENT) fail(BHIP_EINVAL, "Unknown window frame " + std::to_string(f.frame));
+        if (f.frame == BHIP_FRAME_DEFAULT) f.frame = order_by_.empty() ? BHIP_FRAME_PARTITION : BHIP_FRAME_RANGE_TO_CURRENT;      // SQL's default
+        const std::string fname = window_fn_name(f.fn);
+        if (is_ranking(f.fn)) {
+            f.arg = nullptr;
+            sch->fields.push_back(Field{f.name, DT_UINT64, false});
+            continue;
+        }
+        if (!f.arg) fail(BHIP_EINVAL, fname + " needs an argument");
+        const int t = expr_type(f.arg, in);
+        low.rewrite(f.arg, true);
+        const bool large = t == DT_UTF8 && expr_large(f.arg, in), binary = t == DT_UTF8 && expr_binary(f.arg, in);
+        switch (f.fn) {
+            case BHIP_WIN_LAG: case BHIP_WIN_LEAD:
+                if (f.offset < 0) fail(BHIP_EINVAL, fname + " offset must not be negative, got " + std::to_string(f.offset));
+                sch->fields.push_back(Field{f.name, t, true, large, binary});
+                break;
+            case BHIP_WIN_FIRST_VALUE: case BHIP_WIN_LAST_VALUE:
+                sch->fields.push_back(Field{f.name, t, expr_nullable(f.arg, in), large, binary});
+                break;
+            case BHIP_WIN_SUM: case BHIP_WIN_AVG:
+                if (t == DT_UTF8 || t == DT_BOOLEAN) fail(BHIP_EINVAL, fname + " does not support " + dtype_name(t));
+                sch->fields.push_back(Field{f.name, f.fn == BHIP_WIN_AVG || dt_is_float(t) ? DT_FLOAT64 : dt_is_unsigned(t) ? DT_UINT64 : DT_INT64, true});
+                break;
+            case BHIP_WIN_COUNT:
+                sch->fields.push_back(Field{f.name, DT_UINT64, false});
+                break;
+            default:
+                if (t == DT_UTF8 || t == DT_BOOLEAN) fail(BHIP_ENOTIMPL, fname + " over " + dtype_name(t) + " is not supported as a window function");
+                sch->fields.push_back(Field{f.name, t, true});
+                break;
+        }
+    }
+    low.validate();
+    schema_ = sch;
+}
+
+PlanPtr WindowAggExec::with_new_children(const std::vector<PlanPtr>& c) const {
+    if (c.size() != 1) fail(BHIP_EINVAL, "WindowAggExec wrong number of children");
+    return std::make_shared<WindowAggExec>(partition_by_, order_by_, fns_, c[0]);
+}
+
+std::string WindowAggExec::describe() const {
+    std::string s = "WindowAggExec: partition_by=[";
+    for (size_t i = 0; i < partition_by_.size(); ++i) s += (i ? ", " : "") + partition_by_[i]->to_string();
+    s += "], order_by=[";
+    for (size_t i = 0; i < order_by_.size(); ++i)
+        s += (i ? ", " : "") + order_by_[i].expr->to_string() + (order_by_[i].descending ? " DESC" : " ASC") +
+             (order_by_[i].nulls_first ? " NULLS FIRST" : " NULLS LAST");
+    s += "], fns=[";
+    for (size_t i = 0; i < fns_.size(); ++i) {
+        const WindowFnDesc& f = fns_[i];
+        s += (i ? ", " : "") + std::string(window_fn_name(f.fn)) + "(" + (f.arg ? f.arg->to_string() : "");
+        if (f.fn == BHIP_WIN_LAG || f.fn == BHIP_WIN_LEAD) s += ", " + std::to_string(f.offset);
+        s += ")";
+        if (has_frame(f.fn)) s += std::string(" ") + frame_name(f.frame);
+        s += " as " + f.name;
+    }
+    return s + "]";
+}
+
+StreamPtr WindowAggExec::execute(int partition, const Exec& ex) const {
+    if (partition != 0) fail(BHIP_EINVAL, "WindowAggExec invalid partition " + std::to_string(partition));
+    if (input_->output_partitioning().count != 1) fail(BHIP_EINVAL, "WindowAggExec requires a single input partition: put a MergeExec below it");
+    auto self = std::static_pointer_cast<const WindowAggExec>(shared_from_this());
+    return StreamPtr(new LazyStream(schema(), [self, ex]() -> std::vector<BatchPtr> {
+        std::vector<BatchPtr> parts;
+        {
+            auto s = self->input_->execute(0, ex);
+            while (BatchPtr b = s->next())
+                if (b->n_rows > 0) parts.push_back(b);
+        }
+        if (parts.empty()) return {};
+        return {self->run(ex, concat_batches(ex, self->input_->schema(), parts))};
+    }));
+}
+
+BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
+    const LaunchCfg cfg = ex.cfg();
+    const int64_t n = whole->n_rows;
+    // ---- the order: SortExec's own code over (partition keys ASC NULLS FIRST, order keys) -------------------------------------------
+    std::vector<SortDesc> keys;
+    for (auto& e : partition_by_) keys.push_back(SortDesc{e, false, true});
+    for (auto& s : order_by_) keys.push_back(s);
+    BatchPtr sorted = materialize_batch(ex, whole);
+    if (!keys.empty() && n > 1) {
+        BufferPtr perm = sort_permutation(ex, *sorted, keys);
+        sorted = take_batch(ex, *sorted, perm->as<uint32_t>(), n, nullptr, /*permutation=*/true);
+    }
+    // ---- boundary flags from the key columns of the sorted rows ---------------------------------------------------------------------
+    Temp tmp(ex);
+    std::vector<Column> key_cols;                                  // keeps computed key columns alive until the launch is queued
+    WindowKeys K;
+    memset(&K, 0, sizeof(K));
+    K.n_part = (int32_t)partition_by_.size();
+    K.n_order = (int32_t)order_by_.size();
+    for (size_t k = 0; k < keys.size(); ++k) {
+        key_cols.push_back(evaluate_column(ex, *sorted, keys[k].expr));
+        const Column& c = key_cols.back();
+        if (!c.data || (c.dtype == DT_UTF8 && !c.offsets)) fail(BHIP_EEXEC, "WindowAggExec: a key column without buffers");
+        K.col[k] = c.ref();
+    }
+    const size_t words = (size_t)((n + 63) / 64);
+    uint64_t* part_flags = tmp.get<uint64_t>(words);
+    uint64_t* peer_flags = tmp.get<uint64_t>(words);
+    TIMED_LAUNCH_N(ex, "window_flags", n, launch_window_flags(cfg, K, n, part_flags, peer_flags));
+    void* scan_temp = tmp.get<uint8_t>(window_scan_temp_bytes(n));  // one scan at a time uses it (stream order)
+    // ---- bounds, each made when the first function asks for it ----------------------------------------------------------------------
+    uint32_t *part_start = nullptr, *peer_start = nullptr, *peers_to = nullptr, *part_end = nullptr, *peer_end = nullptr;
+    auto need_forward = [&]() {
+        if (part_start) return;
+        part_start = tmp.get<uint32_t>((size_t)n);
+        peer_start = tmp.get<uint32_t>((size_t)n);
+        peers_to = tmp.get<uint32_t>((size_t)n);
+        TIMED_LAUNCH_N(ex, "window_bounds_forward_tiles", n, launch_window_bounds_forward_tiles(cfg, part_flags, peer_flags, n, scan_temp));
+        TIMED_LAUNCH_N(ex, "window_bounds_forward_summaries", n, launch_window_bounds_forward_summaries(cfg, n, scan_temp));
+        TIMED_LAUNCH_N(ex, "window_bounds_forward_apply", n,
+                       launch_window_bounds_forward_apply(cfg, part_flags, peer_flags, n, scan_temp, part_start, peer_start, peers_to));
+    };
+    auto need_backward = [&]() {
+        if (part_end) return;
+        part_end = tmp.get<uint32_t>((size_t)n);
+        peer_end = tmp.get<uint32_t>((size_t)n);
+        TIMED_LAUNCH_N(ex, "window_bounds_backward_tiles", n, launch_window_bounds_backward_tiles(cfg, part_flags, peer_flags, n, scan_temp));
+        TIMED_LAUNCH_N(ex, "window_bounds_backward_summaries", n, launch_window_bounds_backward_summaries(cfg, n, scan_temp));
+        TIMED_LAUNCH_N(ex, "window_bounds_backward_apply", n,
+                       launch_window_bounds_backward_apply(cfg, part_flags, peer_flags, n, scan_temp, part_end, peer_end));
+    };
+    // the last row of row i's frame: null = the row itself
+    auto frame_end = [&](int frame) -> const uint32_t* {
+        if (frame == BHIP_FRAME_ROWS_TO_CURRENT) return nullptr;
+        need_backward();
+        return frame == BHIP_FRAME_PARTITION ? part_end : peer_end;
+    };
+
+    auto out = std::make_shared<Batch>();
+    out->schema = schema_;
+    out->ctx = sorted->ctx;
+    out->n_rows = n;
+    out->cols = sorted->cols;
+    for (const WindowFnDesc& f : fns_) {
+        Column o;
+        o.length = n;
+        if (is_ranking(f.fn)) {
+            need_forward();
+            o.dtype = DT_UINT64;
+            o.data = make_buffer(ex, (size_t)n * 8 + 8);
+            const int kind = f.fn == BHIP_WIN_ROW_NUMBER ? WINDOW_ROW_NUMBER : f.fn == BHIP_WIN_RANK ? WINDOW_RANK : WINDOW_DENSE_RANK;
+            TIMED_LAUNCH_N(ex, "window_rank", n, launch_window_rank(cfg, kind, part_start, peer_start, peers_to, n, o.data->as<uint64_t>()));
+        } else if (!is_aggregate(f.fn)) {
+            // the row to read, then the gather the outer joins use (an index outside the partition is its NULL index)
+            const uint32_t* fe = nullptr;
+            int kind;
+            switch (f.fn) {
+                case BHIP_WIN_LAG: need_forward(); kind = WINDOW_LAG; break;
+                case BHIP_WIN_LEAD: need_backward(); kind = WINDOW_LEAD; break;
+                case BHIP_WIN_FIRST_VALUE: need_forward(); kind = WINDOW_FIRST; break;
+                default: fe = frame_end(f.frame); kind = WINDOW_LAST; break;
+            }
+            BufferPtr idx = make_buffer(ex, (size_t)n * 4 + 8);
+            TIMED_LAUNCH_N(ex, "window_index", n, launch_window_index(cfg, kind, f.offset, part_start, part_end, fe, n, idx->as<uint32_t>()));
+            const Column arg = evaluate_column(ex, *sorted, f.arg);
+            o = f.fn == BHIP_WIN_LAG || f.fn == BHIP_WIN_LEAD ? take_column_nullable(ex, arg, idx->as<uint32_t>(), n)
+                                                              : take_batch_column(ex, arg, idx->as<uint32_t>(), n);
+        } else {
+            // COUNT of a non-NULL literal (COUNT(*)) reads no column at all
+            const bool count_rows = f.fn == BHIP_WIN_COUNT && f.arg->kind == BHIP_EXPR_LITERAL && !f.arg->is_null;
+            Column arg;
+            if (!count_rows) arg = evaluate_column(ex, *sorted, f.arg);
+            ColumnRef ref = arg.ref();
+            const int t = count_rows ? DT_UINT8 : arg.dtype;
+            int op, kind = WINDOW_FINISH_VALUE;
+            switch (f.fn) {
+                case BHIP_WIN_SUM: op = dt_is_float(t) ? WINDOW_OP_ADD_F64 : WINDOW_OP_ADD_I64; o.dtype = dt_is_float(t) ? DT_FLOAT64 : dt_is_unsigned(t) ? DT_UINT64 : DT_INT64; break;
+                case BHIP_WIN_AVG: op = WINDOW_OP_ADD_F64; kind = WINDOW_FINISH_AVG; o.dtype = DT_FLOAT64; break;
+                case BHIP_WIN_COUNT: op = WINDOW_OP_ADD_I64; kind = WINDOW_FINISH_COUNT; o.dtype = DT_UINT64; ref.data = nullptr; break;
+                case BHIP_WIN_MIN: op = dt_is_float(t) ? WINDOW_OP_MIN_F64 : dt_is_unsigned(t) ? WINDOW_OP_MIN_U64 : WINDOW_OP_MIN_I64; o.dtype = t; break;
+                default: op = dt_is_float(t) ? WINDOW_OP_MAX_F64 : dt_is_unsigned(t) ? WINDOW_OP_MAX_U64 : WINDOW_OP_MAX_I64; o.dtype = t; break;
+            }
+            if (kind != WINDOW_FINISH_COUNT && !ref.data) fail(BHIP_EEXEC, "WindowAggExec: an argument column without buffers");
+            uint64_t* run_value = tmp.get<uint64_t>((size_t)n);
+            uint32_t* run_count = tmp.get<uint32_t>((size_t)n);
+            TIMED_LAUNCH_N(ex, "window_scan_tiles", n, launch_window_scan_tiles(cfg, op, ref, part_flags, n, scan_temp));
+            TIMED_LAUNCH_N(ex, "window_scan_summaries", n, launch_window_scan_summaries(cfg, op, n, scan_temp));
+            TIMED_LAUNCH_N(ex, "window_scan_apply", n, launch_window_scan_apply(cfg, op, ref, part_flags, n, scan_temp, run_value, run_count));
+            const uint32_t* fe = frame_end(f.frame);
+            o.data = make_buffer(ex, (size_t)n * dtype_width(o.dtype) + 8);
+            if (kind != WINDOW_FINISH_COUNT) o.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+            TIMED_LAUNCH_N(ex, "window_finish", n,
+                           launch_window_finish(cfg, kind, o.dtype, run_value, run_count, fe, n, o.data->ptr(), o.validity ? o.validity->as<uint64_t>() : nullptr));
+        }
+        out->cols.push_back(std::move(o));
+    }
+    return out;                                                     // (no wait: scratch is released in stream order)
+}
+
+}  // namespace bhip

@@ -293,6 +293,32 @@ private:
     std::vector<SortDesc> exprs_;
 };
 
+// One window specification over the whole input (ops_window.cpp): the rows sorted by (partition keys ASC NULLS FIRST, order keys),
+// the input's columns followed by one column per window function.  No wire form: the C ABI only (bhip_plan_window).
+struct WindowFnDesc {
+    int fn;               // bhip_window_fn
+    ExprPtr arg;          // null for ROW_NUMBER / RANK / DENSE_RANK
+    int64_t offset;       // LAG / LEAD
+    int frame;            // bhip_window_frame, BHIP_FRAME_DEFAULT already resolved
+    std::string name;
+};
+class WindowAggExec : public UnaryExec {
+public:
+    WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<SortDesc> order_by, std::vector<WindowFnDesc> fns, PlanPtr input);
+    const char* name() const override { return "WindowAggExec"; }
+    SchemaPtr schema() const override { return schema_; }
+    Partitioning output_partitioning() const override { return Partitioning{BHIP_PART_UNKNOWN, 1, {}}; }
+    PlanPtr with_new_children(const std::vector<PlanPtr>& c) const override;
+    StreamPtr execute(int partition, const Exec& ex) const override;
+    std::string describe() const override;
+private:
+    BatchPtr run(const Exec& ex, const BatchPtr& in) const;
+    std::vector<ExprPtr> partition_by_;
+    std::vector<SortDesc> order_by_;
+    std::vector<WindowFnDesc> fns_;
+    SchemaPtr schema_;
+};
+
 class RepartitionExec : public UnaryExec {
 public:
     RepartitionExec(PlanPtr input, Partitioning part);

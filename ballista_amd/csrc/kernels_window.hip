@@ -1,0 +1,424 @@
+// kernels_window.hip — WindowAggExec on the device (host/ops_window.cpp; declarations and the tile constants: window_kernels.h).
+//
+// The input is already in (partition keys, order keys) order.  Every kernel is one row per lane over 4-byte and 8-byte streams,
+// lane i of a wave at row base + i (coalesced loads and stores), wave64:
+//   window_flags_kernel                  rows i - 1 and i compared on the key columns -> "starts a partition" / "starts a peer group"
+//   window_{tiles,summaries,apply}       ONE three-launch inclusive scan, instantiated for the partition / peer bounds (forward max +
+//                                        sum, backward min) and for the segmented scans of an argument (add, min, max)
+//   window_rank / window_index           ROW_NUMBER, RANK, DENSE_RANK; the row LAG / LEAD / FIRST_VALUE / LAST_VALUE gather from
+//   window_finish                        the running state at the frame's last row -> the output column and its validity
+//
+// The scan: a tile is WINDOW_TILE_ROWS rows = WINDOW_ROUNDS rounds of one row per thread.  Inside a round the wave-level scan is the
+// __shfl_up ladder of kernels_util.hip's exclusive scans, the four wave totals cross through LDS.  Launch 1 leaves one summary per
+// tile, launch 2 (one workgroup) scans the summaries WINDOW_SUMMARY_STEP at a time with a running carry, launch 3 redoes the
+// tile-local scan with the summary of the tiles before it as carry.  Nothing waits on another workgroup.  The combine tree is a
+// function of the row positions alone (not of the grid or the device), so floating-point sums are reproducible bit for bit.
+#include <hip/hip_runtime.h>
+#include "kernels.h"
+#include "window_kernels.h"
+
+namespace bhip {
+
+namespace {
+
+__device__ inline bool bit_at(const uint64_t* words, int64_t i) { return (words[i >> 6] >> (i & 63)) & 1; }
+
+__device__ inline uint64_t shfl_up_u64(uint64_t x, int d) {
+    const uint32_t lo = __shfl_up((uint32_t)x, d, 64), hi = __shfl_up((uint32_t)(x >> 32), d, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// =============================================================================================
+// boundary flags
+// =============================================================================================
+// rows a and b of one key column are the same key: validity first (NULL equals NULL, whatever lies under it), then the bits
+__device__ inline bool key_equal(const ColumnRef& c, int64_t a, int64_t b) {
+    if (c.validity) {
+        const bool va = bit_at(c.validity, a), vb = bit_at(c.validity, b);
+        if (va != vb) return false;
+        if (!va) return true;
+    }
+    if (c.dtype == DT_UTF8) {
+        const int32_t a0 = c.offsets[a], a1 = c.offsets[a + 1], b0 = c.offsets[b], b1 = c.offsets[b + 1];
+        if (a1 - a0 != b1 - b0) return false;
+        const uint8_t* bytes = static_cast<const uint8_t*>(c.data);
+        for (int32_t k = 0; k < a1 - a0; ++k)
+            if (bytes[a0 + k] != bytes[b0 + k]) return false;
+        return true;
+    }
+    if (c.dtype == DT_BOOLEAN) return bit_at(static_cast<const uint64_t*>(c.data), a) == bit_at(static_cast<const uint64_t*>(c.data), b);
+    switch (dt_width(c.dtype)) {
+        case 1: return static_cast<const uint8_t*>(c.data)[a] == static_cast<const uint8_t*>(c.data)[b];
+        case 2: return static_cast<const uint16_t*>(c.data)[a] == static_cast<const uint16_t*>(c.data)[b];
+        case 4: return static_cast<const uint32_t*>(c.data)[a] == static_cast<const uint32_t*>(c.data)[b];       // floats: by bit pattern
+        default: return static_cast<const uint64_t*>(c.data)[a] == static_cast<const uint64_t*>(c.data)[b];
+    }
+}
+
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_flags_kernel(WindowKeys K, int64_t n, uint64_t* __restrict__ part_flags, uint64_t* __restrict__ peer_flags) {
+    const int64_t i = (int64_t)blockIdx.x * WINDOW_BLOCK + threadIdx.x;
+    bool part = false, peer = false;
+    if (i < n) {
+        part = i == 0;
+        for (int k = 0; k < K.n_part && !part; ++k) part = !key_equal(K.col[k], i - 1, i);
+        peer = part;
+        for (int k = 0; k < K.n_order && !peer; ++k) peer = !key_equal(K.col[K.n_part + k], i - 1, i);
+    }
+    // a wave covers 64 consecutive rows starting at a multiple of 64: one word of each bitmap
+    const uint64_t part_word = __ballot(part), peer_word = __ballot(peer);
+    if ((threadIdx.x & 63) == 0 && i < n) {
+        part_flags[i >> 6] = part_word;
+        peer_flags[i >> 6] = peer_word;
+    }
+}
+
+// =============================================================================================
+// the three-launch inclusive scan over a policy P:
+//   P::State, P::identity(), P::combine(left, right) (associative), P::shfl_up(state, d), p.load(position), p.store(position, state)
+// positions run 0 .. n in SCAN order (the backward policy maps them to rows from the right)
+// =============================================================================================
+template <class P>
+__device__ inline typename P::State block_scan_inclusive(typename P::State x, typename P::State* s_wave, typename P::State& total) {
+    using S = typename P::State;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const S y = P::shfl_up(x, d);
+        if (lane >= d) x = P::combine(y, x);
+    }
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    S before = P::identity(), tot = P::identity();
+#pragma unroll
+    for (int w = 0; w < WINDOW_BLOCK / 64; ++w) {
+        const S s = s_wave[w];
+        if (w < wave) before = P::combine(before, s);
+        tot = P::combine(tot, s);
+    }
+    __syncthreads();                       // the next round overwrites s_wave
+    total = tot;
+    return P::combine(before, x);
+}
+
+template <class P>
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_tiles_kernel(P p, int64_t n, typename P::State* __restrict__ summaries) {
+    using S = typename P::State;
+    __shared__ S s_wave[WINDOW_BLOCK / 64];
+    const int64_t base = (int64_t)blockIdx.x * WINDOW_TILE_ROWS;
+    S carry = P::identity();
+#pragma unroll
+    for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+        const int64_t pos = base + r * WINDOW_BLOCK + threadIdx.x;
+        S total;
+        block_scan_inclusive<P>(pos < n ? p.load(pos, n) : P::identity(), s_wave, total);
+        carry = P::combine(carry, total);
+    }
+    if (threadIdx.x == 0) summaries[blockIdx.x] = carry;
+}
+
+// one workgroup, in place: summaries[t] = combine(summaries[0 .. t])
+template <class P>
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_summaries_kernel(typename P::State* summaries, int64_t n_tiles) {
+    using S = typename P::State;
+    static_assert(WINDOW_SUMMARY_STEP == WINDOW_BLOCK, "one summary per thread and step");
+    __shared__ S s_wave[WINDOW_BLOCK / 64];
+    S carry = P::identity();
+    for (int64_t b = 0; b < n_tiles; b += WINDOW_SUMMARY_STEP) {
+        const int64_t t = b + threadIdx.x;
+        S total;
+        const S incl = block_scan_inclusive<P>(t < n_tiles ? summaries[t] : P::identity(), s_wave, total);
+        if (t < n_tiles) summaries[t] = P::combine(carry, incl);
+        carry = P::combine(carry, total);
+    }
+}
+
+template <class P>
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_apply_kernel(P p, int64_t n, const typename P::State* __restrict__ summaries) {
+    using S = typename P::State;
+    __shared__ S s_wave[WINDOW_BLOCK / 64];
+    const int64_t base = (int64_t)blockIdx.x * WINDOW_TILE_ROWS;
+    S carry = blockIdx.x > 0 ? summaries[blockIdx.x - 1] : P::identity();
+#pragma unroll
+    for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+        const int64_t pos = base + r * WINDOW_BLOCK + threadIdx.x;
+        S total;
+        const S incl = block_scan_inclusive<P>(pos < n ? p.load(pos, n) : P::identity(), s_wave, total);
+        if (pos < n) p.store(pos, n, P::combine(carry, incl));
+        carry = P::combine(carry, total);
+    }
+}
+
+// ---- partition / peer bounds -------------------------------------------------------------------------------------------------
+struct ForwardBounds {
+    struct State { uint32_t part_start, peer_start, peers; };
+    const uint64_t* part_flags;
+    const uint64_t* peer_flags;
+    uint32_t* part_start;
+    uint32_t* peer_start;
+    uint32_t* peers_to;
+    __device__ static State identity() { return State{0u, 0u, 0u}; }
+    __device__ static State combine(const State& a, const State& b) {
+        return State{a.part_start > b.part_start ? a.part_start : b.part_start, a.peer_start > b.peer_start ? a.peer_start : b.peer_start,
+                     a.peers + b.peers};
+    }
+    __device__ static State shfl_up(const State& x, int d) {
+        return State{__shfl_up(x.part_start, d, 64), __shfl_up(x.peer_start, d, 64), __shfl_up(x.peers, d, 64)};
+    }
+    __device__ State load(int64_t i, int64_t) const {
+        const bool part = bit_at(part_flags, i), peer = bit_at(peer_flags, i);
+        return State{part ? (uint32_t)i : 0u, peer ? (uint32_t)i : 0u, peer ? 1u : 0u};
+    }
+    __device__ void store(int64_t i, int64_t, const State& s) const {
+        part_start[i] = s.part_start;
+        peer_start[i] = s.peer_start;
+        peers_to[i] = s.peers;
+    }
+};
+
+// scan position p is row n - 1 - p: the last row of a segment is the row before the next head (or row n - 1)
+struct BackwardBounds {
+    struct State { uint32_t part_end, peer_end; };
+    const uint64_t* part_flags;
+    const uint64_t* peer_flags;
+    uint32_t* part_end;
+    uint32_t* peer_end;
+    __device__ static State identity() { return State{0xFFFFFFFFu, 0xFFFFFFFFu}; }
+    __device__ static State combine(const State& a, const State& b) {
+        return State{a.part_end < b.part_end ? a.part_end : b.part_end, a.peer_end < b.peer_end ? a.peer_end : b.peer_end};
+    }
+    __device__ static State shfl_up(const State& x, int d) { return State{__shfl_up(x.part_end, d, 64), __shfl_up(x.peer_end, d, 64)}; }
+    __device__ State load(int64_t p, int64_t n) const {
+        const int64_t i = n - 1 - p;
+        const bool last_of_part = i == n - 1 || bit_at(part_flags, i + 1), last_of_peers = i == n - 1 || bit_at(peer_flags, i + 1);
+        return State{last_of_part ? (uint32_t)i : 0xFFFFFFFFu, last_of_peers ? (uint32_t)i : 0xFFFFFFFFu};
+    }
+    __device__ void store(int64_t p, int64_t n, const State& s) const {
+        const int64_t i = n - 1 - p;
+        part_end[i] = s.part_end;
+        peer_end[i] = s.peer_end;
+    }
+};
+
+// ---- segmented scan of an argument ---------------------------------------------------------------------------------------------------
+constexpr uint32_t ARG_HEAD = 1, ARG_HAS_NUMBER = 2, ARG_SAW_NAN = 4;
+constexpr uint64_t F64_QUIET_NAN = 0x7FF8000000000000ull;
+
+__device__ inline double f64_of(uint64_t b) { return __longlong_as_double((long long)b); }
+__device__ inline uint64_t bits_of(double d) { return (uint64_t)__double_as_longlong(d); }
+
+template <int OP>
+struct ArgScan {
+    static constexpr bool FLOAT_MINMAX = OP == WINDOW_OP_MIN_F64 || OP == WINDOW_OP_MAX_F64;
+    // value, non-NULL arguments, ARG_HEAD (a partition starts inside the span) | ARG_HAS_NUMBER | ARG_SAW_NAN (float MIN / MAX)
+    struct State { uint64_t value; uint32_t count, flags; };
+    ColumnRef arg;
+    const uint64_t* part_flags;
+    uint64_t* run_value;
+    uint32_t* run_count;
+    __device__ static State identity() { return State{0ull, 0u, 0u}; }
+    __device__ static State shfl_up(const State& x, int d) { return State{shfl_up_u64(x.value, d), __shfl_up(x.count, d, 64), __shfl_up(x.flags, d, 64)}; }
+    // a side that holds nothing (count 0; float MIN / MAX: no number) contributes nothing: the other side's value stands
+    __device__ static uint64_t merge(const State& a, const State& b) {
+        if (OP == WINDOW_OP_ADD_I64) return a.value + b.value;                      // an empty side holds 0
+        const bool has_a = FLOAT_MINMAX ? (a.flags & ARG_HAS_NUMBER) != 0 : a.count != 0;
+        const bool has_b = FLOAT_MINMAX ? (b.flags & ARG_HAS_NUMBER) != 0 : b.count != 0;
+        uint64_t both;
+        if (OP == WINDOW_OP_ADD_F64) both = bits_of(f64_of(a.value) + f64_of(b.value));
+        else if (OP == WINDOW_OP_MIN_I64) both = (int64_t)b.value < (int64_t)a.value ? b.value : a.value;
+        else if (OP == WINDOW_OP_MAX_I64) both = (int64_t)b.value > (int64_t)a.value ? b.value : a.value;
+        else if (OP == WINDOW_OP_MIN_U64) both = b.value < a.value ? b.value : a.value;
+        else if (OP == WINDOW_OP_MAX_U64) both = b.value > a.value ? b.value : a.value;
+        else if (OP == WINDOW_OP_MIN_F64) both = f64_of(b.value) < f64_of(a.value) ? b.value : a.value;
+        else both = f64_of(b.value) > f64_of(a.value) ? b.value : a.value;
+        return !has_a ? b.value : !has_b ? a.value : both;
+    }
+    // the segmented operator: a head on the right cuts the left side off
+    __device__ static State combine(const State& a, const State& b) {
+        const bool cut = (b.flags & ARG_HEAD) != 0;
+        const uint64_t merged = merge(a, b);
+        return State{cut ? b.value : merged, cut ? b.count : a.count + b.count, cut ? b.flags : a.flags | b.flags};
+    }
+    __device__ State load(int64_t i, int64_t) const {
+        uint64_t value = 0;
+        uint32_t count = 0, flags = bit_at(part_flags, i) ? ARG_HEAD : 0u;
+        if (!arg.validity || bit_at(arg.validity, i)) {
+            count = 1;
+            if (arg.data) {                                                         // (COUNT: the validity is all that is read)
+                uint64_t v = dt_load(arg.dtype, arg.data, i);                       // sign- / zero-extended; Float32 as a double's bits
+                if (OP == WINDOW_OP_ADD_F64 && !dt_is_float(arg.dtype)) v = bits_of(dt_is_unsigned(arg.dtype) ? (double)v : (double)(int64_t)v);
+                if (FLOAT_MINMAX) {
+                    const double d = f64_of(v);
+                    const bool nan = d != d;
+                    flags |= nan ? ARG_SAW_NAN : ARG_HAS_NUMBER;
+                    v = nan ? 0ull : v;
+                }
+                value = v;
+            }
+        }
+        return State{value, count, flags};
+    }
+    __device__ void store(int64_t i, int64_t, const State& s) const {
+        run_value[i] = FLOAT_MINMAX && !(s.flags & ARG_HAS_NUMBER) ? F64_QUIET_NAN : s.value;     // NaNs alone: a NaN
+        run_count[i] = s.count;
+    }
+};
+
+// =============================================================================================
+// elementwise: ranks, gather indices, finish
+// =============================================================================================
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_rank_kernel(int kind, const uint32_t* __restrict__ part_start, const uint32_t* __restrict__ peer_start, const uint32_t* __restrict__ peers_to,
+                   int64_t n, uint64_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * WINDOW_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p0 = part_start[i];
+    uint64_t v;
+    if (kind == WINDOW_ROW_NUMBER) v = (uint64_t)i - p0 + 1;
+    else if (kind == WINDOW_RANK) v = (uint64_t)peer_start[i] - p0 + 1;
+    else v = (uint64_t)peers_to[i] - peers_to[p0] + 1;              // p0 starts a peer group: it is counted on both sides
+    out[i] = v;
+}
+
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_index_kernel(int kind, int64_t offset, const uint32_t* __restrict__ part_start, const uint32_t* __restrict__ part_end,
+                    const uint32_t* __restrict__ frame_end, int64_t n, uint32_t* __restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * WINDOW_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t r;
+    if (kind == WINDOW_LAG) r = offset <= i - (int64_t)part_start[i] ? (uint32_t)(i - offset) : WINDOW_NULL_INDEX;
+    else if (kind == WINDOW_LEAD) r = offset <= (int64_t)part_end[i] - i ? (uint32_t)(i + offset) : WINDOW_NULL_INDEX;
+    else if (kind == WINDOW_FIRST) r = part_start[i];
+    else r = frame_end ? frame_end[i] : (uint32_t)i;
+    idx[i] = r;
+}
+
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_finish_kernel(int kind, int out_dtype, const uint64_t* __restrict__ run_value, const uint32_t* __restrict__ run_count,
+                     const uint32_t* __restrict__ frame_end, int64_t n, void* __restrict__ out, uint64_t* __restrict__ validity) {
+    const int64_t i = (int64_t)blockIdx.x * WINDOW_BLOCK + threadIdx.x;
+    bool valid = false;
+    if (i < n) {
+        const int64_t j = frame_end ? (int64_t)frame_end[i] : i;
+        const uint32_t count = run_count[j];
+        valid = count != 0;
+        if (kind == WINDOW_FINISH_COUNT) {
+            static_cast<uint64_t*>(out)[i] = count;
+        } else if (kind == WINDOW_FINISH_AVG) {
+            static_cast<double*>(out)[i] = valid ? f64_of(run_value[j]) / (double)count : 0.0;
+        } else {
+            dt_store(out_dtype, out, i, valid ? run_value[j] : 0ull);
+        }
+    }
+    const uint64_t word = __ballot(valid);                          // 64 consecutive rows from a multiple of 64: one validity word
+    if (validity && (threadIdx.x & 63) == 0 && i < n) validity[i >> 6] = word;
+}
+
+inline unsigned row_blocks(int64_t n) { return (unsigned)((n + WINDOW_BLOCK - 1) / WINDOW_BLOCK); }
+
+template <class P>
+hipError_t run_tiles(const LaunchCfg& cfg, const P& p, int64_t n, void* temp) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((window_tiles_kernel<P>), dim3((unsigned)window_tiles(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, p, n,
+                       static_cast<typename P::State*>(temp));
+    return hipGetLastError();
+}
+template <class P>
+hipError_t run_summaries(const LaunchCfg& cfg, int64_t n, void* temp) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((window_summaries_kernel<P>), dim3(1), dim3(WINDOW_BLOCK), 0, cfg.stream, static_cast<typename P::State*>(temp), window_tiles(n));
+    return hipGetLastError();
+}
+template <class P>
+hipError_t run_apply(const LaunchCfg& cfg, const P& p, int64_t n, const void* temp) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((window_apply_kernel<P>), dim3((unsigned)window_tiles(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, p, n,
+                       static_cast<const typename P::State*>(temp));
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// the widest state (ArgScan: 16 bytes) sizes the scratch of every scan
+size_t window_scan_temp_bytes(int64_t n) { return (size_t)(window_tiles(n) > 0 ? window_tiles(n) : 1) * 16; }
+static_assert(sizeof(ArgScan<WINDOW_OP_ADD_I64>::State) == 16 && sizeof(ForwardBounds::State) <= 16 && sizeof(BackwardBounds::State) <= 16,
+              "window_scan_temp_bytes counts 16 bytes per tile summary");
+
+hipError_t launch_window_flags(const LaunchCfg& cfg, const WindowKeys& K, int64_t n, uint64_t* part_flags, uint64_t* peer_flags) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(window_flags_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, K, n, part_flags, peer_flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_bounds_forward_tiles(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, void* temp) {
+    return run_tiles(cfg, ForwardBounds{part_flags, peer_flags, nullptr, nullptr, nullptr}, n, temp);
+}
+hipError_t launch_window_bounds_forward_summaries(const LaunchCfg& cfg, int64_t n, void* temp) { return run_summaries<ForwardBounds>(cfg, n, temp); }
+hipError_t launch_window_bounds_forward_apply(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, const void* temp,
+                                              uint32_t* part_start, uint32_t* peer_start, uint32_t* peers_to) {
+    return run_apply(cfg, ForwardBounds{part_flags, peer_flags, part_start, peer_start, peers_to}, n, temp);
+}
+hipError_t launch_window_bounds_backward_tiles(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, void* temp) {
+    return run_tiles(cfg, BackwardBounds{part_flags, peer_flags, nullptr, nullptr}, n, temp);
+}
+hipError_t launch_window_bounds_backward_summaries(const LaunchCfg& cfg, int64_t n, void* temp) { return run_summaries<BackwardBounds>(cfg, n, temp); }
+hipError_t launch_window_bounds_backward_apply(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, const void* temp,
+                                               uint32_t* part_end, uint32_t* peer_end) {
+    return run_apply(cfg, BackwardBounds{part_flags, peer_flags, part_end, peer_end}, n, temp);
+}
+
+hipError_t launch_window_rank(const LaunchCfg& cfg, int kind, const uint32_t* part_start, const uint32_t* peer_start, const uint32_t* peers_to,
+                              int64_t n, uint64_t* out) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(window_rank_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, kind, part_start, peer_start, peers_to, n, out);
+    return hipGetLastError();
+}
+hipError_t launch_window_index(const LaunchCfg& cfg, int kind, int64_t offset, const uint32_t* part_start, const uint32_t* part_end,
+                               const uint32_t* frame_end, int64_t n, uint32_t* idx) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(window_index_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, kind, offset, part_start, part_end, frame_end, n, idx);
+    return hipGetLastError();
+}
+
+#define WINDOW_OP_DISPATCH(op, CALL)                                           \
+    switch (op) {                                                              \
+        case WINDOW_OP_ADD_I64: return CALL(WINDOW_OP_ADD_I64);                \
+        case WINDOW_OP_ADD_F64: return CALL(WINDOW_OP_ADD_F64);                \
+        case WINDOW_OP_MIN_I64: return CALL(WINDOW_OP_MIN_I64);                \
+        case WINDOW_OP_MAX_I64: return CALL(WINDOW_OP_MAX_I64);                \
+        case WINDOW_OP_MIN_U64: return CALL(WINDOW_OP_MIN_U64);                \
+        case WINDOW_OP_MAX_U64: return CALL(WINDOW_OP_MAX_U64);                \
+        case WINDOW_OP_MIN_F64: return CALL(WINDOW_OP_MIN_F64);                \
+        case WINDOW_OP_MAX_F64: return CALL(WINDOW_OP_MAX_F64);                \
+        default: return hipErrorInvalidValue;                                  \
+    }
+
+hipError_t launch_window_scan_tiles(const LaunchCfg& cfg, int op, const ColumnRef& arg, const uint64_t* part_flags, int64_t n, void* temp) {
+#define CALL(OP) run_tiles(cfg, ArgScan<OP>{arg, part_flags, nullptr, nullptr}, n, temp)
+    WINDOW_OP_DISPATCH(op, CALL)
+#undef CALL
+}
+hipError_t launch_window_scan_summaries(const LaunchCfg& cfg, int op, int64_t n, void* temp) {
+#define CALL(OP) run_summaries<ArgScan<OP>>(cfg, n, temp)
+    WINDOW_OP_DISPATCH(op, CALL)
+#undef CALL
+}
+hipError_t launch_window_scan_apply(const LaunchCfg& cfg, int op, const ColumnRef& arg, const uint64_t* part_flags, int64_t n, const void* temp,
+                                    uint64_t* run_value, uint32_t* run_count) {
+#define CALL(OP) run_apply(cfg, ArgScan<OP>{arg, part_flags, run_value, run_count}, n, temp)
+    WINDOW_OP_DISPATCH(op, CALL)
+#undef CALL
+}
+
+hipError_t launch_window_finish(const LaunchCfg& cfg, int kind, int out_dtype, const uint64_t* run_value, const uint32_t* run_count,
+                                const uint32_t* frame_end, int64_t n, void* out, uint64_t* validity) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(window_finish_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, kind, out_dtype, run_value, run_count, frame_end, n,
+                       out, validity);
+    return hipGetLastError();
+}
+
+}  // namespace bhip

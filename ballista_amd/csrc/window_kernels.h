@@ -1,0 +1,82 @@
+// window_kernels.h — launchers of kernels_window.hip: what WindowAggExec (host/ops_window.cpp) runs over its SORTED input.
+//
+// Every window function here is a scan or a gather over 4-byte and 8-byte streams:
+//   boundary flags  ->  partition / peer bounds (scans of the flags)  ->  rank or index vectors (elementwise)
+//                   ->  segmented inclusive scan of an argument       ->  finish (read the running state at the frame's last row)
+// The scans are the multi-launch form: per-tile summaries, ONE workgroup's scan of the summaries, then the apply pass.  No
+// workgroup ever waits for another one.  A tile is WINDOW_TILE_ROWS rows whatever the device and the grid, so the order of every
+// floating-point addition is a function of the row positions alone: two runs over the same input give the same bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kernels.h"
+
+namespace bhip {
+
+constexpr int WINDOW_BLOCK = 256;                                  // threads of a workgroup: four waves of 64
+constexpr int WINDOW_ROUNDS = 4;                                   // a tile is scanned in rounds of WINDOW_BLOCK consecutive rows
+constexpr int WINDOW_TILE_ROWS = 1024;                             // rows per tile summary (mirrored as ballista_amd.plan.WINDOW_TILE_ROWS)
+static_assert(WINDOW_TILE_ROWS == WINDOW_BLOCK * WINDOW_ROUNDS, "a tile is WINDOW_ROUNDS rounds of one row per thread");
+constexpr int WINDOW_SUMMARY_STEP = 256;                           // tile summaries the second level scans per step (one per thread)
+constexpr int WINDOW_MAX_KEYS = 8;                                 // partition keys, and order keys, of one specification
+constexpr uint32_t WINDOW_NULL_INDEX = 0xFFFFFFFFu;                // the NULL row of the outer-join gather (take_column_nullable)
+
+// the evaluated key columns of the sorted rows: col[0 .. n_part) partition keys, col[n_part .. n_part + n_order) order keys
+struct WindowKeys {
+    int32_t n_part, n_order;
+    ColumnRef col[2 * WINDOW_MAX_KEYS];
+};
+// bit i of part_flags: row i starts a partition (a partition key differs from row i - 1's, or i == 0); of peer_flags: row i starts
+// a peer group (it starts a partition, or an order key differs).  NULL equals NULL, fixed widths compare by bits, Utf8 by bytes.
+// Both bitmaps have (n + 63) / 64 words; the bits past n in the last word are 0.
+hipError_t launch_window_flags(const LaunchCfg& cfg, const WindowKeys& K, int64_t n, uint64_t* part_flags, uint64_t* peer_flags);
+
+// bytes of the scratch every scan below needs for its tile summaries
+size_t window_scan_temp_bytes(int64_t n);
+inline int64_t window_tiles(int64_t n) { return (n + WINDOW_TILE_ROWS - 1) / WINDOW_TILE_ROWS; }
+
+// part_start[i] / peer_start[i]: first row of row i's partition / peer group (inclusive max-scan of flag ? i : 0);
+// peers_to[i]: peer groups that start at or before row i (inclusive sum of the peer flags)
+hipError_t launch_window_bounds_forward_tiles(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, void* temp);
+hipError_t launch_window_bounds_forward_summaries(const LaunchCfg& cfg, int64_t n, void* temp);
+hipError_t launch_window_bounds_forward_apply(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, const void* temp,
+                                              uint32_t* part_start, uint32_t* peer_start, uint32_t* peers_to);
+// part_end[i] / peer_end[i]: last row of row i's partition / peer group (the mirror image: inclusive min-scan from the right)
+hipError_t launch_window_bounds_backward_tiles(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, void* temp);
+hipError_t launch_window_bounds_backward_summaries(const LaunchCfg& cfg, int64_t n, void* temp);
+hipError_t launch_window_bounds_backward_apply(const LaunchCfg& cfg, const uint64_t* part_flags, const uint64_t* peer_flags, int64_t n, const void* temp,
+                                               uint32_t* part_end, uint32_t* peer_end);
+
+// ROW_NUMBER / RANK / DENSE_RANK as UInt64
+enum WindowRankKind : int32_t { WINDOW_ROW_NUMBER = 0, WINDOW_RANK = 1, WINDOW_DENSE_RANK = 2 };
+hipError_t launch_window_rank(const LaunchCfg& cfg, int kind, const uint32_t* part_start, const uint32_t* peer_start, const uint32_t* peers_to,
+                              int64_t n, uint64_t* out);
+// the row each output row reads, for the outer-join gather: LAG / LEAD by `offset` rows (WINDOW_NULL_INDEX outside the partition),
+// the partition's first row, the frame's last row (`frame_end`: part_end, peer_end, or null = the row itself)
+enum WindowIndexKind : int32_t { WINDOW_LAG = 0, WINDOW_LEAD = 1, WINDOW_FIRST = 2, WINDOW_LAST = 3 };
+hipError_t launch_window_index(const LaunchCfg& cfg, int kind, int64_t offset, const uint32_t* part_start, const uint32_t* part_end,
+                               const uint32_t* frame_end, int64_t n, uint32_t* idx);
+
+// segmented inclusive scan of one argument column; the segment heads are the partition flags.  The running state of row i is
+// (value, number of non-NULL arguments) over rows part_start[i] .. i; a NULL contributes nothing.  The value is 64 bits wide:
+// narrower integers are sign- or zero-extended and Float32 is widened to Float64 on load (exact, and MIN / MAX commute with it).
+enum WindowScanOp : int32_t {
+    WINDOW_OP_ADD_I64 = 0,      // wrapping 64-bit add (signed and unsigned alike); a null `arg.data`: only the count is kept
+    WINDOW_OP_ADD_F64 = 1,      // Float64 add; integer arguments are converted on load (AVG)
+    WINDOW_OP_MIN_I64 = 2, WINDOW_OP_MAX_I64 = 3, WINDOW_OP_MIN_U64 = 4, WINDOW_OP_MAX_U64 = 5,
+    // state (has a number, value, saw a NaN): a NaN is skipped unless nothing else is there, and the rule stays associative
+    WINDOW_OP_MIN_F64 = 6, WINDOW_OP_MAX_F64 = 7
+};
+hipError_t launch_window_scan_tiles(const LaunchCfg& cfg, int op, const ColumnRef& arg, const uint64_t* part_flags, int64_t n, void* temp);
+hipError_t launch_window_scan_summaries(const LaunchCfg& cfg, int op, int64_t n, void* temp);
+// run_value[i]: the value as 64 bits (a MIN / MAX over NaNs alone: a NaN); run_count[i]: the non-NULL count
+hipError_t launch_window_scan_apply(const LaunchCfg& cfg, int op, const ColumnRef& arg, const uint64_t* part_flags, int64_t n, const void* temp,
+                                    uint64_t* run_value, uint32_t* run_count);
+
+// out[i] from the running state at row frame_end[i] (null: at row i itself).  VALUE: the value narrowed to `out_dtype`, NULL when
+// the count is 0; AVG: value / (double)count as Float64, NULL when the count is 0; COUNT: the count as UInt64 (validity may be null)
+enum WindowFinishKind : int32_t { WINDOW_FINISH_VALUE = 0, WINDOW_FINISH_AVG = 1, WINDOW_FINISH_COUNT = 2 };
+hipError_t launch_window_finish(const LaunchCfg& cfg, int kind, int out_dtype, const uint64_t* run_value, const uint32_t* run_count,
+                                const uint32_t* frame_end, int64_t n, void* out, uint64_t* validity);
+
+}  // namespace bhip

@@ -186,6 +186,35 @@ class PhysicalSortExpr:
     nulls_first: bool = True
 
 
+# ---- window expressions (WindowAggExec; no wire form) ---------------------------------
+
+WINDOW_FUNCTIONS = ("ROW_NUMBER", "RANK", "DENSE_RANK", "LAG", "LEAD", "FIRST_VALUE", "LAST_VALUE", "SUM", "AVG", "COUNT", "MIN", "MAX")
+# DEFAULT is SQL's: RANGE_TO_CURRENT with an ORDER BY, PARTITION without one (resolved when the plan is made)
+WINDOW_FRAMES = ("DEFAULT", "PARTITION", "ROWS_TO_CURRENT", "RANGE_TO_CURRENT")
+
+
+@dataclass(eq=False)
+class WindowExpr:
+    """one function over the operator's window: fun(expr[, offset]) [frame] AS name.  ROW_NUMBER / RANK / DENSE_RANK take no
+    argument; offset is LAG / LEAD's k (a plain non-negative integer); frame matters for the aggregates and LAST_VALUE."""
+    fun: str
+    expr: Optional[PhysicalExpr]
+    name: str
+    offset: int = 1
+    frame: str = "DEFAULT"
+
+    def __post_init__(self):
+        if self.fun not in WINDOW_FUNCTIONS:
+            raise NotImplementedError(f"window function '{self.fun}' is not supported")
+        if self.frame not in WINDOW_FRAMES:
+            raise NotImplementedError(f"window frame '{self.frame}' is not supported")
+
+
+def count_star(name, frame="DEFAULT"):
+    """COUNT(*) OVER (...): COUNT of a UInt8 literal 1"""
+    return WindowExpr("COUNT", Literal(1, UINT8), name, frame=frame)
+
+
 # ---- helpers -------------------------------------------------------------------------
 
 def col(name: str) -> Column:

@@ -883,6 +883,38 @@ class SortExec(ExecutionPlan):
         self.expr, self.input = list(expr), input
 
 
+# rows per tile summary of the window scans (csrc/window_kernels.h WINDOW_TILE_ROWS): it fixes the order of floating-point sums
+WINDOW_TILE_ROWS = 1024
+
+
+class WindowAggExec(ExecutionPlan):
+    """WindowAggExec(partition_by, order_by, window_exprs, input): one window specification, the functions over it.  The operator sorts
+    its single input partition itself (partition keys ASC NULLS FIRST, then order_by, stable) and emits the rows in that order: the
+    input's fields, then one field per E.WindowExpr.  No wire form: the C ABI only (bhip_plan_window)."""
+
+    _FN = {name: i + 1 for i, name in enumerate(E.WINDOW_FUNCTIONS)}
+    _FRAME = {name: i for i, name in enumerate(E.WINDOW_FRAMES)}
+
+    def __init__(self, partition_by: Sequence[E.PhysicalExpr], order_by: Sequence[E.PhysicalSortExpr],
+                 window_exprs: Sequence[E.WindowExpr], input: ExecutionPlan):
+        lw = _Lowered()
+        order = (L.SortExprC * max(1, len(order_by)))()
+        for i, s in enumerate(order_by):
+            order[i] = L.SortExprC(lw.expr(s.expr), 1 if s.descending else 0, 1 if s.nulls_first else 0)
+        fns = (L.WindowExprC * max(1, len(window_exprs)))()
+        for i, w in enumerate(window_exprs):
+            nb = w.name.encode()
+            lw.keep.append(nb)
+            arg = lw.expr(w.expr) if w.expr is not None else L.Expr(None, 0)
+            # a function or frame this mirror does not know goes through as the number it was given: the library refuses it
+            fns[i] = L.WindowExprC(self._FN.get(w.fun, w.fun), arg, int(w.offset), self._FRAME.get(w.frame, w.frame), nb)
+        h = C.c_void_p()
+        L.check(L.lib().bhip_plan_window(input._h, len(partition_by), lw.exprs(list(partition_by)), len(order_by), order,
+                                         len(window_exprs), fns, C.byref(h)))
+        super().__init__(h, input.ctx, [input])
+        self.partition_by, self.order_by, self.window_exprs, self.input = list(partition_by), list(order_by), list(window_exprs), input
+
+
 class RepartitionExec(ExecutionPlan):
     """RepartitionExec::try_new(input, partitioning)  (from_proto.rs:133-164)"""
 

@@ -323,6 +323,41 @@ bhip_status bhip_plan_hash_join(bhip_plan* left, bhip_plan* right, int32_t n_on,
 bhip_status bhip_plan_hash_join_filter(bhip_plan* left, bhip_plan* right, int32_t n_on, const char* const* left_keys,
                                        const char* const* right_keys, int32_t join_type, const bhip_expr* filter, bhip_plan** out);
 bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* exprs, bhip_plan** out); /* :291-331 */
+/* WindowAggExec: ONE window specification — PARTITION BY partition_by ORDER BY order_by — and the functions over it; different
+ * specifications are stacked operators.  The operator sorts its input itself (a single input partition, like SortExec: put a MergeExec
+ * below it otherwise) by the partition keys ASC NULLS FIRST and then the order keys as given, with SortExec's stable sort, and the
+ * rows leave in that order in one batch: the input's fields followed by one field per window expression.  Two rows are in one
+ * partition when every partition key is equal and peers when every order key is equal as well — NULL equals NULL, floats by bit
+ * pattern, Utf8 by bytes (the GROUP BY rule).  At most 8 partition keys and 8 order keys (BHIP_ENOTIMPL beyond).
+ *   ROW_NUMBER, RANK, DENSE_RANK   no argument; UInt64, not nullable (RANK / DENSE_RANK without order_by: 1 on every row)
+ *   LAG(x, k), LEAD(x, k)          x: any fixed-width type, Boolean, Utf8; k = `offset` >= 0 rows; the type of x, nullable: NULL
+ *                                  where row i -/+ k lies outside the partition (no default value)
+ *   FIRST_VALUE(x), LAST_VALUE(x)  the type of x; the partition's first row / the FRAME's last row
+ *   SUM, AVG, COUNT, MIN, MAX      over the frame, with the result types and NULL rules of a Final HashAggregateExec: SUM of signed /
+ *                                  unsigned integers Int64 / UInt64 (wrapping), floating SUM and every AVG Float64, COUNT UInt64 and
+ *                                  never NULL, MIN / MAX the type of x (NaN skipped unless nothing else is there); NULL when the frame
+ *                                  holds no non-NULL value.  MIN / MAX over Utf8 or Boolean: BHIP_ENOTIMPL.  COUNT(*) = COUNT of a
+ *                                  UInt8 literal 1.
+ * Frames (the aggregates and LAST_VALUE; ignored elsewhere): PARTITION = the whole partition; ROWS_TO_CURRENT = UNBOUNDED PRECEDING
+ * .. CURRENT ROW; RANGE_TO_CURRENT = UNBOUNDED PRECEDING .. the last peer of the current row; DEFAULT = SQL's: RANGE_TO_CURRENT with
+ * an order_by, PARTITION without one (resolved when the plan is made).  Sliding frames, NTILE, PERCENT_RANK, CUME_DIST, NTH_VALUE and
+ * IGNORE NULLS are not there.  No wire form (the reference's PhysicalPlanNode has no window node). */
+typedef enum {
+    BHIP_WIN_ROW_NUMBER = 1, BHIP_WIN_RANK = 2, BHIP_WIN_DENSE_RANK = 3, BHIP_WIN_LAG = 4, BHIP_WIN_LEAD = 5, BHIP_WIN_FIRST_VALUE = 6,
+    BHIP_WIN_LAST_VALUE = 7, BHIP_WIN_SUM = 8, BHIP_WIN_AVG = 9, BHIP_WIN_COUNT = 10, BHIP_WIN_MIN = 11, BHIP_WIN_MAX = 12
+} bhip_window_fn;
+typedef enum {
+    BHIP_FRAME_DEFAULT = 0, BHIP_FRAME_PARTITION = 1, BHIP_FRAME_ROWS_TO_CURRENT = 2, BHIP_FRAME_RANGE_TO_CURRENT = 3
+} bhip_window_frame;
+typedef struct {
+    int32_t fn;              /* bhip_window_fn */
+    bhip_expr arg;           /* ROW_NUMBER / RANK / DENSE_RANK: unused (nodes may be NULL) */
+    int64_t offset;          /* LAG / LEAD: k, a plain number (not an expression) */
+    int32_t frame;           /* bhip_window_frame */
+    const char* name;        /* output field name */
+} bhip_window_expr;
+bhip_status bhip_plan_window(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
+                             const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns, bhip_plan** out);
 bhip_status bhip_plan_repartition(bhip_plan* input, int32_t scheme, int32_t n_exprs, const bhip_expr* hash_exprs,
                                   int32_t partition_count, bhip_plan** out);                         /* :133-164 */
 bhip_status bhip_plan_coalesce_batches(bhip_plan* input, int64_t target_batch_size, bhip_plan** out);  /* :122-128 */

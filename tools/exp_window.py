@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""What WindowAggExec costs on top of the sort beneath it (run on the GPU box).
+
+2^26 rows (ROWS overrides) of an Int64 partition key with about 2^16 values, an Int64 order key and a Float64 argument, in one batch.
+Three plans, a fresh plan per step as bench.py does, WARMUP untimed steps and then RUNS timed ones (host clock around collect() and
+a device synchronise):
+  SortExec([p, o])                                              the sort alone, over the keys the operator sorts by
+  WindowAggExec([p], [o], [ROW_NUMBER, RANK])
+  WindowAggExec([p], [o], [SUM(v) ROWS_TO_CURRENT, LAG(v, 1)])
+Prints each median, the window pass as the difference from the sort, the GB/s that difference amounts to against the bytes the pass
+must read and write (the two keys, the argument, and the columns it adds), and the per-launch totals of every window_* launch and of
+the gathers from the context's kernel statistics (BHIP_KERNEL_TIMING=1).
+  tools/exp_window.py > profiles/window.txt"""
+import json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("BHIP_KERNEL_TIMING", "1")
+
+import numpy as np
+
+import ballista_amd as ba
+from ballista_amd import expr as E
+from ballista_amd.expr import col
+
+
+def main():
+    n = int(os.environ.get("ROWS", 1 << 26))
+    runs, warmup = int(os.environ.get("RUNS", 5)), int(os.environ.get("WARMUP", 1))
+    rng = np.random.default_rng(1)
+    ctx = ba.Context(0)
+    batch = ba.RecordBatch.from_columns(ctx, [("p", "Int64", rng.integers(0, 1 << 16, n), None), ("o", "Int64", rng.integers(0, 1 << 40, n), None),
+                                              ("v", "Float64", rng.uniform(0.5, 2.0, n), None)])
+    keys = [E.PhysicalSortExpr(col("p")), E.PhysicalSortExpr(col("o"))]
+    leaf = lambda: ba.MemoryExec([[batch]], ctx)
+    plans = {
+        "sort": (lambda: ba.SortExec(keys, leaf()), 0),
+        # read p, o; write two UInt64 columns
+        "row_number+rank": (lambda: ba.WindowAggExec([col("p")], keys[1:], [E.WindowExpr("ROW_NUMBER", None, "rn"), E.WindowExpr("RANK", None, "rk")], leaf()),
+                            16 + 16),
+        # read p, o, v; write a Float64 sum and a Float64 lag, each with a validity bit
+        "running_sum+lag": (lambda: ba.WindowAggExec([col("p")], keys[1:], [E.WindowExpr("SUM", col("v"), "s", frame="ROWS_TO_CURRENT"),
+                                                                            E.WindowExpr("LAG", col("v"), "l", 1)], leaf()), 24 + 16.25),
+    }
+    print(json.dumps(dict(rows=n, partitions=1 << 16, runs=runs, warmup=warmup, tile_rows=ba.plan.WINDOW_TILE_ROWS, cus=ctx.device_cus())), flush=True)
+    medians = {}
+    for name, (make, bytes_per_row) in plans.items():
+        ms = []
+        for it in range(warmup + runs):
+            plan = make()
+            ctx.synchronize()
+            if it == warmup:
+                ctx.kernel_stats(reset=True)
+            t0 = time.perf_counter()
+            out = plan.collect()
+            ctx.synchronize()
+            if it >= warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+            assert sum(b.num_rows for b in out) == n
+            del plan, out
+        medians[name] = sorted(ms)[len(ms) // 2]
+        line = dict(plan=name, ms_median=round(medians[name], 3), ms=[round(x, 3) for x in ms])
+        if name != "sort":
+            extra = medians[name] - medians["sort"]
+            line.update(window_pass_ms=round(extra, 3), pass_bytes_per_row=bytes_per_row,
+                        pass_GBps=round(n * bytes_per_row / (extra * 1e-3) / 1e9, 1) if extra > 0 else None)
+        print(json.dumps(line), flush=True)
+        ks = ctx.kernel_stats(reset=True)
+        for k in sorted(ks, key=lambda k: -ks[k][0]):
+            if name == "sort" or k.startswith("window_") or k.startswith("take_") or k == "scan_project":
+                print(f"    {k:36s} {ks[k][0] / runs:9.3f} ms/step  {ks[k][1] // runs:4d} launches/step", flush=True)
+
+
+if __name__ == "__main__":
+    main()
