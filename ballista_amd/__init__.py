@@ -16,6 +16,6 @@ from . import expr, plan, tpch  # noqa: F401,E402
 from ._lib import (BallistaError, ExecutionError, HipError, NotImplementedOnGpu, PlanError, LIB_PATH)  # noqa: F401,E402
 from .plan import (Context, RecordBatch, RecordBatchStream, ExecutionPlan, Partitioning, MemoryExec, FilterExec,  # noqa: F401,E402
                    ProjectionExec, HashAggregateExec, HashJoinExec, SortExec, RepartitionExec, CoalesceBatchesExec,
-                   MergeExec, GlobalLimitExec, LocalLimitExec, ArrowStreamExec, ParquetExec, CsvExec, IpcFileExec, WindowAggExec)
+                   MergeExec, GlobalLimitExec, LocalLimitExec, ArrowStreamExec, ParquetExec, CsvExec, IpcFileExec, WindowAggExec, NestedLoopJoinExec)
 
 __version__ = "0.1.0"

@@ -134,6 +134,7 @@ SYMBOLS = {
     "bhip_ctx_lean_key_form": (C.c_char_p, [_P]),
     "bhip_ctx_sort_limit_form": (C.c_char_p, [_P]),
     "bhip_ctx_join_key_form": (C.c_char_p, [_P]),
+    "bhip_ctx_nested_loop_form": (C.c_char_p, [_P]),
     "bhip_ctx_device_cus": (C.c_int32, [_P]),
     "bhip_ctx_kernel_stats": (C.c_int32, [_P, C.c_int32, C.c_char_p, C.c_size_t]),
     "bhip_batch_from_host": (C.c_int32, [_P, C.c_int32, C.POINTER(ColumnDesc), C.c_int64, _PP]),
@@ -165,6 +166,7 @@ SYMBOLS = {
                                              C.c_int32, C.POINTER(Aggregate), _PP]),
     "bhip_plan_hash_join": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, _PP]),
     "bhip_plan_hash_join_filter": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.POINTER(Expr), _PP]),
+    "bhip_plan_nested_loop_join": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(Expr), _PP]),
     "bhip_plan_sort": (C.c_int32, [_P, C.c_int32, C.POINTER(SortExprC), _PP]),
     "bhip_plan_window": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.c_int32, C.POINTER(SortExprC), C.c_int32, C.POINTER(WindowExprC), _PP]),
     "bhip_plan_repartition": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(Expr), C.c_int32, _PP]),

@@ -126,6 +126,12 @@ const char* bhip_ctx_join_key_form(bhip_ctx* ctx) {
     return name.c_str();
 }
 
+const char* bhip_ctx_nested_loop_form(bhip_ctx* ctx) {
+    static thread_local std::string name;
+    name = ctx ? ctx->p->nested_loop_form() : std::string();
+    return name.c_str();
+}
+
 // ---- batches ------------------------------------------------------------------------------------------
 static bhip_batch* wrap_batch(BatchPtr b) {
     auto h = new bhip_batch();
@@ -318,6 +324,13 @@ bhip_status bhip_plan_hash_join_filter(bhip_plan* left, bhip_plan* right, int32_
     std::vector<std::pair<std::string, std::string>> on;
     for (int i = 0; i < n_on; ++i) { need(left_keys[i], "left key"); need(right_keys[i], "right key"); on.push_back({left_keys[i], right_keys[i]}); }
     *out = wrap_plan(std::make_shared<HashJoinExec>(plan_of(left, "left"), plan_of(right, "right"), on, join_type, parse_expr(*filter)));
+    BHIP_API_END
+}
+
+bhip_status bhip_plan_nested_loop_join(bhip_plan* left, bhip_plan* right, int32_t join_type, const bhip_expr* filter, bhip_plan** out) {
+    BHIP_API_BEGIN
+    need(out, "out");
+    *out = wrap_plan(std::make_shared<NestedLoopJoinExec>(plan_of(left, "left"), plan_of(right, "right"), join_type, filter ? parse_expr(*filter) : nullptr));
     BHIP_API_END
 }
 

@@ -345,6 +345,16 @@ std::string Context::join_key_form() {
     return k_join_key_form_;
 }
 
+void Context::set_nested_loop_form(const char* form) {
+    std::lock_guard<std::mutex> g(mu_);
+    k_nested_loop_form_ = form ? form : "";
+}
+
+std::string Context::nested_loop_form() {
+    std::lock_guard<std::mutex> g(mu_);
+    return k_nested_loop_form_;
+}
+
 void Context::kernel_time(bool reset, double* ms, uint64_t* launches) {
     std::lock_guard<std::mutex> g(mu_);
     if (ms) *ms = k_ms_;

@@ -92,6 +92,10 @@ public:
     // columns: keys of any width — also when a probe batch forced it beside a packed table); "" before the first one
     void set_join_key_form(const char* form);
     std::string join_key_form();
+    // how NestedLoopJoinExec ran its last probe batch: "compare" (the fused kernel), "general" (chunked candidates through the
+    // filter), "cross" (no filter, pairs emitted directly), "exists" (an existence type without a filter); "" before the first one
+    void set_nested_loop_form(const char* form);
+    std::string nested_loop_form();
     void kernel_time(bool reset, double* ms, uint64_t* launches);
     bool timing_enabled() const { return timing_ > 0; }
     int timing_level() const { return timing_; }
@@ -117,7 +121,7 @@ private:
     bool spin_wait_ = true;
     double k_ms_ = 0;
     uint64_t k_launches_ = 0;
-    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_, k_join_key_form_;
+    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_, k_join_key_form_, k_nested_loop_form_;
     struct PendingTimed { hipEvent_t a, b; const char* name; uint64_t bytes; };
     std::vector<PendingTimed> pending_timed_;
     std::vector<hipEvent_t> event_pool_;

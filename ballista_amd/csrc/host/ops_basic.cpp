@@ -600,9 +600,11 @@ StreamPtr ProjectionExec::execute(int partition, const Exec& ex) const {
         }
     }
     std::shared_ptr<RecordBatchStream> child;
-    if (auto hj = dynamic_cast<const HashJoinExec*>(input_.get())) {
+    auto hj = dynamic_cast<const HashJoinExec*>(input_.get());
+    auto nlj = dynamic_cast<const NestedLoopJoinExec*>(input_.get());
+    if (hj || nlj) {
         // Projection over a join: the join gathers only the columns read here (DataFusion's join copies all of both sides)
-        const Schema& js = *hj->schema();
+        const Schema& js = *input_->schema();
         std::vector<std::string> used;
         for (auto& en : exprs) collect_columns(en.first, used);
         std::vector<bool> needed(js.fields.size(), false);
@@ -610,7 +612,7 @@ StreamPtr ProjectionExec::execute(int partition, const Exec& ex) const {
             const int i = js.index_of(u);
             if (i >= 0) needed[i] = true;
         }
-        child = std::shared_ptr<RecordBatchStream>(hj->execute_needed(partition, ex, needed).release());
+        child = std::shared_ptr<RecordBatchStream>((hj ? hj->execute_needed(partition, ex, needed) : nlj->execute_needed(partition, ex, needed)).release());
     } else {
         child = std::shared_ptr<RecordBatchStream>(input_->execute(partition, ex).release());
     }

@@ -8,8 +8,10 @@
 // dropped when it has the same name as its left partner (Appendix A).  Row order unspecified.
 // The existence joins put ONE side in the output, unchanged: Semi / Anti the build rows with / without a partner, RightSemi /
 // RightAnti the probe rows.  NULL keys never match, so Anti and RightAnti emit the rows that have one (NOT EXISTS semantics).
+// And NestedLoopJoinExec, the join without a key (the last section): its own front end over the same probe tail (JoinExec::Probe).
 #include <mutex>
 
+#include "../nljoin_kernels.h"
 #include "../util_kernels.h"
 #include "hash_kernels.h"
 #include "plan.hpp"
@@ -71,7 +73,7 @@ static bool named_like_left_key(const std::vector<std::pair<std::string, std::st
 }
 
 HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type, ExprPtr filter)
-    : left_(std::move(left)), right_(std::move(right)), on_(std::move(on)), join_type_(join_type), filter_(std::move(filter)) {
+    : JoinExec(std::move(left), std::move(right), join_type, std::move(filter)), on_(std::move(on)) {
     ctx_ = left_->context();
     if (join_type < BHIP_JOIN_INNER || join_type > BHIP_JOIN_RIGHT_ANTI) fail(BHIP_ENOTIMPL, "Unsupported join type");
     // a build row's fate depends on every probe row, and a stream sees one right partition (Left emits its unmatched rows once
@@ -108,7 +110,7 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
         right_cols_.push_back((int)i);
     }
     schema_ = s;
-    if (filter_) check_filter();
+    if (filter_) check_filter(on_);
     // key layout must be valid (surfaces BHIP_ENOTIMPL at plan time); one the packed key cannot hold goes to the wide-key table,
     // whose row-hash program has to be valid instead
     ScanParams P;
@@ -129,7 +131,7 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
 
 // The residual filter is typed against the Inner join's output schema whatever the join type: the left fields, then the right fields
 // minus a right key column named like its left partner (the name then means the left column).  The checks are FilterExec's.
-void HashJoinExec::check_filter() {
+void JoinExec::check_filter(const std::vector<std::pair<std::string, std::string>>& on) {
     const Schema &ls = *left_->schema(), &rs = *right_->schema();
     Schema fs;
     std::vector<FilterCol> origin;
@@ -138,7 +140,7 @@ void HashJoinExec::check_filter() {
         origin.push_back(FilterCol{true, (int)i, ls.fields[i]});
     }
     for (size_t i = 0; i < rs.fields.size(); ++i) {
-        if (named_like_left_key(on_, rs.fields[i].name)) continue;
+        if (named_like_left_key(on, rs.fields[i].name)) continue;
         // (the existence types' outputs would not clash, but the filter's schema does: a ProjectionExec renames)
         if (fs.index_of(rs.fields[i].name) >= 0) fail(BHIP_EINVAL, "join output would have two columns named '" + rs.fields[i].name + "'");
         fs.fields.push_back(rs.fields[i]);
@@ -702,8 +704,12 @@ struct JoinIndices {
 }  // namespace
 
 // ---- probe side: the state of one execute_needed() stream ---------------------------------------------------------------------
-struct HashJoinExec::Probe {
-    const HashJoinExec& J;
+// The front end — where the pairs or candidates of a probe batch come from — is the join's own: the hash join's is the methods from
+// compact() to probe_right_side() below (H: that join; null under a NestedLoopJoinExec, whose front end is NestedLoopJoinExec::Run).
+// The tail is shared: emit / finish, filter_candidates, resolve_kept, select_by_hits, emit_build_rows.
+struct JoinExec::Probe {
+    const JoinExec& J;
+    const HashJoinExec* const H;
     const int partition;
     const Exec& ex;
     const std::vector<bool>&needed, &deferrable;
@@ -723,25 +729,28 @@ struct HashJoinExec::Probe {
     SchemaPtr key_schema;                // the probe-side key columns alone, under their names
     std::vector<BatchPtr> out;
 
-    Probe(const HashJoinExec& j, int part, const Exec& e, const std::vector<bool>& need, const std::vector<bool>& defer)
-        : J(j), partition(part), ex(e), needed(need), deferrable(defer), cfg(e.cfg()), bs(j.build_side(e)), L(*bs->batch), n_lcols(L.cols.size()),
+    Probe(const JoinExec& j, const HashJoinExec* h, std::shared_ptr<const JoinBuildSide> built, int part, const Exec& e, const std::vector<bool>& need,
+          const std::vector<bool>& defer)
+        : J(j), H(h), partition(part), ex(e), needed(need), deferrable(defer), cfg(e.cfg()), bs(std::move(built)), L(*bs->batch), n_lcols(L.cols.size()),
           right_outer(j.join_type_ == BHIP_JOIN_RIGHT || j.join_type_ == BHIP_JOIN_FULL),
-          left_outer(j.join_type_ == BHIP_JOIN_LEFT || j.join_type_ == BHIP_JOIN_FULL), pair(j.pair_keys()),
+          left_outer(j.join_type_ == BHIP_JOIN_LEFT || j.join_type_ == BHIP_JOIN_FULL), pair(h && h->pair_keys()),
           mark_only(build_existence(j.join_type_)), select_only(probe_existence(j.join_type_)),
           anti(j.join_type_ == BHIP_JOIN_ANTI || j.join_type_ == BHIP_JOIN_RIGHT_ANTI), n_lout(select_only ? 0 : n_lcols) {
         for (size_t i = 0; i < n_lout; ++i) need_left = need_left || needed[i];
         if (left_outer || mark_only) {
-            matched = make_buffer(ex, (size_t)(L.n_rows / 32 + 2) * 4);
-            HIP_CHECK(hipMemsetAsync(matched->ptr(), 0, (size_t)(L.n_rows / 32 + 2) * 4, ex.stream));
+            matched = make_buffer(ex, matched_bytes());
+            HIP_CHECK(hipMemsetAsync(matched->ptr(), 0, matched_bytes(), ex.stream));
         }
+        if (!H) return;
         auto ks = std::make_shared<Schema>();
         const Schema& rs = *J.right_->schema();
-        for (auto& p : J.on_) {
+        for (auto& p : H->on_) {
             rcols.push_back(p.second);
             ks->fields.push_back(rs.fields[rs.index_of(p.second)]);
         }
         key_schema = ks;
     }
+    size_t matched_bytes() const { return (size_t)(L.n_rows / 32 + 2) * 4; }
     uint32_t* matched_bits() const { return matched ? matched->as<uint32_t>() : nullptr; }
 
     // output batch from index pairs; o.src: the batch the right columns are gathered from (nullptr: they are NULL).  Columns no
@@ -857,7 +866,7 @@ struct HashJoinExec::Probe {
                 pk = side_keys(ex, probe, rcols, false);
             } catch (const Error& e) {
                 if (!key_width_error(e)) throw;
-                t = sibling = J.wide_sibling(ex, *bs);
+                t = sibling = H->wide_sibling(ex, *bs);
             }
         }
         if (t->wide) pk = side_keys(ex, probe, rcols, true);
@@ -929,35 +938,39 @@ struct HashJoinExec::Probe {
         return filter_indices(ex, *fb, J.filter_, sel);
     }
 
-    void probe_filtered(const JoinBuildSide& t, const ProbeOut& o, const JoinSideKeys& keys, int64_t n_right) {
-        Temp tmp(ex);
-        JoinIndices cand;
-        const uint64_t n_cand = enumerate_pairs(tmp, t, keys, n_right, false, nullptr, "join filter: the key-equal candidate pairs of one probe batch exceed 2^32", cand);
-        // Right / Full / RightSemi / RightAnti answer per probe row of this batch
-        const bool need_hit = right_outer || select_only;
-        TileSelection s(tmp, need_hit ? n_right : 0, false, false, false);
-        if (need_hit) HIP_CHECK(hipMemsetAsync(s.bitmap, 0, ((size_t)(n_right + 63) / 64) * 8, ex.stream));
-        if (n_cand) {
-            const uint32_t *lidx = cand.lidx, *ridx = cand.ridx;
-            BufferPtr sel;
-            const uint64_t n_keep = (uint64_t)filter_candidates(tmp, o, lidx, ridx, n_cand, sel);
-            if (n_keep) {
-                // all kept: the candidates are the pairs, and only the bits are left to set
-                const bool all = n_keep == n_cand, pairs = !mark_only && !select_only;
-                JoinIndices ix = cand;
-                if (pairs && !all) {
-                    ix.lidx = tmp.get<uint32_t>((size_t)n_keep);
-                    ix.ridx = tmp.get<uint32_t>((size_t)n_keep);
-                }
-                if ((pairs && !all) || matched || need_hit)
-                    TIMED_LAUNCH_N(ex, "join_pairs_resolve", n_keep,
-                                   launch_join_pairs_resolve(cfg, all ? nullptr : sel->as<uint32_t>(), lidx, ridx, n_keep, pairs && !all ? ix.lidx : nullptr,
-                                                             pairs && !all ? ix.ridx : nullptr, matched_bits(), need_hit ? s.bitmap : nullptr));
-                if (pairs) finish(tmp, o, ix, n_keep);
-            }
+    // Right / Full / RightSemi / RightAnti answer per probe row of a batch: the `hit` words of its n_right rows (none otherwise)
+    bool need_hit() const { return right_outer || select_only; }
+    TileSelection hit_words(Temp& tmp, int64_t n_right, bool zero) {
+        TileSelection s(tmp, need_hit() ? n_right : 0, false, false, false);
+        if (need_hit() && zero) HIP_CHECK(hipMemsetAsync(s.bitmap, 0, ((size_t)(n_right + 63) / 64) * 8, ex.stream));
+        return s;
+    }
+
+    // candidates (a probe row's consecutive) -> the filter -> join_pairs_resolve: the kept pairs as an output batch, their build rows'
+    // `matched` bits and their probe rows' bits in `hit` (s.bitmap)
+    void resolve_kept(Temp& tmp, const ProbeOut& o, const JoinIndices& cand, uint64_t n_cand, const TileSelection& s) {
+        if (!n_cand) return;
+        const uint32_t *lidx = cand.lidx, *ridx = cand.ridx;
+        BufferPtr sel;
+        const uint64_t n_keep = (uint64_t)filter_candidates(tmp, o, lidx, ridx, n_cand, sel);
+        if (!n_keep) return;
+        // all kept: the candidates are the pairs, and only the bits are left to set
+        const bool all = n_keep == n_cand, pairs = !mark_only && !select_only;
+        JoinIndices ix = cand;
+        if (pairs && !all) {
+            ix.lidx = tmp.get<uint32_t>((size_t)n_keep);
+            ix.ridx = tmp.get<uint32_t>((size_t)n_keep);
         }
-        if (!need_hit) return;
-        // the probe rows with (RightSemi) / without (Right / Full: with NULL left columns; RightAnti) a partner
+        if ((pairs && !all) || matched || need_hit())
+            TIMED_LAUNCH_N(ex, "join_pairs_resolve", n_keep,
+                           launch_join_pairs_resolve(cfg, all ? nullptr : sel->as<uint32_t>(), lidx, ridx, n_keep, pairs && !all ? ix.lidx : nullptr,
+                                                     pairs && !all ? ix.ridx : nullptr, matched_bits(), need_hit() ? s.bitmap : nullptr));
+        if (pairs) finish(tmp, o, ix, n_keep);
+    }
+
+    // the probe rows with (RightSemi) / without (Right / Full: with NULL left columns; RightAnti) a partner, from the batch's `hit` words
+    void select_by_hits(Temp& tmp, const ProbeOut& o, const TileSelection& s, int64_t n_right) {
+        if (!need_hit()) return;
         TIMED_LAUNCH_N(ex, "join_hit_select", n_right, launch_join_hit_select(cfg, s.bitmap, (uint32_t)n_right, right_outer || anti, s.tile_counts));
         HIP_CHECK(exclusive_scan_u32_u64(ex.stream, s.tile_counts, s.n_tiles, s.tile_off, false, s.total, s.scan_tmp));
         const uint64_t n_sel = read_device(ex, s.total);
@@ -966,6 +979,15 @@ struct HashJoinExec::Probe {
         ix.ridx = tmp.get<uint32_t>((size_t)n_sel);
         TIMED_LAUNCH_N(ex, "select_indices", n_right, launch_select_indices(cfg, s.bitmap, s.tile_off, n_right, ix.ridx));
         finish(tmp, o, ix, n_sel);
+    }
+
+    void probe_filtered(const JoinBuildSide& t, const ProbeOut& o, const JoinSideKeys& keys, int64_t n_right) {
+        Temp tmp(ex);
+        JoinIndices cand;
+        const uint64_t n_cand = enumerate_pairs(tmp, t, keys, n_right, false, nullptr, "join filter: the key-equal candidate pairs of one probe batch exceed 2^32", cand);
+        const TileSelection s = hit_words(tmp, n_right, true);
+        resolve_kept(tmp, o, cand, n_cand, s);
+        select_by_hits(tmp, o, s, n_right);
     }
 
     // ---- narrow build side: one pass over the probe rows: ranges -> key-set bit -> rank map / table (kernels_join.hip) -----
@@ -1074,7 +1096,8 @@ struct HashJoinExec::Probe {
         uint64_t* offsets = tmp.get<uint64_t>((size_t)n_left + 1);
         uint64_t* total = tmp.get<uint64_t>(1);
         void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_left));
-        const bool direct = left_outer || bs->unique || J.filter_;          // (a residual filter marks the very rows that passed it)
+        // (a residual filter marks the very rows that passed it; so does every route of a join without keys)
+        const bool direct = left_outer || bs->unique || J.filter_ || !H;
         const bool want_unmatched = left_outer || anti;
         auto flags_of = [&](const JoinBuildSide& t, bool anti_now, bool merge) {
             // a wide table's rows find their slots by their hashes, which are not kept after the build: once more, for this one pass
@@ -1082,7 +1105,7 @@ struct HashJoinExec::Probe {
             JoinSideKeys keys = t.keys.view();
             SideKeys again;
             if (rehash) {
-                again = side_keys(ex, L, J.left_keys_, true);
+                again = side_keys(ex, L, H->left_keys_, true);
                 keys.keys = again.keys->as<uint64_t>();
             }
             TIMED_LAUNCH_N(ex, kernel_name(K_EXISTS_FLAGS, rehash), n_left,
@@ -1111,10 +1134,242 @@ StreamPtr HashJoinExec::execute_needed(int partition, const Exec& ex, const std:
     needed.resize(schema_->fields.size(), true);
     deferrable.resize(schema_->fields.size(), false);
     return StreamPtr(new LazyStream(schema_, [self, partition, ex, needed, deferrable]() {
-        Probe p(*self, partition, ex, needed, deferrable);
+        Probe p(*self, self.get(), self->build_side(ex), partition, ex, needed, deferrable);
         p.probe_right_side();
         p.emit_build_rows();
         return std::move(p.out);
+    }));
+}
+
+// ---- nested loop join ---------------------------------------------------------------------------------------------------------------
+// NestedLoopJoinExec: no key, so no table — the build side is the collected left rows and nothing else, and the candidates of a probe
+// batch are ALL its pairs with them, numbered p = ri * nL + li.  Three routes per probe batch (Context::nested_loop_form):
+//   cross    no filter: the pairs of a chunk [p0, p1) are written out (nlj_cross_pairs) and emitted, a batch per chunk
+//   general  any filter: the same chunks as candidates through the shared tail (filter_candidates -> join_pairs_resolve -> finish);
+//            the matched / hit bits add up over the chunks, the probe rows are selected once after the last one
+//   compare  a filter that is an AND of up to four `left column OP right column` terms: nlj_compare_count -> scan -> nlj_compare_emit
+//            (kernels_nljoin.hip) — a pair costs register compares, and only the partners ever reach memory
+// and `exists` for an existence type without a filter: every row of a side has a partner iff the other side has a row.
+
+static uint64_t nlj_chunk_pairs() {
+    // BHIP_NLJ_CHUNK_PAIRS=<n>: pairs per chunk (a test forces many ragged chunks on a small input); candidates are addressed by
+    // 32-bit positions inside a chunk
+    static const uint64_t chunk = [] {
+        const char* v = getenv("BHIP_NLJ_CHUNK_PAIRS");
+        const long long n = v ? atoll(v) : 0;
+        return n < 1 ? NLJ_CHUNK_PAIRS : (uint64_t)(n > (1ll << 30) ? (1ll << 30) : n);
+    }();
+    return chunk;
+}
+
+NestedLoopJoinExec::NestedLoopJoinExec(PlanPtr left, PlanPtr right, int join_type, ExprPtr filter)
+    : JoinExec(std::move(left), std::move(right), join_type, std::move(filter)) {
+    ctx_ = left_->context();
+    if (join_type < BHIP_JOIN_INNER || join_type > BHIP_JOIN_RIGHT_ANTI) fail(BHIP_ENOTIMPL, "Unsupported join type");
+    // a build row's fate depends on every probe row, and a stream sees one right partition
+    if ((join_type == BHIP_JOIN_LEFT || join_type == BHIP_JOIN_FULL || build_existence(join_type)) && right_->output_partitioning().count > 1)
+        fail(BHIP_ENOTIMPL, std::string(join_name(join_type)) + " join over a right child of " + std::to_string(right_->output_partitioning().count) +
+                                " partitions: put a MergeExec under the right child");
+    const Schema &ls = *left_->schema(), &rs = *right_->schema();
+    auto s = std::make_shared<Schema>();
+    const bool left_nullable = join_type == BHIP_JOIN_RIGHT || join_type == BHIP_JOIN_FULL;
+    const bool right_nullable = join_type == BHIP_JOIN_LEFT || join_type == BHIP_JOIN_FULL;
+    for (auto f : ls.fields) {
+        if (probe_existence(join_type)) break;
+        if (left_nullable) f.nullable = true;
+        s->fields.push_back(f);
+    }
+    for (size_t i = 0; i < rs.fields.size(); ++i) {
+        if (build_existence(join_type)) break;
+        Field f = rs.fields[i];
+        if (right_nullable) f.nullable = true;
+        if (s->index_of(f.name) >= 0) fail(BHIP_EINVAL, "join output would have two columns named '" + f.name + "'");
+        s->fields.push_back(f);
+        right_cols_.push_back((int)i);
+    }
+    schema_ = s;
+    cache_ = std::make_shared<BuildCache>();
+    if (!filter_) return;
+    check_filter({});
+    // the fused form: AND of terms `column OP column`, one column of each side, both of one fixed-width type (so the coercion put
+    // no cast over either).  Anything else — a literal, arithmetic, a cast, Utf8, Boolean, a fifth term — takes the general route.
+    std::vector<ExprPtr> conj{filter_};
+    for (size_t i = 0; i < conj.size();) {
+        const ExprPtr e = conj[i];
+        if (e->kind == BHIP_EXPR_BINARY && e->name == "And" && e->args.size() == 2) {
+            conj[i] = e->args[0];
+            conj.insert(conj.begin() + i + 1, e->args[1]);
+        } else {
+            ++i;
+        }
+    }
+    static const char* const ops[] = {"Eq", "NotEq", "Lt", "LtEq", "Gt", "GtEq"};                     // CmpKind order
+    static const int flipped[] = {CMP_EQ, CMP_NE, CMP_GT, CMP_GE, CMP_LT, CMP_LE};
+    for (auto& e : conj) {
+        int cmp = -1;
+        for (int k = 0; k < 6; ++k)
+            if (e->kind == BHIP_EXPR_BINARY && e->name == ops[k]) cmp = k;
+        if (cmp < 0 || e->args.size() != 2 || e->args[0]->kind != BHIP_EXPR_COLUMN || e->args[1]->kind != BHIP_EXPR_COLUMN) { terms_.clear(); return; }
+        int l = ls.index_of(e->args[0]->name), r = rs.index_of(e->args[1]->name);
+        if (l < 0 || r < 0) {                                  // right column first: the same term with the operator flipped
+            l = ls.index_of(e->args[1]->name);
+            r = rs.index_of(e->args[0]->name);
+            cmp = flipped[cmp];
+        }
+        const int t = l >= 0 && r >= 0 ? ls.fields[l].dtype : 0;
+        if (!t || t != rs.fields[r].dtype || dt_width(t) == 0 || conj.size() > (size_t)NLJ_MAX_TERMS) { terms_.clear(); return; }
+        terms_.push_back(Term{l, r, cmp, dt_is_float(t) ? NLJ_F64 : (t == DT_UINT64 ? NLJ_U64 : NLJ_I64)});
+    }
+}
+
+PlanPtr NestedLoopJoinExec::with_new_children(const std::vector<PlanPtr>& c) const {
+    if (c.size() != 2) fail(BHIP_EINVAL, "NestedLoopJoinExec wrong number of children");
+    return std::make_shared<NestedLoopJoinExec>(c[0], c[1], join_type_, filter_);
+}
+
+std::string NestedLoopJoinExec::describe() const {
+    return std::string("NestedLoopJoinExec: join_type=") + join_name(join_type_) + ", filter=" + (filter_ ? filter_->to_string() : std::string("None"));
+}
+
+// the left child, all its partitions, as one batch; built once and shared by every right partition's task
+std::shared_ptr<const JoinBuildSide> NestedLoopJoinExec::build_side(const Exec& ex) const {
+    std::lock_guard<std::mutex> g(cache_->mu);
+    if (cache_->built) return cache_->built;
+    auto bs = std::make_shared<JoinBuildSide>();
+    std::vector<BatchPtr> parts;
+    const int np = left_->output_partitioning().count;
+    for (int p = 0; p < np; ++p) {
+        auto s = left_->execute(p, ex);
+        while (BatchPtr b = s->next())
+            if (b->n_rows > 0) parts.push_back(materialize_batch(ex, b));
+    }
+    bs->batch = parts.empty() ? empty_batch(ex, left_->schema()) : concat_batches(ex, left_->schema(), parts);
+    // build rows are 32-bit indices, and 0xFFFFFFFF is the NULL row of the outer joins
+    if (bs->batch->n_rows > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "nested loop join build side of more than 2^31 rows");
+    stream_wait(ex);                     // other tasks (other streams) read the batch: complete before it is published
+    cache_->built = bs;
+    return bs;
+}
+
+struct NestedLoopJoinExec::Run : JoinExec::Probe {
+    const NestedLoopJoinExec& N;
+    const uint64_t nL;
+    uint64_t probe_rows = 0;             // of the whole stream
+    Run(const NestedLoopJoinExec& n, int part, const Exec& e, const std::vector<bool>& need, const std::vector<bool>& defer)
+        : Probe(n, nullptr, n.build_side(e), part, e, need, defer), N(n), nL((uint64_t)L.n_rows) {}
+
+    void set_all(void* bits, size_t bytes) { HIP_CHECK(hipMemsetAsync(bits, 0xFF, bytes, ex.stream)); }
+
+    // the candidates [p0, p1) as index vectors in `tmp`
+    JoinIndices pairs_of(Temp& tmp, uint64_t p0, uint64_t p1) {
+        JoinIndices ix;
+        ix.lidx = tmp.get<uint32_t>((size_t)(p1 - p0));
+        ix.ridx = tmp.get<uint32_t>((size_t)(p1 - p0));
+        TIMED_LAUNCH_N(ex, "nlj_cross_pairs", p1 - p0, launch_nlj_cross_pairs(cfg, (uint32_t)nL, p0, p1, ix.lidx, ix.ridx));
+        return ix;
+    }
+
+    // no filter.  Existence types enumerate nothing; the others emit every pair, a batch per chunk.  Either way a side's rows all
+    // have a partner, or none has: the bits are set wholesale.
+    void cross(const ProbeOut& o, int64_t n_right) {
+        if (matched) set_all(matched->ptr(), matched_bytes());
+        Temp tmp(ex);
+        // probe rows come out of here when all have a partner (RightSemi) or none has (RightAnti; Right / Full: with NULL left columns)
+        const bool all_hit = nL > 0;
+        if (need_hit() && (select_only ? all_hit != anti : !all_hit)) {
+            const TileSelection s = hit_words(tmp, n_right, !all_hit);
+            if (all_hit) set_all(s.bitmap, ((size_t)(n_right + 63) / 64) * 8);
+            select_by_hits(tmp, o, s, n_right);
+        }
+        if (mark_only || select_only) return;
+        const uint64_t total = nL * (uint64_t)n_right, chunk = nlj_chunk_pairs();
+        for (uint64_t p0 = 0; p0 < total; p0 += chunk) {
+            Temp ctmp(ex);
+            const uint64_t p1 = std::min(total, p0 + chunk);
+            finish(ctmp, o, pairs_of(ctmp, p0, p1), p1 - p0);
+        }
+    }
+
+    void general(const ProbeOut& o, int64_t n_right) {
+        Temp tmp(ex);
+        const TileSelection s = hit_words(tmp, n_right, true);
+        const uint64_t total = nL * (uint64_t)n_right, chunk = nlj_chunk_pairs();
+        for (uint64_t p0 = 0; p0 < total; p0 += chunk) {
+            Temp ctmp(ex);
+            const uint64_t p1 = std::min(total, p0 + chunk);
+            resolve_kept(ctmp, o, pairs_of(ctmp, p0, p1), p1 - p0, s);
+        }
+        select_by_hits(tmp, o, s, n_right);
+    }
+
+    void compare(const ProbeOut& o, int64_t n_right) {
+        NljTerms T;
+        memset(&T, 0, sizeof(T));
+        T.n = (int32_t)N.terms_.size();
+        for (int i = 0; i < T.n; ++i) {
+            const Term& t = N.terms_[i];
+            T.t[i].build = L.cols[t.left].ref();
+            T.t[i].probe = o.src->cols[t.right].ref();
+            T.t[i].cmp = t.cmp;
+            T.t[i].vclass = t.vclass;
+        }
+        Temp tmp(ex);
+        uint64_t* total = tmp.get<uint64_t>(1);
+        uint32_t* counts = tmp.get<uint32_t>((size_t)n_right + 1);
+        uint64_t* offsets = tmp.get<uint64_t>((size_t)n_right + 1);
+        void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_right));
+        const TileSelection s = hit_words(tmp, n_right, false);                   // (the count kernel writes every word)
+        TIMED_LAUNCH_N(ex, "nlj_compare_count", n_right,
+                       launch_nlj_compare_count(cfg, T, (uint32_t)nL, (uint32_t)n_right, counts, matched_bits(), need_hit() ? s.bitmap : nullptr));
+        if (!mark_only && !select_only) {
+            HIP_CHECK(exclusive_scan_u32_u64(ex.stream, counts, n_right, offsets, false, total, scan_tmp));
+            const uint64_t n = read_device(ex, total);
+            if (n > 0xFFFFFFF0ull) fail(BHIP_EEXEC, "join output of one probe batch exceeds 2^32 rows");
+            if (n) {
+                JoinIndices ix;
+                ix.lidx = tmp.get<uint32_t>((size_t)n);
+                ix.ridx = tmp.get<uint32_t>((size_t)n);
+                TIMED_LAUNCH_N(ex, "nlj_compare_emit", n_right, launch_nlj_compare_emit(cfg, T, (uint32_t)nL, (uint32_t)n_right, offsets, ix.lidx, ix.ridx));
+                finish(tmp, o, ix, n);
+            }
+        }
+        select_by_hits(tmp, o, s, n_right);
+    }
+
+    void run() {
+        // BHIP_NO_NLJ_FUSED=1: the general route where the fused one would run (the A/B partner)
+        static const bool no_fused = env_flag("BHIP_NO_NLJ_FUSED");
+        auto rs = N.right_->execute(partition, ex);
+        while (BatchPtr rb = rs->next()) {
+            const int64_t n_right = rb->n_rows;
+            if (n_right > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "nested loop join probe batch of more than 2^31 rows");
+            probe_rows += (uint64_t)n_right;
+            const ProbeOut o{rb.get(), nullptr, nullptr};
+            const char* form = !N.filter_ ? (mark_only || select_only ? "exists" : "cross") : (!N.terms_.empty() && !no_fused ? "compare" : "general");
+            ex.ctx->set_nested_loop_form(form);
+            if (n_right == 0) continue;
+            if (!N.filter_) cross(o, n_right);
+            else if (form[0] == 'c') compare(o, n_right);
+            else general(o, n_right);
+        }
+        emit_build_rows();
+    }
+};
+
+StreamPtr NestedLoopJoinExec::execute(int partition, const Exec& ex) const {
+    return execute_needed(partition, ex, std::vector<bool>(schema_->fields.size(), true));
+}
+
+StreamPtr NestedLoopJoinExec::execute_needed(int partition, const Exec& ex, const std::vector<bool>& needed_in) const {
+    check_partition(*this, partition);
+    auto self = std::static_pointer_cast<const NestedLoopJoinExec>(shared_from_this());
+    std::vector<bool> needed = needed_in;
+    needed.resize(schema_->fields.size(), true);
+    const std::vector<bool> deferrable(schema_->fields.size(), false);
+    return StreamPtr(new LazyStream(schema_, [self, partition, ex, needed, deferrable]() {
+        Run r(*self, partition, ex, needed, deferrable);
+        r.run();
+        return std::move(r.out);
     }));
 }
 

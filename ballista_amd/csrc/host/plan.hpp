@@ -231,15 +231,39 @@ HashAggResult hash_aggregate(const Exec& ex, Temp& tmp, const ScanParams& P0, co
                              bool nullable, ScanStatus* status, std::atomic<int>* clustered_hint, bool slot_keys);
 
 struct JoinBuildSide;
-class HashJoinExec : public ExecutionPlan {
+// What HashJoinExec and NestedLoopJoinExec share: the two children (left = build side, collected whole; right = probe side, one
+// stream per partition), the join type, the output schema and the filter; and the probe of one right partition (ops_join.cpp
+// JoinExec::Probe), whose tail — candidates -> filter -> kept pairs / matched / hit bits -> output batches, and the build rows at the
+// end of the stream — is one piece of code for both.
+class JoinExec : public ExecutionPlan {
+public:
+    SchemaPtr schema() const override { return schema_; }
+    Partitioning output_partitioning() const override { return right_->output_partitioning(); }
+    std::vector<PlanPtr> children() const override { return {left_, right_}; }
+protected:
+    JoinExec(PlanPtr left, PlanPtr right, int join_type, ExprPtr filter)
+        : left_(std::move(left)), right_(std::move(right)), join_type_(join_type), filter_(std::move(filter)) {}
+    struct Probe;                    // the probe of one right partition against the build side (ops_join.cpp)
+    PlanPtr left_, right_;
+    int join_type_;
+    SchemaPtr schema_;
+    std::vector<int> right_cols_;   // right columns kept in the output
+    ExprPtr filter_;
+    // the columns filter_ reads, each once, in the order the expression first names them (the schema of the batch the filter runs
+    // over at run time is built from this list): column `index` of the left / right child's schema
+    struct FilterCol { bool left; int index; Field field; };
+    std::vector<FilterCol> filter_cols_;
+    // the plan-time checks of filter_ (FilterExec's) against the Inner output schema, and filter_cols_; on: the key pairs (a right key
+    // column named like its left partner is not in that schema)
+    void check_filter(const std::vector<std::pair<std::string, std::string>>& on);
+};
+
+class HashJoinExec : public JoinExec {
 public:
     // filter (may be null): the residual predicate over the Inner join's output schema of the two children — a build row and a probe
     // row are partners when their keys are equal AND it is TRUE (ops_join.cpp "residual filter")
     HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<std::string, std::string>> on, int join_type, ExprPtr filter = nullptr);
     const char* name() const override { return "HashJoinExec"; }
-    SchemaPtr schema() const override { return schema_; }
-    Partitioning output_partitioning() const override { return right_->output_partitioning(); }
-    std::vector<PlanPtr> children() const override { return {left_, right_}; }
     PlanPtr with_new_children(const std::vector<PlanPtr>& c) const override;
     StreamPtr execute(int partition, const Exec& ex) const override;
     // the same stream with only the output columns a parent reads materialised (needed[i]: column i of schema()); the other
@@ -250,20 +274,10 @@ public:
     StreamPtr execute_needed(int partition, const Exec& ex, const std::vector<bool>& needed, const std::vector<bool>& deferrable = {}) const;
     std::string describe() const override;
 private:
+    friend struct JoinExec::Probe;   // the hash front end of the probe reads the keys and the build side
     std::shared_ptr<const JoinBuildSide> build_side(const Exec& ex) const;
-    struct Probe;                    // the probe of one partition against the build side (ops_join.cpp)
-    PlanPtr left_, right_;
     std::vector<std::pair<std::string, std::string>> on_;
     std::vector<std::string> left_keys_;   // on_[i].first
-    int join_type_;
-    SchemaPtr schema_;
-    std::vector<int> right_cols_;   // right columns kept in the output
-    ExprPtr filter_;
-    // the columns filter_ reads, each once, in the order the expression first names them (the schema of the batch the filter runs
-    // over at run time is built from this list): column `index` of the left / right child's schema
-    struct FilterCol { bool left; int index; Field field; };
-    std::vector<FilterCol> filter_cols_;
-    void check_filter();             // the plan-time checks of filter_ (FilterExec's), and filter_cols_
     int narrow_key_width() const;
     bool pair_keys() const;          // TWO 4-byte integer key pairs: packed into one 8-byte key per side, then the single-key machinery
     // the build side (hash table over the whole left child) is built once and shared by every
@@ -275,6 +289,29 @@ private:
     std::shared_ptr<const JoinBuildSide> wide_sibling(const Exec& ex, const JoinBuildSide& packed) const;
     bool static_wide_ = false;                      // the key LAYOUT does not fit the 16-byte packed key: always the wide-key table
     mutable std::atomic<bool> wide_keys_{false};    // a build found key values the packed key cannot hold: later builds skip the attempt
+};
+
+// A join without an equality key (ops_join.cpp "nested loop join"): a build row and a probe row are partners when `filter` is TRUE
+// for the pair; no filter: every pair (the cross join).  All eight join types with HashJoinExec's meaning; output = the left fields
+// then the right fields.  No wire form: the C ABI only (bhip_plan_nested_loop_join).
+class NestedLoopJoinExec : public JoinExec {
+public:
+    NestedLoopJoinExec(PlanPtr left, PlanPtr right, int join_type, ExprPtr filter = nullptr);
+    const char* name() const override { return "NestedLoopJoinExec"; }
+    PlanPtr with_new_children(const std::vector<PlanPtr>& c) const override;
+    StreamPtr execute(int partition, const Exec& ex) const override;
+    // as HashJoinExec::execute_needed: only the output columns a parent reads are gathered (never as views)
+    StreamPtr execute_needed(int partition, const Exec& ex, const std::vector<bool>& needed) const;
+    std::string describe() const override;
+private:
+    struct Run;                      // one right partition against the build rows
+    std::shared_ptr<const JoinBuildSide> build_side(const Exec& ex) const;
+    // filter_ as an AND of 1 .. 4 `left column OP right column` terms over fixed-width columns of one type: the fused route's form
+    // (columns as indices of the children's schemas; nljoin_kernels.h NljTerm without the pointers)
+    struct Term { int left, right, cmp, vclass; };
+    std::vector<Term> terms_;        // empty: the filter (if any) takes the general route
+    struct BuildCache { std::mutex mu; std::shared_ptr<const JoinBuildSide> built; };
+    std::shared_ptr<BuildCache> cache_;
 };
 
 class SortExec : public UnaryExec {

@@ -103,6 +103,12 @@ class Context:
         any width, or BHIP_JOIN_WIDE=1), "" before the first build"""
         return L.lib().bhip_ctx_join_key_form(self._h).decode()
 
+    def nested_loop_form(self):
+        """how NestedLoopJoinExec ran its last probe batch: "compare" (the fused kernel: an AND of up to four column-to-column
+        comparisons), "general" (chunks of candidate pairs through the filter, or BHIP_NO_NLJ_FUSED=1), "cross" (no filter),
+        "exists" (an existence type without a filter), "" before the first one"""
+        return L.lib().bhip_ctx_nested_loop_form(self._h).decode()
+
     def device_cus(self):
         """compute units of the device (the kernels size their grids by it)"""
         return int(L.lib().bhip_ctx_device_cus(self._h))
@@ -867,6 +873,28 @@ class HashJoinExec(ExecutionPlan):
                                                        lw.strings([b for _, b in on]), self._JT[join_type], C.byref(ex), C.byref(h)))
         super().__init__(h, left.ctx, [left, right])
         self.left, self.right, self.on, self.join_type, self.filter = left, right, list(on), join_type, filter
+
+
+# build rows the fused kernel of NestedLoopJoinExec stages in LDS at a time (csrc/nljoin_kernels.h NLJ_BUILD_TILE)
+NLJ_BUILD_TILE = 1024
+
+
+class NestedLoopJoinExec(ExecutionPlan):
+    """The join without an equality key: left is the build side (collected whole), right the probe side.  Rows are partners when
+    `filter` (typed against the Inner output schema: left fields then right fields) is TRUE; filter None: the cross join.  All eight
+    join types as in HashJoinExec; LEFT, FULL, SEMI and ANTI need a right child of one partition (MergeExec).  No wire form: the
+    C ABI only (bhip_plan_nested_loop_join).  Context.nested_loop_form() says which route the last probe batch took."""
+
+    def __init__(self, left: ExecutionPlan, right: ExecutionPlan, join_type: str = INNER, filter: Optional[E.PhysicalExpr] = None):
+        if join_type not in HashJoinExec._JT:
+            raise L.PlanError(L.EINVAL, f"Unsupported join type {join_type}")
+        lw = _Lowered()
+        h = C.c_void_p()
+        ex = lw.expr(filter) if filter is not None else None
+        L.check(L.lib().bhip_plan_nested_loop_join(left._h, right._h, HashJoinExec._JT[join_type], C.byref(ex) if ex is not None else None,
+                                                   C.byref(h)))
+        super().__init__(h, left.ctx, [left, right])
+        self.left, self.right, self.join_type, self.filter = left, right, join_type, filter
 
 
 class SortExec(ExecutionPlan):

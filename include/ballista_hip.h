@@ -322,6 +322,16 @@ bhip_status bhip_plan_hash_join(bhip_plan* left, bhip_plan* right, int32_t n_on,
  * bhip_plan_hash_join.  No wire form (HashJoinExecNode has no field for it). */
 bhip_status bhip_plan_hash_join_filter(bhip_plan* left, bhip_plan* right, int32_t n_on, const char* const* left_keys,
                                        const char* const* right_keys, int32_t join_type, const bhip_expr* filter, bhip_plan** out);
+/* NestedLoopJoinExec: the join without an equality key (a range or band predicate, a cross product, a one-row subquery).  left is the
+ * build side, collected whole; right the probe side, one output stream per right partition.  A left and a right row are partners when
+ * `filter` is TRUE (NULL is not a match); filter NULL: every pair (the cross join).  All eight bhip_join_type values, with the meaning
+ * and the nullability they have in bhip_plan_hash_join; output schema: the left fields then the right fields (SEMI / ANTI: left only,
+ * RIGHT_SEMI / RIGHT_ANTI: right only); two output columns of one name are BHIP_EINVAL.  The filter is typed against the INNER output
+ * schema whatever the join type (so with a filter a name on both sides is BHIP_EINVAL for the existence types too); one that reads no
+ * column is BHIP_ENOTIMPL.  LEFT / FULL / SEMI / ANTI need a right child of one partition (BHIP_ENOTIMPL otherwise: MergeExec).
+ * No wire form (the reference's PhysicalPlanNode has no such node): this entry point only. */
+bhip_status bhip_plan_nested_loop_join(bhip_plan* left, bhip_plan* right, int32_t join_type, const bhip_expr* filter /* NULL: cross */,
+                                       bhip_plan** out);
 bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* exprs, bhip_plan** out); /* :291-331 */
 /* WindowAggExec: ONE window specification — PARTITION BY partition_by ORDER BY order_by — and the functions over it; different
  * specifications are stacked operators.  The operator sorts its input itself (a single input partition, like SortExec: put a MergeExec
@@ -596,6 +606,11 @@ const char* bhip_ctx_sort_limit_form(bhip_ctx* ctx);
  * hashes whose equality test reads the key columns: keys of any width; also reported when a probe batch whose keys outgrew the
  * packed key went through the wide table built beside a packed one); "" before the first build; valid until the next call */
 const char* bhip_ctx_join_key_form(bhip_ctx* ctx);
+/* how NestedLoopJoinExec ran the last probe batch on the context: "compare" (the filter is an AND of up to four column-to-column
+ * comparisons: the fused kernel), "general" (any other filter: chunks of candidate pairs through the filter), "cross" (no filter:
+ * the pairs are emitted directly), "exists" (SEMI / ANTI / RIGHT_SEMI / RIGHT_ANTI without a filter: nothing is enumerated);
+ * "" before the first one; valid until the next call */
+const char* bhip_ctx_nested_loop_form(bhip_ctx* ctx);
 /* compute units of the context's device (what the kernels size their grids by) */
 int32_t bhip_ctx_device_cus(bhip_ctx* ctx);
 
