@@ -642,11 +642,34 @@ bhip_status bhip_batch_concat(bhip_ctx* ctx, int32_t n, bhip_batch* const* batch
     if (n < 1) fail(BHIP_EINVAL, "concat of zero batches");
     std::vector<BatchPtr> parts;
     for (int i = 0; i < n; ++i) { need(batches[i], "batch"); parts.push_back(batches[i]->p); }
+    // the result takes the first part's schema: every other part must have its columns' types (a column copied at another
+    // type's width reads past its buffer).  Names and nullability may differ: a column of the result is nullable when it is in
+    // any part (an operator above trusts the flag: COUNT over a NOT NULL column counts rows, a filter folds IS NULL away).
+    const std::vector<Field>& f0 = parts[0]->schema->fields;
+    std::vector<bool> nullable(f0.size());
+    for (size_t c = 0; c < f0.size(); ++c) nullable[c] = f0[c].nullable;
+    for (int i = 1; i < n; ++i) {
+        const std::vector<Field>& fi = parts[i]->schema->fields;
+        if (fi.size() != f0.size())
+            fail(BHIP_EINVAL, "concat: batch " + std::to_string(i) + " has " + std::to_string(fi.size()) + " columns, batch 0 has " +
+                                  std::to_string(f0.size()));
+        for (size_t c = 0; c < f0.size(); ++c)
+            if (fi[c].dtype != f0[c].dtype)
+                fail(BHIP_EINVAL, "concat: column " + std::to_string(c) + " of batch " + std::to_string(i) + " is " +
+                                      dtype_name(fi[c].dtype) + ", batch 0 has " + dtype_name(f0[c].dtype));
+        for (size_t c = 0; c < f0.size(); ++c) nullable[c] = nullable[c] || fi[c].nullable;
+    }
+    SchemaPtr schema = parts[0]->schema;
+    if (n > 1) {
+        auto s = std::make_shared<Schema>(*parts[0]->schema);
+        for (size_t c = 0; c < f0.size(); ++c) s->fields[c].nullable = nullable[c];
+        schema = s;
+    }
     ctx->p->set_device();
     Exec ex{ctx->p, ctx->p->acquire_stream()};
     BatchPtr r;
     try {
-        r = concat_batches(ex, parts[0]->schema, parts);
+        r = concat_batches(ex, schema, parts);
         HIP_CHECK(hipStreamSynchronize(ex.stream));
     } catch (...) { ctx->p->release_stream(ex.stream); throw; }
     ctx->p->release_stream(ex.stream);

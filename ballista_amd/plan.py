@@ -1207,6 +1207,8 @@ def hash_partition(batch: RecordBatch, exprs: Sequence[E.PhysicalExpr], n: int) 
 
 
 def concat(ctx: Context, batches: Sequence[RecordBatch]) -> RecordBatch:
+    """bhip_batch_concat: the batches' rows in order as one batch.  They must agree in column count and types (PlanError otherwise);
+    a column is nullable in the result when it is in any of them"""
     arr = (C.c_void_p * len(batches))(*[b._h for b in batches])
     h = C.c_void_p()
     L.check(L.lib().bhip_batch_concat(ctx._h, len(batches), arr, C.byref(h)))

@@ -488,6 +488,9 @@ bhip_status bhip_ipc_open_file(const char* path, struct ArrowArrayStream* out);
  * order kept) so the caller can exchange them (RCCL all-to-all) — used by the multi-GPU path. */
 bhip_status bhip_batch_hash_partition(bhip_batch* batch, int32_t n_exprs, const bhip_expr* hash_exprs, int32_t n,
                                       bhip_batch** out /* n handles */);
+/* concat: the rows of batches[0 .. n) in order, as one batch with the first batch's column names.  Every batch must have the first
+ * one's column count and types (BHIP_EINVAL otherwise); a column of the result is nullable when it is in any of them.  n = 1 hands
+ * the batch back as it is. */
 bhip_status bhip_batch_concat(bhip_ctx* ctx, int32_t n, bhip_batch* const* batches, bhip_batch** out);
 
 /* ---- exchange between the GPUs of one node (RCCL over xGMI, inside the library) -----------------------------
