@@ -135,6 +135,7 @@ SYMBOLS = {
     "bhip_ctx_sort_limit_form": (C.c_char_p, [_P]),
     "bhip_ctx_join_key_form": (C.c_char_p, [_P]),
     "bhip_ctx_nested_loop_form": (C.c_char_p, [_P]),
+    "bhip_ctx_join_probe_form": (C.c_char_p, [_P]),
     "bhip_ctx_device_cus": (C.c_int32, [_P]),
     "bhip_ctx_kernel_stats": (C.c_int32, [_P, C.c_int32, C.c_char_p, C.c_size_t]),
     "bhip_batch_from_host": (C.c_int32, [_P, C.c_int32, C.POINTER(ColumnDesc), C.c_int64, _PP]),

@@ -132,6 +132,12 @@ const char* bhip_ctx_nested_loop_form(bhip_ctx* ctx) {
     return name.c_str();
 }
 
+const char* bhip_ctx_join_probe_form(bhip_ctx* ctx) {
+    static thread_local std::string name;
+    name = ctx ? ctx->p->join_probe_form() : std::string();
+    return name.c_str();
+}
+
 // ---- batches ------------------------------------------------------------------------------------------
 static bhip_batch* wrap_batch(BatchPtr b) {
     auto h = new bhip_batch();

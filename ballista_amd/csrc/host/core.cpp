@@ -355,6 +355,16 @@ std::string Context::nested_loop_form() {
     return k_nested_loop_form_;
 }
 
+void Context::set_join_probe_form(const char* form) {
+    std::lock_guard<std::mutex> g(mu_);
+    k_join_probe_form_ = form ? form : "";
+}
+
+std::string Context::join_probe_form() {
+    std::lock_guard<std::mutex> g(mu_);
+    return k_join_probe_form_;
+}
+
 void Context::kernel_time(bool reset, double* ms, uint64_t* launches) {
     std::lock_guard<std::mutex> g(mu_);
     if (ms) *ms = k_ms_;

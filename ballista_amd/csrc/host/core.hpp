@@ -96,6 +96,11 @@ public:
     // filter), "cross" (no filter, pairs emitted directly), "exists" (an existence type without a filter); "" before the first one
     void set_nested_loop_form(const char* form);
     std::string nested_loop_form();
+    // the probe kernel variant the narrow path launched for its last probe batch (kernels_join.hip launch_join_filter_probe):
+    // "rank/mapbuf", "rank/flat", "rank/bits" (+perm, +resid, +rows8, +gather), "filter/map", "filter/table" (+present, +resid);
+    // "" before the first one
+    void set_join_probe_form(const char* form);
+    std::string join_probe_form();
     void kernel_time(bool reset, double* ms, uint64_t* launches);
     bool timing_enabled() const { return timing_ > 0; }
     int timing_level() const { return timing_; }
@@ -121,7 +126,7 @@ private:
     bool spin_wait_ = true;
     double k_ms_ = 0;
     uint64_t k_launches_ = 0;
-    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_, k_join_key_form_, k_nested_loop_form_;
+    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_, k_join_key_form_, k_nested_loop_form_, k_join_probe_form_;
     struct PendingTimed { hipEvent_t a, b; const char* name; uint64_t bytes; };
     std::vector<PendingTimed> pending_timed_;
     std::vector<hipEvent_t> event_pool_;

@@ -190,7 +190,10 @@ struct ProbeFilter {
 };
 hipError_t launch_join_filter_probe(const LaunchCfg& cfg, const NarrowJoinTable& T, const ProbeFilter& F, const void* rkeys, int key_width,
                                     const uint64_t* rsel, uint32_t n_right, bool right_outer, uint64_t* bitmap, uint32_t* tile_counts,
-                                    uint32_t* staging, uint32_t* matched, const uint32_t* resid_probe = nullptr, uint32_t* staging_rows = nullptr);
+                                    uint32_t* staging, uint32_t* matched, const uint32_t* resid_probe = nullptr, uint32_t* staging_rows = nullptr,
+                                    char* form = nullptr);
+// `form` (JOIN_PROBE_FORM_LEN bytes, may be null) receives the name of the variant the launcher picked (Context::join_probe_form)
+constexpr int JOIN_PROBE_FORM_LEN = 48;
 hipError_t launch_and_bitmaps(const LaunchCfg& cfg, const uint64_t* a, const uint64_t* b, int64_t n_bits, uint64_t* out);
 // out[i] = a[i] << 32 | b[i] (4-byte integer columns); validity_out (when not null) = va & vb (a null input bitmap = all valid)
 hipError_t launch_pack_key_pair(const LaunchCfg& cfg, const void* a, const void* b, const uint64_t* va, const uint64_t* vb, int64_t n, uint64_t* out,

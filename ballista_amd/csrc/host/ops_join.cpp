@@ -1000,11 +1000,13 @@ struct JoinExec::Probe {
         // (named after the kernel the launcher picks — kernels_join.hip launch_join_filter_probe: rank map, no NULL probe keys,
         // an inner join -> join_rank_probe_kernel — so that bench.py's roofline line and the rocprofv3 summaries agree)
         const bool direct = bs->ntable.rpack != nullptr && !kc.validity && !left_outer && !right_outer;
+        char form[JOIN_PROBE_FORM_LEN];
         TIMED_LAUNCH_B(ex, direct ? "join_rank_probe" : "join_filter_probe", n, (uint64_t)n * (uint64_t)(bs->narrow_width + 4 * F.n) + (uint64_t)n / 8,
                        launch_join_filter_probe(cfg, bs->ntable, F, kc.data->ptr(), bs->narrow_width,
                                                 kc.validity ? kc.validity->as<uint64_t>() : nullptr, (uint32_t)n, right_outer, s.bitmap,
                                                 s.tile_counts, s.staging, matched_bits(),
-                                                resid ? resid->data->as<uint32_t>() : nullptr, s.staging_rows));
+                                                resid ? resid->data->as<uint32_t>() : nullptr, s.staging_rows, form));
+        ex.ctx->set_join_probe_form(form);
         compact(tmp, s, o);
     }
 

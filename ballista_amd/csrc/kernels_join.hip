@@ -19,6 +19,7 @@
 // dependent reads, so a pass pays ONE round trip for all of them instead of one per row slot.
 // Algorithmic bytes per probe row: predicate columns + key column once, + 1 bit; per emitted row 4 B partner twice.
 #include <hip/hip_runtime.h>
+#include <cstdio>
 #include <type_traits>
 #include "host/hash_kernels.h"
 #include "launch_common.h"
@@ -911,7 +912,8 @@ static void launch_rank_probe(hipStream_t st, unsigned grid, bool map_buf, bool 
 
 hipError_t launch_join_filter_probe(const LaunchCfg& cfg, const NarrowJoinTable& T, const ProbeFilter& F, const void* rkeys, int key_width,
                                     const uint64_t* rsel, uint32_t n_right, bool right_outer, uint64_t* bitmap, uint32_t* tile_counts,
-                                    uint32_t* staging, uint32_t* matched, const uint32_t* resid_probe, uint32_t* staging_rows) {
+                                    uint32_t* staging, uint32_t* matched, const uint32_t* resid_probe, uint32_t* staging_rows, char* form) {
+    if (form) form[0] = 0;
     if (n_right == 0) return hipSuccess;
     if ((resid_probe != nullptr) != (T.resid_build != nullptr)) return hipErrorInvalidValue;
     const int64_t n_tiles = ((int64_t)n_right + SEL_TILE - 1) / SEL_TILE;
@@ -933,6 +935,15 @@ hipError_t launch_join_filter_probe(const LaunchCfg& cfg, const NarrowJoinTable&
     // nothing staged (a semi-join), sorted one-column build side: the key-set words alone (BHIP_PROBE_NO_BITS=1: the packed map, the A/B partner)
     static const bool no_bits = env_flag("BHIP_PROBE_NO_BITS");
     const bool bits_only = !no_bits && map_buf && T.rbits != nullptr && staging == nullptr && T.rperm == nullptr && resid_probe == nullptr;
+    if (form) {                                          // the same decisions as the macros below, by name
+        if (direct) {
+            const bool perm = T.rperm != nullptr, bits = bits_only && !perm, desc = bits || map_buf;
+            snprintf(form, JOIN_PROBE_FORM_LEN, "rank/%s%s%s%s%s", bits ? "bits" : map_buf ? "mapbuf" : "flat", perm ? "+perm" : "", resid_probe ? "+resid" : "",
+                     !perm && probe_rows == 8 && key_width == 4 ? "+rows8" : "", desc && !T.scalar_map ? "+gather" : "");
+        } else {
+            snprintf(form, JOIN_PROBE_FORM_LEN, "filter/%s%s%s", T.rpack ? "map" : "table", !T.rpack && T.present ? "+present" : "", resid_probe ? "+resid" : "");
+        }
+    }
 #define BHIP_PROBE_R(KW_, NF_, ROWS_, RESID_, PERM_)                                                                                  \
     launch_rank_probe<KW_, NF_, ROWS_, RESID_, PERM_>(cfg.stream, (unsigned)grid, map_buf, bits_only, T, F, rkeys, n_right, bitmap, tile_counts, staging, \
                                                       resid_probe, staging_rows)

@@ -103,6 +103,12 @@ class Context:
         any width, or BHIP_JOIN_WIDE=1), "" before the first build"""
         return L.lib().bhip_ctx_join_key_form(self._h).decode()
 
+    def join_probe_form(self):
+        """the probe kernel variant HashJoinExec's single-key path launched for its last probe batch: "rank/mapbuf", "rank/flat" or
+        "rank/bits" (join_rank_probe_kernel; +perm, +resid, +rows8, +gather where they apply), "filter/map" or "filter/table"
+        (join_filter_probe_kernel; +present, +resid), "" before the first one"""
+        return L.lib().bhip_ctx_join_probe_form(self._h).decode()
+
     def nested_loop_form(self):
         """how NestedLoopJoinExec ran its last probe batch: "compare" (the fused kernel: an AND of up to four column-to-column
         comparisons), "general" (chunks of candidate pairs through the filter, or BHIP_NO_NLJ_FUSED=1), "cross" (no filter),

@@ -614,6 +614,13 @@ const char* bhip_ctx_join_key_form(bhip_ctx* ctx);
  * the pairs are emitted directly), "exists" (SEMI / ANTI / RIGHT_SEMI / RIGHT_ANTI without a filter: nothing is enumerated);
  * "" before the first one; valid until the next call */
 const char* bhip_ctx_nested_loop_form(bhip_ctx* ctx);
+/* the probe kernel variant HashJoinExec's single-key path launched for its last probe batch: "rank/mapbuf" (the one-read kernel, the
+ * packed map through a buffer descriptor), "rank/flat" (the same through flat loads and an explicit window test), "rank/bits" (the key-set
+ * words alone: nothing staged, sorted one-column build side), each with "+perm" (unsorted build side), "+resid" (second key column),
+ * "+rows8" (eight rows per lane) or "+gather" (no scalar map reads) where they apply; "filter/map" and "filter/table" (the general
+ * kernel over the rank map / the CAS table, "+present" with the key-set bitmap in front of it, "+resid"); "" before the first one;
+ * valid until the next call */
+const char* bhip_ctx_join_probe_form(bhip_ctx* ctx);
 /* compute units of the context's device (what the kernels size their grids by) */
 int32_t bhip_ctx_device_cus(bhip_ctx* ctx);
 
