@@ -42,57 +42,23 @@ static int flip_cmp(int k) {
         default: return k;
     }
 }
-static const char* MATH_FNS[] = {"sqrt", "abs", "floor", "ceil", "round", "trunc", "signum", "exp", "ln",
-                                 "log2", "log10", "sin", "cos", "tan", "asin", "acos", "atan"};
-static int math_fn(const std::string& n) {
-    for (int i = 0; i < (int)(sizeof(MATH_FNS) / sizeof(MATH_FNS[0])); ++i)
-        if (n == MATH_FNS[i]) return i;
-    return -1;
-}
-
-int str_fn(const std::string& name) {
-    static const char* names[] = {"lower", "upper", "trim", "ltrim", "rtrim"};
-    for (int i = 0; i < 5; ++i)
-        if (name == names[i]) return i;
-    return -1;
-}
-
-int sha_fn(const std::string& name) {
-    return name == "sha224" ? 224 : name == "sha256" ? 256 : name == "sha384" ? 384 : name == "sha512" ? 512 : 0;
-}
-
-int str_range_fn(const std::string& name) { return name == "substr" ? STR_SUBSTR : name == "left" ? STR_LEFT : name == "right" ? STR_RIGHT : -1; }
-bool str_typed_fn(const std::string& name) { return name == "char_length" || name == "strpos" || name == "starts_with"; }
-
-// substring -> substr; length, character_length -> char_length: one name per function from here on
-static std::string canonical_fn(const std::string& name) {
-    if (name == "substring") return "substr";
-    if (name == "length" || name == "character_length") return "char_length";
-    return name;
-}
-
 void check_scalar_function(const std::string& alias, int n_args) {
-    const std::string name = canonical_fn(alias);
-    if (name == "substr") {
-        if (n_args != 2 && n_args != 3) fail(BHIP_EINVAL, "scalar function 'substr' takes two or three arguments");
-        return;
+    const ScalarFn* f = find_scalar_fn(alias);
+    if (!f) fail(BHIP_ENOTIMPL, "scalar function '" + alias + "' is not supported");
+    if (n_args >= f->min_args && n_args <= f->max_args) return;
+    const std::string name = f->name;
+    if (f->max_args > 3) {                  // any number of arguments up to a limit of the kernels
+        if (n_args < f->min_args) fail(BHIP_EINVAL, name + " takes at least one argument");
+        fail(BHIP_ENOTIMPL, name + " with more than " + std::to_string(f->max_args) + " arguments");
     }
-    if (str_range_fn(name) >= 0 || name == "strpos" || name == "starts_with" || name == "date_part") {
-        if (n_args != 2) fail(BHIP_EINVAL, "scalar function '" + name + "' takes two arguments");
-        return;
-    }
-    if (name == "concat") {
-        if (n_args < 1) fail(BHIP_EINVAL, "concat takes at least one argument");
-        if (n_args > STR_CONCAT_MAX) fail(BHIP_ENOTIMPL, "concat with more than 8 arguments");
-        return;
-    }
-    if (name == "nullif" || name == "date_trunc") {
-        if (n_args != 2) fail(BHIP_EINVAL, "scalar function '" + name + "' takes two arguments");
-        return;
-    }
-    if (math_fn(name) < 0 && str_fn(name) < 0 && sha_fn(name) == 0 && name != "octet_length" && name != "to_timestamp" && name != "char_length")
-        fail(BHIP_ENOTIMPL, "scalar function '" + name + "' is not supported");
-    if (n_args != 1) fail(BHIP_EINVAL, "scalar function takes one argument");
+    if (f->max_args == 1) fail(BHIP_EINVAL, "scalar function takes one argument");
+    fail(BHIP_EINVAL, "scalar function '" + name + "' takes two " + (f->max_args == 3 ? "or three " : "") + "arguments");
+}
+
+ExprPtr fold_scalar_literal(const ExprPtr& e, const Schema& schema) {
+    if (e->kind != BHIP_EXPR_SCALAR_FN) return nullptr;
+    const ScalarFn& f = scalar_fn(*e);
+    return f.fold ? f.fold(e, schema) : nullptr;
 }
 
 static ExprPtr make_literal(int dtype, bool is_null, int64_t i64) {
@@ -115,35 +81,42 @@ int date_trunc_granularity(const Expr& e, const Schema& schema) {
     return gran;
 }
 
-ExprPtr fold_temporal_literal(const ExprPtr& e, const Schema& schema) {
-    if (e->kind != BHIP_EXPR_SCALAR_FN) return nullptr;
-    if (e->name == "to_timestamp") {
-        const Expr& x = *e->args[0];
-        if (x.kind != BHIP_EXPR_LITERAL || x.dtype != DT_UTF8 || x.is_null) return nullptr;         // (a NULL literal: a column of NULLs, utf8_exprs.cpp)
-        int64_t ns = 0;
-        const CastPtrReader rd{reinterpret_cast<const uint8_t*>(x.name.data())};
-        if (!to_timestamp_parse(rd, 0, (int64_t)x.name.size(), ns)) fail(BHIP_EEXEC, "to_timestamp: '" + x.name + "' is not a timestamp");
-        return make_literal(DT_TIMESTAMP_NS, false, ns);
-    }
-    if (e->name == "date_trunc") {
-        ExprPtr x = e->args[1];
-        if (x->kind != BHIP_EXPR_LITERAL) x = fold_temporal_literal(x, schema);
-        if (!x) return nullptr;
-        const int gran = date_trunc_granularity(*e, schema);
-        int64_t v = 0;
-        const bool ok = !x->is_null && temporal_trunc(x->dtype, gran, x->i64, v);
-        return make_literal(x->dtype, !ok, v);
-    }
-    if (e->name == "date_part") {
-        ExprPtr x = e->args[1];
-        if (x->kind != BHIP_EXPR_LITERAL) x = fold_temporal_literal(x, schema);
-        if (!x) return nullptr;
-        const int part = date_part_of(*e, schema);
-        int32_t v = 0;
-        const bool ok = !x->is_null && temporal_part(x->dtype, part, x->i64, v);
-        return make_literal(DT_INT32, !ok, v);
-    }
-    return nullptr;
+int check_to_timestamp(const Expr& e, const Schema& schema) {
+    if (expr_type(e.args[0], schema) != DT_UTF8) fail(BHIP_EINVAL, "to_timestamp requires a Utf8 argument");
+    return 0;
+}
+
+ExprPtr fold_to_timestamp(const ExprPtr& e, const Schema&) {
+    const Expr& x = *e->args[0];
+    if (x.kind != BHIP_EXPR_LITERAL || x.dtype != DT_UTF8 || x.is_null) return nullptr;         // (a NULL literal: a column of NULLs, utf8_exprs.cpp)
+    int64_t ns = 0;
+    const CastPtrReader rd{reinterpret_cast<const uint8_t*>(x.name.data())};
+    if (!to_timestamp_parse(rd, 0, (int64_t)x.name.size(), ns)) fail(BHIP_EEXEC, "to_timestamp: '" + x.name + "' is not a timestamp");
+    return make_literal(DT_TIMESTAMP_NS, false, ns);
+}
+
+// the temporal argument of date_trunc / date_part as a literal (itself, or what a temporal call folds to), else null
+static ExprPtr temporal_literal(const ExprPtr& x, const Schema& schema) {
+    if (x->kind == BHIP_EXPR_LITERAL) return x;
+    return dt_is_temporal(expr_type(x, schema)) ? fold_scalar_literal(x, schema) : nullptr;
+}
+
+ExprPtr fold_date_trunc(const ExprPtr& e, const Schema& schema) {
+    const ExprPtr x = temporal_literal(e->args[1], schema);
+    if (!x) return nullptr;
+    const int gran = date_trunc_granularity(*e, schema);
+    int64_t v = 0;
+    const bool ok = !x->is_null && temporal_trunc(x->dtype, gran, x->i64, v);
+    return make_literal(x->dtype, !ok, v);
+}
+
+ExprPtr fold_date_part(const ExprPtr& e, const Schema& schema) {
+    const ExprPtr x = temporal_literal(e->args[1], schema);
+    if (!x) return nullptr;
+    const int part = date_part_of(*e, schema);
+    int32_t v = 0;
+    const bool ok = !x->is_null && temporal_part(x->dtype, part, x->i64, v);
+    return make_literal(DT_INT32, !ok, v);
 }
 
 int date_part_of(const Expr& e, const Schema& schema) {
@@ -157,10 +130,10 @@ int date_part_of(const Expr& e, const Schema& schema) {
     return part;
 }
 
-void check_string_fn(const Expr& e, const Schema& schema) {
+int check_string_fn(const Expr& e, const Schema& schema) {
     const int t0 = expr_type(e.args[0], schema);
     if (t0 != DT_UTF8) fail(BHIP_EINVAL, e.name + " requires a Utf8 first argument, not " + dtype_name(t0));
-    if (str_range_fn(e.name) >= 0) {
+    if (scalar_fn(e).where == FN_UTF8) {                // substr / left / right
         for (size_t k = 1; k < e.args.size(); ++k) {
             const int t = expr_type(e.args[k], schema);
             if (t != DT_INT64) fail(BHIP_EINVAL, e.name + " requires Int64 arguments after the first, not " + dtype_name(t));
@@ -171,8 +144,9 @@ void check_string_fn(const Expr& e, const Schema& schema) {
         const int t = expr_type(e.args[1], schema);
         if (t != DT_UTF8) fail(BHIP_EINVAL, e.name + " requires Utf8 arguments, not " + dtype_name(t));
         if (e.args[1]->kind == BHIP_EXPR_LITERAL && e.args[1]->name.size() > (size_t)STR_LITERAL_MAX)
-            fail(BHIP_ENOTIMPL, e.name + " with a literal longer than 240 bytes");
+            fail(BHIP_ENOTIMPL, e.name + " with a literal longer than " + std::to_string(STR_LITERAL_MAX) + " bytes");
     }
+    return 0;
 }
 
 static ExprPtr make_utf8_literal(const std::string& text) {
@@ -184,7 +158,7 @@ static ExprPtr make_utf8_literal(const std::string& text) {
 }
 
 ExprPtr fold_string_literal(const ExprPtr& e, const Schema& schema) {
-    if (e->kind != BHIP_EXPR_SCALAR_FN || (str_range_fn(e->name) < 0 && !str_typed_fn(e->name))) return nullptr;
+    const ScalarFn& f = scalar_fn(*e);
     check_string_fn(*e, schema);
     bool all_literals = true, any_null = false;
     for (auto& a : e->args) {
@@ -197,16 +171,15 @@ ExprPtr fold_string_literal(const ExprPtr& e, const Schema& schema) {
     const std::string& s = e->args[0]->name;
     const CastPtrReader rd{reinterpret_cast<const uint8_t*>(s.data())};
     const int64_t end = (int64_t)s.size();
-    const int fn = str_range_fn(e->name);
-    if (fn >= 0) {
+    if (f.where == FN_UTF8) {
         int64_t b = 0, q = 0;
-        str_range(fn, rd, 0, end, e->args[1]->i64, e->args.size() == 3, e->args.size() == 3 ? e->args[2]->i64 : 0, b, q);      // (count < 0: refused above)
+        str_range(f.param, rd, 0, end, e->args[1]->i64, e->args.size() == 3, e->args.size() == 3 ? e->args[2]->i64 : 0, b, q);      // (count < 0: refused above)
         return make_utf8_literal(s.substr((size_t)b, (size_t)(q - b)));
     }
-    if (e->name == "char_length") return make_literal(DT_INT32, false, str_char_count(rd, 0, end));
+    if (f.param == STR_CHAR_LENGTH) return make_literal(DT_INT32, false, str_char_count(rd, 0, end));
     const std::string& sub = e->args[1]->name;
     const CastPtrReader sr{reinterpret_cast<const uint8_t*>(sub.data())};
-    if (e->name == "strpos") return make_literal(DT_INT32, false, str_strpos(rd, 0, end, sr, 0, (int64_t)sub.size()));
+    if (f.param == STR_STRPOS) return make_literal(DT_INT32, false, str_strpos(rd, 0, end, sr, 0, (int64_t)sub.size()));
     return make_literal(DT_BOOLEAN, false, str_starts_with(rd, 0, end, sr, 0, (int64_t)sub.size()) ? 1 : 0);
 }
 
@@ -292,7 +265,7 @@ ExprPtr parse_expr(const bhip_expr& pe) {
             } break;
             case BHIP_EXPR_SCALAR_FN: {
                 check_scalar_function(n.name ? n.name : "", n.n_args);
-                e->name = canonical_fn(n.name);
+                e->name = find_scalar_fn(n.name)->name;            // one name per function from here on, whatever alias came in
                 e->args.resize((size_t)n.n_args);
                 for (int k = n.n_args - 1; k >= 0; --k) e->args[(size_t)k] = pop();
             } break;
@@ -392,14 +365,10 @@ int expr_type(const ExprPtr& e, const Schema& schema) {
             case_layout(*e, fw, np);
             return expr_type(e->args[fw + 1], schema);
         }
-        case BHIP_EXPR_SCALAR_FN:
-            if (e->name == "nullif") return expr_type(e->args[0], schema);
-            if (e->name == "date_trunc") return expr_type(e->args[1], schema);
-            if (e->name == "to_timestamp") return DT_TIMESTAMP_NS;
-            if (str_range_fn(e->name) >= 0) return DT_UTF8;
-            if (e->name == "char_length" || e->name == "strpos" || e->name == "date_part") return DT_INT32;
-            if (e->name == "starts_with") return DT_BOOLEAN;
-            return (str_fn(e->name) >= 0 || sha_fn(e->name) || e->name == "concat") ? DT_UTF8 : (e->name == "octet_length" ? DT_INT32 : DT_FLOAT64);
+        case BHIP_EXPR_SCALAR_FN: {
+            const int t = scalar_fn(*e).result;
+            return t >= 0 ? t : expr_type(e->args[(size_t)(-1 - t)], schema);
+        }
         default: fail(BHIP_ENOTIMPL, "unsupported expression kind");
     }
 }
@@ -410,13 +379,12 @@ bool expr_large(const ExprPtr& e, const Schema& schema) {
             const int i = schema.index_of(e->name);
             return i >= 0 && schema.fields[i].large;
         }
-        case BHIP_EXPR_SCALAR_FN:
-            if (e->name == "concat") {
-                for (auto& a : e->args)
-                    if (expr_large(a, schema)) return true;
-                return false;
-            }
-            return (str_fn(e->name) >= 0 || str_range_fn(e->name) >= 0) && expr_large(e->args[0], schema);
+        case BHIP_EXPR_SCALAR_FN: {
+            const int from = scalar_fn(*e).large;
+            for (size_t k = 0; k < (from == LARGE_ANY_ARG ? e->args.size() : from == LARGE_ARG0 ? 1 : 0); ++k)
+                if (expr_large(e->args[k], schema)) return true;
+            return false;
+        }
         case BHIP_EXPR_CASE: {
             size_t fw, np;
             case_layout(*e, fw, np);
@@ -434,7 +402,7 @@ bool expr_binary(const ExprPtr& e, const Schema& schema) {
             const int i = schema.index_of(e->name);
             return i >= 0 && schema.fields[i].binary;
         }
-        case BHIP_EXPR_SCALAR_FN: return sha_fn(e->name) != 0;
+        case BHIP_EXPR_SCALAR_FN: return scalar_fn(*e).binary;
         case BHIP_EXPR_CASE: {
             size_t fw, np;
             case_layout(*e, fw, np);
@@ -539,13 +507,12 @@ ExprPtr coerce_expr(const ExprPtr& e, const Schema& schema) {
         }
         case BHIP_EXPR_SCALAR_FN: {
             auto c = std::make_shared<Expr>(*e);
-            const bool math = math_fn(e->name) >= 0;        // Signature::Uniform(1, [Float64, Float32]): the first type the argument coerces to
-            for (auto& a : c->args) a = math ? cast_to(coerce_expr(a, schema), DT_FLOAT64, schema) : coerce_expr(a, schema);
-            if (str_range_fn(e->name) >= 0)             // start, count, n: integers of any width, brought to Int64 like a side of a comparison
+            const int rule = scalar_fn(*e).coerce;
+            for (auto& a : c->args) a = rule == COERCE_FLOAT64 ? cast_to(coerce_expr(a, schema), DT_FLOAT64, schema) : coerce_expr(a, schema);
+            if (rule == COERCE_INT64_REST)
                 for (size_t k = 1; k < c->args.size(); ++k)
                     if (numeric_rank(expr_type(c->args[k], schema)) && !dt_is_float(expr_type(c->args[k], schema))) c->args[k] = cast_to(c->args[k], DT_INT64, schema);
-            if (e->name == "nullif" && c->args.size() == 2) {
-                // the two sides of `a = b`: one common type, which is the result's (a Utf8 `a` is refused when it is compiled)
+            if (rule == COERCE_LIKE_EQ && c->args.size() == 2) {         // (a Utf8 `a` is refused when it is compiled)
                 const int ta = expr_type(c->args[0], schema), tb = expr_type(c->args[1], schema);
                 if (ta != DT_UTF8 && tb != DT_UTF8) {
                     const int t = common_type(ta, tb);
@@ -583,9 +550,7 @@ bool expr_nullable(const ExprPtr& e, const Schema& schema) {
             return expr_nullable(e->args[0], schema);
         }
         case BHIP_EXPR_SCALAR_FN:
-            // nullif makes NULLs of its own; a date_trunc floor may not fit int64.  (concat, to_timestamp: nullable iff an argument is)
-            // a date_part field may not fit Int32
-            if (e->name == "nullif" || e->name == "date_trunc" || e->name == "date_part") return true;
+            if (scalar_fn(*e).own_nulls) return true;
             [[fallthrough]];
         case BHIP_EXPR_CASE:
             if (e->kind == BHIP_EXPR_CASE && !e->has_else) return true;
@@ -1081,7 +1046,13 @@ Operand ProgramBuilder::compile_uncached(const ExprPtr& ep) {
             return result;
         }
         case BHIP_EXPR_SCALAR_FN: {
-            if (e.name == "octet_length") {
+            const ScalarFn& f = scalar_fn(e);
+            if (f.where == FN_VM_MATH) {
+                if (expr_type(e.args[0], schema_) != DT_FLOAT64) fail(BHIP_EINVAL, e.name + " requires a Float64 argument");
+                Operand a = materialize(compile(e.args[0]));
+                return emit(OP_MATH_F64, &a, nullptr, false, VC_F64, DT_FLOAT64, (uint16_t)f.param);
+            }
+            if (f.where == FN_VM && f.param == VM_OCTET_LENGTH) {
                 if (expr_type(e.args[0], schema_) != DT_UTF8) fail(BHIP_EINVAL, "octet_length requires a Utf8 argument");
                 Operand a = compile(e.args[0]);
                 if (!a.is_utf8_col) fail(BHIP_ENOTIMPL, "octet_length of a Utf8 expression that is not a column");
@@ -1089,8 +1060,8 @@ Operand ProgramBuilder::compile_uncached(const ExprPtr& ep) {
                 instrs_.back().ins.c = (uint8_t)a.col;
                 return o;
             }
-            if (e.name == "nullif") {
-                // CASE WHEN a = b THEN NULL ELSE a END: `a = b` is the library's own Eq, no VM instruction of its own
+            if (f.where == FN_VM) {
+                // nullif: CASE WHEN a = b THEN NULL ELSE a END: `a = b` is the library's own Eq, no VM instruction of its own
                 const int t = expr_type(e.args[0], schema_);
                 if (t == DT_UTF8) fail(BHIP_ENOTIMPL, "nullif over Utf8 values");
                 if (expr_type(e.args[1], schema_) != t)
@@ -1101,26 +1072,14 @@ Operand ProgramBuilder::compile_uncached(const ExprPtr& ep) {
                 c->args = {make_binary(e.args[0], "Eq", e.args[1]), make_literal(t, true, 0), e.args[0]};
                 return compile(c);
             }
-            if (e.name == "to_timestamp" || e.name == "date_trunc") {
-                if (e.name == "date_trunc") (void)date_trunc_granularity(e, schema_);
-                else if (expr_type(e.args[0], schema_) != DT_UTF8) fail(BHIP_EINVAL, "to_timestamp requires a Utf8 argument");
-                if (const ExprPtr l = fold_temporal_literal(ep, schema_)) return compile(l);
+            // a lowered function reaches the VM only as the literal it folds to: the node itself is a column by now (host/utf8_exprs.cpp)
+            if (f.where == FN_FIXED) {
+                (void)f.check(e, schema_);
+                if (const ExprPtr l = f.fold(ep, schema_)) return compile(l);
                 fail(BHIP_ENOTIMPL, "expression " + e.name + "() outside the lowering (evaluated as a column, host/utf8_exprs.cpp)");
             }
-            if (e.name == "date_part") {
-                (void)date_part_of(e, schema_);
-                if (const ExprPtr l = fold_temporal_literal(ep, schema_)) return compile(l);
-                fail(BHIP_ENOTIMPL, "expression " + e.name + "() outside the lowering (evaluated as a column, host/utf8_exprs.cpp)");
-            }
-            if (str_typed_fn(e.name)) {
-                if (const ExprPtr l = fold_string_literal(ep, schema_)) return compile(l);
-                fail(BHIP_ENOTIMPL, "expression " + e.name + "() outside the lowering (evaluated as a column, host/utf8_exprs.cpp)");
-            }
-            if (str_range_fn(e.name) >= 0) fail(BHIP_ENOTIMPL, "expression producing Utf8: " + e.name + "() (evaluated as a column, host/utf8_exprs.cpp)");
-            if (str_fn(e.name) >= 0 || sha_fn(e.name) || e.name == "concat") fail(BHIP_ENOTIMPL, "expression producing Utf8 / Binary: " + e.name + "() (evaluated as a column, host/utf8_exprs.cpp)");
-            if (expr_type(e.args[0], schema_) != DT_FLOAT64) fail(BHIP_EINVAL, e.name + " requires a Float64 argument");
-            Operand a = materialize(compile(e.args[0]));
-            return emit(OP_MATH_F64, &a, nullptr, false, VC_F64, DT_FLOAT64, (uint16_t)math_fn(e.name));
+            // (the functions that fold, substr / left / right, never give Binary and say so)
+            fail(BHIP_ENOTIMPL, std::string("expression producing Utf8") + (f.fold ? ": " : " / Binary: ") + e.name + "() (evaluated as a column, host/utf8_exprs.cpp)");
         }
         default: fail(BHIP_ENOTIMPL, "unsupported expression kind");
     }

@@ -74,23 +74,68 @@ struct Operand {
 // a Utf8-valued expression whose Arrow form is LargeUtf8 (Field::large of the columns it comes from)
 bool expr_large(const ExprPtr& e, const Schema& schema);
 bool expr_binary(const ExprPtr& e, const Schema& schema);         // ... is Binary (a Binary column, sha224 .. sha512)
-int sha_fn(const std::string& name);                              // digest bits of sha224 / sha256 / sha384 / sha512, 0 otherwise
-// index of a string-valued scalar function (lower, upper, trim, ltrim, rtrim; evaluated as columns, utf8_exprs.cpp), -1 otherwise
-int str_fn(const std::string& name);
+
+// ---- scalar functions ---------------------------------------------------------------------------
+// One row per function, under its canonical name: everything the library knows about it.  The table is SCALAR_FNS in utf8_exprs.cpp,
+// beside the evaluators of the lowered functions; typing, coercion, folding, the VM's compiler and the lowering all read it.
+enum FnWhere {
+    FN_VM_MATH,       // OP_MATH_F64, `param` its index
+    FN_VM,            // compiled by the VM's compiler in its own way (`param`: a VmFn)
+    FN_UTF8,          // lowered: evaluated as a Utf8 / Binary column (utf8_exprs.cpp)
+    FN_FIXED          // lowered: evaluated as a fixed-width column, unless the call folds to a literal
+};
+enum VmFn { VM_OCTET_LENGTH, VM_NULLIF };
+enum StrTypedFn { STR_CHAR_LENGTH, STR_STRPOS, STR_STARTS_WITH };
+enum FnCoerce {
+    COERCE_NONE,
+    COERCE_FLOAT64,   // Signature::Uniform(1, [Float64, Float32]): the first type the argument coerces to
+    COERCE_INT64_REST,// integers of any width after the first argument are brought to Int64, like a side of a comparison
+    COERCE_LIKE_EQ    // the two sides of `a = b`: one common type, which is the result's
+};
+enum FnLarge { LARGE_NEVER, LARGE_ARG0, LARGE_ANY_ARG };           // whose LargeUtf8 flag the result carries
+constexpr int TYPE_OF_ARG(int k) { return -1 - k; }                // ScalarFn::result: the type of argument k
+struct ScalarFn {
+    const char* name;
+    int min_args, max_args;
+    int where;                    // FnWhere
+    int param;                    // math index | VmFn | string transform (str_kernels.h) | digest bits | StrRangeFn | StrTypedFn
+    int result;                   // a dtype, or TYPE_OF_ARG(k)
+    int coerce;                   // FnCoerce
+    int large;                    // FnLarge
+    bool binary;                  // the result is Binary
+    bool own_nulls;               // makes NULLs of its own (else: nullable iff an argument is)
+    const char* aliases[2];       // further names on the wire
+    // the literal the call folds to (by the functions the kernels run), null when it does not
+    ExprPtr (*fold)(const ExprPtr& e, const Schema& schema);
+    // the call's own plan-time checks; returns what they worked out (date_trunc: the granularity, date_part: the part), else 0
+    int (*check)(const Expr& e, const Schema& schema);
+    // lowered functions: the plan-time check of the node with its arguments, and the evaluator (both in utf8_exprs.cpp)
+    void (*validate)(const ExprPtr& e, const Schema& in, const ScalarFn& f);
+    Column (*eval)(const Exec& ex, const Batch& in, const ExprPtr& e, const ScalarFn& f);
+};
+// the row of a canonical name or a wire alias, null for a function the library does not have
+const ScalarFn* find_scalar_fn(const std::string& name);
+// ... of a parsed call (its name is canonical and known: check_scalar_function)
+inline const ScalarFn& scalar_fn(const Expr& e) { return *find_scalar_fn(e.name); }
+// the literal a call over literals folds to (ScalarFn::fold), else null
+ExprPtr fold_scalar_literal(const ExprPtr& e, const Schema& schema);
+
+// the hooks of the table that live in expr.cpp -----------------------------------------------------
 // date_trunc(g, t): every plan-time check of the call (BHIP_ENOTIMPL for a granularity that is no literal, BHIP_EINVAL for an unknown
 // one or a `t` that is no Timestamp); returns the TruncGranularity (temporal_text.h)
 int date_trunc_granularity(const Expr& e, const Schema& schema);
-// to_timestamp / date_trunc over literals alone: the literal they fold to (by temporal_text.h, what the kernels run), else null.
-// A to_timestamp literal outside the grammar fails here with BHIP_EEXEC, as the same text in a column would when the query runs.
-ExprPtr fold_temporal_literal(const ExprPtr& e, const Schema& schema);
 // date_part('part', x): every plan-time check of the call (BHIP_ENOTIMPL for a part that is no literal, BHIP_EINVAL for an unknown one
 // or an `x` that is no Date32 / Date64 / Timestamp); returns the DatePart (temporal_text.h)
 int date_part_of(const Expr& e, const Schema& schema);
-// the code-point string functions (str_text.h): StrRangeFn of substr / left / right, -1 otherwise; char_length / strpos / starts_with
-int str_range_fn(const std::string& name);
-bool str_typed_fn(const std::string& name);
-// ... their plan-time checks (BHIP_EINVAL: an argument of the wrong type, a literal count < 0) ...
-void check_string_fn(const Expr& e, const Schema& schema);
+int check_to_timestamp(const Expr& e, const Schema& schema);
+// to_timestamp / date_trunc / date_part over literals alone: the literal they fold to (by temporal_text.h, what the kernels run).
+// A to_timestamp literal outside the grammar fails here with BHIP_EEXEC, as the same text in a column would when the query runs.
+ExprPtr fold_to_timestamp(const ExprPtr& e, const Schema& schema);
+ExprPtr fold_date_trunc(const ExprPtr& e, const Schema& schema);
+ExprPtr fold_date_part(const ExprPtr& e, const Schema& schema);
+// the code-point string functions (str_text.h) substr / left / right / char_length / strpos / starts_with: their plan-time checks
+// (BHIP_EINVAL: an argument of the wrong type, a literal count < 0) ...
+int check_string_fn(const Expr& e, const Schema& schema);
 // ... and what a call folds to: a NULL literal when any argument is a NULL literal, the value (by str_text.h, what the kernels run)
 // when every argument is a literal, else null
 ExprPtr fold_string_literal(const ExprPtr& e, const Schema& schema);

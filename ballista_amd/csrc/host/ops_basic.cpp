@@ -53,6 +53,55 @@ static ScanStatus* new_status(Temp& tmp) {
     return st;
 }
 
+// ---- computed columns ------------------------------------------------------------------------------
+Column fixed_column(const Exec& ex, int dtype, int64_t n, bool with_validity) {
+    Column c;
+    c.dtype = dtype;
+    c.length = n;
+    c.data = make_buffer(ex, (dtype == DT_BOOLEAN ? bitmap_bytes(n) : (size_t)n * dtype_width(dtype)) + 8);
+    if (with_validity) c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+    return c;
+}
+
+Column utf8_from_lengths(const Exec& ex, Temp& tmp, uint32_t* lengths, int64_t n, Utf8Total& total) {
+    Column out;
+    out.dtype = DT_UTF8;
+    out.length = n;
+    out.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
+    total.dev = tmp.get<uint64_t>(1);
+    void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n));
+    HIP_CHECK(exclusive_scan_u32_i32(ex.stream, lengths, n, out.offsets->as<int32_t>(), true, total.dev, scan_tmp));
+    return out;
+}
+
+void utf8_alloc_data(const Exec& ex, Column& out, int64_t bytes) {
+    if ((uint64_t)bytes > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
+    out.data = make_buffer(ex, (size_t)bytes + 8);
+}
+
+void utf8_size_data(const Exec& ex, Column& out, int64_t bound, Utf8Total& total) {
+    if (total.host < 0 && bound > (64 << 20)) total.host = (int64_t)read_device(ex, total.dev);
+    utf8_alloc_data(ex, out, total.host >= 0 ? total.host : bound);
+}
+
+uint32_t utf8_read_total(const Exec& ex, Temp& tmp, Column& out, Utf8Total& total, const uint32_t* status_dev) {
+    uint32_t status = 0;
+    if (status_dev) {
+        struct Back { uint64_t total; uint32_t status, pad; };
+        static_assert(sizeof(Back) == 16, "one read");
+        Back* back = tmp.get<Back>(1);
+        HIP_CHECK(hipMemcpyAsync(&back->total, total.dev, 8, hipMemcpyDeviceToDevice, ex.stream));
+        HIP_CHECK(hipMemcpyAsync(&back->status, status_dev, 4, hipMemcpyDeviceToDevice, ex.stream));
+        const Back b = read_device(ex, back);
+        total.host = (int64_t)b.total;
+        status = b.status;
+    } else if (total.host < 0) {
+        total.host = (int64_t)read_device(ex, total.dev);
+    }
+    out.data_bytes = total.host;
+    return status;
+}
+
 // ---- take ------------------------------------------------------------------------------------------
 // known_bytes >= 0: the caller knows the Utf8 value bytes of the result (a permutation keeps them) — no
 // host round trip for the total
@@ -65,14 +114,11 @@ Column take_column(const Exec& ex, const Column& c, const uint32_t* idx, int64_t
         Temp tmp(ex);
         uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
         TIMED_LAUNCH_N(ex, "take_utf8_lengths", n, launch_take_utf8_lengths(cfg, c.offsets->as<int32_t>(), idx, n, lengths));
-        out.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
-        uint64_t* total = tmp.get<uint64_t>(1);
-        void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n));
-        HIP_CHECK(exclusive_scan_u32_i32(ex.stream, lengths, n, out.offsets->as<int32_t>(), true, total, scan_tmp));
-        const uint64_t bytes = known_bytes >= 0 ? (uint64_t)known_bytes : read_device(ex, total);
-        if (bytes > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
-        out.data_bytes = (int64_t)bytes;
-        out.data = make_buffer(ex, (size_t)bytes + 8);
+        Utf8Total total;
+        out = utf8_from_lengths(ex, tmp, lengths, n, total);
+        total.host = known_bytes;
+        utf8_size_data(ex, out, INT64_MAX, total);           // no bound to go by: the total, read unless the caller knew it
+        out.data_bytes = total.host;
         TIMED_LAUNCH_N(ex, "take_utf8_copy", n, launch_take_utf8_copy(cfg, c.offsets->as<int32_t>(), c.data->as<uint8_t>(), c.data_bytes, idx, n,
                                         out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
     } else if (c.dtype == DT_BOOLEAN) {
@@ -237,17 +283,18 @@ Column take_batch_column(const Exec& ex, const Column& c, const uint32_t* idx, i
 
 Column null_column(const Exec& ex, int dtype, int64_t n) {
     Column c;
-    c.dtype = dtype;
-    c.length = n;
-    const size_t bytes = dtype == DT_UTF8 ? 8 : (dtype == DT_BOOLEAN ? bitmap_bytes(n) : (size_t)n * dtype_width(dtype));
-    c.data = make_buffer(ex, bytes + 8);
-    HIP_CHECK(hipMemsetAsync(c.data->ptr(), 0, bytes + 8, ex.stream));
-    if (dtype == DT_UTF8) {
+    if (dtype != DT_UTF8) {
+        c = fixed_column(ex, dtype, n, true);
+    } else {
+        c.dtype = dtype;
+        c.length = n;
+        c.data = make_buffer(ex, 8 + 8);                      // no value bytes
         c.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
         HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, (size_t)(n + 1) * 4, ex.stream));
+        c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
     }
-    c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-    HIP_CHECK(hipMemsetAsync(c.validity->ptr(), 0, bitmap_bytes(n) + 8, ex.stream));
+    HIP_CHECK(hipMemsetAsync(c.data->ptr(), 0, c.data->bytes(), ex.stream));
+    HIP_CHECK(hipMemsetAsync(c.validity->ptr(), 0, c.validity->bytes(), ex.stream));
     return c;
 }
 
