@@ -4,6 +4,8 @@
 // analogue of the reference's `RecordBatchStream` (rust/core/src/memory_stream.rs:57-92); the
 // C Data Interface carries one RecordBatch as a struct array.  The Rust executor side would
 // produce/consume these through arrow-rs' `ffi` module.
+#include "arrow_c.hpp"
+
 #include <cstdlib>
 #include <cstring>
 
@@ -14,7 +16,6 @@
 
 using namespace bhip;
 
-// Arrow C Data Interface format strings <-> bhip_dtype (shared with ipc.cpp)
 namespace bhip {
 int dtype_from_format(const char* f) {
     if (!f) return 0;
@@ -51,23 +52,10 @@ const char* format_of_dtype(int dt) {
         default: return "u";
     }
 }
-}  // namespace bhip
 
-namespace {
-
-const char* format_of(int dt) { return format_of_dtype(dt); }
-
-// what the device operators carry: every primitive type the serde ships (rust/core/proto/ballista.proto:755-790) except
-// LargeUtf8, Binary, Float16, Time32/64, Interval, Duration, Decimal and the nested types — a batch of those is refused here
-// (BHIP_ENOTIMPL: keep the CPU operator); timestamps with a time zone likewise
-int device_dtype_from_format(const char* f) {
-    const int dt = dtype_from_format(f);
-    return (dt >= DT_INT32 && dt <= DT_LAST) || dt == DT_LARGE_UTF8 || dt == DT_BINARY ? dt : 0;
-}
-
-// copy n bits starting at bit `off` of src into a fresh, zero-padded bitmap
-std::vector<uint8_t> realign_bits(const uint8_t* src, int64_t off, int64_t n) {
-    std::vector<uint8_t> out((size_t)((n + 63) / 64) * 8 + 8, 0);
+std::vector<uint8_t> slice_bits(const uint8_t* src, int64_t off, int64_t n) {
+    std::vector<uint8_t> out(bitmap_bytes(n) + 8, 0);
+    if (n == 0) return out;
     if ((off & 7) == 0) { memcpy(out.data(), src + off / 8, (size_t)((n + 7) / 8)); }
     else
         for (int64_t i = 0; i < n; ++i) {
@@ -79,163 +67,179 @@ std::vector<uint8_t> realign_bits(const uint8_t* src, int64_t off, int64_t n) {
     return out;
 }
 
-// ---- export ------------------------------------------------------------------------------------------
-struct ExportedArray {
-    std::vector<void*> owned;                 // malloc'd buffers
-    std::vector<const void*> buffers;
-    std::vector<ArrowArray> child_storage;
-    std::vector<ArrowArray*> child_ptrs;
-    std::vector<ExportedArray*> child_priv;
-    ~ExportedArray() { for (void* p : owned) free(p); }
-};
+template <class O>
+ArrowColumn<O> normalise_array(const ArrowArray& a, int64_t off, int dt, const char* name) {
+    ArrowColumn<O> c;
+    const int64_t n = c.n = a.length;
+    const uint8_t* validity = a.n_buffers > 0 ? static_cast<const uint8_t*>(a.buffers[0]) : nullptr;
+    if (validity && a.null_count != 0) {
+        c.has_validity = true;
+        c.validity = slice_bits(validity, off, n);
+        int64_t valid = 0;
+        for (int64_t k = 0; k < (n + 7) / 8; ++k) valid += __builtin_popcount(c.validity[(size_t)k]);
+        c.null_count = n - valid;
+    }
+    if (dt == DT_UTF8) {
+        // the C Data spec lets a length-0 array come without an offsets buffer; any other array must have one
+        if (!a.buffers[1] && n > 0) fail(BHIP_EINVAL, std::string("Arrow array of column ") + name + " has no offsets buffer");
+        if (a.buffers[1]) {
+            c.offsets = static_cast<const O*>(a.buffers[1]) + off;
+            c.base = c.offsets[0];
+            c.data_bytes = (int64_t)(c.offsets[n] - c.base);
+        }
+        if (a.buffers[2]) c.data = static_cast<const uint8_t*>(a.buffers[2]) + c.base;      // only the referenced bytes travel
+    } else if (dt == DT_BOOLEAN) {
+        c.bits = slice_bits(static_cast<const uint8_t*>(a.buffers[1]), off, n);
+    } else {
+        c.data = static_cast<const uint8_t*>(a.buffers[1]) + off * dtype_width(dt);
+        c.data_bytes = n * dtype_width(dt);
+    }
+    return c;
+}
+template ArrowColumn<int32_t> normalise_array<int32_t>(const ArrowArray&, int64_t, int, const char*);
+template ArrowColumn<int64_t> normalise_array<int64_t>(const ArrowArray&, int64_t, int, const char*);
 
-void release_array(ArrowArray* a) {
+// ---- export: the struct array shell ---------------------------------------------------------------------
+static void release_shell_child(ArrowArray* a) { a->release = nullptr; }
+static void release_shell(ArrowArray* a) {
     if (!a || !a->release) return;
-    auto* priv = static_cast<ExportedArray*>(a->private_data);
-    for (auto& c : priv->child_storage)
-        if (c.release) c.release(&c);
-    delete priv;
+    delete static_cast<StructArrayShell*>(a->private_data);
     a->release = nullptr;
 }
 
-struct ExportedSchema {
-    std::string format, name;
-    std::vector<ArrowSchema> child_storage;
-    std::vector<ArrowSchema*> child_ptrs;
-};
+StructArrayShell::StructArrayShell(size_t n_children) : children(n_children), buffers(n_children) {
+    for (auto& c : children) { memset(&c, 0, sizeof(c)); child_ptrs.push_back(&c); }
+}
+StructArrayShell::~StructArrayShell() { for (void* p : owned) free(p); }
 
-void release_schema(ArrowSchema* s) {
-    if (!s || !s->release) return;
-    auto* priv = static_cast<ExportedSchema*>(s->private_data);
-    for (auto& c : priv->child_storage)
-        if (c.release) c.release(&c);
-    delete priv;
-    s->release = nullptr;
+void* StructArrayShell::alloc(size_t bytes) {
+    void* h = malloc(bytes ? bytes : 8);
+    if (!h) fail(BHIP_EOOM, "host allocation failed");
+    owned.push_back(h);
+    return h;
 }
 
+void StructArrayShell::finish_child(size_t i, int64_t n_rows, int64_t null_count) {
+    ArrowArray& a = children[i];
+    a.length = n_rows;
+    a.null_count = null_count;
+    a.n_buffers = (int64_t)buffers[i].size();
+    a.buffers = buffers[i].data();
+    a.release = release_shell_child;
+}
+
+void StructArrayShell::finish(std::unique_ptr<StructArrayShell> shell, int64_t n_rows, ArrowArray* out) {
+    memset(out, 0, sizeof(*out));
+    out->length = n_rows;
+    out->null_count = 0;
+    out->n_buffers = 1;
+    out->buffers = &shell->top_buffer;
+    out->n_children = (int64_t)shell->children.size();
+    out->children = shell->child_ptrs.data();
+    out->release = release_shell;
+    out->private_data = shell.release();
+}
+
+// ---- export: schema -------------------------------------------------------------------------------------
+namespace {
+struct ExportedSchema {
+    std::vector<std::string> names;
+    std::vector<ArrowSchema> children;
+    std::vector<ArrowSchema*> child_ptrs;
+};
+void release_schema_child(ArrowSchema* s) { s->release = nullptr; }
+void release_schema(ArrowSchema* s) {
+    if (!s || !s->release) return;
+    delete static_cast<ExportedSchema*>(s->private_data);
+    s->release = nullptr;
+}
+}  // namespace
+
 void export_schema(const Schema& schema, ArrowSchema* out) {
-    auto* top = new ExportedSchema();
-    top->format = "+s";
-    top->name = "";
-    top->child_storage.resize(schema.fields.size());
+    auto top = std::make_unique<ExportedSchema>();
+    top->children.resize(schema.fields.size());
+    for (auto& f : schema.fields) top->names.push_back(f.name);
     for (size_t i = 0; i < schema.fields.size(); ++i) {
-        auto* cp = new ExportedSchema();
-        cp->format = format_of(schema.fields[i].binary ? (int)DT_BINARY : schema.fields[i].large ? (int)DT_LARGE_UTF8 : schema.fields[i].dtype);
-        cp->name = schema.fields[i].name;
-        ArrowSchema& c = top->child_storage[i];
+        const Field& f = schema.fields[i];
+        ArrowSchema& c = top->children[i];
         memset(&c, 0, sizeof(c));
-        c.format = cp->format.c_str();
-        c.name = cp->name.c_str();
-        c.flags = schema.fields[i].nullable ? ARROW_FLAG_NULLABLE : 0;
-        c.release = release_schema;
-        c.private_data = cp;
+        c.format = format_of_dtype(f.binary ? (int)DT_BINARY : f.large ? (int)DT_LARGE_UTF8 : f.dtype);
+        c.name = top->names[i].c_str();
+        c.flags = f.nullable ? ARROW_FLAG_NULLABLE : 0;
+        c.release = release_schema_child;
         top->child_ptrs.push_back(&c);
     }
     memset(out, 0, sizeof(*out));
-    out->format = top->format.c_str();
-    out->name = top->name.c_str();
+    out->format = "+s";
+    out->name = "";
     out->n_children = (int64_t)schema.fields.size();
     out->children = top->child_ptrs.data();
     out->release = release_schema;
-    out->private_data = top;
+    out->private_data = top.release();
+}
+}  // namespace bhip
+
+namespace {
+
+// what the device operators carry: every primitive type the serde ships (rust/core/proto/ballista.proto:755-790) except
+// LargeUtf8, Binary, Float16, Time32/64, Interval, Duration, Decimal and the nested types — a batch of those is refused here
+// (BHIP_ENOTIMPL: keep the CPU operator); timestamps with a time zone likewise
+int device_dtype_from_format(const char* f) {
+    const int dt = dtype_from_format(f);
+    return (dt >= DT_INT32 && dt <= DT_LAST) || dt == DT_LARGE_UTF8 || dt == DT_BINARY ? dt : 0;
 }
 
-// small batches (stage outputs of aggregates: a few rows x a dozen columns): every buffer is packed into one
-// device block by ONE kernel and comes back in ONE copy, instead of one blocking copy per buffer
-static bool plan_small_export(const Batch& b, PackDesc& d, size_t& total) {
-    const int64_t n = b.n_rows;
-    d.n = 0;
-    total = 0;
-    auto add = [&](const void* dev, size_t bytes) -> bool {
-        if (d.n >= PACK_MAX || bytes > (1u << 20)) return false;
-        d.src[d.n] = dev; d.bytes[d.n] = (uint32_t)bytes; d.dst[d.n] = (uint32_t)total;
-        ++d.n;
-        total += (bytes + 63) & ~(size_t)63;
-        return true;
-    };
-    for (const Column& c : b.cols) {
-        if (c.validity && !add(c.validity->ptr(), (size_t)((n + 7) / 8))) return false;
-        if (c.dtype == DT_UTF8) {
-            if (!add(c.offsets->ptr(), (size_t)(n + 1) * 4) || !add(c.data->ptr(), (size_t)c.data_bytes)) return false;
-        } else if (c.dtype == DT_BOOLEAN) {
-            if (!add(c.data->ptr(), (size_t)((n + 7) / 8))) return false;
-        } else if (!add(c.data->ptr(), (size_t)n * dtype_width(c.dtype))) return false;
-    }
-    return total <= (4u << 20) && d.n > 0;
-}
-
+// ---- export: a device batch -----------------------------------------------------------------------------
+// ONE walk lists every buffer of the batch in Arrow order.  Small batches (stage outputs of aggregates: a few rows x a dozen
+// columns) pack the list into one device block by ONE kernel and fetch it in ONE copy; any other batch takes one blocking copy
+// per buffer.  The two differ only in where a buffer's host bytes come from.
 void export_batch(const Batch& b, ArrowArray* out) {
     b.ctx->set_device();
     HIP_CHECK(hipDeviceSynchronize());
-    auto* top = new ExportedArray();
-    std::unique_ptr<ExportedArray> guard(top);
-    top->child_storage.resize(b.cols.size());
-    for (auto& c : top->child_storage) memset(&c, 0, sizeof(c));
-    PackDesc pd;
-    size_t packed_total = 0;
+    const int64_t n = b.n_rows;
+    auto shell = std::make_unique<StructArrayShell>(b.cols.size());
+    struct Piece { size_t col; BufferRole role; const void* dev; size_t bytes, at; };
+    std::vector<Piece> pieces;
+    size_t total = 0;
+    bool small = true;
+    for (size_t i = 0; i < b.cols.size(); ++i) {
+        const Column& c = b.cols[i];
+        const ColumnLayout L = column_layout(c.dtype, n, c.data_bytes, (bool)c.validity);
+        if (!c.validity) shell->buffers[i].push_back(nullptr);
+        for (BufferRole r : {BUF_VALIDITY, BUF_OFFSETS, BUF_DATA}) {
+            if (!L[r].present) continue;
+            pieces.push_back({i, r, column_buffer(c, r)->ptr(), L[r].arrow_bytes, total});
+            small = small && L[r].arrow_bytes <= (1u << 20);
+            total += (L[r].arrow_bytes + 63) & ~(size_t)63;
+        }
+    }
+    small = small && !pieces.empty() && pieces.size() <= (size_t)PACK_MAX && total <= (4u << 20);
     uint8_t* packed = nullptr;
-    int packed_next = 0;
-    if (plan_small_export(b, pd, packed_total)) {
-        packed = static_cast<uint8_t*>(malloc(packed_total + 64));
-        if (!packed) fail(BHIP_EOOM, "host allocation failed");
-        top->owned.push_back(packed);
-        void* dev_block = b.ctx->alloc(packed_total + 64, nullptr);
+    if (small) {
+        packed = static_cast<uint8_t*>(shell->alloc(total + 64));
+        PackDesc pd;
+        pd.n = (int32_t)pieces.size();
+        for (size_t k = 0; k < pieces.size(); ++k) {
+            pd.src[k] = pieces[k].dev; pd.bytes[k] = (uint32_t)pieces[k].bytes; pd.dst[k] = (uint32_t)pieces[k].at;
+        }
+        void* dev_block = b.ctx->alloc(total + 64, nullptr);
         hipError_t e = launch_pack_buffers(LaunchCfg{b.ctx->cus(), nullptr}, pd, static_cast<uint8_t*>(dev_block));
-        if (e == hipSuccess) e = hipMemcpy(packed, dev_block, packed_total, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(packed, dev_block, total, hipMemcpyDeviceToHost);
         b.ctx->free(dev_block, nullptr);
         HIP_CHECK(e);
     }
-    for (size_t i = 0; i < b.cols.size(); ++i) {
-        const Column& c = b.cols[i];
-        auto* cp = new ExportedArray();
-        ArrowArray& a = top->child_storage[i];
-        a.private_data = cp;
-        a.release = release_array;
-        auto host_copy = [&](const void* dev, size_t bytes) -> void* {
-            if (packed) return packed + pd.dst[packed_next++];       // same order as plan_small_export
-            void* h = malloc(bytes ? bytes : 8);
-            if (!h) fail(BHIP_EOOM, "host allocation failed");
-            cp->owned.push_back(h);
-            if (bytes) HIP_CHECK(hipMemcpy(h, dev, bytes, hipMemcpyDeviceToHost));
-            return h;
-        };
-        const int64_t n = b.n_rows;
-        const void* validity = c.validity ? host_copy(c.validity->ptr(), (size_t)((n + 7) / 8)) : nullptr;
-        cp->buffers.push_back(validity);
-        if (c.dtype == DT_UTF8) {
-            const void* off32 = host_copy(c.offsets->ptr(), (size_t)(n + 1) * 4);
-            if (i < b.schema->fields.size() && b.schema->fields[i].large) {              // LargeUtf8: the same offsets as int64
-                auto* wide = static_cast<int64_t*>(malloc(((size_t)n + 1) * 8));
-                if (!wide) fail(BHIP_EOOM, "host allocation failed");
-                cp->owned.push_back(wide);
-                for (int64_t r = 0; r <= n; ++r) wide[r] = static_cast<const int32_t*>(off32)[r];
-                cp->buffers.push_back(wide);
-            } else {
-                cp->buffers.push_back(off32);
-            }
-            cp->buffers.push_back(host_copy(c.data->ptr(), (size_t)c.data_bytes));
-        } else if (c.dtype == DT_BOOLEAN) {
-            cp->buffers.push_back(host_copy(c.data->ptr(), (size_t)((n + 7) / 8)));
-        } else {
-            cp->buffers.push_back(host_copy(c.data->ptr(), (size_t)n * dtype_width(c.dtype)));
+    for (const Piece& p : pieces) {
+        void* h = packed ? packed + p.at : shell->alloc(p.bytes);
+        if (!packed && p.bytes) HIP_CHECK(hipMemcpy(h, p.dev, p.bytes, hipMemcpyDeviceToHost));
+        if (p.role == BUF_OFFSETS && p.col < b.schema->fields.size() && b.schema->fields[p.col].large) {   // LargeUtf8: the same offsets as int64
+            auto* wide = static_cast<int64_t*>(shell->alloc(((size_t)n + 1) * 8));
+            for (int64_t r = 0; r <= n; ++r) wide[r] = static_cast<const int32_t*>(h)[r];
+            h = wide;
         }
-        a.length = n;
-        a.null_count = c.validity ? -1 : 0;
-        a.offset = 0;
-        a.n_buffers = (int64_t)cp->buffers.size();
-        a.buffers = cp->buffers.data();
-        top->child_ptrs.push_back(&a);
+        shell->buffers[p.col].push_back(h);
     }
-    top->buffers.push_back(nullptr);
-    memset(out, 0, sizeof(*out));
-    out->length = b.n_rows;
-    out->null_count = 0;
-    out->n_buffers = 1;
-    out->buffers = top->buffers.data();
-    out->n_children = (int64_t)b.cols.size();
-    out->children = top->child_ptrs.data();
-    out->release = release_array;
-    out->private_data = guard.release();
+    for (size_t i = 0; i < b.cols.size(); ++i) shell->finish_child(i, n, b.cols[i].validity ? -1 : 0);
+    StructArrayShell::finish(std::move(shell), n, out);
 }
 
 // ---- C stream ------------------------------------------------------------------------------------------
@@ -274,6 +278,34 @@ void stream_release(ArrowArrayStream* st) {
     st->release = nullptr;
 }
 
+// ---- import ----------------------------------------------------------------------------------------------
+// one column of an incoming batch as a bhip_column_desc over host buffers; what had to be rebuilt lives in `bits` / `offs`.
+// The importer's policy: a validity buffer is kept whenever the array does not rule NULLs out (batch_from_host drops an all-ones
+// one); offsets are int32 on the device, so LargeUtf8 offsets are narrowed and more than 2 GiB of value bytes refused.
+template <class O>
+void describe_column(const ArrowArray& ca, int64_t off, int dt, const char* name, bhip_column_desc& d,
+                     std::vector<std::vector<uint8_t>>& bits, std::vector<std::vector<int32_t>>& offs) {
+    ArrowColumn<O> c = normalise_array<O>(ca, off, dt, name);
+    if (c.has_validity) {
+        bits.push_back(std::move(c.validity));
+        d.validity = bits.back().data();
+    }
+    if (dt == DT_UTF8) {
+        if (c.data_bytes > 0x7FFFFFFFll)
+            fail(BHIP_ENOTIMPL, std::string("LargeUtf8 column ") + name + " holds more than 2 GiB of value bytes in one batch");
+        offs.emplace_back((size_t)c.n + 1);
+        c.rebase_into(offs.back().data());
+        d.offsets = offs.back().data();
+        d.data = c.data ? c.data : "";
+        d.data_bytes = c.data_bytes;
+    } else if (dt == DT_BOOLEAN) {
+        bits.push_back(std::move(c.bits));
+        d.data = bits.back().data();
+    } else {
+        d.data = c.data;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -292,63 +324,26 @@ bhip_status bhip_batch_import_arrow(bhip_ctx* ctx, struct ArrowArray* array, str
         for (int i = 0; i < n_cols; ++i) {
             const ArrowSchema* cs = schema->children[i];
             const ArrowArray* ca = array->children[i];
+            const char* name = cs->name ? cs->name : "";
             const int dt = device_dtype_from_format(cs->format);
-            if (!dt) fail(BHIP_ENOTIMPL, std::string("unsupported Arrow type '") + cs->format + "' for column " + (cs->name ? cs->name : ""));
+            if (!dt) fail(BHIP_ENOTIMPL, std::string("unsupported Arrow type '") + cs->format + "' for column " + name);
             if (ca->dictionary) fail(BHIP_ENOTIMPL, "dictionary arrays are not supported");
             // the array must have the buffers its declared format implies (a producer whose batches do not match
             // the stream's schema would otherwise be read out of bounds)
             const bool large = dt == DT_LARGE_UTF8, binary = dt == DT_BINARY;
-            const int64_t need_buffers = (dt == DT_UTF8 || large || binary) ? 3 : 2;
-            if (ca->n_buffers < need_buffers || ca->length != n_rows)
-                fail(BHIP_EINVAL, std::string("Arrow array of column ") + (cs->name ? cs->name : "") + " does not match its schema");
-            const int64_t off = ca->offset + array->offset;
+            const int device_dt = (large || binary) ? (int)DT_UTF8 : dt;
+            if (ca->n_buffers < (device_dt == DT_UTF8 ? 3 : 2) || ca->length != n_rows)
+                fail(BHIP_EINVAL, std::string("Arrow array of column ") + name + " does not match its schema");
             bhip_column_desc& d = descs[i];
             memset(&d, 0, sizeof(d));
-            d.name = cs->name ? cs->name : "";
-            d.dtype = (large || binary) ? (int)DT_UTF8 : dt;
+            d.name = name;
+            d.dtype = device_dt;
             d.nullable = (cs->flags & ARROW_FLAG_NULLABLE) ? 1 : 0;
             large_cols.push_back(large);
             binary_cols.push_back(binary);
-            const uint8_t* validity = ca->n_buffers > 0 ? static_cast<const uint8_t*>(ca->buffers[0]) : nullptr;
-            if (validity && ca->null_count != 0) {
-                bit_storage.push_back(realign_bits(validity, off, n_rows));
-                d.validity = bit_storage.back().data();
-            }
-            if (large) {
-                // 64-bit offsets, rebased to 0 and narrowed: a batch's strings must fit the device column's int32 offsets
-                const int64_t* offsets = static_cast<const int64_t*>(ca->buffers[1]) + off;
-                off_storage.emplace_back((size_t)n_rows + 1);
-                auto& o = off_storage.back();
-                if (!ca->buffers[1] && n_rows > 0)
-                    fail(BHIP_EINVAL, std::string("Arrow array of column ") + (cs->name ? cs->name : "") + " has no offsets buffer");
-                const int64_t first = ca->buffers[1] ? offsets[0] : 0;
-                if (ca->buffers[1] && offsets[n_rows] - first > 0x7FFFFFFFll)
-                    fail(BHIP_ENOTIMPL, std::string("LargeUtf8 column ") + (cs->name ? cs->name : "") + " holds more than 2 GiB of value bytes in one batch");
-                for (int64_t r = 0; r <= n_rows; ++r) o[(size_t)r] = ca->buffers[1] ? (int32_t)(offsets[r] - first) : 0;
-                d.offsets = o.data();
-                d.data = static_cast<const uint8_t*>(ca->buffers[2]) + first;
-                d.data_bytes = o[(size_t)n_rows];
-                if (!ca->buffers[2]) d.data = "";
-            } else if (dt == DT_UTF8 || binary) {
-                const int32_t* offsets = static_cast<const int32_t*>(ca->buffers[1]) + off;
-                // rebase to 0 so only the referenced bytes are shipped
-                off_storage.emplace_back((size_t)n_rows + 1);
-                auto& o = off_storage.back();
-                // the C Data spec lets a length-0 array come without an offsets buffer; any other array must have one
-                if (!ca->buffers[1] && n_rows > 0)
-                    fail(BHIP_EINVAL, std::string("Arrow array of column ") + (cs->name ? cs->name : "") + " has no offsets buffer");
-                const int32_t first = ca->buffers[1] ? offsets[0] : 0;
-                for (int64_t r = 0; r <= n_rows; ++r) o[(size_t)r] = ca->buffers[1] ? offsets[r] - first : 0;
-                d.offsets = o.data();
-                d.data = static_cast<const uint8_t*>(ca->buffers[2]) + first;
-                d.data_bytes = o[(size_t)n_rows];
-                if (!ca->buffers[2]) d.data = "";
-            } else if (dt == DT_BOOLEAN) {
-                bit_storage.push_back(realign_bits(static_cast<const uint8_t*>(ca->buffers[1]), off, n_rows));
-                d.data = bit_storage.back().data();
-            } else {
-                d.data = static_cast<const uint8_t*>(ca->buffers[1]) + off * dtype_width(dt);
-            }
+            const int64_t off = ca->offset + array->offset;
+            if (large) describe_column<int64_t>(*ca, off, device_dt, name, d, bit_storage, off_storage);
+            else describe_column<int32_t>(*ca, off, device_dt, name, d, bit_storage, off_storage);
         }
         BatchPtr b = batch_from_host(ctx->p, n_cols, descs.data(), n_rows, false);
         // schema nullability follows the Arrow field flag
@@ -482,7 +477,7 @@ bhip_status bhip_batch_export_arrow(bhip_batch* batch, struct ArrowArray* out_ar
     try {
         if (!batch || !out_array || !out_schema) fail(BHIP_EINVAL, "null argument");
         export_schema(*batch->p->schema, out_schema);
-        try { export_batch(*batch->p, out_array); } catch (...) { release_schema(out_schema); throw; }
+        try { export_batch(*batch->p, out_array); } catch (...) { out_schema->release(out_schema); throw; }
         return BHIP_OK;
     } catch (const bhip::Error& e) { set_last_error(e.what()); return e.code; }
     catch (const std::exception& e) { set_last_error(e.what()); return BHIP_EINVAL; }

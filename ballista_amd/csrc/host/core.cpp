@@ -387,12 +387,28 @@ Buffer::~Buffer() {
 
 BufferPtr make_buffer(const Exec& ex, size_t bytes) { return std::make_shared<Buffer>(ex.ctx, bytes, ex.stream); }
 
+ColumnLayout column_layout(int dtype, int64_t n_rows, int64_t data_bytes, bool has_validity) {
+    ColumnLayout L;
+    const size_t n = (size_t)n_rows, bits = (n + 7) / 8;
+    auto set = [&](BufferRole r, bool bitmap, size_t arrow, size_t slack) {
+        const size_t dev = bitmap ? bitmap_bytes(n_rows) : arrow;
+        L.buf[r] = BufferSpec{true, bitmap, arrow, dev, dev + slack};
+    };
+    if (has_validity) set(BUF_VALIDITY, true, bits, 8);
+    if (dtype == DT_UTF8) {
+        set(BUF_OFFSETS, false, (n + 1) * 4, 0);
+        set(BUF_DATA, false, (size_t)data_bytes, 8);
+    } else if (dtype == DT_BOOLEAN) {
+        set(BUF_DATA, true, bits, 8);
+    } else {
+        set(BUF_DATA, false, n * dtype_width(dtype), 8);
+    }
+    return L;
+}
+
 int64_t Column::memory_size() const {
     int64_t b = 0;
-    if (dtype == DT_UTF8) b += data_bytes + (length + 1) * 4;
-    else if (dtype == DT_BOOLEAN) b += (length + 7) / 8;
-    else b += length * dtype_width(dtype);
-    if (validity) b += (length + 7) / 8;
+    for (const BufferSpec& s : column_layout(*this).buf) b += (int64_t)s.arrow_bytes;
     return b;
 }
 
@@ -410,101 +426,72 @@ BatchPtr batch_from_host(const ContextPtr& ctx, int n_cols, const bhip_column_de
     auto batch = std::make_shared<Batch>();
     batch->ctx = ctx;
     batch->n_rows = n_rows;
-    hipStream_t st = nullptr;   // null stream: synchronous wrt the caller
-    Exec ex{ctx, st};
-    // small host batches (stage inputs of a Final aggregate, dimension tables): all buffers travel in ONE block
-    // and ONE copy; the columns are slices of it (256-byte aligned, zero padded to whole words + slack)
-    std::vector<uint8_t> staging;
-    std::vector<size_t> slice_off;
-    BufferPtr block;
-    // a validity bitmap with every bit set says "no NULLs" (Arrow producers often attach one): the column is
-    // imported without it, so the NULL-free kernels serve it; the schema keeps its nullability
-    std::vector<const uint8_t*> validity((size_t)n_cols, nullptr);
-    for (int i = 0; i < n_cols; ++i) {
-        validity[i] = cols[i].validity;
-        if (device_ptrs || !cols[i].validity) continue;
-        const uint8_t* v = cols[i].validity;
-        const int64_t whole = n_rows / 8;
-        bool all = true;
-        for (int64_t k = 0; k < whole && all; ++k) all = v[k] == 0xFF;
-        if (all && (n_rows & 7)) all = (v[whole] & ((1u << (n_rows & 7)) - 1u)) == ((1u << (n_rows & 7)) - 1u);
-        if (all) validity[i] = nullptr;
-    }
-    if (!device_ptrs) {
-        size_t total = 0;
-        bool small = true;
-        auto plan = [&](const void* p, size_t bytes) {
-            if (!p) return;
-            slice_off.push_back(total);
-            total += (bytes + 8 + BUFFER_SLACK + 255) & ~(size_t)255;
-            if (bytes > (1u << 20)) small = false;
-        };
-        for (int i = 0; i < n_cols && small; ++i) {
-            const bhip_column_desc& d = cols[i];
-            if (d.dtype < DT_INT32 || d.dtype > DT_LAST) { small = false; break; }
-            const size_t db = d.dtype == DT_UTF8 ? (size_t)d.data_bytes : d.dtype == DT_BOOLEAN ? bitmap_bytes(n_rows) : (size_t)n_rows * dtype_width(d.dtype);
-            plan(d.data ? d.data : (const void*)"", db);
-            if (d.offsets) plan(d.offsets, (size_t)(n_rows + 1) * 4);
-            if (validity[i]) plan(validity[i], bitmap_bytes(n_rows));
-        }
-        if (small && total > 0 && total <= (4u << 20)) {
-            staging.assign(total, 0);
-            block = make_buffer(ex, total);
-        } else {
-            slice_off.clear();
-        }
-    }
-    size_t next_slice = 0;
-    auto slice = [&](const void* host, size_t copy_bytes, size_t logical_bytes) -> BufferPtr {
-        const size_t off = slice_off[next_slice++];
-        if (copy_bytes && host) memcpy(staging.data() + off, host, copy_bytes);
-        return std::make_shared<Buffer>(ctx, block, static_cast<uint8_t*>(block->ptr()) + off, logical_bytes);
-    };
+    Exec ex{ctx, nullptr};      // null stream: synchronous wrt the caller
+    // every buffer of the batch, in the order data, offsets, validity within a column
+    struct Piece { int col; BufferRole role; const void* src; BufferSpec spec; };
+    std::vector<Piece> pieces;
     for (int i = 0; i < n_cols; ++i) {
         const bhip_column_desc& d = cols[i];
         if (!d.name) fail(BHIP_EINVAL, "column without a name");
         if (d.dtype < DT_INT32 || d.dtype > DT_LAST) fail(BHIP_ENOTIMPL, std::string("unsupported data type for column ") + d.name);
+        if (d.dtype == DT_UTF8 && !d.offsets) fail(BHIP_EINVAL, std::string("Utf8 column without offsets: ") + d.name);
         schema->fields.push_back(Field{d.name, d.dtype, d.nullable != 0 || d.validity != nullptr});
+        // a validity bitmap with every bit set says "no NULLs" (Arrow producers often attach one): the column is
+        // imported without it, so the NULL-free kernels serve it; the schema keeps its nullability
+        const uint8_t* validity = d.validity;
+        if (validity && !device_ptrs) {
+            const int64_t whole = n_rows / 8;
+            const unsigned tail = (1u << (n_rows & 7)) - 1u;
+            bool all = true;
+            for (int64_t k = 0; k < whole && all; ++k) all = validity[k] == 0xFF;
+            if (all && tail) all = (validity[whole] & tail) == tail;
+            if (all) validity = nullptr;
+        }
         Column c;
         c.dtype = d.dtype;
         c.length = n_rows;
-        size_t data_bytes;
-        if (d.dtype == DT_UTF8) {
-            if (!d.offsets) fail(BHIP_EINVAL, std::string("Utf8 column without offsets: ") + d.name);
-            data_bytes = (size_t)d.data_bytes;
-            c.data_bytes = d.data_bytes;
-        } else if (d.dtype == DT_BOOLEAN) {
-            data_bytes = (size_t)((n_rows + 7) / 8);
-        } else {
-            data_bytes = (size_t)n_rows * dtype_width(d.dtype);
-        }
-        if (!d.data && data_bytes > 0) fail(BHIP_EINVAL, std::string("column without data: ") + d.name);
-        if (device_ptrs) {
-            c.data = std::make_shared<Buffer>(ctx, const_cast<void*>(d.data), data_bytes);
-            if (d.offsets) c.offsets = std::make_shared<Buffer>(ctx, const_cast<int32_t*>(d.offsets), (size_t)(n_rows + 1) * 4);
-            if (d.validity) c.validity = std::make_shared<Buffer>(ctx, const_cast<uint8_t*>(d.validity), bitmap_bytes(n_rows));
-        } else if (block) {
-            const size_t padded = d.dtype == DT_BOOLEAN ? bitmap_bytes(n_rows) : data_bytes;
-            c.data = slice(d.data, data_bytes, padded + 8);
-            if (d.offsets) c.offsets = slice(d.offsets, (size_t)(n_rows + 1) * 4, (size_t)(n_rows + 1) * 4);
-            if (validity[i]) c.validity = slice(validity[i], (size_t)((n_rows + 7) / 8), bitmap_bytes(n_rows) + 8);
-        } else {
-            // device copies are padded to whole 64-bit words (bitmaps are read as u64)
-            const size_t padded = d.dtype == DT_BOOLEAN ? bitmap_bytes(n_rows) : data_bytes;
-            c.data = make_buffer(ex, padded + 8);
-            if (d.dtype == DT_BOOLEAN) HIP_CHECK(hipMemset(c.data->ptr(), 0, padded + 8));
-            if (data_bytes) HIP_CHECK(hipMemcpy(c.data->ptr(), d.data, data_bytes, hipMemcpyHostToDevice));
-            if (d.offsets) {
-                c.offsets = make_buffer(ex, (size_t)(n_rows + 1) * 4);
-                HIP_CHECK(hipMemcpy(c.offsets->ptr(), d.offsets, (size_t)(n_rows + 1) * 4, hipMemcpyHostToDevice));
-            }
-            if (validity[i]) {
-                c.validity = make_buffer(ex, bitmap_bytes(n_rows) + 8);
-                HIP_CHECK(hipMemset(c.validity->ptr(), 0, bitmap_bytes(n_rows) + 8));
-                HIP_CHECK(hipMemcpy(c.validity->ptr(), validity[i], (size_t)((n_rows + 7) / 8), hipMemcpyHostToDevice));
-            }
-        }
+        if (d.dtype == DT_UTF8) c.data_bytes = d.data_bytes;
+        const ColumnLayout L = column_layout(c.dtype, n_rows, c.data_bytes, validity != nullptr);
+        if (!d.data && L[BUF_DATA].arrow_bytes > 0) fail(BHIP_EINVAL, std::string("column without data: ") + d.name);
+        pieces.push_back({i, BUF_DATA, d.data, L[BUF_DATA]});
+        if (L[BUF_OFFSETS].present) pieces.push_back({i, BUF_OFFSETS, d.offsets, L[BUF_OFFSETS]});
+        if (validity) pieces.push_back({i, BUF_VALIDITY, validity, L[BUF_VALIDITY]});
         batch->cols.push_back(std::move(c));
+    }
+    // small host batches (stage inputs of a Final aggregate, dimension tables): all buffers travel in ONE block
+    // and ONE copy; the columns are slices of it (256-byte aligned, zero padded to whole words + slack)
+    std::vector<uint8_t> staging;
+    BufferPtr block;
+    auto slot = [](const BufferSpec& s) { return (s.device_bytes + 8 + BUFFER_SLACK + 255) & ~(size_t)255; };
+    if (!device_ptrs) {
+        size_t total = 0;
+        bool small = true;
+        for (const Piece& p : pieces) {
+            small = small && p.spec.device_bytes <= (1u << 20);
+            total += slot(p.spec);
+        }
+        if (small && total > 0 && total <= (4u << 20)) {
+            staging.assign(total, 0);
+            block = make_buffer(ex, total);
+        }
+    }
+    size_t at = 0;
+    for (const Piece& p : pieces) {
+        const BufferSpec& s = p.spec;
+        BufferPtr buf;
+        if (device_ptrs) {          // borrowed as it is: the caller's values in their Arrow size, its bitmaps read as whole words
+            buf = std::make_shared<Buffer>(ctx, const_cast<void*>(p.src), p.role == BUF_DATA ? s.arrow_bytes : s.device_bytes);
+        } else if (block) {
+            if (s.arrow_bytes && p.src) memcpy(staging.data() + at, p.src, s.arrow_bytes);
+            buf = std::make_shared<Buffer>(ctx, block, block->as<uint8_t>() + at, s.alloc_bytes);
+            at += slot(s);
+        } else {                    // device copies are padded to whole 64-bit words (bitmaps are read as u64)
+            buf = make_buffer(ex, s.alloc_bytes);
+            if (s.bitmap) HIP_CHECK(hipMemset(buf->ptr(), 0, s.alloc_bytes));
+            if (s.arrow_bytes) HIP_CHECK(hipMemcpy(buf->ptr(), p.src, s.arrow_bytes, hipMemcpyHostToDevice));
+        }
+        Column& c = batch->cols[(size_t)p.col];
+        (p.role == BUF_DATA ? c.data : p.role == BUF_OFFSETS ? c.offsets : c.validity) = std::move(buf);
     }
     if (block) HIP_CHECK(hipMemcpy(block->ptr(), staging.data(), staging.size(), hipMemcpyHostToDevice));
     batch->schema = schema;
@@ -516,18 +503,15 @@ void column_to_host(const Batch& b, int i, void* data, int32_t* offsets, uint8_t
     b.ctx->set_device();
     HIP_CHECK(hipDeviceSynchronize());
     const Column& c = b.cols[i];
-    if (data) {
-        size_t bytes;
-        if (c.dtype == DT_UTF8) bytes = (size_t)c.data_bytes;
-        else if (c.dtype == DT_BOOLEAN) bytes = (size_t)((c.length + 7) / 8);
-        else bytes = (size_t)c.length * dtype_width(c.dtype);
-        if (bytes) HIP_CHECK(hipMemcpy(data, c.data->ptr(), bytes, hipMemcpyDeviceToHost));
-    }
-    if (offsets && c.offsets) HIP_CHECK(hipMemcpy(offsets, c.offsets->ptr(), (size_t)(c.length + 1) * 4, hipMemcpyDeviceToHost));
+    const ColumnLayout L = column_layout(c.dtype, c.length, c.data_bytes, true);
+    auto fetch = [&](void* host, BufferRole r) {
+        if (L[r].arrow_bytes) HIP_CHECK(hipMemcpy(host, column_buffer(c, r)->ptr(), L[r].arrow_bytes, hipMemcpyDeviceToHost));
+    };
+    if (data) fetch(data, BUF_DATA);
+    if (offsets && c.offsets) fetch(offsets, BUF_OFFSETS);
     if (validity) {
-        const size_t bytes = (size_t)((c.length + 7) / 8);
-        if (c.validity) { if (bytes) HIP_CHECK(hipMemcpy(validity, c.validity->ptr(), bytes, hipMemcpyDeviceToHost)); }
-        else memset(validity, 0xFF, bytes);
+        if (c.validity) fetch(validity, BUF_VALIDITY);
+        else memset(validity, 0xFF, L[BUF_VALIDITY].arrow_bytes);
     }
 }
 

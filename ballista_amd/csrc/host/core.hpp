@@ -264,6 +264,25 @@ struct Column {
     int64_t memory_size() const;
 };
 
+// The buffers of a materialised column: THE place that knows which buffers a column of a type has and how many bytes each holds.
+// Everything that moves a column across the library's edge (host import and export, the packed blocks of the exchange) walks
+// this, in the order it needs.
+enum BufferRole { BUF_VALIDITY = 0, BUF_OFFSETS = 1, BUF_DATA = 2 };
+struct BufferSpec {
+    bool present = false;
+    bool bitmap = false;       // validity, Boolean values: the device copy is zero-padded to whole words
+    size_t arrow_bytes = 0;    // what the Arrow buffer holds: (n+7)/8, (n+1)*4, the Utf8 value bytes, n*width
+    size_t device_bytes = 0;   // on the device: bitmaps as whole 64-bit words (they are read as u64), everything else as in Arrow
+    size_t alloc_bytes = 0;    // logical size of a device copy made at the edge: device_bytes, + 8 of slack on values and bitmaps
+};
+struct ColumnLayout {
+    BufferSpec buf[3];         // by BufferRole
+    const BufferSpec& operator[](BufferRole r) const { return buf[r]; }
+};
+ColumnLayout column_layout(int dtype, int64_t n_rows, int64_t data_bytes, bool has_validity);
+inline ColumnLayout column_layout(const Column& c) { return column_layout(c.dtype, c.length, c.data_bytes, (bool)c.validity); }
+inline const BufferPtr& column_buffer(const Column& c, BufferRole r) { return r == BUF_VALIDITY ? c.validity : r == BUF_OFFSETS ? c.offsets : c.data; }
+
 struct Field {
     std::string name;
     int dtype;

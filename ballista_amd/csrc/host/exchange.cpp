@@ -98,97 +98,90 @@ inline size_t align_up(size_t v) { return (v + ALIGN - 1) & ~(ALIGN - 1); }
 // header: [0] = rows, [1] = block bytes, then per column [data bytes, has offsets, has validity]
 size_t pack_header_words(const Schema& s) { return 2 + 3 * s.fields.size(); }
 
-static size_t column_data_bytes(const Column& c, int64_t n_rows) {
-    if (c.dtype == DT_UTF8) return (size_t)c.data_bytes;
-    if (c.dtype == DT_BOOLEAN) return bitmap_bytes(n_rows);
-    return (size_t)n_rows * dtype_width(c.dtype);
+// The layout of a block, computed from its header (and so the same on the packing and the unpacking rank): per column the data,
+// then the offsets, then the validity; every piece at a 64-byte boundary; data pieces carry BUFFER_SLACK behind them (kernels
+// may over-read short strings), validity pieces 8 bytes.
+struct BlockPiece { size_t col; BufferRole role; size_t at, bytes; };
+struct BlockLayout { std::vector<BlockPiece> pieces; size_t total = 0; };
+
+static BlockLayout block_layout(size_t n_cols, const int64_t* h) {
+    BlockLayout L;
+    auto add = [&](size_t col, BufferRole role, size_t bytes, size_t slack) {
+        L.pieces.push_back({col, role, L.total, bytes});
+        L.total += align_up(bytes + slack);
+    };
+    for (size_t i = 0; i < n_cols; ++i) {
+        add(i, BUF_DATA, (size_t)h[2 + 3 * i], BUFFER_SLACK);
+        if (h[3 + 3 * i]) add(i, BUF_OFFSETS, (size_t)(h[0] + 1) * 4, 0);
+        if (h[4 + 3 * i]) add(i, BUF_VALIDITY, bitmap_bytes(h[0]), 8);
+    }
+    return L;
 }
 
 void pack_header(const Batch& b, int64_t* h) {
     h[0] = b.n_rows;
-    size_t total = 0;
     for (size_t i = 0; i < b.cols.size(); ++i) {
         const Column& c = b.cols[i];
-        const size_t db = column_data_bytes(c, b.n_rows);
-        h[2 + 3 * i] = (int64_t)db;
-        h[3 + 3 * i] = c.dtype == DT_UTF8 ? 1 : 0;
-        h[4 + 3 * i] = c.validity ? 1 : 0;
-        total += align_up(db + BUFFER_SLACK);                       // slack: kernels may over-read short strings
-        if (c.dtype == DT_UTF8) total += align_up((size_t)(b.n_rows + 1) * 4);
-        if (c.validity) total += align_up(bitmap_bytes(b.n_rows) + 8);
+        const ColumnLayout L = column_layout(c.dtype, b.n_rows, c.data_bytes, (bool)c.validity);
+        h[2 + 3 * i] = (int64_t)L[BUF_DATA].device_bytes;
+        h[3 + 3 * i] = L[BUF_OFFSETS].present ? 1 : 0;
+        h[4 + 3 * i] = L[BUF_VALIDITY].present ? 1 : 0;
     }
-    h[1] = (int64_t)total;
+    h[1] = (int64_t)block_layout(b.cols.size(), h).total;
 }
 
-// copies every buffer of `b` to `dst` (device) in header order
-void pack_batch(const Exec& ex, const Batch& b, uint8_t* dst) {
-    struct Piece { const void* src; size_t bytes; size_t at; };
-    std::vector<Piece> pieces;
-    size_t at = 0;
-    for (auto& c : b.cols) {
-        const size_t db = column_data_bytes(c, b.n_rows);
-        pieces.push_back({c.data ? c.data->ptr() : nullptr, db, at});
-        at += align_up(db + BUFFER_SLACK);
-        if (c.dtype == DT_UTF8) {
-            // (a 0-row Utf8 column may come without an offsets buffer — empty partitions are common after hash partitioning;
-            // the block is zero-filled where nothing is copied, and offsets[0] = 0 is the whole offsets array of an empty column)
-            pieces.push_back({c.offsets ? c.offsets->ptr() : nullptr, (size_t)(b.n_rows + 1) * 4, at});
-            at += align_up((size_t)(b.n_rows + 1) * 4);
-        }
-        if (c.validity) {
-            pieces.push_back({c.validity->ptr(), bitmap_bytes(b.n_rows), at});
-            at += align_up(bitmap_bytes(b.n_rows) + 8);
-        }
-    }
-    bool small = pieces.size() <= PACK_MAX;
-    for (auto& p : pieces) small = small && p.bytes <= (1u << 20);
+// copies every buffer of `b` to `dst` (device), laid out as its header `h` says
+void pack_batch(const Exec& ex, const Batch& b, const int64_t* h, uint8_t* dst) {
+    const BlockLayout L = block_layout(b.cols.size(), h);
+    // (a 0-row Utf8 column may come without an offsets buffer — empty partitions are common after hash partitioning;
+    // the block is zero-filled where nothing is copied, and offsets[0] = 0 is the whole offsets array of an empty column)
+    auto src_of = [&](const BlockPiece& p) -> const void* {
+        const BufferPtr& buf = column_buffer(b.cols[p.col], p.role);
+        return buf ? buf->ptr() : nullptr;
+    };
+    bool small = L.pieces.size() <= PACK_MAX;
+    for (auto& p : L.pieces) small = small && p.bytes <= (1u << 20);
     if (small) {
         PackDesc pd;
         pd.n = 0;
-        for (auto& p : pieces) {
-            if (!p.bytes || !p.src) continue;
-            pd.src[pd.n] = p.src;
+        for (auto& p : L.pieces) {
+            if (!p.bytes || !src_of(p)) continue;
+            pd.src[pd.n] = src_of(p);
             pd.bytes[pd.n] = (uint32_t)p.bytes;
             pd.dst[pd.n] = (uint32_t)p.at;
             ++pd.n;
         }
         if (pd.n) HIP_CHECK(launch_pack_buffers(ex.cfg(), pd, dst));
-        for (auto& p : pieces)                       // a buffer the batch does not have (offsets of a 0-row Utf8 column): zeros
-            if (p.bytes && !p.src) HIP_CHECK(hipMemsetAsync(dst + p.at, 0, p.bytes, ex.stream));
-        return;
     }
-    for (auto& p : pieces)
-        if (p.bytes && p.src) HIP_CHECK(hipMemcpyAsync(dst + p.at, p.src, p.bytes, hipMemcpyDeviceToDevice, ex.stream));
-        else if (p.bytes) HIP_CHECK(hipMemsetAsync(dst + p.at, 0, p.bytes, ex.stream));
+    for (auto& p : L.pieces) {
+        if (!p.bytes) continue;
+        if (!src_of(p)) HIP_CHECK(hipMemsetAsync(dst + p.at, 0, p.bytes, ex.stream));       // a buffer the batch does not have: zeros
+        else if (!small) HIP_CHECK(hipMemcpyAsync(dst + p.at, src_of(p), p.bytes, hipMemcpyDeviceToDevice, ex.stream));
+    }
 }
 
 // the batch whose buffers are slices of `block` (kept alive by the columns)
 BatchPtr unpack_batch(const ContextPtr& ctx, const SchemaPtr& schema, const BufferPtr& block, size_t block_offset, const int64_t* h) {
+    const BlockLayout L = block_layout(schema->fields.size(), h);
+    if ((int64_t)L.total != h[1]) fail(BHIP_EEXEC, "exchange: block layout does not match its header");
     auto b = std::make_shared<Batch>();
     b->schema = schema;
     b->ctx = ctx;
     b->n_rows = h[0];
-    uint8_t* base = block->as<uint8_t>() + block_offset;
-    size_t at = 0;
-    for (size_t i = 0; i < schema->fields.size(); ++i) {
+    for (auto& f : schema->fields) {
         Column c;
-        c.dtype = schema->fields[i].dtype;
+        c.dtype = f.dtype;
         c.length = b->n_rows;
-        const size_t db = (size_t)h[2 + 3 * i];
-        c.data = std::make_shared<Buffer>(ctx, block, base + at, db);
-        at += align_up(db + BUFFER_SLACK);
-        if (h[3 + 3 * i]) {
-            c.offsets = std::make_shared<Buffer>(ctx, block, base + at, (size_t)(b->n_rows + 1) * 4);
-            at += align_up((size_t)(b->n_rows + 1) * 4);
-            c.data_bytes = (int64_t)db;
-        }
-        if (h[4 + 3 * i]) {
-            c.validity = std::make_shared<Buffer>(ctx, block, base + at, bitmap_bytes(b->n_rows));
-            at += align_up(bitmap_bytes(b->n_rows) + 8);
-        }
         b->cols.push_back(std::move(c));
     }
-    if ((int64_t)at != h[1]) fail(BHIP_EEXEC, "exchange: block layout does not match its header");
+    uint8_t* base = block->as<uint8_t>() + block_offset;
+    for (auto& p : L.pieces) {
+        Column& c = b->cols[p.col];
+        auto buf = std::make_shared<Buffer>(ctx, block, base + p.at, p.bytes);
+        if (p.role == BUF_DATA) c.data = buf;
+        else if (p.role == BUF_VALIDITY) c.validity = buf;
+        else { c.offsets = buf; c.data_bytes = h[2 + 3 * p.col]; }
+    }
     return b;
 }
 
@@ -378,20 +371,6 @@ private:
     int world_;
 };
 
-static BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema) {
-    auto e = std::make_shared<Batch>();
-    e->schema = schema;
-    e->ctx = ex.ctx;
-    for (auto& f : schema->fields) {
-        Column c;
-        c.dtype = f.dtype;
-        c.data = make_buffer(ex, 8);
-        if (f.dtype == DT_UTF8) { c.offsets = make_buffer(ex, 8); HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream)); }
-        e->cols.push_back(c);
-    }
-    return e;
-}
-
 static void same_schema(const Schema& a, const Schema& b, const char* what) {
     bool ok = a.fields.size() == b.fields.size();
     for (size_t i = 0; ok && i < a.fields.size(); ++i) ok = a.fields[i].dtype == b.fields[i].dtype;
@@ -447,7 +426,7 @@ public:
         auto recv = make_buffer(ex, SLOT * (size_t)world_);
         HIP_CHECK(hipMemsetAsync(send->ptr(), 0, fits ? SLOT : head_bytes, stream_));
         HIP_CHECK(hipMemcpyAsync(send->ptr(), h.data(), H * 8, hipMemcpyHostToDevice, stream_));
-        if (fits) pack_batch(ex, *mine, send->as<uint8_t>() + head_bytes);
+        if (fits) pack_batch(ex, *mine, h.data(), send->as<uint8_t>() + head_bytes);
         t_->all_gather(send->ptr(), recv->ptr(), SLOT, stream_);
         std::vector<int64_t> heads((size_t)world_ * H);
         // every rank's header in ONE strided copy (a copy call per rank is ~10 us each: eight of them per all_gather of an 8-GPU step)
@@ -465,22 +444,14 @@ public:
         }
         // round 2: blocks of any size, point to point (every rank took the same branch: the headers are common knowledge)
         auto mine_block = make_buffer(ex, (size_t)h[1] + ALIGN);
-        pack_batch(ex, *mine, mine_block->as<uint8_t>());
-        std::vector<BufferPtr> blocks(world_);
-        std::vector<Xfer> sends, recvs;
+        pack_batch(ex, *mine, h.data(), mine_block->as<uint8_t>());
+        std::vector<Xfer> to_peer(world_);
+        std::vector<const int64_t*> head(world_);
         for (int p = 0; p < world_; ++p) {
-            if (p == rank_) continue;
-            const size_t nb = (size_t)heads[(size_t)p * H + 1];
-            blocks[p] = make_buffer(ex, nb + ALIGN);
-            if (h[1]) sends.push_back(Xfer{mine_block->ptr(), (size_t)h[1], p});
-            if (nb) recvs.push_back(Xfer{blocks[p]->ptr(), nb, p});
+            to_peer[p] = Xfer{mine_block->ptr(), (size_t)h[1], p};
+            head[p] = &heads[(size_t)p * H];
         }
-        t_->exchange(sends, recvs, stream_);
-        HIP_CHECK(hipStreamSynchronize(stream_));
-        for (int r = 0; r < world_; ++r) {
-            if (r != rank_) blocks[r]->set_stream(nullptr);
-            out[r] = r == rank_ ? mine : unpack_batch(ctx_, schema, blocks[r], 0, &heads[(size_t)r * H]);
-        }
+        out = exchange_blocks(ex, schema, to_peer, head, mine);
         account(t0, (uint64_t)h[1] * (uint64_t)(world_ - 1));
         return out;
     }
@@ -505,31 +476,21 @@ public:
         for (int d = 0; d < world_; ++d) pack_header(*parts[d], &mine[(size_t)d * H]);
         const std::vector<int64_t> all = gather_words(mine);
         // pack while nothing else is pending
-        std::vector<BufferPtr> sendb(world_), recvb(world_);
+        std::vector<BufferPtr> sendb(world_);
+        std::vector<Xfer> send(world_);
+        std::vector<const int64_t*> head(world_);
         uint64_t out_bytes = 0;
         for (int d = 0; d < world_; ++d) {
+            head[d] = &all[((size_t)d * world_ + rank_) * H];          // what rank d holds for this rank
             if (d == rank_) continue;
             const size_t nb = (size_t)mine[(size_t)d * H + 1];
             sendb[d] = make_buffer(ex, nb + ALIGN);
-            pack_batch(ex, *parts[d], sendb[d]->as<uint8_t>());
+            pack_batch(ex, *parts[d], &mine[(size_t)d * H], sendb[d]->as<uint8_t>());
+            send[d] = Xfer{sendb[d]->ptr(), nb, d};
             out_bytes += nb;
         }
-        auto head_of = [&](int src, int dst) { return &all[((size_t)src * world_ + dst) * H]; };
-        for (int s = 0; s < world_; ++s) check_header(head_of(s, rank_), *schema, "all_to_all");
-        std::vector<Xfer> sends, recvs;
-        for (int p = 0; p < world_; ++p) {
-            if (p == rank_) continue;
-            const size_t out_b = (size_t)mine[(size_t)p * H + 1], in_b = (size_t)head_of(p, rank_)[1];
-            recvb[p] = make_buffer(ex, in_b + ALIGN);
-            if (out_b) sends.push_back(Xfer{sendb[p]->ptr(), out_b, p});
-            if (in_b) recvs.push_back(Xfer{recvb[p]->ptr(), in_b, p});
-        }
-        t_->exchange(sends, recvs, stream_);
-        HIP_CHECK(hipStreamSynchronize(stream_));
-        for (int s = 0; s < world_; ++s) {
-            if (s != rank_) recvb[s]->set_stream(nullptr);
-            out[s] = s == rank_ ? parts[s] : unpack_batch(ctx_, schema, recvb[s], 0, head_of(s, rank_));
-        }
+        for (int s = 0; s < world_; ++s) check_header(head[s], *schema, "all_to_all");
+        out = exchange_blocks(ex, schema, send, head, parts[rank_]);
         account(t0, out_bytes);
         return out;
     }
@@ -747,6 +708,29 @@ private:
             if (ok && w > 0) ok = h[2 + 3 * i] == h[0] * w;
         }
         if (!ok) fail(BHIP_EEXEC, std::string(what) + ": a peer's block header does not fit this rank's schema (collective calls need ONE schema on every rank)");
+    }
+    // The tail of a point-to-point round.  Per peer p: `send[p]`, a region of a block this rank packed (nothing where it has no
+    // bytes), and `head[p]`, the header of the block p sends here.  One grouped exchange; out[p] = p's block unpacked (its
+    // columns are slices of the received block), out[rank_] = `own`.
+    std::vector<BatchPtr> exchange_blocks(const Exec& ex, const SchemaPtr& schema, const std::vector<Xfer>& send,
+                                          const std::vector<const int64_t*>& head, const BatchPtr& own) {
+        std::vector<BufferPtr> blocks(world_);
+        std::vector<Xfer> sends, recvs;
+        for (int p = 0; p < world_; ++p) {
+            if (p == rank_) continue;
+            const size_t nb = (size_t)head[p][1];
+            blocks[p] = make_buffer(ex, nb + ALIGN);
+            if (send[p].bytes) sends.push_back(send[p]);
+            if (nb) recvs.push_back(Xfer{blocks[p]->ptr(), nb, p});
+        }
+        t_->exchange(sends, recvs, stream_);
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        std::vector<BatchPtr> out(world_);
+        for (int r = 0; r < world_; ++r) {
+            if (r != rank_) blocks[r]->set_stream(nullptr);
+            out[r] = r == rank_ ? own : unpack_batch(ctx_, schema, blocks[r], 0, head[r]);
+        }
+        return out;
     }
     // all_gather of a few int64 words per rank (the same count on every rank) -> [rank][words]
     std::vector<int64_t> gather_words(const std::vector<int64_t>& mine) {
@@ -1014,7 +998,7 @@ bhip_status bhip_batch_pack(bhip_batch* batch, int64_t* header, int32_t header_c
     try {
         auto dev = make_buffer(ex, (size_t)header[1] + 64);
         HIP_CHECK(hipMemsetAsync(dev->ptr(), 0, (size_t)header[1], ex.stream));
-        pack_batch(ex, b, dev->as<uint8_t>());
+        pack_batch(ex, b, header, dev->as<uint8_t>());
         HIP_CHECK(hipMemcpyAsync(host_block, dev->ptr(), (size_t)header[1], hipMemcpyDeviceToHost, ex.stream));
         HIP_CHECK(hipStreamSynchronize(ex.stream));
     } catch (...) { b.ctx->release_stream(ex.stream); throw; }

@@ -16,12 +16,10 @@
 #include <fstream>
 #include <memory>
 
+#include "arrow_c.hpp"
 #include "plan.hpp"
 
 namespace bhip {
-
-int dtype_from_format(const char* fmt);       // arrow_c.cpp
-const char* format_of_dtype(int dt);
 
 namespace {
 
@@ -338,70 +336,30 @@ std::vector<uint8_t> message_bytes(Fb& fb, uint8_t header_type, uint32_t header,
 inline int64_t pad8(int64_t n) { return (n + 7) / 8 * 8; }
 
 // ---- host columns (Arrow C Data Interface) ----------------------------------------------------------------------------------
-bool bit_get(const uint8_t* bits, int64_t i) { return (bits[i >> 3] >> (i & 7)) & 1; }
-
-// bits [off, off + n) of `src` as a bitmap starting at bit 0
-std::vector<uint8_t> slice_bits(const uint8_t* src, int64_t off, int64_t n) {
-    std::vector<uint8_t> out((size_t)pad8((n + 7) / 8), 0);
-    if ((off & 7) == 0) {
-        memcpy(out.data(), src + (off >> 3), (size_t)((n + 7) / 8));
-        if (n & 7) out[(size_t)(n >> 3)] &= (uint8_t)((1u << (n & 7)) - 1);
-    } else {
-        for (int64_t i = 0; i < n; ++i)
-            if (bit_get(src, off + i)) out[(size_t)(i >> 3)] |= (uint8_t)(1u << (i & 7));
-    }
-    return out;
-}
-
 struct BodyPiece { const void* ptr; int64_t bytes; std::vector<uint8_t> owned; };
 
-// the body buffers of one column in IPC order (validity, [offsets,] data), re-based to array offset 0
-void column_pieces(const ArrowArray& a, int dt, std::vector<BodyPiece>& out, int64_t& null_count) {
-    const int64_t n = a.length, off = a.offset;
-    const uint8_t* validity = a.n_buffers > 0 ? static_cast<const uint8_t*>(a.buffers[0]) : nullptr;
-    null_count = 0;
-    if (validity && a.null_count != 0) {
-        BodyPiece p{nullptr, 0, slice_bits(validity, off, n)};
-        for (int64_t i = 0; i < n; ++i) null_count += !bit_get(p.owned.data(), i);
-        if (null_count) { p.bytes = (n + 7) / 8; out.push_back(std::move(p)); }
-        else out.push_back(BodyPiece{nullptr, 0, {}});
-    } else {
-        out.push_back(BodyPiece{nullptr, 0, {}});                  // V5: an absent validity buffer has length 0
-    }
-    if (dt == DT_LARGE_UTF8) {
-        const int64_t* o = static_cast<const int64_t*>(a.buffers[1]) + off;
-        const char* d = static_cast<const char*>(a.buffers[2]);
-        BodyPiece po{nullptr, (n + 1) * 8, {}};
-        const int64_t base = a.buffers[1] ? o[0] : 0;
-        if (!a.buffers[1]) po.owned.assign(16, 0);
-        else if (base == 0) po.ptr = o;
-        else {
-            po.owned.resize((size_t)(n + 1) * 8);
-            int64_t* r = reinterpret_cast<int64_t*>(po.owned.data());
-            for (int64_t i = 0; i <= n; ++i) r[i] = o[i] - base;
+// the body buffers of one column in IPC order (validity, [offsets,] data), re-based to array offset 0.  The writer's policy: the
+// NULLs are counted and a bitmap without any is written as a buffer of length 0; offsets keep their width, and the caller's own
+// are written in place where they start at 0 already.
+template <class O>
+void column_pieces(const ArrowArray& a, int dt, const char* name, std::vector<BodyPiece>& out, int64_t& null_count) {
+    ArrowColumn<O> c = normalise_array<O>(a, a.offset, dt, name);
+    const int64_t n = c.n;
+    null_count = c.null_count;
+    if (null_count) out.push_back(BodyPiece{nullptr, (n + 7) / 8, std::move(c.validity)});
+    else out.push_back(BodyPiece{nullptr, 0, {}});                 // V5: an absent validity buffer has length 0
+    if (dt == DT_UTF8) {
+        BodyPiece po{c.offsets, (n + 1) * (int64_t)sizeof(O), {}};
+        if (!c.offsets || c.base != 0) {                           // (an empty array may come without an offsets buffer)
+            po.owned.resize((size_t)po.bytes);
+            c.rebase_into(reinterpret_cast<O*>(po.owned.data()));
         }
         out.push_back(std::move(po));
-        out.push_back(BodyPiece{d ? d + base : nullptr, (n && a.buffers[1]) ? (int64_t)(o[n] - base) : 0, {}});
-    } else if (dt == DT_UTF8) {
-        const int32_t* o = static_cast<const int32_t*>(a.buffers[1]) + off;
-        const char* d = static_cast<const char*>(a.buffers[2]);
-        BodyPiece po{nullptr, (n + 1) * 4, {}};
-        const int32_t base = a.buffers[1] ? o[0] : 0;
-        if (!a.buffers[1]) po.owned.assign(8, 0);                       // an empty array may come without an offsets buffer
-        else if (base == 0) po.ptr = o;
-        else {
-            po.owned.resize((size_t)(n + 1) * 4);
-            int32_t* r = reinterpret_cast<int32_t*>(po.owned.data());
-            for (int64_t i = 0; i <= n; ++i) r[i] = o[i] - base;
-        }
-        out.push_back(std::move(po));
-        out.push_back(BodyPiece{d ? d + base : nullptr, (n && a.buffers[1]) ? (int64_t)(o[n] - base) : 0, {}});
+        out.push_back(BodyPiece{c.data, c.data_bytes, {}});
     } else if (dt == DT_BOOLEAN) {
-        BodyPiece p{nullptr, (n + 7) / 8, slice_bits(static_cast<const uint8_t*>(a.buffers[1]), off, n)};
-        out.push_back(std::move(p));
+        out.push_back(BodyPiece{nullptr, (n + 7) / 8, std::move(c.bits)});
     } else {
-        const int w = dtype_width(dt);
-        out.push_back(BodyPiece{static_cast<const uint8_t*>(a.buffers[1]) + off * w, n * w, {}});
+        out.push_back(BodyPiece{c.data, c.data_bytes, {}});
     }
 }
 
@@ -463,7 +421,9 @@ void ipc_write_file(ArrowArrayStream* stream, const std::string& path, uint64_t*
             if (a.length != arr.length) fail(BHIP_EINVAL, "Arrow IPC: column length differs from the batch length");
             const size_t first = pieces.size();
             int64_t nulls = 0;
-            column_pieces(a, schema->fields[c].large ? (int)DT_LARGE_UTF8 : schema->fields[c].dtype, pieces, nulls);
+            const Field& fld = schema->fields[c];
+            if (fld.large) column_pieces<int64_t>(a, fld.dtype, fld.name.c_str(), pieces, nulls);
+            else column_pieces<int32_t>(a, fld.dtype, fld.name.c_str(), pieces, nulls);
             nodes.push_back({a.length, nulls});
             for (size_t k = first; k < pieces.size(); ++k) {
                 buffers.push_back({body, pieces[k].bytes});
@@ -525,20 +485,6 @@ struct IpcFile {
     std::string path;
 };
 
-struct ExportedBatch {                   // owns what an exported ArrowArray points to
-    std::shared_ptr<IpcFile> file;
-    std::vector<ArrowArray> children;
-    std::vector<ArrowArray*> child_ptrs;
-    std::vector<std::vector<const void*>> buffers;
-    std::vector<const void*> top_buffers;
-};
-
-void release_exported(ArrowArray* a) {
-    delete static_cast<ExportedBatch*>(a->private_data);
-    a->release = nullptr;
-}
-void release_child(ArrowArray* a) { a->release = nullptr; }
-
 void load_file(IpcFile& F) {
     std::ifstream in(F.path, std::ios::binary | std::ios::ate);
     if (!in) fail(BHIP_EEXEC, "Ballista Error: cannot open " + F.path);
@@ -568,6 +514,23 @@ void load_file(IpcFile& F) {
         }
 }
 
+const int64_t zero_offset[2] = {0, 0};       // what stands in for a buffer of length 0
+
+// the offsets and data buffers of a variable-width column, checked: long enough, inside the data buffer, ascending
+template <class O, class NextBuf>
+void string_buffers(int64_t n_rows, NextBuf& next_buf, std::vector<const void*>& buffers) {
+    int64_t bl, dl;
+    const void* o = next_buf(bl);
+    if (n_rows > 0 && bl < (n_rows + 1) * (int64_t)sizeof(O)) fail(BHIP_EEXEC, "Arrow IPC: offsets buffer too short");
+    const O* oi = o ? static_cast<const O*>(o) : reinterpret_cast<const O*>(zero_offset);
+    const void* d = next_buf(dl);
+    if (n_rows > 0 && (oi[0] < 0 || oi[n_rows] < oi[0] || oi[n_rows] > dl)) fail(BHIP_EEXEC, "Arrow IPC: string offsets outside the data buffer");
+    for (int64_t i = 0; i < n_rows; ++i)                  // interior offsets reach a device gather: they must ascend
+        if (oi[i + 1] < oi[i]) fail(BHIP_EEXEC, "Arrow IPC: string offsets do not ascend");
+    buffers.push_back(oi);
+    buffers.push_back(d ? d : (const void*)zero_offset);
+}
+
 void export_next(const std::shared_ptr<IpcFile>& Fp, ArrowArray* out) {
     IpcFile& F = *Fp;
     memset(out, 0, sizeof(*out));
@@ -595,12 +558,10 @@ void export_next(const std::shared_ptr<IpcFile>& Fp, ArrowArray* out) {
     rb.vec(1, nodes, n_nodes);
     rb.vec(2, bufs, n_bufs);
     const uint8_t* body = p + m + (size_t)blk.meta;
-    auto X = std::make_unique<ExportedBatch>();
-    X->file = Fp;
+    auto X = std::make_unique<StructArrayShell>(F.schema->fields.size());
+    X->owner = Fp;
     const size_t nc = F.schema->fields.size();
     if (n_nodes != nc) fail(BHIP_EEXEC, "Arrow IPC: record batch does not match the file's schema");
-    X->children.resize(nc);
-    X->buffers.resize(nc);
     uint32_t bi = 0;
     auto next_buf = [&](int64_t& blen) -> const void* {
         if (bi >= n_bufs) fail(BHIP_EEXEC, "Arrow IPC: record batch has too few buffers");
@@ -612,100 +573,34 @@ void export_next(const std::shared_ptr<IpcFile>& Fp, ArrowArray* out) {
         return bl ? body + off : nullptr;
     };
     for (size_t c = 0; c < nc; ++c) {
-        ArrowArray& a = X->children[c];
-        memset(&a, 0, sizeof(a));
-        a.length = rb.rd<int64_t>(nodes + 16 * c);
-        a.null_count = rb.rd<int64_t>(nodes + 16 * c + 8);
-        if (a.length != n_rows) fail(BHIP_EEXEC, "Arrow IPC: field node length differs from the batch length");
-        if (a.null_count < 0 || a.null_count > n_rows) fail(BHIP_EEXEC, "Arrow IPC: field node null count out of range");
-        const int dt = F.schema->fields[c].large ? (int)DT_LARGE_UTF8 : F.schema->fields[c].dtype;
+        const int64_t length = rb.rd<int64_t>(nodes + 16 * c), null_count = rb.rd<int64_t>(nodes + 16 * c + 8);
+        if (length != n_rows) fail(BHIP_EEXEC, "Arrow IPC: field node length differs from the batch length");
+        if (null_count < 0 || null_count > n_rows) fail(BHIP_EEXEC, "Arrow IPC: field node null count out of range");
+        const Field& fld = F.schema->fields[c];
+        std::vector<const void*>& buffers = X->buffers[c];
         int64_t bl;
         const void* validity = next_buf(bl);
-        if (a.null_count > 0 && (!validity || bl < (n_rows + 7) / 8)) fail(BHIP_EEXEC, "Arrow IPC: validity buffer too short");
-        X->buffers[c].push_back(a.null_count > 0 ? validity : nullptr);
-        static const int32_t zero_offset[4] = {0, 0, 0, 0};
-        if (dt == DT_LARGE_UTF8) {
-            const void* o = next_buf(bl);
-            if (n_rows > 0 && bl < (n_rows + 1) * 8) fail(BHIP_EEXEC, "Arrow IPC: offsets buffer too short");
-            const int64_t* oi = o ? static_cast<const int64_t*>(o) : reinterpret_cast<const int64_t*>(zero_offset);
-            int64_t dl;
-            const void* d = next_buf(dl);
-            if (n_rows > 0 && (oi[0] < 0 || oi[n_rows] < oi[0] || oi[n_rows] > dl)) fail(BHIP_EEXEC, "Arrow IPC: string offsets outside the data buffer");
-            for (int64_t i = 0; i < n_rows; ++i)                  // interior offsets reach a device gather: they must ascend
-                if (oi[i + 1] < oi[i]) fail(BHIP_EEXEC, "Arrow IPC: string offsets do not ascend");
-            X->buffers[c].push_back(oi);
-            X->buffers[c].push_back(d ? d : (const void*)zero_offset);
-        } else if (dt == DT_UTF8) {
-            const void* o = next_buf(bl);
-            if (n_rows > 0 && bl < (n_rows + 1) * 4) fail(BHIP_EEXEC, "Arrow IPC: offsets buffer too short");
-            const int32_t* oi = o ? static_cast<const int32_t*>(o) : zero_offset;
-            int64_t dl;
-            const void* d = next_buf(dl);
-            if (n_rows > 0 && (oi[0] < 0 || oi[n_rows] < oi[0] || oi[n_rows] > dl)) fail(BHIP_EEXEC, "Arrow IPC: string offsets outside the data buffer");
-            for (int64_t i = 0; i < n_rows; ++i)
-                if (oi[i + 1] < oi[i]) fail(BHIP_EEXEC, "Arrow IPC: string offsets do not ascend");
-            X->buffers[c].push_back(oi);
-            X->buffers[c].push_back(d ? d : (const void*)zero_offset);
+        if (null_count > 0 && (!validity || bl < (n_rows + 7) / 8)) fail(BHIP_EEXEC, "Arrow IPC: validity buffer too short");
+        buffers.push_back(null_count > 0 ? validity : nullptr);
+        if (fld.dtype == DT_UTF8) {
+            if (fld.large) string_buffers<int64_t>(n_rows, next_buf, buffers);
+            else string_buffers<int32_t>(n_rows, next_buf, buffers);
         } else {
             const void* d = next_buf(bl);
-            const int64_t need = dt == DT_BOOLEAN ? (n_rows + 7) / 8 : n_rows * dtype_width(dt);
+            const int64_t need = fld.dtype == DT_BOOLEAN ? (n_rows + 7) / 8 : n_rows * dtype_width(fld.dtype);
             if (bl < need) fail(BHIP_EEXEC, "Arrow IPC: data buffer too short");
-            X->buffers[c].push_back(d ? d : (const void*)zero_offset);
+            buffers.push_back(d ? d : (const void*)zero_offset);
         }
-        a.n_buffers = (int64_t)X->buffers[c].size();
-        a.buffers = X->buffers[c].data();
-        a.release = release_child;
+        X->finish_child(c, n_rows, null_count);
     }
-    for (auto& c : X->children) X->child_ptrs.push_back(&c);
-    X->top_buffers.push_back(nullptr);
-    out->length = n_rows;
-    out->null_count = 0;
-    out->n_buffers = 1;
-    out->buffers = X->top_buffers.data();
-    out->n_children = (int64_t)nc;
-    out->children = X->child_ptrs.data();
-    out->release = release_exported;
-    out->private_data = X.release();
-}
-
-// schema export (struct of the columns)
-struct SchemaHold {
-    std::vector<ArrowSchema> children;
-    std::vector<ArrowSchema*> ptrs;
-    std::vector<std::string> names;
-};
-void release_schema_child(ArrowSchema* s) { s->release = nullptr; }
-void release_schema_top(ArrowSchema* s) {
-    delete static_cast<SchemaHold*>(s->private_data);
-    s->release = nullptr;
-}
-void export_schema_c(const Schema& s, ArrowSchema* out) {
-    auto H = std::make_unique<SchemaHold>();
-    H->children.resize(s.fields.size());
-    for (auto& f : s.fields) H->names.push_back(f.name);
-    for (size_t i = 0; i < s.fields.size(); ++i) {
-        ArrowSchema& c = H->children[i];
-        memset(&c, 0, sizeof(c));
-        c.format = format_of_dtype(s.fields[i].binary ? (int)DT_BINARY : s.fields[i].large ? (int)DT_LARGE_UTF8 : s.fields[i].dtype);
-        c.name = H->names[i].c_str();
-        c.flags = s.fields[i].nullable ? ARROW_FLAG_NULLABLE : 0;
-        c.release = release_schema_child;
-        H->ptrs.push_back(&c);
-    }
-    memset(out, 0, sizeof(*out));
-    out->format = "+s";
-    out->name = "";
-    out->n_children = (int64_t)s.fields.size();
-    out->children = H->ptrs.data();
-    out->release = release_schema_top;
-    out->private_data = H.release();
+    StructArrayShell::finish(std::move(X), n_rows, out);
 }
 
 struct StreamPriv { std::shared_ptr<IpcFile> file; };
 
 int s_get_schema(ArrowArrayStream* s, ArrowSchema* out) {
     auto* P = static_cast<StreamPriv*>(s->private_data);
-    try { export_schema_c(*P->file->schema, out); return 0; }
+    try { export_schema(*P->file->schema, out); return 0; }
     catch (const std::exception& e) { P->file->error = e.what(); return 5; }
 }
 int s_get_next(ArrowArrayStream* s, ArrowArray* out) {

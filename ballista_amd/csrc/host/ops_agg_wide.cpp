@@ -190,21 +190,8 @@ std::vector<BatchPtr> HashAggregateExec::run_strings(int partition, const Exec& 
             if (b->n_rows > 0) parts.push_back(b);
     }
     BatchPtr in;
-    if (parts.empty()) {
-        auto e = std::make_shared<Batch>();
-        e->schema = in_schema;
-        e->ctx = ex.ctx;
-        for (auto& f : in_schema->fields) {
-            Column c;
-            c.dtype = f.dtype;
-            c.data = make_buffer(ex, 8);
-            if (f.dtype == DT_UTF8) { c.offsets = make_buffer(ex, 8); HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream)); }
-            e->cols.push_back(c);
-        }
-        in = e;
-    } else {
-        in = parts.size() == 1 ? parts[0] : concat_batches(ex, in_schema, parts);
-    }
+    if (parts.empty()) in = empty_batch(ex, in_schema);
+    else in = parts.size() == 1 ? parts[0] : concat_batches(ex, in_schema, parts);
     parts.clear();
     const int64_t n = in->n_rows;
     const LaunchCfg cfg = ex.cfg();

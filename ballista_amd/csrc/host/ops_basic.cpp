@@ -273,6 +273,20 @@ BatchPtr materialize_batch(const Exec& ex, const BatchPtr& b) {
     return out;
 }
 
+BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema) {
+    auto e = std::make_shared<Batch>();
+    e->schema = schema;
+    e->ctx = ex.ctx;
+    for (auto& f : schema->fields) {
+        Column c;
+        c.dtype = f.dtype;
+        c.data = make_buffer(ex, 8);
+        if (f.dtype == DT_UTF8) { c.offsets = make_buffer(ex, 8); HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream)); }
+        e->cols.push_back(c);
+    }
+    return e;
+}
+
 Column take_column_nullable(const Exec& ex, const Column& c, const uint32_t* idx, int64_t n) {
     return take_column_v(ex, c, idx, n, true);
 }

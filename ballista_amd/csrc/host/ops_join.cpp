@@ -461,21 +461,6 @@ static bool try_narrow(const Exec& ex, JoinBuildSide* bs, int64_t n, uint64_t ca
     return false;
 }
 
-// a child that yields no build rows: a batch of its schema with zero rows
-static BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema) {
-    auto e = std::make_shared<Batch>();
-    e->schema = schema;
-    e->ctx = ex.ctx;
-    for (auto& f : schema->fields) {
-        Column c;
-        c.dtype = f.dtype;
-        c.data = make_buffer(ex, 8);
-        if (f.dtype == DT_UTF8) { c.offsets = make_buffer(ex, 8); HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream)); }
-        e->cols.push_back(c);
-    }
-    return e;
-}
-
 // the general table, duplicates chained through next[]: over packed 16-byte keys (any key types that fit them), or (wide) over
 // row hashes with the key columns of the build batch as the keys — any width
 static void build_general_table(const Exec& ex, JoinBuildSide* bs, const std::vector<std::string>& key_names, uint64_t cap, bool wide) {

@@ -428,6 +428,8 @@ std::vector<Column> take_columns(const Exec& ex, const std::vector<const Column*
 // view columns (core.hpp Column::view_base) as ordinary columns
 Column materialize_column(const Exec& ex, const Column& c);
 BatchPtr materialize_batch(const Exec& ex, const BatchPtr& b);
+// a batch of `schema` with zero rows (a child that yielded none); a Utf8 column's offsets are the one zero
+BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema);
 // n NULLs of the given type
 Column null_column(const Exec& ex, int dtype, int64_t n);
 // a fixed-width column of n rows that a kernel is about to fill: the value buffer, and a validity bitmap where asked for

@@ -46,12 +46,56 @@ def mixed_batch(n, seed=3):
         ("u", OCol("UInt64", rng.integers(0, 2 ** 62, n).astype(np.uint64)))])
 
 
-@pytest.mark.parametrize("n", [0, 1, 63, 64, 1000, 70_001])
+def expected_block(t, n, block_bytes):
+    """The packed block of oracle batch `t`, from the layout rule alone: per column the data, then the Utf8 offsets, then the
+    validity, each at the next 64-byte boundary; a data piece is followed by 16 bytes of slack, a validity piece by 8, bitmaps
+    (Boolean values, validity) are whole 64-bit words; everything else is zero.  Returns the block and where its bitmaps are."""
+    block, bitmaps, at = np.zeros(block_bytes, np.uint8), [], 0
+
+    def place(raw, slack):
+        nonlocal at
+        raw = np.frombuffer(raw, np.uint8) if isinstance(raw, bytes) else np.ascontiguousarray(raw).view(np.uint8).ravel()
+        block[at:at + raw.size] = raw
+        at += (raw.size + slack + 63) // 64 * 64
+
+    def bitmap(bools, slack):
+        words = np.zeros((n + 63) // 64 * 8, np.uint8)
+        packed = np.packbits(np.asarray(bools, np.bool_), bitorder="little")
+        words[:packed.size] = packed
+        bitmaps.append(at)
+        place(words, slack)
+
+    for c in t.values():
+        if c.dtype == "Utf8":
+            enc = [s.encode() for s in c.values]
+            place(b"".join(enc), 16)
+            place(np.concatenate([[0], np.cumsum([len(e) for e in enc])]).astype(np.int32), 0)
+        elif c.dtype == "Boolean":
+            bitmap(c.values, 16)
+        else:
+            place(c.values, 16)
+        if c.valid is not None:
+            bitmap(c.valid, 8)
+    assert at == block_bytes
+    return block, bitmaps
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 1000, 70_001, 140_000])
 def test_pack_unpack_roundtrip(ctx, n):
+    """(n = 140_000: the Int64 column is larger than 1 MiB, so the block is filled piece by piece, not by the one pack launch)"""
     t = mixed_batch(n)
     dev = helpers.to_device(ctx, t)
     header, block = ba.plan.pack_batch(dev)
     assert header[0] == n and header[1] == block.size and block.size % 64 == 0
+    # the block, byte for byte, against the layout stated independently; only the bits past row n in the last word of a bitmap are open
+    want, bitmaps = expected_block(t, n, int(header[1]))
+    got = block.copy()
+    if n % 64:
+        for at in bitmaps:
+            last = at + (n // 64) * 8
+            for b in (got, want):
+                b[last:last + 8].view(np.uint64)[0] &= np.uint64((1 << (n % 64)) - 1)
+    assert np.array_equal(got, want), f"first differing byte: {int(np.flatnonzero(got != want)[0])}"
     back = ba.plan.unpack_batch(ctx, dev.schema3(), header, block)
     helpers.assert_rows_equal(helpers.from_device(back), t, ordered=True)
     if n:

@@ -51,12 +51,31 @@ def test_files_written_here_are_read_by_pyarrow(tmp_path, sizes):
     assert again.equals(pa.Table.from_batches(batches, schema=schema))
 
 
-def test_sliced_arrays_are_rebased(tmp_path):
-    t = table(500, seed=3)
-    sl = t.slice(123, 201)                       # non-zero offsets in every buffer, bit offsets not a multiple of 8
+def sliced_cases():
+    import arrow_slice_cases as cases
+    yield pytest.param(None, None, id="every-type-123-201")
+    for start in cases.STARTS:
+        for length in cases.LENGTHS:
+            yield pytest.param(start, length, id=f"{start}-{length}")
+
+
+@pytest.mark.parametrize("start,length", sliced_cases())
+def test_sliced_arrays_are_rebased(tmp_path, start, length):
+    """non-zero offsets in every buffer: bit offsets that are and are not a multiple of 8, Utf8 / LargeUtf8 / Binary offsets that
+    do and do not start at 0, an all-ones validity buffer on a NULL-free column (tests/arrow_slice_cases.py)"""
+    if start is None:
+        batches = table(500, seed=3).slice(123, 201).to_batches()
+    else:
+        import arrow_slice_cases as cases
+        batches = [cases.sliced(start, length)]
+        assert all(c.offset == start for c in batches[0].columns) and batches[0].column("all_valid").buffers()[0] is not None
+    sl = pa.Table.from_batches(batches)
     path = str(tmp_path / "sliced.arrow")
-    ba.plan.ipc_write_file(pa.RecordBatchReader.from_batches(sl.schema, sl.to_batches()), path)
-    assert pa.ipc.open_file(path).read_all().equals(sl)
+    ba.plan.ipc_write_file(pa.RecordBatchReader.from_batches(sl.schema, batches), path)
+    with pa.ipc.open_file(path) as f:
+        assert f.num_record_batches == len(batches)
+        back = f.read_all()
+    assert back.schema.equals(sl.schema) and back.equals(sl)
 
 
 @pytest.mark.parametrize("version", ["V5", "V4"])

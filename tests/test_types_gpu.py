@@ -273,6 +273,47 @@ def test_large_utf8_at_the_boundary(ctx, tmp_path):
     assert out.schema.field("s").type == pa.large_string() and out.num_rows == len(words) + 1
 
 
+def sliced_cases():
+    from tests import arrow_slice_cases as cases
+    return [pytest.param(start, length, id=f"{start}-{length}") for start in cases.STARTS for length in cases.LENGTHS]
+
+
+@pytest.mark.parametrize("start,length", sliced_cases())
+def test_sliced_arrays_are_rebased_on_import(ctx, start, length):
+    """the importer's side of test_ipc.py::test_sliced_arrays_are_rebased (the same normaliser serves both): a sliced record
+    batch — bit offsets that are no multiple of 8, string offsets that do not start at 0, an all-ones validity buffer — comes back
+    from the device equal to the slice, types included"""
+    from tests import arrow_slice_cases as cases
+    sl = cases.sliced(start, length)
+    got = ba.RecordBatch.from_pyarrow(ctx, sl).to_pyarrow()
+    assert got.schema.types == sl.schema.types and got.schema.names == sl.schema.names
+    assert got.num_rows == length and got.equals(sl)
+
+
+def small_large_cases():
+    """(id, columns, rows, NULLs): on both sides of every limit of the one-block route of import and export — at most 64 buffers,
+    each at most 1 MiB, at most 4 MiB in all; beyond any of them every buffer travels on its own"""
+    return [pytest.param(21, 3, True, id="utf8x21-63-buffers-packed"),
+            pytest.param(22, 3, True, id="utf8x22-66-buffers-per-buffer"),
+            pytest.param(1, 1 << 20, False, id="u8-1MiB-packed"),
+            pytest.param(1, (1 << 20) + 1, False, id="u8-1MiB+1-per-buffer"),
+            pytest.param(5, 1_000_000, False, id="u8x5-over-4MiB-per-buffer")]
+
+
+@pytest.mark.parametrize("n_cols,n,utf8", small_large_cases())
+def test_small_and_large_batches_cross_the_edge_alike(ctx, n_cols, n, utf8):
+    import pyarrow as pa
+    rng = np.random.default_rng(n_cols * 31 + n)
+    if utf8:        # nullable Utf8: validity, offsets, data = three buffers a column
+        arrays = [pa.array([None if r == c % n else f"c{c}r{r}" * (r + c % 3) for r in range(n)], pa.string()) for c in range(n_cols)]
+        assert all(a.null_count == 1 for a in arrays)
+    else:
+        arrays = [pa.array(rng.integers(0, 256, n).astype(np.uint8)) for _ in range(n_cols)]
+    rb = pa.RecordBatch.from_arrays(arrays, names=[f"c{i}" for i in range(n_cols)])
+    got = ba.RecordBatch.from_pyarrow(ctx, rb).to_pyarrow()
+    assert got.schema.types == rb.schema.types and got.equals(rb)
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 7, 15, 16, 17, 63, 65, 255, 257, 1023, 1025])
 def test_narrow_columns_of_odd_lengths_through_the_vm(ctx, n):
     """1- / 2- / 4-byte values and Booleans are read as the aligned 4-byte word that holds them (vm_device.h): lengths that end
