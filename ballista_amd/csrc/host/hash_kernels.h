@@ -93,10 +93,11 @@ hipError_t launch_hash_agg_compact(const LaunchCfg& cfg, const HashAggTable& T, 
                                    GroupRec* out);
 
 // group keys of any width: rep[row] = a row of the same batch whose key columns equal row's (NULL == NULL);
-// table = zeroed [mask + 1] words, mask + 1 a power of two >= 2 n; hashes = 64-bit row hashes of the key columns
+// table = zeroed [mask + 1] words, mask + 1 a power of two >= 2 n; hashes = 64-bit row hashes of the key columns (of the first
+// VM_MAX_KEYPARTS of them; hashes2 = those of the rest, null when there are none)
 struct WideKeyCols { ColumnRef col[VM_MAX_COLS]; int32_t n; int32_t pad; };
-hipError_t launch_wide_key_assign(const LaunchCfg& cfg, const WideKeyCols& K, const uint64_t* hashes, uint32_t* table, uint64_t mask,
-                                  uint32_t n, uint32_t* rep);
+hipError_t launch_wide_key_assign(const LaunchCfg& cfg, const WideKeyCols& K, const uint64_t* hashes, const uint64_t* hashes2, uint32_t* table,
+                                  uint64_t mask, uint32_t n, uint32_t* rep);
 
 // ---- join -------------------------------------------------------------------------------------
 struct JoinTable {

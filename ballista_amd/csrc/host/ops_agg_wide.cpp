@@ -20,7 +20,8 @@ const char* const kRepName = "__group_rep";
 bool key_width_error(const Error& e) {
     if (e.code != BHIP_ENOTIMPL) return false;
     const std::string m = e.what();
-    return m.find("packed key") != std::string::npos || m.find("packed-key") != std::string::npos;
+    // (more key parts than one program packs: the same answer as a layout wider than 16 bytes)
+    return m.find("packed key") != std::string::npos || m.find("packed-key") != std::string::npos || m.find("more than 8 key columns") != std::string::npos;
 }
 
 bool HashAggregateExec::run_single_partial(const Exec& ex, std::vector<BatchPtr>& out) const {
@@ -113,17 +114,22 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
     BufferPtr rep = make_buffer(ex, (size_t)n * 4 + 8);
     {
         Temp tmp(ex);
-        ProgramBuilder pb(*in_schema);
-        pb.set_hash_only();
-        for (auto& g : group_) pb.add_key(g.first);
-        ScanParams P;
-        pb.finish(P);
-        ProgramBuilder::bind(P, pb.columns(), *in, pb.creates_nulls());
+        // one hash program holds VM_MAX_KEYPARTS key parts: up to 8 group expressions are one pass, 9 .. 16 a second pass over the rest
+        // (the kernel folds the two hashes of a row; equality is on the key columns either way)
         uint64_t* hashes = tmp.get<uint64_t>((size_t)n);
+        uint64_t* hashes2 = group_.size() > (size_t)VM_MAX_KEYPARTS ? tmp.get<uint64_t>((size_t)n) : nullptr;
         ScanStatus* st = tmp.get<ScanStatus>(1);
-        HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
-        TIMED_LAUNCH(ex, "scan_keys", launch_scan_keys(cfg, P, nullptr, hashes, nullptr, st));
-        check_scan_status(ex, st);
+        for (size_t first = 0; first < group_.size(); first += VM_MAX_KEYPARTS) {
+            ProgramBuilder pb(*in_schema);
+            pb.set_hash_only();
+            for (size_t i = first; i < std::min(group_.size(), first + VM_MAX_KEYPARTS); ++i) pb.add_key(group_[i].first);
+            ScanParams P;
+            pb.finish(P);
+            ProgramBuilder::bind(P, pb.columns(), *in, pb.creates_nulls());
+            HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
+            TIMED_LAUNCH(ex, "scan_keys", launch_scan_keys(cfg, P, nullptr, first ? hashes2 : hashes, nullptr, st));
+            check_scan_status(ex, st);
+        }
         const uint64_t cap = table_capacity((uint64_t)n);
         uint32_t* table = tmp.get<uint32_t>(cap);
         HIP_CHECK(hipMemsetAsync(table, 0, cap * 4, ex.stream));
@@ -131,7 +137,7 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
         memset(&K, 0, sizeof(K));
         K.n = (int32_t)keys.size();
         for (size_t i = 0; i < keys.size(); ++i) K.col[i] = keys[i].ref();
-        TIMED_LAUNCH(ex, "wide_key_assign", launch_wide_key_assign(cfg, K, hashes, table, cap - 1, (uint32_t)n, rep->as<uint32_t>()));
+        TIMED_LAUNCH(ex, "wide_key_assign", launch_wide_key_assign(cfg, K, hashes, hashes2, table, cap - 1, (uint32_t)n, rep->as<uint32_t>()));
     }
 
     // ---- the ordinary aggregate, keyed by the representative row ---------------------------------------------

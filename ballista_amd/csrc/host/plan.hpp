@@ -410,7 +410,7 @@ private:
 std::vector<BatchPtr> hash_partition_batch(const Exec& ex, const BatchPtr& in, const std::vector<ExprPtr>& exprs, int n);
 void check_scan_status(const Exec& ex, const ScanStatus* dev_status, ScanStatus* host_out = nullptr);
 void check_scan_flags(const ScanStatus& host_status);   // the same checks on a status already read back
-// `e` says that keys do not fit the 16-byte packed key — the layout at plan time, or a Utf8 value at run time (ops_agg_wide.cpp):
+// `e` says that keys do not fit the 16-byte packed key — the layout or the number of key parts at plan time, or a Utf8 value at run time (ops_agg_wide.cpp):
 // what HashAggregateExec and HashJoinExec answer with their wide-key forms
 bool key_width_error(const Error& e);
 // value of `e` over `in` as a column (a plain Column reference shares the input buffers)

@@ -704,9 +704,11 @@ __device__ inline bool wide_keys_equal(const WideKeyCols& K, uint32_t a, uint32_
 }
 
 __global__ void __launch_bounds__(BLOCK)
-wide_key_assign_kernel(const WideKeyCols K, const uint64_t* hashes, uint32_t* table, uint64_t mask, uint32_t n, uint32_t* rep) {
+wide_key_assign_kernel(const WideKeyCols K, const uint64_t* hashes, const uint64_t* hashes2, uint32_t* table, uint64_t mask, uint32_t n,
+                       uint32_t* rep) {
     for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n; row += gridDim.x * BLOCK) {
-        uint64_t slot = mix64(hashes[row]) & mask;
+        // hashes2 (more than 8 key columns): the row hash of the columns after the eighth, folded in the way hash_row folds a column
+        uint64_t slot = mix64(hashes2 ? mix64(hashes[row] ^ hashes2[row]) : hashes[row]) & mask;
         for (;;) {
             uint32_t o = table[slot];
             if (o == 0) {
@@ -808,10 +810,10 @@ hipError_t launch_join_build_narrow(const LaunchCfg& cfg, const NarrowJoinTable&
         hipLaunchKernelGGL(join_build_narrow64_kernel, dim3(grid_rows(cfg, n_left)), dim3(BLOCK), 0, cfg.stream, T, (const uint64_t*)keys, sel, n_left);
     return hipGetLastError();
 }
-hipError_t launch_wide_key_assign(const LaunchCfg& cfg, const WideKeyCols& K, const uint64_t* hashes, uint32_t* table, uint64_t mask,
-                                  uint32_t n, uint32_t* rep) {
+hipError_t launch_wide_key_assign(const LaunchCfg& cfg, const WideKeyCols& K, const uint64_t* hashes, const uint64_t* hashes2, uint32_t* table,
+                                  uint64_t mask, uint32_t n, uint32_t* rep) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(wide_key_assign_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, K, hashes, table, mask, n, rep);
+    hipLaunchKernelGGL(wide_key_assign_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, K, hashes, hashes2, table, mask, n, rep);
     return hipGetLastError();
 }
 hipError_t launch_join_key_present64(const LaunchCfg& cfg, const uint64_t* keys, const uint64_t* sel, uint32_t n, uint64_t kmin,

@@ -180,12 +180,17 @@ def test_limit_accumulators(ctx, n_rows, grouped):
 
 
 def test_limit_key_parts(ctx):
+    """8 key parts are the packed key's bound.  An aggregate with 9 to 16 group expressions answers it the way it answers a layout wider
+    than 16 bytes, on its wide-key route (representative rows); 17 are refused.  Every other consumer of key parts refuses the ninth"""
     src = leaf(ctx, X.float_batch(1025, True))
     keys = lambda k: [(f(i) > lit(1.0), f"g{i}") for i in range(k)]
     aggs = [E.Count(f(0), "c"), E.Min(f(9), "m")]
-    check(ba.HashAggregateExec("Partial", keys(8), aggs, src), "8 key parts", ordered=False, key_cols=[f"g{i}" for i in range(8)],
-          zero_sign_cols=["m[min]"])
-    refused(lambda: ba.HashAggregateExec("Partial", keys(9), aggs, src), "more than 8 key columns")
+    for k in (8, 9, 16):
+        check(ba.HashAggregateExec("Partial", keys(k), aggs, src), f"{k} key parts", ordered=False, key_cols=[f"g{i}" for i in range(k)],
+              zero_sign_cols=["m[min]"])
+    refused(lambda: ba.HashAggregateExec("Partial", keys(17), aggs, src), "more than 16 group expressions")
+    nine = [f(i) > lit(1.0) for i in range(9)]
+    refused(lambda: ba.RepartitionExec(src, ba.Partitioning.Hash(nine, 3)), "more than 8 key columns")
 
 
 # ---- the value-slot sweep -------------------------------------------------------------------------------------------------------
