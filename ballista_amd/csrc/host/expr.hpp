@@ -54,6 +54,11 @@ struct AggregateDesc {
     ExprPtr arg;
     std::string name;
 };
+inline bool is_distinct_fn(int fn) { return fn >= BHIP_AGG_COUNT_DISTINCT && fn <= BHIP_AGG_AVG_DISTINCT; }
+// COUNT_DISTINCT -> COUNT, SUM_DISTINCT -> SUM, AVG_DISTINCT -> AVG: the function that runs over the rows the marking pass leaves
+inline int distinct_plain_fn(int fn) {
+    return fn == BHIP_AGG_COUNT_DISTINCT ? BHIP_AGG_COUNT : fn == BHIP_AGG_SUM_DISTINCT ? BHIP_AGG_SUM : fn == BHIP_AGG_AVG_DISTINCT ? BHIP_AGG_AVG : fn;
+}
 
 struct SortDesc {
     ExprPtr expr;

@@ -99,6 +99,15 @@ struct WideKeyCols { ColumnRef col[VM_MAX_COLS]; int32_t n; int32_t pad; };
 hipError_t launch_wide_key_assign(const LaunchCfg& cfg, const WideKeyCols& K, const uint64_t* hashes, const uint64_t* hashes2, uint32_t* table,
                                   uint64_t mask, uint32_t n, uint32_t* rep);
 
+// DISTINCT aggregates: K = the group key columns followed by the argument x, xvalid = x's validity (null: no NULLs); table and
+// hashes as above.  claim: table[slot] = 1 + the SMALLEST row among the rows with x valid whose K columns are equal, slot_of[row] =
+// that slot (rows with x NULL: not written).  mark (after claim): bit `row` of validity_out = x valid and row is that smallest row;
+// validity_out = (n + 63) / 64 words, each written whole.
+hipError_t launch_distinct_claim(const LaunchCfg& cfg, const WideKeyCols& K, const uint64_t* xvalid, const uint64_t* hashes, const uint64_t* hashes2,
+                                 uint32_t* table, uint64_t mask, uint32_t n, uint32_t* slot_of);
+hipError_t launch_distinct_mark(const LaunchCfg& cfg, const uint64_t* xvalid, const uint32_t* table, const uint32_t* slot_of, uint32_t n,
+                                uint64_t* validity_out);
+
 // ---- join -------------------------------------------------------------------------------------
 struct JoinTable {
     uint64_t* owner;          // [capacity] (id+1 of the build row whose key defines the slot) | (high half of the key hash) << 32

@@ -1,4 +1,4 @@
-// ops_agg.cpp — HashAggregateExec (Partial / Final) over the fused scan kernels.
+// ops_agg.cpp — HashAggregateExec (Partial / Final; Single is the two as one operator, ops_agg_wide.cpp) over the fused scan kernels.
 //
 // Reference: built at rust/core/src/serde/physical_plan/from_proto.rs:173-252 (mode :181-184,
 // aggregates via create_aggregate_expr :230-236; only Sum/Avg/Count are serialisable,
@@ -46,7 +46,7 @@ static const char* lowcard_launch_name(int gmax, bool batches) {
 }
 
 static const char* agg_name(int fn) {
-    switch (fn) {
+    switch (distinct_plain_fn(fn)) {
         case BHIP_AGG_SUM: return "SUM";
         case BHIP_AGG_AVG: return "AVG";
         case BHIP_AGG_COUNT: return "COUNT";
@@ -60,8 +60,16 @@ HashAggregateExec::HashAggregateExec(int mode, std::vector<std::pair<ExprPtr, st
     : mode_(mode), group_(std::move(group_exprs)), aggr_(std::move(aggr)) {
     input_ = std::move(input);
     ctx_ = input_->context();
-    if (mode != BHIP_AGG_PARTIAL && mode != BHIP_AGG_FINAL) fail(BHIP_EINVAL, "Unsupported aggregate mode");
+    if (mode != BHIP_AGG_PARTIAL && mode != BHIP_AGG_FINAL && mode != BHIP_AGG_SINGLE) fail(BHIP_EINVAL, "Unsupported aggregate mode");
     const Schema& in = *input_->schema();
+    if (mode == BHIP_AGG_SINGLE) {
+        check_single();                                    // ops_agg_wide.cpp: legality, schema_, single_plan_
+        return;
+    }
+    for (auto& a : aggr_)
+        if (is_distinct_fn(a.fn))
+            fail(BHIP_ENOTIMPL, std::string(agg_name(a.fn)) + "(DISTINCT " + a.arg->to_string() + ") in a " + (mode == BHIP_AGG_PARTIAL ? "Partial" : "Final") +
+                                    " aggregate: the state of a DISTINCT aggregate is a set, not a column; use the Single mode (BHIP_AGG_SINGLE)");
     auto s = std::make_shared<Schema>();
     for (auto& g : group_) {
         const int t = expr_type(g.first, in);
@@ -116,11 +124,11 @@ PlanPtr HashAggregateExec::with_new_children(const std::vector<PlanPtr>& c) cons
 }
 
 std::string HashAggregateExec::describe() const {
-    std::string s = std::string("HashAggregateExec: mode=") + (mode_ == BHIP_AGG_PARTIAL ? "Partial" : "Final") + ", gby=[";
+    std::string s = std::string("HashAggregateExec: mode=") + (mode_ == BHIP_AGG_PARTIAL ? "Partial" : mode_ == BHIP_AGG_FINAL ? "Final" : "Single") + ", gby=[";
     for (size_t i = 0; i < group_.size(); ++i) s += (i ? ", " : "") + group_[i].first->to_string();
     s += "], aggr=[";
     for (size_t i = 0; i < aggr_.size(); ++i)
-        s += (i ? ", " : "") + std::string(agg_name(aggr_[i].fn)) + "(" + aggr_[i].arg->to_string() + ")";
+        s += (i ? ", " : "") + std::string(agg_name(aggr_[i].fn)) + (is_distinct_fn(aggr_[i].fn) ? "(DISTINCT " : "(") + aggr_[i].arg->to_string() + ")";
     return s + "]";
 }
 

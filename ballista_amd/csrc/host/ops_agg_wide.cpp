@@ -7,6 +7,8 @@
 //      (hash table of row ids over 64-bit row hashes; equality on the key columns themselves, NULL == NULL);
 //   2. the ordinary aggregate runs with that ONE Int32 column as its key, and the key columns of the result are
 //      gathered from the input at the representative rows.
+// Also here: the Single mode (run_single) — Final over Partial as one operator, and COUNT / SUM / AVG (DISTINCT x) on top of it
+// through distinct_claim_kernel / distinct_mark_kernel, which mark the first row of every distinct (group key, x).  No wire form.
 #include "../str_kernels.h"
 #include "hash_kernels.h"
 #include "plan.hpp"
@@ -76,6 +78,7 @@ bool HashAggregateExec::run_single_partial(const Exec& ex, std::vector<BatchPtr>
 }
 
 std::vector<BatchPtr> HashAggregateExec::run(int partition, const Exec& ex) const {
+    if (mode_ == BHIP_AGG_SINGLE) return run_single(partition, ex);
     if (strings_) return run_strings(partition, ex);
     {
         std::vector<BatchPtr> out;
@@ -181,6 +184,165 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
         outv.push_back(out);
     }
     return outv;
+}
+
+// ---- Single mode: raw rows in, final values out; COUNT / SUM / AVG (DISTINCT x) ----------------------------------------
+// Final(Merge(Partial(source))) with the operator's expressions: the Merge is there because run_single_partial's elision only
+// fires through one — with it the pair is ONE aggregation whose group table is emitted as the Final's columns.
+namespace {
+PlanPtr final_over_partial(const std::vector<std::pair<ExprPtr, std::string>>& group, const std::vector<AggregateDesc>& aggr, const PlanPtr& source) {
+    auto partial = std::make_shared<HashAggregateExec>(BHIP_AGG_PARTIAL, group, aggr, source);
+    const Schema& ps = *partial->schema();
+    std::vector<std::pair<ExprPtr, std::string>> fgroup;
+    for (auto& g : group) fgroup.push_back({make_column(g.second), g.second});
+    std::vector<AggregateDesc> faggr;
+    size_t pos = group.size();
+    for (auto& a : aggr) {                                   // a Final reads its states by position: the argument only names the first
+        faggr.push_back(AggregateDesc{a.fn, make_column(ps.fields[pos].name), a.name});
+        pos += a.fn == BHIP_AGG_AVG ? 2 : 1;
+    }
+    return std::make_shared<HashAggregateExec>(BHIP_AGG_FINAL, fgroup, faggr, std::make_shared<MergeExec>(partial));
+}
+std::string distinct_name(size_t i) { return "__distinct_" + std::to_string(i); }
+}  // namespace
+
+void HashAggregateExec::check_single() {
+    const Schema& in = *input_->schema();
+    // every group must lie in ONE input partition: execute(p) sees partition p alone
+    const Partitioning part = input_->output_partitioning();
+    if (part.count > 1) {
+        bool ok = part.scheme == BHIP_PART_HASH && !group_.empty() && !part.exprs.empty();
+        for (auto& pe : part.exprs) {
+            bool found = false;
+            for (auto& g : group_) found = found || g.first->to_string() == pe->to_string();
+            ok = ok && found;
+        }
+        if (!ok)
+            fail(BHIP_EINVAL, "Single aggregate over an input of " + std::to_string(part.count) +
+                                  " partitions that is not hash-partitioned on group expressions: put a MergeExec or a RepartitionExec(Hash on the "
+                                  "group expressions) under it");
+    }
+    std::vector<AggregateDesc> plain = aggr_;
+    bool group_strings = false;
+    for (auto& g : group_) group_strings = group_strings || has_lowered_node(g.first, in);
+    for (auto& a : plain) {
+        if (a.fn < BHIP_AGG_SUM || a.fn > BHIP_AGG_AVG_DISTINCT) fail(BHIP_ENOTIMPL, "Unsupported aggregate function");
+        if (!is_distinct_fn(a.fn)) continue;
+        a.fn = distinct_plain_fn(a.fn);
+        const std::string printed = a.arg->to_string();
+        bool seen = false;
+        for (auto& d : distinct_args_) seen = seen || d->to_string() == printed;
+        if (seen) continue;
+        if (has_lowered_node(a.arg, in) || (a.arg->kind == BHIP_EXPR_LITERAL && a.arg->dtype == DT_UTF8))
+            fail(BHIP_ENOTIMPL, "DISTINCT over a string function: " + printed + " (project it to a column first)");
+        if (group_strings) fail(BHIP_ENOTIMPL, "DISTINCT aggregate beside group expressions with a string function (project them to columns first)");
+        if (distinct_args_.size() == 8) fail(BHIP_ENOTIMPL, "more than 8 different DISTINCT arguments in one aggregate");
+        if (group_.size() + 1 > (size_t)VM_MAX_COLS) fail(BHIP_ENOTIMPL, "more than 15 group expressions with a DISTINCT aggregate");
+        {
+            ProgramBuilder pb(in);                           // x is hashed like a group key: what a key cannot be, x cannot be
+            pb.set_hash_only();
+            pb.add_key(a.arg);
+        }
+        distinct_args_.push_back(a.arg);
+    }
+    for (size_t i = 0; i < distinct_args_.size(); ++i)
+        if (in.index_of(distinct_name(i)) >= 0) fail(BHIP_EINVAL, "column name '" + distinct_name(i) + "' is reserved");
+    single_plan_ = final_over_partial(group_, plain, input_);         // (every other plan-time check of the expressions is the pair's)
+    auto s = std::make_shared<Schema>(*single_plan_->schema());
+    schema_ = s;
+}
+
+std::vector<BatchPtr> HashAggregateExec::run_single(int partition, const Exec& ex) const {
+    const SchemaPtr in_schema = input_->schema();
+    auto reschema = [&](std::vector<BatchPtr> res) {
+        for (auto& r : res) {
+            auto out = std::make_shared<Batch>(*r);
+            out->schema = schema_;
+            r = out;
+        }
+        return res;
+    };
+    if (distinct_args_.empty() && input_->output_partitioning().count == 1) {
+        auto s = single_plan_->execute(0, ex);
+        return reschema(drain(*s));
+    }
+    // this partition alone, as one resident batch
+    std::vector<BatchPtr> parts;
+    {
+        auto s = input_->execute(partition, ex);
+        while (BatchPtr b = s->next())
+            if (b->n_rows > 0) parts.push_back(b);
+    }
+    if (distinct_args_.empty()) {
+        if (parts.empty() && !group_.empty()) return {};
+        auto src = std::make_shared<MemoryExec>(ex.ctx, in_schema, std::vector<std::vector<BatchPtr>>{parts});
+        std::vector<AggregateDesc> plain = aggr_;
+        auto s = final_over_partial(group_, plain, src)->execute(0, ex);
+        return reschema(drain(*s));
+    }
+    if (parts.empty() && !group_.empty()) return {};
+    const BatchPtr in = parts.empty() ? empty_batch(ex, in_schema) : parts.size() == 1 ? parts[0] : concat_batches(ex, in_schema, parts);
+    parts.clear();
+    const int64_t n = in->n_rows;
+    if (n > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "DISTINCT aggregate over more than 2^31 input rows per partition");
+    const LaunchCfg cfg = ex.cfg();
+
+    auto s2 = std::make_shared<Schema>(*in_schema);
+    auto aug = std::make_shared<Batch>(*in);
+    std::vector<Column> keys;
+    for (auto& g : group_) keys.push_back(evaluate_column(ex, *in, g.first));
+    for (size_t d = 0; d < distinct_args_.size(); ++d) {
+        const ExprPtr& xe = distinct_args_[d];
+        Column x = evaluate_column(ex, *in, xe);
+        Column marked = x;                                   // x's data and offsets; valid = the first row of every distinct (key, x)
+        if (n > 0) {
+            Temp tmp(ex);
+            std::vector<ExprPtr> cols;
+            for (auto& g : group_) cols.push_back(g.first);
+            cols.push_back(xe);
+            // the row hash of (group keys ..., x): one hash program holds VM_MAX_KEYPARTS parts, a second pass covers the rest (run_wide)
+            uint64_t* hashes = tmp.get<uint64_t>((size_t)n);
+            uint64_t* hashes2 = cols.size() > (size_t)VM_MAX_KEYPARTS ? tmp.get<uint64_t>((size_t)n) : nullptr;
+            ScanStatus* st = tmp.get<ScanStatus>(1);
+            for (size_t first = 0; first < cols.size(); first += VM_MAX_KEYPARTS) {
+                ProgramBuilder pb(*in_schema);
+                pb.set_hash_only();
+                for (size_t i = first; i < std::min(cols.size(), first + VM_MAX_KEYPARTS); ++i) pb.add_key(cols[i]);
+                ScanParams P;
+                pb.finish(P);
+                ProgramBuilder::bind(P, pb.columns(), *in, pb.creates_nulls());
+                HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
+                TIMED_LAUNCH(ex, "scan_keys", launch_scan_keys(cfg, P, nullptr, first ? hashes2 : hashes, nullptr, st));
+                check_scan_status(ex, st);
+            }
+            const uint64_t cap = table_capacity((uint64_t)n);
+            uint32_t* table = tmp.get<uint32_t>(cap);
+            uint32_t* slot_of = tmp.get<uint32_t>((size_t)n);
+            HIP_CHECK(hipMemsetAsync(table, 0, cap * 4, ex.stream));
+            WideKeyCols K;
+            memset(&K, 0, sizeof(K));
+            K.n = (int32_t)keys.size() + 1;
+            for (size_t i = 0; i < keys.size(); ++i) K.col[i] = keys[i].ref();
+            K.col[keys.size()] = x.ref();
+            const uint64_t* xvalid = x.validity ? x.validity->as<uint64_t>() : nullptr;
+            marked.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+            TIMED_LAUNCH_N(ex, "distinct_claim", n, launch_distinct_claim(cfg, K, xvalid, hashes, hashes2, table, cap - 1, (uint32_t)n, slot_of));
+            TIMED_LAUNCH_N(ex, "distinct_mark", n, launch_distinct_mark(cfg, xvalid, table, slot_of, (uint32_t)n, marked.validity->as<uint64_t>()));
+        }
+        s2->fields.push_back(Field{distinct_name(d), x.dtype, true});
+        aug->cols.push_back(std::move(marked));
+    }
+    aug->schema = s2;
+    std::vector<AggregateDesc> plain = aggr_;
+    for (auto& a : plain) {
+        if (!is_distinct_fn(a.fn)) continue;
+        a.fn = distinct_plain_fn(a.fn);
+        for (size_t d = 0; d < distinct_args_.size(); ++d)
+            if (distinct_args_[d]->to_string() == a.arg->to_string()) { a.arg = make_column(distinct_name(d)); break; }
+    }
+    auto src = std::make_shared<MemoryExec>(ex.ctx, s2, std::vector<std::vector<BatchPtr>>{{BatchPtr(aug)}});
+    auto s = final_over_partial(group_, plain, src)->execute(0, ex);
+    return reschema(drain(*s));
 }
 
 // ---- string nodes in the keys / arguments, MIN / MAX over Utf8 -------------------------------------------------------

@@ -209,6 +209,14 @@ private:
     // group / argument expressions with string nodes (lower(s), CASE ... THEN 'a'), MIN / MAX over Utf8: the strings become
     // columns, MIN / MAX(Utf8) become MIN / MAX over sort ranks, and the ordinary aggregate runs on that (ops_agg_wide.cpp)
     std::vector<BatchPtr> run_strings(int partition, const Exec& ex) const;
+    // Single mode (ops_agg_wide.cpp): raw rows in, final values out.  Without a DISTINCT function the operator IS
+    // Final(Merge(Partial(source))) over the partition; with one, the first row of every distinct (group key, x) is marked first
+    // (distinct_claim / distinct_mark), COUNT(DISTINCT x) becomes COUNT of a column that shares x's buffers and is valid on those
+    // rows only, and the same pair runs over that.
+    std::vector<BatchPtr> run_single(int partition, const Exec& ex) const;
+    void check_single();               // the constructor's part of the mode: legality, schema_, single_plan_
+    PlanPtr single_plan_;              // Single: Final(Merge(Partial(input_))) with every DISTINCT function as its plain one
+    std::vector<ExprPtr> distinct_args_;   // Single: the different DISTINCT arguments (as printed), in order of first use
     bool strings_ = false;
     int mode_;
     std::vector<std::pair<ExprPtr, std::string>> group_;

@@ -721,6 +721,57 @@ wide_key_assign_kernel(const WideKeyCols K, const uint64_t* hashes, const uint64
     }
 }
 
+// ---- DISTINCT aggregates: the FIRST row of every distinct (group key ..., x) -------------------------------------------------
+// (HashAggregateExec in Single mode, COUNT / SUM / AVG (DISTINCT x): ops_agg_wide.cpp run_single.)  K = the group key columns
+// followed by x; xvalid = x's validity (null: no NULLs).  Rows whose x is NULL take no part: their slot_of entry is not written
+// and the mark kernel does not read it.
+//
+// distinct_claim is wide_key_assign's probe loop with one difference in what a slot's word means: not "the row that won the CAS"
+// but "the smallest row number seen so far among the rows equal to the slot's key".  A slot's KEY never changes once it is claimed:
+// every row that ever writes the word — the CAS winner, then atomicMin callers — has first compared equal to a row the word held,
+// and equality on the immutable columns is transitive.  So the word `o` a prober loaded may be stale (a larger row number than the
+// word holds by now, or one read through a cache the atomics of other CUs bypass), and the comparison against row o - 1 still
+// answers "is this my key's slot".  The word only ever decreases; a row that loaded o <= row + 1 skips its atomicMin, because the
+// word is then already <= row + 1 and stays so.  Every other equal row executes atomicMin(row + 1), the CAS winner's own number
+// went in with the CAS: when the kernel ends the word is the minimum over ALL rows of the key, whatever the order the waves ran
+// in — the survivor is the smallest row number and never the winner of a race.
+__global__ void __launch_bounds__(BLOCK)
+distinct_claim_kernel(const WideKeyCols K, const uint64_t* xvalid, const uint64_t* hashes, const uint64_t* hashes2, uint32_t* table,
+                      uint64_t mask, uint32_t n, uint32_t* slot_of) {
+    for (uint32_t row = blockIdx.x * BLOCK + threadIdx.x; row < n; row += gridDim.x * BLOCK) {
+        if (!bit_at(xvalid, row)) continue;
+        uint64_t slot = mix64(hashes2 ? mix64(hashes[row] ^ hashes2[row]) : hashes[row]) & mask;
+        for (;;) {
+            uint32_t o = table[slot];
+            if (o == 0) {
+                o = atomicCAS(&table[slot], 0u, row + 1u);
+                if (o == 0) break;                                     // claimed: the word is row + 1
+            }
+            if (wide_keys_equal(K, o - 1u, row)) {
+                if (o > row + 1u) atomicMin(&table[slot], row + 1u);
+                break;
+            }
+            slot = (slot + 1) & mask;
+        }
+        slot_of[row] = (uint32_t)slot;                                 // mask + 1 <= 2^32 slots
+    }
+}
+
+// validity_out bit of a row = x is valid AND the row is the smallest of its (key, x): table[slot_of[row]] == row + 1 (final after
+// distinct_claim: the kernel boundary).  A wave's 64 rows start at a multiple of 64 (BLOCK and the stride are multiples of 64),
+// so one ballot is one validity word, stored whole by lane 0 with a plain store; rows at and beyond n contribute 0.
+__global__ void __launch_bounds__(BLOCK)
+distinct_mark_kernel(const uint64_t* xvalid, const uint32_t* table, const uint32_t* slot_of, uint32_t n, uint64_t* validity_out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    // 64-bit row numbers: n rounded up to a whole word may pass 2^32 - stride
+    for (uint64_t row = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; row - lane < n; row += (uint64_t)gridDim.x * BLOCK) {
+        bool first = false;
+        if (row < n && bit_at(xvalid, (uint32_t)row)) first = table[slot_of[row]] == (uint32_t)row + 1u;
+        const uint64_t word = __ballot(first);
+        if (lane == 0) validity_out[row >> 6] = word;
+    }
+}
+
 // ---- the same for ONE Int64 / UInt64 key (TPC-H at SF1000: l_orderkey / o_orderkey are Int64): 16-byte slots
 // {key, build row + 1}.  The build claims a slot with a 32-bit CAS on the row word and compares against the key
 // COLUMN of the claiming row (immutable input), so no reader ever depends on a half-written slot; the key word is
@@ -814,6 +865,18 @@ hipError_t launch_wide_key_assign(const LaunchCfg& cfg, const WideKeyCols& K, co
                                   uint64_t mask, uint32_t n, uint32_t* rep) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(wide_key_assign_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, K, hashes, hashes2, table, mask, n, rep);
+    return hipGetLastError();
+}
+hipError_t launch_distinct_claim(const LaunchCfg& cfg, const WideKeyCols& K, const uint64_t* xvalid, const uint64_t* hashes, const uint64_t* hashes2,
+                                 uint32_t* table, uint64_t mask, uint32_t n, uint32_t* slot_of) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(distinct_claim_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, K, xvalid, hashes, hashes2, table, mask, n, slot_of);
+    return hipGetLastError();
+}
+hipError_t launch_distinct_mark(const LaunchCfg& cfg, const uint64_t* xvalid, const uint32_t* table, const uint32_t* slot_of, uint32_t n,
+                                uint64_t* validity_out) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(distinct_mark_kernel, dim3(grid_rows(cfg, n)), dim3(BLOCK), 0, cfg.stream, xvalid, table, slot_of, n, validity_out);
     return hipGetLastError();
 }
 hipError_t launch_join_key_present64(const LaunchCfg& cfg, const uint64_t* keys, const uint64_t* sel, uint32_t n, uint64_t kmin,

@@ -162,12 +162,12 @@ class ScalarFunctionExpr(PhysicalExpr):
 
 @dataclass(eq=False)
 class AggregateExpr:
-    fun: str            # "SUM" | "AVG" | "COUNT" | "MIN" | "MAX"
+    fun: str            # "SUM" | "AVG" | "COUNT" | "MIN" | "MAX" | "COUNT_DISTINCT" | "SUM_DISTINCT" | "AVG_DISTINCT" (plan.SINGLE only)
     expr: PhysicalExpr
     name: str
 
     def __post_init__(self):
-        if self.fun not in ("SUM", "AVG", "COUNT", "MIN", "MAX"):
+        if self.fun not in ("SUM", "AVG", "COUNT", "MIN", "MAX", "COUNT_DISTINCT", "SUM_DISTINCT", "AVG_DISTINCT"):
             raise NotImplementedError(f"aggregate function '{self.fun}' is not supported")
 
 
@@ -176,6 +176,9 @@ def Avg(expr, name): return AggregateExpr("AVG", expr, name)
 def Count(expr, name): return AggregateExpr("COUNT", expr, name)
 def Min(expr, name): return AggregateExpr("MIN", expr, name)
 def Max(expr, name): return AggregateExpr("MAX", expr, name)
+def CountDistinct(expr, name): return AggregateExpr("COUNT_DISTINCT", expr, name)
+def SumDistinct(expr, name): return AggregateExpr("SUM_DISTINCT", expr, name)
+def AvgDistinct(expr, name): return AggregateExpr("AVG_DISTINCT", expr, name)
 
 
 @dataclass(eq=False)

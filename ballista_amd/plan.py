@@ -31,6 +31,7 @@ NP_DTYPE = {E.INT32: np.int32, E.INT64: np.int64, E.UINT8: np.uint8, E.UINT64: n
             E.TIMESTAMP_MS: np.int64, E.TIMESTAMP_US: np.int64, E.TIMESTAMP_NS: np.int64}
 
 PARTIAL, FINAL = "Partial", "Final"
+SINGLE = "Single"       # raw rows in, final values out (no wire form): the only mode that takes the DISTINCT aggregates
 INNER, LEFT, RIGHT = "Inner", "Left", "Right"
 FULL, SEMI, ANTI, RIGHT_SEMI, RIGHT_ANTI = "Full", "Semi", "Anti", "RightSemi", "RightAnti"
 
@@ -832,13 +833,16 @@ class ProjectionExec(ExecutionPlan):
 
 class HashAggregateExec(ExecutionPlan):
     """HashAggregateExec::try_new(mode, group_expr: Vec<(expr, name)>, aggr_expr, input)
-    (from_proto.rs:173-252)"""
+    (from_proto.rs:173-252).  mode SINGLE: the output of FINAL over PARTIAL with the same expressions, from one operator, partition by
+    partition: the input has one partition or is Hash-partitioned on group expressions.  E.CountDistinct / E.SumDistinct /
+    E.AvgDistinct are SINGLE only."""
 
-    _FN = {"SUM": 1, "AVG": 2, "COUNT": 3, "MIN": 4, "MAX": 5}
+    _FN = {"SUM": 1, "AVG": 2, "COUNT": 3, "MIN": 4, "MAX": 5, "COUNT_DISTINCT": 6, "SUM_DISTINCT": 7, "AVG_DISTINCT": 8}
+    _MODE = {PARTIAL: 0, FINAL: 1, SINGLE: 2}
 
     def __init__(self, mode: str, group_expr: Sequence[Tuple[E.PhysicalExpr, str]],
                  aggr_expr: Sequence[E.AggregateExpr], input: ExecutionPlan):
-        if mode not in (PARTIAL, FINAL):
+        if mode not in self._MODE:
             raise L.PlanError(L.EINVAL, f"Unsupported aggregate mode {mode}")
         lw = _Lowered()
         aggs = (L.Aggregate * max(1, len(aggr_expr)))()
@@ -847,7 +851,7 @@ class HashAggregateExec(ExecutionPlan):
             lw.keep.append(nb)
             aggs[i] = L.Aggregate(self._FN[a.fun], lw.expr(a.expr), nb)
         h = C.c_void_p()
-        L.check(L.lib().bhip_plan_hash_aggregate(input._h, 0 if mode == PARTIAL else 1, len(group_expr),
+        L.check(L.lib().bhip_plan_hash_aggregate(input._h, self._MODE[mode], len(group_expr),
                                                  lw.exprs([e for e, _ in group_expr]),
                                                  lw.strings([n for _, n in group_expr]),
                                                  len(aggr_expr), aggs, C.byref(h)))

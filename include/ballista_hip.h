@@ -234,7 +234,18 @@ typedef struct {
 
 /* AggregateExpr (to_proto.rs:348-378: Sum / Avg / Count are what the serde ships; Min / Max are
  * accepted too) */
-typedef enum { BHIP_AGG_SUM = 1, BHIP_AGG_AVG = 2, BHIP_AGG_COUNT = 3, BHIP_AGG_MIN = 4, BHIP_AGG_MAX = 5 } bhip_agg_fn;
+/* COUNT / SUM / AVG (DISTINCT x): the function over the distinct non-NULL values of x in the group.  BHIP_AGG_SINGLE only (the
+ * state is a set, not a fixed-width column: BHIP_ENOTIMPL in PARTIAL / FINAL); no wire form.  Two values are the same value when
+ * a GROUP BY on wide keys would put them into one group: fixed-width types by their bits (-0.0 and +0.0, NaNs of different payloads
+ * are different values), Utf8 by length and bytes ("" is a value, NULL is none), Boolean by its bit.  COUNT_DISTINCT takes every
+ * type a group key can have, SUM_DISTINCT / AVG_DISTINCT what SUM / AVG take.  One operator may mix plain aggregates with DISTINCT
+ * ones over up to 8 different argument expressions (arguments that print alike count once), with at most 15 group expressions;
+ * neither those arguments nor the group expressions beside them may hold a string-valued function (lower(s), CAST(x AS Utf8) ...:
+ * BHIP_ENOTIMPL), plain Utf8 columns may stand in both places; input column names __distinct_0 .. are reserved (BHIP_EINVAL). */
+typedef enum {
+    BHIP_AGG_SUM = 1, BHIP_AGG_AVG = 2, BHIP_AGG_COUNT = 3, BHIP_AGG_MIN = 4, BHIP_AGG_MAX = 5,
+    BHIP_AGG_COUNT_DISTINCT = 6, BHIP_AGG_SUM_DISTINCT = 7, BHIP_AGG_AVG_DISTINCT = 8
+} bhip_agg_fn;
 typedef struct {
     int32_t fn;              /* bhip_agg_fn */
     bhip_expr arg;
@@ -248,7 +259,13 @@ typedef struct {
     int32_t nulls_first;
 } bhip_sort_expr;
 
-typedef enum { BHIP_AGG_PARTIAL = 0, BHIP_AGG_FINAL = 1 } bhip_agg_mode;       /* from_proto.rs:181-184 */
+/* PARTIAL / FINAL: from_proto.rs:181-184.  SINGLE (no wire form): raw rows in, final values out, in one operator — the output
+ * schema of FINAL over PARTIAL with the same expressions (COUNT / COUNT_DISTINCT UInt64 not nullable, SUM_DISTINCT the SUM type,
+ * AVG_DISTINCT Float64, both nullable); legal for every function.  execute(p) aggregates input partition p alone and the output
+ * partitioning is the input's, so the constructor takes the mode only when every group lies in one partition: the input has one
+ * partition, or it is Hash-partitioned on expressions that are all among the group expressions (compared as printed) and there is
+ * a group expression; otherwise BHIP_EINVAL, naming the MergeExec or RepartitionExec(Hash ...) to put under it. */
+typedef enum { BHIP_AGG_PARTIAL = 0, BHIP_AGG_FINAL = 1, BHIP_AGG_SINGLE = 2 } bhip_agg_mode;
 /* HashJoinExec join types; left is the build side.  0-2 are the wire values of from_proto.rs:268-272; FULL / SEMI / ANTI carry the
    wire values of the JoinType enum that followed it (3, 4, 5) and decode from a plan; RIGHT_SEMI / RIGHT_ANTI have no wire value
    and are reached through bhip_plan_hash_join only.  SEMI / ANTI: the left rows with / without a partner, left fields only;
