@@ -453,6 +453,17 @@ BatchPtr batch_from_host(const ContextPtr& ctx, int n_cols, const bhip_column_de
         if (d.dtype == DT_UTF8) c.data_bytes = d.data_bytes;
         const ColumnLayout L = column_layout(c.dtype, n_rows, c.data_bytes, validity != nullptr);
         if (!d.data && L[BUF_DATA].arrow_bytes > 0) fail(BHIP_EINVAL, std::string("column without data: ") + d.name);
+        if (device_ptrs) {
+            // borrowed buffers are read where they lie: each must have the alignment the kernels' loads assume
+            // (include/ballista_hip.h, "device columns")
+            auto aligned = [&](const void* p, size_t a, const char* what) {
+                if ((uintptr_t)p % a)
+                    fail(BHIP_EINVAL, std::string("device column ") + d.name + ": " + what + " not aligned to " + std::to_string(a) + " bytes");
+            };
+            aligned(d.data, L[BUF_DATA].bitmap ? 8 : d.dtype == DT_UTF8 ? 1 : (size_t)dtype_width(d.dtype), "data");
+            if (L[BUF_OFFSETS].present) aligned(d.offsets, 4, "offsets");
+            aligned(validity, 8, "validity");
+        }
         pieces.push_back({i, BUF_DATA, d.data, L[BUF_DATA]});
         if (L[BUF_OFFSETS].present) pieces.push_back({i, BUF_OFFSETS, d.offsets, L[BUF_OFFSETS]});
         if (validity) pieces.push_back({i, BUF_VALIDITY, validity, L[BUF_VALIDITY]});

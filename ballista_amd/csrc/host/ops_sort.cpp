@@ -163,12 +163,16 @@ BatchPtr first_k(const Exec& ex, const BatchPtr& in, const std::vector<SortDesc>
         Temp tmp(ex);
         void* state = tmp.get<uint8_t>(topk_state_bytes());
         // every pass is queued before anything is read: the picks leave prefix, mask and the rows still wanted in `state`
-        TIMED_LAUNCH_N(ex, "topk_diff", n, launch_topk_diff(cfg, key, n, k, state));
+        // (a fixed-width key off a 16-byte boundary — a borrowed column, a partition's slice — is read one row per thread)
+        // the form is chosen once, here, and handed to the launchers: the names below say what ran
+        const int vec = topk_rows_per_load(key);
+        const bool by_row = key_col.dtype != DT_UTF8 && vec == 1;
+        TIMED_LAUNCH_N(ex, by_row ? "topk_diff_row" : "topk_diff", n, launch_topk_diff(cfg, key, vec, n, k, state));
         if (key.col.validity) TIMED_LAUNCH_N(ex, "topk_pick", n, launch_topk_pick(cfg, TOPK_NULL_BYTE, state));
         const uint32_t bytes = topk_key_bytes(key_col.dtype);
         for (int byte = 7; byte >= 0; --byte) {
             if (!((bytes >> byte) & 1)) continue;
-            TIMED_LAUNCH_N(ex, "topk_hist", n, launch_topk_hist(cfg, key, n, byte, state));
+            TIMED_LAUNCH_N(ex, by_row ? "topk_hist_row" : "topk_hist", n, launch_topk_hist(cfg, key, vec, n, byte, state));
             TIMED_LAUNCH_N(ex, "topk_pick", n, launch_topk_pick(cfg, byte, state));
         }
         const TopkCount cnt = read_device(ex, topk_state_count(state));        // the one wait of the selection

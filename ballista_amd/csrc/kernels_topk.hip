@@ -244,6 +244,8 @@ static int topk_vec(const TopkKey& key) {
     const int w = topk_width(key.col.dtype);
     return w > 0 && (reinterpret_cast<uintptr_t>(key.col.data) & 15) == 0 ? 16 / w : 1;
 }
+int topk_rows_per_load(const TopkKey& key) { return topk_vec(key); }
+static bool topk_vec_ok(const TopkKey& key, int vec) { return vec == 1 || vec == topk_vec(key); }
 static unsigned topk_grid(const LaunchCfg& cfg, int64_t n, int vec) {
     const int64_t groups = (n + vec - 1) / vec;
     int64_t g = (groups + TK_BLOCK - 1) / TK_BLOCK;
@@ -260,18 +262,16 @@ static unsigned topk_grid(const LaunchCfg& cfg, int64_t n, int vec) {
         default: hipLaunchKernelGGL((KERNEL<8, 2>), dim3(grid), dim3(TK_BLOCK), 0, cfg.stream, __VA_ARGS__); break;              \
     }
 
-hipError_t launch_topk_diff(const LaunchCfg& cfg, const TopkKey& key, int64_t n, int64_t k, void* state) {
-    if (!topk_args_ok(key, n) || k < 1 || k > n) return hipErrorInvalidValue;
+hipError_t launch_topk_diff(const LaunchCfg& cfg, const TopkKey& key, int vec, int64_t n, int64_t k, void* state) {
+    if (!topk_args_ok(key, n) || !topk_vec_ok(key, vec) || k < 1 || k > n) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(state, 0, sizeof(TopkState), cfg.stream);
     if (e != hipSuccess) return e;
-    const int vec = topk_vec(key);
     TOPK_LAUNCH(topk_diff_kernel, topk_grid(cfg, n, vec), key, n, k, static_cast<TopkState*>(state));
     return hipGetLastError();
 }
 
-hipError_t launch_topk_hist(const LaunchCfg& cfg, const TopkKey& key, int64_t n, int byte, void* state) {
-    if (!topk_args_ok(key, n) || byte < 0 || byte >= TOPK_NULL_BYTE) return hipErrorInvalidValue;
-    const int vec = topk_vec(key);
+hipError_t launch_topk_hist(const LaunchCfg& cfg, const TopkKey& key, int vec, int64_t n, int byte, void* state) {
+    if (!topk_args_ok(key, n) || !topk_vec_ok(key, vec) || byte < 0 || byte >= TOPK_NULL_BYTE) return hipErrorInvalidValue;
     TOPK_LAUNCH(topk_hist_kernel, topk_grid(cfg, n, vec), key, n, byte, static_cast<TopkState*>(state));
     return hipGetLastError();
 }

@@ -23,10 +23,14 @@ constexpr int TOPK_NULL_BYTE = 8;                    // the pick over the NULL r
 size_t topk_state_bytes();
 const TopkCount* topk_state_count(const void* state);
 
+// rows one thread of the diff and histogram passes loads per step: 16 bytes' worth from a fixed-width key on a 16-byte boundary,
+// else one.  The host asks once per batch and hands the answer to both launchers, which instantiate exactly that form (1 is always
+// allowed, anything else only where this function gives it): what the host times under "topk_*_row" is what ran.
+int topk_rows_per_load(const TopkKey& key);
 // zeroes `state`, sets the rank wanted (k, 1 <= k <= n) and gathers: the image bits that differ between any two rows, the rows per NULL rank
-hipError_t launch_topk_diff(const LaunchCfg& cfg, const TopkKey& key, int64_t n, int64_t k, void* state);
+hipError_t launch_topk_diff(const LaunchCfg& cfg, const TopkKey& key, int rows_per_load, int64_t n, int64_t k, void* state);
 // histogram of image byte `byte` over the rows that match the prefix chosen so far; nothing when all images agree on the byte
-hipError_t launch_topk_hist(const LaunchCfg& cfg, const TopkKey& key, int64_t n, int byte, void* state);
+hipError_t launch_topk_hist(const LaunchCfg& cfg, const TopkKey& key, int rows_per_load, int64_t n, int byte, void* state);
 // the bin of byte `byte` (or of the NULL rank: TOPK_NULL_BYTE) that holds the k-th row -> prefix, mask, rows still wanted, counts
 hipError_t launch_topk_pick(const LaunchCfg& cfg, int byte, void* state);
 // bit i = row i is a candidate (composite <= threshold) + per-tile counts (tile = SEL_TILE rows): the inputs of launch_select_indices

@@ -93,8 +93,11 @@ __device__ inline void vm_load_issue_a(const ScanParams& P, int64_t tile_base, i
     // (raw bits go straight into g.x / g.ok and are converted in place: no second set of registers)
     // TWO load shapes only (more cases and the compiler's chain of flag-guarded blocks makes it wait before loads that write a
     // register some other case may have written): an 8-byte value as one dwordx2; everything narrower as the ALIGNED 4-byte word
-    // that holds it (1- / 2- / 4-byte values, the Boolean's byte), a Utf8 row as its two 4-byte offsets.  (An aligned word that
-    // holds a valid byte lies inside the buffer's allocation granule.)
+    // that holds it (1- / 2- / 4-byte values, the Boolean's byte), a Utf8 row as its two 4-byte offsets.  The word is aligned
+    // relative to the column's first byte, not to the address: a borrowed column or a partition's slice may start on any boundary
+    // of its type.  The last word of a 1- or 2-byte column reaches up to 3 bytes past the last value: owned buffers have
+    // BUFFER_SLACK behind them, a slice lies inside one, and a borrowed buffer provides them by the import contract
+    // (include/ballista_hip.h, "extent"); a bitmap is whole 64-bit words.
 #pragma unroll
     for (int j = 0; j < LOAD_GROUP; ++j) {
         if (g0 + j < G.n_loads) {

@@ -328,7 +328,13 @@ class RecordBatch:
     @staticmethod
     def from_device_columns(ctx: Context, owner: "RecordBatch") -> "RecordBatch":
         """bhip_batch_from_device: a batch that BORROWS the device buffers of `owner` (zero copy; the
-        result keeps `owner` alive).  Any caller-owned device memory laid out as Arrow works the same."""
+        result keeps `owner` alive).  Any caller-owned device memory laid out as Arrow works the same, under the
+        contract of include/ballista_hip.h.  Alignment: values on their own width, Utf8 offsets on 4 bytes, validity
+        bitmaps and Boolean values on 8 bytes (else PlanError); 16-byte aligned buffers take the wide-load kernels,
+        any other placement gives the same results.  Bytes read: a bitmap to the end of the 64-bit word that holds
+        its last bit, 1- and 2-byte values to the end of the 4-byte word (counted from the buffer's first byte) that
+        holds the last value — what lies past the last row there may hold anything — and nothing else beyond the
+        Arrow sizes."""
         descs, keep = [], []
         for i in range(owner.num_columns):
             name, dtype, nullable, nbytes, _ = owner.column_info(i)
@@ -414,7 +420,10 @@ class RecordBatch:
     @staticmethod
     def from_device_pointers(ctx: Context, columns, n_rows: int, keep=None) -> "RecordBatch":
         """bhip_batch_from_device over caller-owned device memory: columns = [(name, dtype, data_ptr)], fixed-width
-        NULL-free columns (e.g. buffers an RCCL collective has just filled).  `keep`: whatever owns the memory."""
+        NULL-free columns (e.g. buffers an RCCL collective has just filled).  `keep`: whatever owns the memory.
+        Each pointer is aligned to its value's width (else PlanError; 16 bytes for the wide-load kernels, the same
+        results without).  n_rows * width bytes are read behind it; for 1- and 2-byte values that count is rounded
+        up to a multiple of 4, and the bytes past the last value may hold anything (include/ballista_hip.h)."""
         descs, names = [], []
         for name, dtype, ptr in columns:
             if dtype in (E.UTF8, E.BOOLEAN):

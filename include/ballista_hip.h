@@ -123,7 +123,20 @@ bhip_status bhip_ctx_memory(bhip_ctx* ctx, uint64_t* in_use, uint64_t* peak);
  * bhip_batch_from_device adopts device pointers without copying (caller keeps them alive and
  * unchanged until the batch is released).  Layout per column = Arrow: fixed-width values, or
  * Utf8 int32 offsets (length+1) + bytes, Boolean = bitmap; validity bitmap optional (NULL =
- * no nulls); offset must be 0 for device columns. */
+ * no nulls); offset must be 0 for device columns.
+ *
+ * Device columns are read where they lie, so bhip_batch_from_device asks of each buffer:
+ *   alignment   values: the value's own width (1, 2, 4 or 8 bytes); Utf8 offsets: 4 bytes; Utf8 bytes: none;
+ *               validity bitmaps and Boolean values: 8 bytes.  A pointer that breaks it -> BHIP_EINVAL.
+ *               (Buffers on a 16-byte boundary take the wide-load kernels; any other placement gives the same
+ *               results through the general ones.)
+ *   extent      the library reads a bitmap up to the end of the 64-bit word that holds its last bit — the caller
+ *               provides ((n_rows + 63) / 64) * 8 readable bytes; the bits past n_rows may hold anything.
+ *               1- and 2-byte values are read as 4-byte words counted from the buffer's first byte (wherever that
+ *               lies), up to the end of the word that holds the last value: the caller provides
+ *               ((n_rows * width + 3) / 4) * 4 readable bytes; the bytes past the last value may hold anything.
+ *               Nothing else is read beyond the Arrow sizes: n_rows * width bytes of 4- and 8-byte values,
+ *               (n_rows + 1) * 4 bytes of offsets, data_bytes bytes of Utf8 values. */
 typedef struct {
     const char* name;
     int32_t dtype;            /* bhip_dtype */
