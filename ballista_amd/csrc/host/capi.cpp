@@ -697,19 +697,10 @@ static TpchCard tpch_card(double sf) {
 }
 
 static Column gen_col(const Exec& ex, int dtype, int64_t n) {
-    Column c;
-    c.dtype = dtype;
-    c.length = n;
-    c.data = make_buffer(ex, (size_t)n * dtype_width(dtype) + 8);
-    return c;
+    return alloc_column(ex, dtype, n, false);
 }
 static Column gen_char_col(const Exec& ex, int64_t n) {
-    Column c;
-    c.dtype = DT_UTF8;
-    c.length = n;
-    c.data = make_buffer(ex, (size_t)n + 8);
-    c.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
-    c.data_bytes = n;
+    Column c = alloc_column(ex, DT_UTF8, n, false, n);
     c.offsets->set_uniform_width(n, 1);       // the generators write one byte per row
     return c;
 }
@@ -731,10 +722,8 @@ bhip_status bhip_tpch_lineitem_opts(bhip_ctx* ctx, double sf, uint64_t seed, uin
     const TpchCard card = tpch_card(sf);
     ctx->p->set_device();
     Exec ex{ctx->p, nullptr};
-    auto b = std::make_shared<Batch>();
     auto s = std::make_shared<Schema>();
-    b->ctx = ctx->p;
-    b->n_rows = (int64_t)n;
+    auto b = new_batch(ctx->p, s, (int64_t)n);
     auto add = [&](const char* name, Column c) { s->fields.push_back(Field{name, c.dtype, false}); b->cols.push_back(std::move(c)); };
     GenLineitemOut o;
     memset(&o, 0, sizeof(o));
@@ -757,7 +746,6 @@ bhip_status bhip_tpch_lineitem_opts(bhip_ctx* ctx, double sf, uint64_t seed, uin
         if (gen_wants(opts, "l_receiptdate")) { c = gen_col(ex, DT_DATE32, n); o.l_receiptdate = c.data->as<int32_t>(); add("l_receiptdate", c); }
     }
     if (s->fields.empty()) fail(BHIP_EINVAL, "bhip_tpch_lineitem_opts: no such column");
-    b->schema = s;
     const GenKeyLayout keys{opts ? opts->key_base : 0, opts && opts->sparse_keys ? 1 : 0};
     HIP_CHECK(launch_gen_lineitem(ex.cfg(), seed, row0, n, card.orders, card.part, card.supplier, o, keys));
     HIP_CHECK(hipDeviceSynchronize());
@@ -773,10 +761,8 @@ bhip_status bhip_tpch_orders_opts(bhip_ctx* ctx, double sf, uint64_t seed, uint6
     const TpchCard card = tpch_card(sf);
     ctx->p->set_device();
     Exec ex{ctx->p, nullptr};
-    auto b = std::make_shared<Batch>();
     auto s = std::make_shared<Schema>();
-    b->ctx = ctx->p;
-    b->n_rows = (int64_t)n;
+    auto b = new_batch(ctx->p, s, (int64_t)n);
     auto add = [&](const char* name, Column c) { s->fields.push_back(Field{name, c.dtype, false}); b->cols.push_back(std::move(c)); };
     GenOrdersOut o;
     memset(&o, 0, sizeof(o));
@@ -790,7 +776,6 @@ bhip_status bhip_tpch_orders_opts(bhip_ctx* ctx, double sf, uint64_t seed, uint6
     if (gen_wants(opts, "o_orderdate")) { c = gen_col(ex, DT_DATE32, n); o.o_orderdate = c.data->as<int32_t>(); add("o_orderdate", c); }
     if (gen_wants(opts, "o_shippriority")) { c = gen_col(ex, DT_INT32, n); o.o_shippriority = c.data->as<int32_t>(); add("o_shippriority", c); }
     if (s->fields.empty()) fail(BHIP_EINVAL, "bhip_tpch_orders_opts: no such column");
-    b->schema = s;
     const GenKeyLayout keys{opts ? opts->key_base : 0, opts && opts->sparse_keys ? 1 : 0};
     HIP_CHECK(launch_gen_orders(ex.cfg(), seed, row0, n, card.customer, o, keys));
     HIP_CHECK(hipDeviceSynchronize());

@@ -406,6 +406,34 @@ ColumnLayout column_layout(int dtype, int64_t n_rows, int64_t data_bytes, bool h
     return L;
 }
 
+Column alloc_column(const Exec& ex, int dtype, int64_t n_rows, bool with_validity, int64_t utf8_data_bytes) {
+    Column c;
+    c.dtype = dtype;
+    c.length = n_rows;
+    const bool data_later = dtype == DT_UTF8 && utf8_data_bytes < 0;
+    if (dtype == DT_UTF8 && !data_later) c.data_bytes = utf8_data_bytes;
+    const ColumnLayout L = column_layout(dtype, n_rows, c.data_bytes, with_validity);
+    // data, offsets, validity: the order the table generators and most operators have always asked in (where a resident table's
+    // columns lie in HBM follows the order of their first allocation, and a scan's speed follows that)
+    if (dtype == DT_UTF8 && !data_later) utf8_alloc_data(ex, c, utf8_data_bytes);
+    else if (!data_later) c.data = make_buffer(ex, L[BUF_DATA].alloc_bytes);
+    if (L[BUF_OFFSETS].present) {
+        c.offsets = make_buffer(ex, L[BUF_OFFSETS].alloc_bytes);
+        if (n_rows == 0) HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 4, ex.stream));
+    }
+    if (with_validity) c.validity = make_buffer(ex, L[BUF_VALIDITY].alloc_bytes);
+    return c;
+}
+
+void utf8_alloc_data(const Exec& ex, Column& out, int64_t bytes) {
+    if ((uint64_t)bytes > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
+    out.data = make_buffer(ex, column_layout(DT_UTF8, out.length, bytes, false)[BUF_DATA].alloc_bytes);
+}
+
+BufferPtr validity_buffer(const Exec& ex, int64_t n_rows) {
+    return make_buffer(ex, column_layout(DT_BOOLEAN, n_rows, 0, true)[BUF_VALIDITY].alloc_bytes);
+}
+
 int64_t Column::memory_size() const {
     int64_t b = 0;
     for (const BufferSpec& s : column_layout(*this).buf) b += (int64_t)s.arrow_bytes;

@@ -216,6 +216,8 @@ private:
 };
 using BufferPtr = std::shared_ptr<Buffer>;
 BufferPtr make_buffer(const Exec& ex, size_t bytes);
+// n uint32_t row indices: a selection, a permutation, a view's index vector
+inline BufferPtr index_buffer(const Exec& ex, int64_t n) { return make_buffer(ex, (size_t)n * 4 + 8); }
 inline size_t bitmap_bytes(int64_t n_bits) { return (size_t)((n_bits + 63) / 64) * 8; }
 // slots of an open-addressing table over `rows` keys: the power of two >= 2 x rows, at least 1024
 inline uint64_t table_capacity(uint64_t rows) { uint64_t cap = 1024; while (cap < 2 * rows) cap <<= 1; return cap; }
@@ -252,11 +254,13 @@ struct Column {
     // BufferPtr with a shifted start would have to carry the shift here (or drop the fact), or the fixed-width key form
     // would read the wrong bytes.
     int32_t utf8_width(int64_t rows) const { return dtype == DT_UTF8 && offsets ? offsets->uniform_width(rows) : 0; }
+    // the validity bitmap as the kernels take it, nullptr where there is none (not const: as Buffer::as, it serves whoever fills the column too)
+    uint64_t* validity_words() const { return validity ? validity->as<uint64_t>() : nullptr; }
     ColumnRef ref() const {
         ColumnRef r;
         r.data = data ? data->ptr() : nullptr;
         r.offsets = offsets ? offsets->as<int32_t>() : nullptr;
-        r.validity = validity ? validity->as<uint64_t>() : nullptr;
+        r.validity = validity_words();
         r.dtype = dtype;
         r.data_bytes = (int32_t)data_bytes;
         return r;
@@ -266,14 +270,14 @@ struct Column {
 
 // The buffers of a materialised column: THE place that knows which buffers a column of a type has and how many bytes each holds.
 // Everything that moves a column across the library's edge (host import and export, the packed blocks of the exchange) walks
-// this, in the order it needs.
+// this, in the order it needs, and every column an operator produces is allocated from it (alloc_column below).
 enum BufferRole { BUF_VALIDITY = 0, BUF_OFFSETS = 1, BUF_DATA = 2 };
 struct BufferSpec {
     bool present = false;
     bool bitmap = false;       // validity, Boolean values: the device copy is zero-padded to whole words
     size_t arrow_bytes = 0;    // what the Arrow buffer holds: (n+7)/8, (n+1)*4, the Utf8 value bytes, n*width
     size_t device_bytes = 0;   // on the device: bitmaps as whole 64-bit words (they are read as u64), everything else as in Arrow
-    size_t alloc_bytes = 0;    // logical size of a device copy made at the edge: device_bytes, + 8 of slack on values and bitmaps
+    size_t alloc_bytes = 0;    // logical size of a buffer the library allocates: device_bytes, + 8 of slack on values and bitmaps
 };
 struct ColumnLayout {
     BufferSpec buf[3];         // by BufferRole
@@ -282,6 +286,17 @@ struct ColumnLayout {
 ColumnLayout column_layout(int dtype, int64_t n_rows, int64_t data_bytes, bool has_validity);
 inline ColumnLayout column_layout(const Column& c) { return column_layout(c.dtype, c.length, c.data_bytes, (bool)c.validity); }
 inline const BufferPtr& column_buffer(const Column& c, BufferRole r) { return r == BUF_VALIDITY ? c.validity : r == BUF_OFFSETS ? c.offsets : c.data; }
+
+// THE allocator of a column the library produces: dtype, length and data_bytes set, and every buffer that column_layout marks
+// present allocated at its alloc_bytes — uninitialised, but for the one zero that is the offsets of a zero-row Utf8 column.
+// utf8_data_bytes < 0: a Utf8 column whose value bytes are known only once its offsets are written (plan.hpp utf8_from_lengths):
+// no data buffer yet, utf8_alloc_data brings it.
+Column alloc_column(const Exec& ex, int dtype, int64_t n_rows, bool with_validity, int64_t utf8_data_bytes = 0);
+// ... the data buffer, with room for `bytes` value bytes (BHIP_EEXEC above 2 GiB: the offsets are Int32).  `bytes` may be a bound:
+// out.data_bytes stays with whoever knows the total.
+void utf8_alloc_data(const Exec& ex, Column& out, int64_t bytes);
+// a validity bitmap over n rows, for a column that turns out to need one after it was allocated
+BufferPtr validity_buffer(const Exec& ex, int64_t n_rows);
 
 struct Field {
     std::string name;
@@ -312,6 +327,14 @@ struct Batch {
     int64_t memory_size() const;
 };
 using BatchPtr = std::shared_ptr<const Batch>;
+// a batch of n_rows rows whose columns the caller is about to fill
+inline std::shared_ptr<Batch> new_batch(const ContextPtr& ctx, const SchemaPtr& schema, int64_t n_rows) {
+    auto b = std::make_shared<Batch>();
+    b->schema = schema;
+    b->ctx = ctx;
+    b->n_rows = n_rows;
+    return b;
+}
 
 // host <-> device movement
 BatchPtr batch_from_host(const ContextPtr& ctx, int n_cols, const bhip_column_desc* cols, int64_t n_rows, bool device_ptrs);

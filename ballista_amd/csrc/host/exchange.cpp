@@ -164,10 +164,7 @@ void pack_batch(const Exec& ex, const Batch& b, const int64_t* h, uint8_t* dst) 
 BatchPtr unpack_batch(const ContextPtr& ctx, const SchemaPtr& schema, const BufferPtr& block, size_t block_offset, const int64_t* h) {
     const BlockLayout L = block_layout(schema->fields.size(), h);
     if ((int64_t)L.total != h[1]) fail(BHIP_EEXEC, "exchange: block layout does not match its header");
-    auto b = std::make_shared<Batch>();
-    b->schema = schema;
-    b->ctx = ctx;
-    b->n_rows = h[0];
+    auto b = new_batch(ctx, schema, h[0]);
     for (auto& f : schema->fields) {
         Column c;
         c.dtype = f.dtype;
@@ -592,17 +589,10 @@ public:
         if (n_out > 0xFFFFFFF0ll) fail(BHIP_ENOTIMPL, "shuffle: this rank would receive more than 2^32-16 rows in one batch");
         // ---- result columns, two staging sets -----------------------------------------------------------------------------------
         const size_t n_cols = in->cols.size();
-        auto out = std::make_shared<Batch>();
-        out->schema = in->schema;
-        out->ctx = ctx_;
-        out->n_rows = n_out;
+        auto out = new_batch(ctx_, in->schema, n_out);
         size_t row_bytes = 0;
         for (auto& c : in->cols) {
-            Column oc;
-            oc.dtype = c.dtype;
-            oc.length = n_out;
-            oc.data = make_buffer(ex, (size_t)n_out * dtype_width(c.dtype) + 8);
-            out->cols.push_back(oc);
+            out->cols.push_back(alloc_column(ex, c.dtype, n_out, false));
             row_bytes += (size_t)dtype_width(c.dtype);
         }
         const int64_t stage_rows = std::min<int64_t>(chunk_rows, std::max<int64_t>(n, 1));
@@ -610,6 +600,7 @@ public:
         BufferPtr scatter_tmp[2];
         const int n_stage = C > 1 ? 2 : 1;
         for (int b = 0; b < n_stage; ++b) {
+            // (scratch of one chunk on the auxiliary stream, never a column of a batch)
             for (auto& c : in->cols) stage[b].push_back(make_buffer(ax, (size_t)stage_rows * dtype_width(c.dtype) + 8));
             scatter_tmp[b] = make_buffer(ax, partition_scatter_temp_bytes(stage_rows) + 64);
         }

@@ -223,40 +223,22 @@ struct EmitColumns {
 EmitColumns alloc_emit_columns(const Exec& ex, const SchemaPtr& out_schema, const KeyLayout& kinfo, size_t n_keys,
                                const std::vector<EmitValueSpec>& emits, bool nullable, int64_t n) {
     EmitColumns E;
-    E.out = std::make_shared<Batch>();
-    E.out->schema = out_schema;
-    E.out->ctx = ex.ctx;
-    E.out->n_rows = n;
+    E.out = new_batch(ex.ctx, out_schema, n);
     for (size_t gi = 0; gi < n_keys; ++gi) {
-        Column c;
-        c.dtype = out_schema->fields[gi].dtype;
-        c.length = n;
-        E.key.push_back(EmitKeySpec{kinfo[gi].pos, kinfo[gi].width, kinfo[gi].nullable, c.dtype});
-        if (kinfo[gi].nullable) c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-        if (c.dtype == DT_UTF8) {
-            c.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
-            c.data = make_buffer(ex, (size_t)n * (size_t)kinfo[gi].width + 8);
-            E.utf8_cols.push_back(gi);
-        } else {
-            c.data = make_buffer(ex, (c.dtype == DT_BOOLEAN ? bitmap_bytes(n) : (size_t)n * dtype_width(c.dtype)) + 8);
-        }
-        E.out->cols.push_back(std::move(c));
+        const int dtype = out_schema->fields[gi].dtype;
+        E.key.push_back(EmitKeySpec{kinfo[gi].pos, kinfo[gi].width, kinfo[gi].nullable, dtype});
+        if (dtype == DT_UTF8) E.utf8_cols.push_back(gi);
+        // Utf8: room for the packed key's bound; finish_table sets data_bytes
+        E.out->cols.push_back(alloc_column(ex, dtype, n, kinfo[gi].nullable, n * (int64_t)kinfo[gi].width));
     }
     for (size_t k = 0; k < emits.size(); ++k) {
         const Field& fld = out_schema->fields[n_keys + k];
-        Column c;
-        c.dtype = fld.dtype;
-        c.length = n;
-        c.data = make_buffer(ex, (size_t)n * dtype_width(c.dtype) + 8);
-        if (fld.nullable) c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
         E.value.push_back(emits[k]);
         E.value.back().count_is_rows = nullable ? 0 : 1;
-        E.out->cols.push_back(std::move(c));
+        E.out->cols.push_back(alloc_column(ex, fld.dtype, n, fld.nullable));
     }
     return E;
 }
-
-uint64_t* validity_of(const Column& c) { return c.validity ? c.validity->as<uint64_t>() : nullptr; }
 
 // every column in one launch (emit_all_kernel, emit_slots_kernel); totals[gi]: where a Utf8 key column's byte total goes
 EmitAllArgs emit_all_args(const EmitColumns& E, uint64_t* totals) {
@@ -268,14 +250,14 @@ EmitAllArgs emit_all_args(const EmitColumns& E, uint64_t* totals) {
         const Column& c = E.out->cols[gi];
         A.key[gi] = E.key[gi];
         A.key_data[gi] = c.data->ptr();
-        A.key_validity[gi] = validity_of(c);
+        A.key_validity[gi] = c.validity_words();
         if (c.offsets) { A.key_offsets[gi] = c.offsets->as<int32_t>(); A.key_total[gi] = totals + gi; }
     }
     for (size_t k = 0; k < E.value.size(); ++k) {
         const Column& c = E.out->cols[E.key.size() + k];
         A.value[k] = E.value[k];
         A.value_data[k] = c.data->ptr();
-        A.value_validity[k] = validity_of(c);
+        A.value_validity[k] = c.validity_words();
     }
     return A;
 }
@@ -488,7 +470,7 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
         for (size_t gi = 0; gi < group_.size(); ++gi) {
             const Column& c = E.out->cols[gi];
             const EmitKeySpec& ks = E.key[gi];
-            uint64_t* vptr = validity_of(c);
+            uint64_t* vptr = c.validity_words();
             if (c.dtype != DT_UTF8) {
                 if (n_alloc) TIMED_LAUNCH(ex, "emit_group_key", launch_emit_group_key(cfg, tab, n_alloc, ks, c.data->ptr(), vptr, nullptr, dev_n));
             } else if (n_alloc > 0 && n_alloc <= EMIT_UTF8_SMALL_MAX) {
@@ -509,7 +491,7 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
             const Column& c = E.out->cols[group_.size() + k];
             vb.spec[vb.n] = E.value[k];
             vb.data[vb.n] = c.data->ptr();
-            vb.validity[vb.n] = validity_of(c);
+            vb.validity[vb.n] = c.validity_words();
             if (++vb.n == EMIT_BATCH_MAX || k + 1 == emits.size()) {
                 TIMED_LAUNCH(ex, "emit_group_values", launch_emit_group_values(cfg, tab, n_alloc, vb, dev_n));
                 vb.n = 0;

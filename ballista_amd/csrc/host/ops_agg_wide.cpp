@@ -114,7 +114,7 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
     // ---- key columns, their row hashes, the representative of every row -------------------------------------
     std::vector<Column> keys;
     for (auto& g : group_) keys.push_back(evaluate_column(ex, *in, g.first));
-    BufferPtr rep = make_buffer(ex, (size_t)n * 4 + 8);
+    Column rep = alloc_column(ex, DT_INT32, n, false);
     {
         Temp tmp(ex);
         // one hash program holds VM_MAX_KEYPARTS key parts: up to 8 group expressions are one pass, 9 .. 16 a second pass over the rest
@@ -140,29 +140,20 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
         memset(&K, 0, sizeof(K));
         K.n = (int32_t)keys.size();
         for (size_t i = 0; i < keys.size(); ++i) K.col[i] = keys[i].ref();
-        TIMED_LAUNCH(ex, "wide_key_assign", launch_wide_key_assign(cfg, K, hashes, hashes2, table, cap - 1, (uint32_t)n, rep->as<uint32_t>()));
+        TIMED_LAUNCH(ex, "wide_key_assign", launch_wide_key_assign(cfg, K, hashes, hashes2, table, cap - 1, (uint32_t)n, rep.data->as<uint32_t>()));
     }
 
     // ---- the ordinary aggregate, keyed by the representative row ---------------------------------------------
     auto s2 = std::make_shared<Schema>();
-    auto aug = std::make_shared<Batch>();
-    aug->ctx = ex.ctx;
-    aug->n_rows = n;
+    auto aug = new_batch(ex.ctx, s2, n);
     s2->fields.push_back(Field{kRepName, DT_INT32, false});
-    {
-        Column c;
-        c.dtype = DT_INT32;
-        c.length = n;
-        c.data = rep;
-        aug->cols.push_back(std::move(c));
-    }
+    aug->cols.push_back(rep);
     // Partial: the arguments are expressions over the input's names; Final: the state columns follow the key by position
     const size_t first = mode_ == BHIP_AGG_PARTIAL ? 0 : group_.size();
     for (size_t i = first; i < in_schema->fields.size(); ++i) {
         s2->fields.push_back(in_schema->fields[i]);
         aug->cols.push_back(in->cols[i]);
     }
-    aug->schema = s2;
     auto src = std::make_shared<MemoryExec>(ex.ctx, s2, std::vector<std::vector<BatchPtr>>{{BatchPtr(aug)}});
     auto inner = std::make_shared<HashAggregateExec>(
         mode_, std::vector<std::pair<ExprPtr, std::string>>{{make_column(kRepName), kRepName}}, aggr_, src);
@@ -172,10 +163,7 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
     // ---- key columns of the groups: the input's, at the representative rows ----------------------------------
     std::vector<BatchPtr> outv;
     for (auto& r : res) {
-        auto out = std::make_shared<Batch>();
-        out->schema = schema_;
-        out->ctx = ex.ctx;
-        out->n_rows = r->n_rows;
+        auto out = new_batch(ex.ctx, schema_, r->n_rows);
         std::vector<const Column*> kp;
         for (auto& k : keys) kp.push_back(&k);
         std::vector<Column> got = take_columns(ex, kp, r->cols[0].data->as<uint32_t>(), r->n_rows, false);
@@ -324,8 +312,8 @@ std::vector<BatchPtr> HashAggregateExec::run_single(int partition, const Exec& e
             K.n = (int32_t)keys.size() + 1;
             for (size_t i = 0; i < keys.size(); ++i) K.col[i] = keys[i].ref();
             K.col[keys.size()] = x.ref();
-            const uint64_t* xvalid = x.validity ? x.validity->as<uint64_t>() : nullptr;
-            marked.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+            const uint64_t* xvalid = x.validity_words();
+            marked.validity = validity_buffer(ex, n);
             TIMED_LAUNCH_N(ex, "distinct_claim", n, launch_distinct_claim(cfg, K, xvalid, hashes, hashes2, table, cap - 1, (uint32_t)n, slot_of));
             TIMED_LAUNCH_N(ex, "distinct_mark", n, launch_distinct_mark(cfg, xvalid, table, slot_of, (uint32_t)n, marked.validity->as<uint64_t>()));
         }
@@ -397,10 +385,7 @@ std::vector<BatchPtr> HashAggregateExec::run_strings(int partition, const Exec& 
         Ranked r;
         r.agg = i;
         r.strings = strings;
-        Column rank;
-        rank.dtype = DT_INT64;
-        rank.length = n;
-        rank.data = make_buffer(ex, (size_t)n * 8 + 8);
+        Column rank = alloc_column(ex, DT_INT64, n, false);
         rank.validity = strings.validity;
         if (n > 0) {
             r.perm = sort_permutation(ex, *aug, {SortDesc{make_column(s2->fields[ci].name), false, false}});
@@ -431,8 +416,8 @@ std::vector<BatchPtr> HashAggregateExec::run_strings(int partition, const Exec& 
             size_t col = group_.size();
             for (size_t i = 0; i < rk.agg; ++i) col += aggr_[i].fn == BHIP_AGG_AVG && mode_ == BHIP_AGG_PARTIAL ? 2 : 1;
             const Column& ranks = r->cols[col];
-            BufferPtr idx = make_buffer(ex, (size_t)r->n_rows * 4 + 8);
-            TIMED_LAUNCH_N(ex, "rank_to_row", r->n_rows, launch_rank_to_row(cfg, ranks.data->as<int64_t>(), ranks.validity ? ranks.validity->as<uint64_t>() : nullptr,
+            BufferPtr idx = index_buffer(ex, r->n_rows);
+            TIMED_LAUNCH_N(ex, "rank_to_row", r->n_rows, launch_rank_to_row(cfg, ranks.data->as<int64_t>(), ranks.validity_words(),
                                                                              rk.perm ? rk.perm->as<uint32_t>() : nullptr, r->n_rows, idx->as<uint32_t>()));
             std::vector<const Column*> one{&rk.strings};
             out->cols[col] = take_columns(ex, one, idx->as<uint32_t>(), r->n_rows, /*may_null=*/true, false)[0];

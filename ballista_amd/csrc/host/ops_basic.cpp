@@ -54,29 +54,12 @@ static ScanStatus* new_status(Temp& tmp) {
 }
 
 // ---- computed columns ------------------------------------------------------------------------------
-Column fixed_column(const Exec& ex, int dtype, int64_t n, bool with_validity) {
-    Column c;
-    c.dtype = dtype;
-    c.length = n;
-    c.data = make_buffer(ex, (dtype == DT_BOOLEAN ? bitmap_bytes(n) : (size_t)n * dtype_width(dtype)) + 8);
-    if (with_validity) c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-    return c;
-}
-
 Column utf8_from_lengths(const Exec& ex, Temp& tmp, uint32_t* lengths, int64_t n, Utf8Total& total) {
-    Column out;
-    out.dtype = DT_UTF8;
-    out.length = n;
-    out.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
+    Column out = alloc_column(ex, DT_UTF8, n, false, /*utf8_data_bytes: once the offsets are scanned*/ -1);
     total.dev = tmp.get<uint64_t>(1);
     void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n));
     HIP_CHECK(exclusive_scan_u32_i32(ex.stream, lengths, n, out.offsets->as<int32_t>(), true, total.dev, scan_tmp));
     return out;
-}
-
-void utf8_alloc_data(const Exec& ex, Column& out, int64_t bytes) {
-    if ((uint64_t)bytes > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
-    out.data = make_buffer(ex, (size_t)bytes + 8);
 }
 
 void utf8_size_data(const Exec& ex, Column& out, int64_t bound, Utf8Total& total) {
@@ -107,28 +90,24 @@ uint32_t utf8_read_total(const Exec& ex, Temp& tmp, Column& out, Utf8Total& tota
 // host round trip for the total
 Column take_column(const Exec& ex, const Column& c, const uint32_t* idx, int64_t n, int64_t known_bytes) {
     const LaunchCfg cfg = ex.cfg();
-    Column out;
-    out.dtype = c.dtype;
-    out.length = n;
     if (c.dtype == DT_UTF8) {
         Temp tmp(ex);
         uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
         TIMED_LAUNCH_N(ex, "take_utf8_lengths", n, launch_take_utf8_lengths(cfg, c.offsets->as<int32_t>(), idx, n, lengths));
         Utf8Total total;
-        out = utf8_from_lengths(ex, tmp, lengths, n, total);
+        Column out = utf8_from_lengths(ex, tmp, lengths, n, total);
         total.host = known_bytes;
         utf8_size_data(ex, out, INT64_MAX, total);           // no bound to go by: the total, read unless the caller knew it
         out.data_bytes = total.host;
         TIMED_LAUNCH_N(ex, "take_utf8_copy", n, launch_take_utf8_copy(cfg, c.offsets->as<int32_t>(), c.data->as<uint8_t>(), c.data_bytes, idx, n,
                                         out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
-    } else if (c.dtype == DT_BOOLEAN) {
-        out.data = make_buffer(ex, bitmap_bytes(n) + 8);
-        TIMED_LAUNCH(ex, "take_bitmap", launch_take_bitmap(cfg, c.data->as<uint64_t>(), idx, n, out.data->as<uint64_t>()));
-    } else {
-        const int w = dtype_width(c.dtype);
-        out.data = make_buffer(ex, (size_t)n * w + 8);
-        TIMED_LAUNCH_N(ex, "take_fixed", n, launch_take_fixed(cfg, c.data->ptr(), w, idx, n, out.data->ptr()));
+        return out;
     }
+    Column out = alloc_column(ex, c.dtype, n, false);
+    if (c.dtype == DT_BOOLEAN)
+        TIMED_LAUNCH(ex, "take_bitmap", launch_take_bitmap(cfg, c.data->as<uint64_t>(), idx, n, out.data->as<uint64_t>()));
+    else
+        TIMED_LAUNCH_N(ex, "take_fixed", n, launch_take_fixed(cfg, c.data->ptr(), dtype_width(c.dtype), idx, n, out.data->ptr()));
     return out;
 }
 
@@ -137,9 +116,8 @@ static Column take_column_v(const Exec& ex, const Column& c, const uint32_t* idx
                             bool permutation = false) {
     Column out = take_column(ex, c, idx, n, permutation && c.dtype == DT_UTF8 ? c.data_bytes : -1);
     if (c.validity || may_null) {
-        out.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-        TIMED_LAUNCH(ex, "take_bitmap", launch_take_bitmap(ex.cfg(), c.validity ? c.validity->as<uint64_t>() : nullptr, idx, n,
-                                     out.validity->as<uint64_t>()));
+        out.validity = validity_buffer(ex, n);
+        TIMED_LAUNCH(ex, "take_bitmap", launch_take_bitmap(ex.cfg(), c.validity_words(), idx, n, out.validity->as<uint64_t>()));
     }
     return out;
 }
@@ -164,7 +142,7 @@ std::vector<Column> take_columns(const Exec& ex, const std::vector<const Column*
             if (c.is_view()) {
                 BufferPtr& comp = composed[c.view_idx.get()];
                 if (!comp) {
-                    comp = make_buffer(ex, (size_t)n * 4 + 8);
+                    comp = index_buffer(ex, n);
                     TIMED_LAUNCH_N(ex, "compose_indices", n, launch_compose_indices(ex.cfg(), c.view_idx->as<uint32_t>(), idx, n, comp->as<uint32_t>()));
                 }
                 if (keep_views) {
@@ -183,7 +161,7 @@ std::vector<Column> take_columns(const Exec& ex, const std::vector<const Column*
             } else if (keep_views) {
                 if (!own_idx && idx_owner && idx_owner->ptr() == (const void*)idx) own_idx = idx_owner;     // the caller's own buffer: kept, not copied
                 if (!own_idx) {
-                    own_idx = make_buffer(ex, (size_t)n * 4 + 8);
+                    own_idx = index_buffer(ex, n);
                     if (n) HIP_CHECK(hipMemcpyAsync(own_idx->ptr(), idx, (size_t)n * 4, hipMemcpyDeviceToDevice, ex.stream));
                 }
                 Column& o = out[i];
@@ -229,19 +207,11 @@ std::vector<Column> take_columns(const Exec& ex, const std::vector<const Column*
         if (c.dtype == DT_UTF8) {
             o = take_column(ex, c, idx, n, permutation ? c.data_bytes : -1);
         } else {
-            o.dtype = c.dtype;
-            o.length = n;
-            if (c.dtype == DT_BOOLEAN) {
-                o.data = make_buffer(ex, bitmap_bytes(n) + 8);
-                add(c.data->ptr(), o.data->ptr(), 0);
-            } else {
-                const int w = dtype_width(c.dtype);
-                o.data = make_buffer(ex, (size_t)n * w + 8);
-                add(c.data->ptr(), o.data->ptr(), w);
-            }
+            o = alloc_column(ex, c.dtype, n, false);
+            add(c.data->ptr(), o.data->ptr(), c.dtype == DT_BOOLEAN ? 0 : dtype_width(c.dtype));
         }
         if (c.validity || may_null) {
-            o.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+            o.validity = validity_buffer(ex, n);
             add(c.validity ? c.validity->ptr() : nullptr, o.validity->ptr(), 0);
         }
     }
@@ -250,10 +220,7 @@ std::vector<Column> take_columns(const Exec& ex, const std::vector<const Column*
 }
 
 BatchPtr take_batch(const Exec& ex, const Batch& in, const uint32_t* idx, int64_t n_out, SchemaPtr schema, bool permutation) {
-    auto out = std::make_shared<Batch>();
-    out->schema = schema ? schema : in.schema;
-    out->ctx = in.ctx;
-    out->n_rows = n_out;
+    auto out = new_batch(in.ctx, schema ? schema : in.schema, n_out);
     std::vector<const Column*> cols;
     for (const auto& c : in.cols) cols.push_back(&c);
     out->cols = take_columns(ex, cols, idx, n_out, false, permutation);
@@ -274,16 +241,8 @@ BatchPtr materialize_batch(const Exec& ex, const BatchPtr& b) {
 }
 
 BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema) {
-    auto e = std::make_shared<Batch>();
-    e->schema = schema;
-    e->ctx = ex.ctx;
-    for (auto& f : schema->fields) {
-        Column c;
-        c.dtype = f.dtype;
-        c.data = make_buffer(ex, 8);
-        if (f.dtype == DT_UTF8) { c.offsets = make_buffer(ex, 8); HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream)); }
-        e->cols.push_back(c);
-    }
+    auto e = new_batch(ex.ctx, schema, 0);
+    for (auto& f : schema->fields) e->cols.push_back(alloc_column(ex, f.dtype, 0, false));
     return e;
 }
 
@@ -296,17 +255,8 @@ Column take_batch_column(const Exec& ex, const Column& c, const uint32_t* idx, i
 }
 
 Column null_column(const Exec& ex, int dtype, int64_t n) {
-    Column c;
-    if (dtype != DT_UTF8) {
-        c = fixed_column(ex, dtype, n, true);
-    } else {
-        c.dtype = dtype;
-        c.length = n;
-        c.data = make_buffer(ex, 8 + 8);                      // no value bytes
-        c.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
-        HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, (size_t)(n + 1) * 4, ex.stream));
-        c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-    }
+    Column c = alloc_column(ex, dtype, n, true);              // Utf8: no value bytes
+    if (c.offsets) HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, c.offsets->bytes(), ex.stream));
     HIP_CHECK(hipMemsetAsync(c.data->ptr(), 0, c.data->bytes(), ex.stream));
     HIP_CHECK(hipMemsetAsync(c.validity->ptr(), 0, c.validity->bytes(), ex.stream));
     return c;
@@ -316,38 +266,22 @@ Column null_column(const Exec& ex, int dtype, int64_t n) {
 BatchPtr concat_batches(const Exec& ex, const SchemaPtr& schema, const std::vector<BatchPtr>& parts) {
     if (parts.size() == 1) return parts[0];
     const LaunchCfg cfg = ex.cfg();
-    auto out = std::make_shared<Batch>();
-    out->schema = schema;
-    out->ctx = ex.ctx;
     int64_t total = 0;
     for (auto& p : parts) total += p->n_rows;
     if (total > 0xFFFFFFF0ll) fail(BHIP_EEXEC, "concatenated batch exceeds 2^32 rows");
-    out->n_rows = total;
+    auto out = new_batch(ex.ctx, schema, total);
     const int n_cols = (int)schema->fields.size();
     for (int ci = 0; ci < n_cols; ++ci) {
-        Column oc;
-        oc.dtype = schema->fields[ci].dtype;
-        oc.length = total;
         bool any_validity = false;
-        for (auto& p : parts) any_validity |= (bool)p->cols[ci].validity;
-        if (any_validity) {
-            oc.validity = make_buffer(ex, bitmap_bytes(total) + 8);
-            HIP_CHECK(hipMemsetAsync(oc.validity->ptr(), 0, bitmap_bytes(total) + 8, ex.stream));
+        int64_t bytes = 0;                  // Utf8 value bytes
+        for (auto& p : parts) {
+            any_validity |= (bool)p->cols[ci].validity;
+            bytes += p->cols[ci].data_bytes;
         }
-        if (oc.dtype == DT_UTF8) {
-            int64_t bytes = 0;
-            for (auto& p : parts) bytes += p->cols[ci].data_bytes;
-            if (bytes > 0x7FFFFFFFll) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
-            oc.data_bytes = bytes;
-            oc.data = make_buffer(ex, (size_t)bytes + 8);
-            oc.offsets = make_buffer(ex, (size_t)(total + 1) * 4);
-            if (total == 0) HIP_CHECK(hipMemsetAsync(oc.offsets->ptr(), 0, 4, ex.stream));
-        } else if (oc.dtype == DT_BOOLEAN) {
-            oc.data = make_buffer(ex, bitmap_bytes(total) + 8);
-            HIP_CHECK(hipMemsetAsync(oc.data->ptr(), 0, bitmap_bytes(total) + 8, ex.stream));
-        } else {
-            oc.data = make_buffer(ex, (size_t)total * dtype_width(oc.dtype) + 8);
-        }
+        Column oc = alloc_column(ex, schema->fields[ci].dtype, total, any_validity, bytes);
+        // copy_bits ORs into whole words
+        if (any_validity) HIP_CHECK(hipMemsetAsync(oc.validity->ptr(), 0, oc.validity->bytes(), ex.stream));
+        if (oc.dtype == DT_BOOLEAN) HIP_CHECK(hipMemsetAsync(oc.data->ptr(), 0, oc.data->bytes(), ex.stream));
         int64_t row = 0, byte = 0;
         for (auto& p : parts) {
             const Column& c = p->cols[ci];
@@ -367,8 +301,7 @@ BatchPtr concat_batches(const Exec& ex, const SchemaPtr& schema, const std::vect
                                          hipMemcpyDeviceToDevice, ex.stream));
             }
             if (any_validity)
-                TIMED_LAUNCH(ex, "copy_bits", launch_copy_bits(cfg, c.validity ? c.validity->as<uint64_t>() : nullptr, 0,
-                                           oc.validity->as<uint64_t>(), row, n));
+                TIMED_LAUNCH(ex, "copy_bits", launch_copy_bits(cfg, c.validity_words(), 0, oc.validity->as<uint64_t>(), row, n));
             row += n;
         }
         out->cols.push_back(std::move(oc));
@@ -407,7 +340,7 @@ int64_t filter_indices(const Exec& ex, const Batch& in, const ExprPtr& predicate
     uint64_t* bitmap = tmp.get<uint64_t>((size_t)(n + 63) / 64 + 1);
     uint32_t* tile_counts = tmp.get<uint32_t>((size_t)n_tiles + 1);
     ScanStatus* st = nullptr;                       // the expression VM's error flags: only when it is the VM that runs
-    if (n == 0) { indices_out = make_buffer(ex, 8); return 0; }
+    if (n == 0) { indices_out = index_buffer(ex, 0); return 0; }
     // AND of column-vs-literal comparisons over NULL-free numeric columns: the wide-load range kernel
     // (kernels_range.hip) writes the same bitmap + tile counts as the expression VM
     static const bool range_disabled = env_flag("BHIP_NO_RANGE_FILTER");
@@ -433,7 +366,7 @@ int64_t filter_indices(const Exec& ex, const Batch& in, const ExprPtr& predicate
     SopPlan rp;
     if (str_col) {
         TIMED_LAUNCH_N(ex, "utf8_eq_bitmap", n, launch_utf8_eq_bitmap(ex.cfg(), str_col->offsets->as<int32_t>(), str_col->data->ptr(),
-                                                                    str_col->validity ? str_col->validity->as<uint64_t>() : nullptr, n, str_lit, str_negate,
+                                                                    str_col->validity_words(), n, str_lit, str_negate,
                                                                     bitmap, tile_counts));
     } else if (!range_disabled && build_sop(*in.schema, predicate, {}, {}, rp) && rp.prog.n_ranges >= 1 && sop_columns_bindable(rp, in, true) &&
         lean_bindable(rp, in)) {
@@ -449,7 +382,7 @@ int64_t filter_indices(const Exec& ex, const Batch& in, const ExprPtr& predicate
     HIP_CHECK(exclusive_scan_u32_u64(ex.stream, tile_counts, n_tiles, tile_off, false, total, scan_tmp));
     const uint64_t count = read_device(ex, total);
     if (st && pb.can_raise()) check_scan_status(ex, st);       // (after the wait above: immediate; the specialised kernels raise nothing)
-    indices_out = make_buffer(ex, (size_t)count * 4 + 8);
+    indices_out = index_buffer(ex, (int64_t)count);
     if (count) TIMED_LAUNCH_N(ex, "select_indices", n, launch_select_indices(ex.cfg(), bitmap, tile_off, n, indices_out->as<uint32_t>()));
     return (int64_t)count;
 }
@@ -560,10 +493,7 @@ BatchPtr project_batch(const Exec& ex, const Batch& in, const std::vector<std::p
             return project_batch(ex, *aug, e2, schema);
         }
     }
-    auto out = std::make_shared<Batch>();
-    out->schema = schema;
-    out->ctx = in.ctx;
-    out->n_rows = in.n_rows;
+    auto out = new_batch(in.ctx, schema, in.n_rows);
     out->cols.resize(exprs.size());
     ProgramBuilder pb(*in.schema);
     std::vector<int> computed;
@@ -577,32 +507,21 @@ BatchPtr project_batch(const Exec& ex, const Batch& in, const std::vector<std::p
             computed.push_back((int)i);
         }
     }
-    if (computed.empty() || in.n_rows == 0) {
-        for (int i : computed) {
-            Column c;
-            c.dtype = schema->fields[i].dtype;
-            c.data = make_buffer(ex, 8);
-            out->cols[i] = c;
-        }
-        return out;
-    }
+    if (computed.empty()) return out;
     ScanParams P;
     pb.finish(P);
+    if (in.n_rows == 0) {           // nothing to launch over
+        for (int i : computed) out->cols[i] = alloc_column(ex, schema->fields[i].dtype, 0, P.prog.nullable);
+        return out;
+    }
     ProgramBuilder::bind(P, pb.columns(), in, pb.creates_nulls());
     ProjectOut po;
     memset(&po, 0, sizeof(po));
     const int64_t n = in.n_rows;
     for (size_t k = 0; k < computed.size(); ++k) {
-        Column c;
-        c.dtype = schema->fields[computed[k]].dtype;
-        c.length = n;
-        const size_t bytes = c.dtype == DT_BOOLEAN ? bitmap_bytes(n) : (size_t)n * dtype_width(c.dtype);
-        c.data = make_buffer(ex, bytes + 8);
+        Column c = alloc_column(ex, schema->fields[computed[k]].dtype, n, P.prog.nullable);
         po.data[k] = c.data->ptr();
-        if (P.prog.nullable) {
-            c.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-            po.validity[k] = c.validity->as<uint64_t>();
-        }
+        if (c.validity) po.validity[k] = c.validity->as<uint64_t>();
         out->cols[computed[k]] = c;
     }
     Temp tmp(ex);
@@ -648,10 +567,7 @@ StreamPtr ProjectionExec::execute(int partition, const Exec& ex) const {
                 while (BatchPtr b = child->next()) {
                     BufferPtr idx;
                     const int64_t n = filter_indices(ex, *b, pred, idx);
-                    auto nb = std::make_shared<Batch>();
-                    nb->schema = nsch;
-                    nb->ctx = b->ctx;
-                    nb->n_rows = b->n_rows;
+                    auto nb = new_batch(b->ctx, nsch, b->n_rows);
                     for (int ci : keep) nb->cols.push_back(b->cols[ci]);
                     BatchPtr sel = n == b->n_rows ? BatchPtr(nb) : take_batch(ex, *nb, idx->as<uint32_t>(), n);
                     out.push_back(project_batch(ex, *sel, exprs, sch));

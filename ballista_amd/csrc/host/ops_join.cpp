@@ -218,7 +218,7 @@ static SideKeys side_keys(const Exec& ex, const Batch& b, const std::vector<std:
     ProgramBuilder::bind(P, pb.columns(), b, pb.creates_nulls());
     k.keys = make_buffer(ex, (size_t)b.n_rows * (wide ? 8 : 16) + 16);
     k.has_sel = (bool)pred;
-    if (k.has_sel) k.sel = make_buffer(ex, bitmap_bytes(b.n_rows) + 8);
+    if (k.has_sel) k.sel = validity_buffer(ex, b.n_rows);
     if (b.n_rows == 0) return k;
     Temp tmp(ex);
     ScanStatus* st = tmp.get<ScanStatus>(1);
@@ -243,14 +243,9 @@ bool HashJoinExec::pair_keys() const {
 
 // the key column the single-key path works on: the column itself, or the two 4-byte key columns packed into one Int64 column
 static Column pack_key_pair(const Exec& ex, const Column& a, const Column& b, int64_t n) {
-    Column k;
-    k.dtype = DT_INT64;
-    k.length = n;
-    k.data = make_buffer(ex, (size_t)n * 8 + 8);
-    if (a.validity || b.validity) k.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-    TIMED_LAUNCH_N(ex, "pack_key_pair", n, launch_pack_key_pair(ex.cfg(), a.data->ptr(), b.data->ptr(), a.validity ? a.validity->as<uint64_t>() : nullptr,
-                                                                 b.validity ? b.validity->as<uint64_t>() : nullptr, n, k.data->as<uint64_t>(),
-                                                                 k.validity ? k.validity->as<uint64_t>() : nullptr));
+    Column k = alloc_column(ex, DT_INT64, n, a.validity || b.validity);
+    TIMED_LAUNCH_N(ex, "pack_key_pair", n, launch_pack_key_pair(ex.cfg(), a.data->ptr(), b.data->ptr(), a.validity_words(), b.validity_words(), n,
+                                                                 k.data->as<uint64_t>(), k.validity_words()));
     return k;
 }
 
@@ -307,10 +302,7 @@ static StreamPtr open_join_child(const PlanPtr& child, int partition, const Exec
     return StreamPtr(new LazyStream(sch, [inner, sch, src]() {
         std::vector<BatchPtr> out;
         while (BatchPtr b = inner->next()) {
-            auto nb = std::make_shared<Batch>();
-            nb->schema = sch;
-            nb->ctx = b->ctx;
-            nb->n_rows = b->n_rows;
+            auto nb = new_batch(b->ctx, sch, b->n_rows);
             for (int i : src) nb->cols.push_back(b->cols[i]);
             out.push_back(nb);
         }
@@ -341,7 +333,7 @@ static bool try_narrow(const Exec& ex, JoinBuildSide* bs, int64_t n, uint64_t ca
     // BHIP_JOIN_TABLE=1: always the CAS table (+ key-set bitmap), the round-1 design — the A/B partner of the rank map
     static const bool force_table = env_flag("BHIP_JOIN_TABLE");
     // optimistic: the build side of a key join is almost always unique
-    const uint64_t* ksel = kc.validity ? kc.validity->as<uint64_t>() : nullptr;
+    const uint64_t* ksel = kc.validity_words();
     const uint64_t bias = nkw == 4 ? 0x80000000ull : (1ull << 63);
     memset(&bs->ntable, 0, sizeof(bs->ntable));
     bs->narrow_width = nkw;
@@ -353,7 +345,7 @@ static bool try_narrow(const Exec& ex, JoinBuildSide* bs, int64_t n, uint64_t ca
     // three reads; anything else — a wider span, duplicate keys — carries on below as if nothing had happened
     static const bool no_tiny = env_flag("BHIP_NO_TINY_BUILD");
     if (!no_tiny && !force_table && n >= 1 && n <= tiny_rank_build_max_rows()) {
-        BufferPtr rp = make_buffer(ex, tiny_rank_build_map_words() * 8 + 16), pm = make_buffer(ex, (size_t)n * 4 + 8);
+        BufferPtr rp = make_buffer(ex, tiny_rank_build_map_words() * 8 + 16), pm = index_buffer(ex, n);
         uint64_t* out = tmp.get<uint64_t>(3);
         TIMED_LAUNCH(ex, "tiny_rank_build", launch_tiny_rank_build(ex.cfg(), kc.data->ptr(), nkw, ksel, (uint32_t)n, rp->as<uint64_t>(), pm->as<uint32_t>(), out));
         const Stats3 got = read_device(ex, reinterpret_cast<const Stats3*>(out));
@@ -411,7 +403,7 @@ static bool try_narrow(const Exec& ex, JoinBuildSide* bs, int64_t n, uint64_t ca
         if (!sorted) {
             dup = read_device(ex, bs->dup->as<uint32_t>()) != 0;           // duplicates would collide in perm[]
             if (!dup) {
-                bs->rperm = make_buffer(ex, (size_t)n * 4 + 8);
+                bs->rperm = index_buffer(ex, n);
                 TIMED_LAUNCH_N(ex, "rank_perm", n, launch_rank_perm(ex.cfg(), kc.data->ptr(), nkw, ksel, (uint32_t)n, kmin, bs->rpack->as<uint64_t>(),
                                                                    bs->rperm->as<uint32_t>()));
             }
@@ -469,7 +461,7 @@ static void build_general_table(const Exec& ex, JoinBuildSide* bs, const std::ve
     bs->wide = wide;
     bs->owner = make_buffer(ex, cap * 8);
     bs->head = make_buffer(ex, cap * 4);
-    bs->next = make_buffer(ex, (size_t)(n + 1) * 4);
+    bs->next = make_buffer(ex, (size_t)(n + 1) * 4);            // (the table's chain links: scratch, no column's offsets)
     HIP_CHECK(hipMemsetAsync(bs->owner->ptr(), 0, cap * 8, ex.stream));
     HIP_CHECK(hipMemsetAsync(bs->head->ptr(), 0, cap * 4, ex.stream));
     bs->table.owner = bs->owner->as<uint64_t>();
@@ -540,8 +532,8 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
             // the second columns agree (join_filter_probe_kernel<RESID>).  Second: both columns packed into one 8-byte key.
             Column first = c0;
             if (c1.validity) {                         // a build row with a NULL in either part matches nothing
-                first.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-                HIP_CHECK(launch_and_bitmaps(ex.cfg(), c0.validity ? c0.validity->as<uint64_t>() : nullptr, c1.validity->as<uint64_t>(), n, first.validity->as<uint64_t>()));
+                first.validity = validity_buffer(ex, n);
+                HIP_CHECK(launch_and_bitmaps(ex.cfg(), c0.validity_words(), c1.validity->as<uint64_t>(), n, first.validity->as<uint64_t>()));
             }
             if (try_narrow(ex, bs.get(), n, cap, first, 4)) {
                 bs->key_holder = first;
@@ -744,10 +736,7 @@ struct JoinExec::Probe {
     // (lbuf / rbuf: the buffers that own lidx / ridx, when the caller has them — view columns keep them instead of a copy)
     void emit(const ProbeOut& o, const uint32_t* lidx, const uint32_t* ridx, int64_t n_out, const BufferPtr& lbuf = nullptr, const BufferPtr& rbuf = nullptr) {
         const Schema& os = *J.schema_;
-        auto b = std::make_shared<Batch>();
-        b->schema = J.schema_;
-        b->ctx = ex.ctx;
-        b->n_rows = n_out;
+        auto b = new_batch(ex.ctx, J.schema_, n_out);
         b->cols.resize(os.fields.size());
         for (size_t i = 0; i < b->cols.size(); ++i) { b->cols[i].dtype = os.fields[i].dtype; b->cols[i].length = n_out; }
         // [0]: gathered now; [1]: handed on as views (the parent asked for them that way; a column that arrives as a view is
@@ -783,7 +772,7 @@ struct JoinExec::Probe {
     // an index vector of n entries: scratch of this probe, or (keep) a buffer of its own
     uint32_t* index_vector(Temp& tmp, bool keep, uint64_t n, BufferPtr& own) {
         if (!keep) return tmp.get<uint32_t>((size_t)n);
-        own = make_buffer(ex, (size_t)n * 4 + 8);
+        own = index_buffer(ex, (int64_t)n);
         return own->as<uint32_t>();
     }
 
@@ -901,10 +890,8 @@ struct JoinExec::Probe {
             if (fc.left) { lc.push_back(&L.cols[fc.index]); lpos.push_back(k); }
             else { rc.push_back(&o.src->cols[o.fmap ? (*o.fmap)[k] : fc.index]); rpos.push_back(k); }
         }
-        auto fb = std::make_shared<Batch>();
         auto fs = std::make_shared<Schema>();
-        fb->ctx = ex.ctx;
-        fb->n_rows = (int64_t)n_cand;
+        auto fb = new_batch(ex.ctx, fs, (int64_t)n_cand);
         fb->cols.resize(J.filter_cols_.size());
         if (!lc.empty()) {
             auto got = take_columns(ex, lc, lidx, (int64_t)n_cand, false);
@@ -919,7 +906,6 @@ struct JoinExec::Probe {
             f.nullable = f.nullable || (bool)fb->cols[k].validity;
             fs->fields.push_back(f);
         }
-        fb->schema = fs;
         return filter_indices(ex, *fb, J.filter_, sel);
     }
 
@@ -988,7 +974,7 @@ struct JoinExec::Probe {
         char form[JOIN_PROBE_FORM_LEN];
         TIMED_LAUNCH_B(ex, direct ? "join_rank_probe" : "join_filter_probe", n, (uint64_t)n * (uint64_t)(bs->narrow_width + 4 * F.n) + (uint64_t)n / 8,
                        launch_join_filter_probe(cfg, bs->ntable, F, kc.data->ptr(), bs->narrow_width,
-                                                kc.validity ? kc.validity->as<uint64_t>() : nullptr, (uint32_t)n, right_outer, s.bitmap,
+                                                kc.validity_words(), (uint32_t)n, right_outer, s.bitmap,
                                                 s.tile_counts, s.staging, matched_bits(),
                                                 resid ? resid->data->as<uint32_t>() : nullptr, s.staging_rows, form));
         ex.ctx->set_join_probe_form(form);
@@ -1013,8 +999,8 @@ struct JoinExec::Probe {
         } else {
             Column first = keys[0];
             if (keys[1].validity) {                    // a NULL in either part never matches
-                first.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-                HIP_CHECK(launch_and_bitmaps(cfg, keys[0].validity ? keys[0].validity->as<uint64_t>() : nullptr, keys[1].validity->as<uint64_t>(), n, first.validity->as<uint64_t>()));
+                first.validity = validity_buffer(ex, n);
+                HIP_CHECK(launch_and_bitmaps(cfg, keys[0].validity_words(), keys[1].validity->as<uint64_t>(), n, first.validity->as<uint64_t>()));
             }
             probe_narrow(n, F, first, &keys[1], o);
         }

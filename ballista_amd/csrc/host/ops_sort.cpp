@@ -28,7 +28,7 @@ void radix_sort_pairs(const Exec& ex, BufferPtr& keys, BufferPtr& perm, int64_t 
     HIP_CHECK(radix_key_diff(cfg, keys->as<uint64_t>(), n, diff_dev));
     const uint64_t diff = read_device(ex, diff_dev);
     if (diff == 0) return;   // all keys equal: already in order
-    BufferPtr keys2 = make_buffer(ex, (size_t)n * 8 + 8), perm2 = make_buffer(ex, (size_t)n * 4 + 8);
+    BufferPtr keys2 = make_buffer(ex, (size_t)n * 8 + 8), perm2 = index_buffer(ex, n);
     void* pass_tmp = tmp.get<uint8_t>(radix_sort_temp_bytes(n));
     for (int byte = 0; byte < 8; ++byte) {
         if (((diff >> (8 * byte)) & 0xFF) == 0) continue;   // this byte is the same in every key
@@ -94,32 +94,15 @@ StreamPtr SortExec::execute(int partition, const Exec& ex) const {
                 A.desc[k] = sd.descending ? 1 : 0;
                 A.nulls_first[k] = sd.nulls_first ? 1 : 0;
             }
-            auto out = std::make_shared<Batch>();
-            out->schema = in->schema;
-            out->ctx = in->ctx;
-            out->n_rows = n;
+            auto out = new_batch(in->ctx, in->schema, n);
             for (size_t ci = 0; ci < in->cols.size(); ++ci) {
                 const Column& c = in->cols[ci];
-                Column o;
-                o.dtype = c.dtype;
-                o.length = n;
+                Column o = alloc_column(ex, c.dtype, n, (bool)c.validity, c.data_bytes);      // a permutation keeps the value bytes
                 A.col[ci] = c.ref();
-                if (c.dtype == DT_UTF8) {
-                    o.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
-                    o.data = make_buffer(ex, (size_t)c.data_bytes + 8);
-                    o.data_bytes = c.data_bytes;               // a permutation keeps the value bytes
-                    A.out_offsets[ci] = o.offsets->as<int32_t>();
-                } else if (c.dtype == DT_BOOLEAN) {
-                    o.data = make_buffer(ex, bitmap_bytes(n) + 8);
-                } else {
-                    A.width[ci] = (uint8_t)dtype_width(c.dtype);
-                    o.data = make_buffer(ex, (size_t)n * dtype_width(c.dtype) + 8);
-                }
+                if (c.dtype == DT_UTF8) A.out_offsets[ci] = o.offsets->as<int32_t>();
+                else if (c.dtype != DT_BOOLEAN) A.width[ci] = (uint8_t)dtype_width(c.dtype);
                 A.out_data[ci] = o.data->ptr();
-                if (c.validity) {
-                    o.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-                    A.out_validity[ci] = o.validity->as<uint64_t>();
-                }
+                if (o.validity) A.out_validity[ci] = o.validity->as<uint64_t>();
                 out->cols.push_back(std::move(o));
             }
             TIMED_LAUNCH(ex, "rowsort", launch_rowsort(cfg, A));
@@ -186,7 +169,7 @@ BatchPtr first_k(const Exec& ex, const BatchPtr& in, const std::vector<SortDesc>
             void* scan_tmp = tmp.get<uint8_t>(exclusive_scan_temp_bytes(n_tiles));
             TIMED_LAUNCH_N(ex, "topk_mark", n, launch_topk_mark(cfg, key, n, state, bitmap, tile_counts));
             HIP_CHECK(exclusive_scan_u32_u64(ex.stream, tile_counts, n_tiles, tile_off, false, nullptr, scan_tmp));
-            BufferPtr idx = make_buffer(ex, (size_t)n_cand * 4 + 8);
+            BufferPtr idx = index_buffer(ex, n_cand);
             TIMED_LAUNCH_N(ex, "select_indices", n, launch_select_indices(cfg, bitmap, tile_off, n, idx->as<uint32_t>()));
             BatchPtr cand = take_batch(ex, *in, idx->as<uint32_t>(), n_cand);
             form = std::max(form, (int)FORM_TOPK);
@@ -257,7 +240,7 @@ BufferPtr sort_permutation(const Exec& ex, const Batch& batch, const std::vector
             ++K.n_words;
         }
         if (fits) {
-            BufferPtr perm = make_buffer(ex, (size_t)n * 4 + 8);
+            BufferPtr perm = index_buffer(ex, n);
             Temp tmp(ex);
             void* temp = tmp.get<uint8_t>(bucket_sort_temp_bytes(n, K.n_words));
             uint32_t* status_dev = nullptr;
@@ -267,7 +250,7 @@ BufferPtr sort_permutation(const Exec& ex, const Batch& batch, const std::vector
         }
     }
     {
-        BufferPtr perm = make_buffer(ex, (size_t)n * 4 + 8);
+        BufferPtr perm = index_buffer(ex, n);
         BufferPtr keys = make_buffer(ex, (size_t)n * 8 + 8);
         TIMED_LAUNCH(ex, "iota_u32", launch_iota_u32(cfg, perm->as<uint32_t>(), n, 0));
         for (size_t k = exprs.size(); k-- > 0;) {
@@ -326,7 +309,7 @@ std::vector<BatchPtr> hash_partition_batch(const Exec& ex, const BatchPtr& in, c
             std::vector<BufferPtr> whole;
             for (auto& c : in->cols) {
                 const int w = dtype_width(c.dtype);
-                whole.push_back(make_buffer(ex, (size_t)n * w + 8));
+                whole.push_back(alloc_column(ex, c.dtype, n, false).data);
                 tm.src[tm.n] = c.data->ptr(); tm.dst[tm.n] = whole.back()->ptr(); tm.width[tm.n] = w;
                 ++tm.n;
             }
@@ -334,10 +317,7 @@ std::vector<BatchPtr> hash_partition_batch(const Exec& ex, const BatchPtr& in, c
             void* temp = tmp.get<uint8_t>(partition_scatter_temp_bytes(n));
             HIP_CHECK(partition_scatter(cfg, kc->data->ptr(), kw, n, (uint32_t)n_parts, tm, temp, first.data()));
             for (int p = 0; p < n_parts; ++p) {
-                auto b = std::make_shared<Batch>();
-                b->schema = in->schema;
-                b->ctx = in->ctx;
-                b->n_rows = (int64_t)first[p + 1] - (int64_t)first[p];
+                auto b = new_batch(in->ctx, in->schema, (int64_t)first[p + 1] - (int64_t)first[p]);
                 for (size_t ci = 0; ci < in->cols.size(); ++ci) {
                     const int w = dtype_width(in->cols[ci].dtype);
                     Column c;
@@ -353,7 +333,7 @@ std::vector<BatchPtr> hash_partition_batch(const Exec& ex, const BatchPtr& in, c
             return out;
         }
     }
-    BufferPtr perm = make_buffer(ex, (size_t)n * 4 + 8);
+    BufferPtr perm = index_buffer(ex, n);
     if (n > 0) {
         ProgramBuilder pb(*in->schema);
         pb.set_hash_only();

@@ -197,18 +197,13 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
         return frame == BHIP_FRAME_PARTITION ? part_end : peer_end;
     };
 
-    auto out = std::make_shared<Batch>();
-    out->schema = schema_;
-    out->ctx = sorted->ctx;
-    out->n_rows = n;
+    auto out = new_batch(sorted->ctx, schema_, n);
     out->cols = sorted->cols;
     for (const WindowFnDesc& f : fns_) {
         Column o;
-        o.length = n;
         if (is_ranking(f.fn)) {
             need_forward();
-            o.dtype = DT_UINT64;
-            o.data = make_buffer(ex, (size_t)n * 8 + 8);
+            o = alloc_column(ex, DT_UINT64, n, false);
             const int kind = f.fn == BHIP_WIN_ROW_NUMBER ? WINDOW_ROW_NUMBER : f.fn == BHIP_WIN_RANK ? WINDOW_RANK : WINDOW_DENSE_RANK;
             TIMED_LAUNCH_N(ex, "window_rank", n, launch_window_rank(cfg, kind, part_start, peer_start, peers_to, n, o.data->as<uint64_t>()));
         } else if (!is_aggregate(f.fn)) {
@@ -221,7 +216,7 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
                 case BHIP_WIN_FIRST_VALUE: need_forward(); kind = WINDOW_FIRST; break;
                 default: fe = frame_end(f.frame); kind = WINDOW_LAST; break;
             }
-            BufferPtr idx = make_buffer(ex, (size_t)n * 4 + 8);
+            BufferPtr idx = index_buffer(ex, n);
             TIMED_LAUNCH_N(ex, "window_index", n, launch_window_index(cfg, kind, f.offset, part_start, part_end, fe, n, idx->as<uint32_t>()));
             const Column arg = evaluate_column(ex, *sorted, f.arg);
             o = f.fn == BHIP_WIN_LAG || f.fn == BHIP_WIN_LEAD ? take_column_nullable(ex, arg, idx->as<uint32_t>(), n)
@@ -233,13 +228,13 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
             if (!count_rows) arg = evaluate_column(ex, *sorted, f.arg);
             ColumnRef ref = arg.ref();
             const int t = count_rows ? DT_UINT8 : arg.dtype;
-            int op, kind = WINDOW_FINISH_VALUE;
+            int op, kind = WINDOW_FINISH_VALUE, dtype;
             switch (f.fn) {
-                case BHIP_WIN_SUM: op = dt_is_float(t) ? WINDOW_OP_ADD_F64 : WINDOW_OP_ADD_I64; o.dtype = dt_is_float(t) ? DT_FLOAT64 : dt_is_unsigned(t) ? DT_UINT64 : DT_INT64; break;
-                case BHIP_WIN_AVG: op = WINDOW_OP_ADD_F64; kind = WINDOW_FINISH_AVG; o.dtype = DT_FLOAT64; break;
-                case BHIP_WIN_COUNT: op = WINDOW_OP_ADD_I64; kind = WINDOW_FINISH_COUNT; o.dtype = DT_UINT64; ref.data = nullptr; break;
-                case BHIP_WIN_MIN: op = dt_is_float(t) ? WINDOW_OP_MIN_F64 : dt_is_unsigned(t) ? WINDOW_OP_MIN_U64 : WINDOW_OP_MIN_I64; o.dtype = t; break;
-                default: op = dt_is_float(t) ? WINDOW_OP_MAX_F64 : dt_is_unsigned(t) ? WINDOW_OP_MAX_U64 : WINDOW_OP_MAX_I64; o.dtype = t; break;
+                case BHIP_WIN_SUM: op = dt_is_float(t) ? WINDOW_OP_ADD_F64 : WINDOW_OP_ADD_I64; dtype = dt_is_float(t) ? DT_FLOAT64 : dt_is_unsigned(t) ? DT_UINT64 : DT_INT64; break;
+                case BHIP_WIN_AVG: op = WINDOW_OP_ADD_F64; kind = WINDOW_FINISH_AVG; dtype = DT_FLOAT64; break;
+                case BHIP_WIN_COUNT: op = WINDOW_OP_ADD_I64; kind = WINDOW_FINISH_COUNT; dtype = DT_UINT64; ref.data = nullptr; break;
+                case BHIP_WIN_MIN: op = dt_is_float(t) ? WINDOW_OP_MIN_F64 : dt_is_unsigned(t) ? WINDOW_OP_MIN_U64 : WINDOW_OP_MIN_I64; dtype = t; break;
+                default: op = dt_is_float(t) ? WINDOW_OP_MAX_F64 : dt_is_unsigned(t) ? WINDOW_OP_MAX_U64 : WINDOW_OP_MAX_I64; dtype = t; break;
             }
             if (kind != WINDOW_FINISH_COUNT && !ref.data) fail(BHIP_EEXEC, "WindowAggExec: an argument column without buffers");
             uint64_t* run_value = tmp.get<uint64_t>((size_t)n);
@@ -248,10 +243,9 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
             TIMED_LAUNCH_N(ex, "window_scan_summaries", n, launch_window_scan_summaries(cfg, op, n, scan_temp));
             TIMED_LAUNCH_N(ex, "window_scan_apply", n, launch_window_scan_apply(cfg, op, ref, part_flags, n, scan_temp, run_value, run_count));
             const uint32_t* fe = frame_end(f.frame);
-            o.data = make_buffer(ex, (size_t)n * dtype_width(o.dtype) + 8);
-            if (kind != WINDOW_FINISH_COUNT) o.validity = make_buffer(ex, bitmap_bytes(n) + 8);
+            o = alloc_column(ex, dtype, n, kind != WINDOW_FINISH_COUNT);
             TIMED_LAUNCH_N(ex, "window_finish", n,
-                           launch_window_finish(cfg, kind, o.dtype, run_value, run_count, fe, n, o.data->ptr(), o.validity ? o.validity->as<uint64_t>() : nullptr));
+                           launch_window_finish(cfg, kind, o.dtype, run_value, run_count, fe, n, o.data->ptr(), o.validity_words()));
         }
         out->cols.push_back(std::move(o));
     }

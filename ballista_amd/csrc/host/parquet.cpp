@@ -136,11 +136,8 @@ Column upload_chunk(const Exec& ex, const PqColumn& pc, const HostChunk& hc, std
     // the bit width travels with each run), ONE expansion, ONE gather — one host wait per string column chunk — and PLAIN pages are
     // copied straight to their rows of the column.
     if (hc.staged == pq::STAGED_FIXED) {                      // the host walk left ONE buffer: one copy
-        Column c;
-        c.dtype = pc.dtype;
-        c.length = hc.rows;
         const double t0 = trace_now();
-        c.data = make_buffer(ex, hc.staged_bytes.size() + 16);
+        Column c = alloc_column(ex, pc.dtype, hc.rows, false);           // staged_bytes: `width` bytes per row
         if (!hc.staged_bytes.empty()) HIP_CHECK(hipMemcpyAsync(c.data->ptr(), hc.staged_bytes.data(), hc.staged_bytes.size(), hipMemcpyHostToDevice, ex.stream));
         g_trace.copies += trace_now() - t0;
         return c;
@@ -174,11 +171,8 @@ Column upload_chunk(const Exec& ex, const PqColumn& pc, const HostChunk& hc, std
     }
     static const bool per_page = env_flag("BHIP_PARQUET_PER_PAGE");           // A/B: the page-at-a-time path
     if (!per_page && !any_nulls && hc.pages.size() > 1 && all_fixed && width) {
-        Column c;
-        c.dtype = pc.dtype;
-        c.length = rows_total;
         const double t0 = trace_now();
-        c.data = make_buffer(ex, width * (size_t)rows_total + 16);
+        Column c = alloc_column(ex, pc.dtype, rows_total, false);
         int64_t row = 0;
         for (const HostPage& pg : hc.pages) {
             if (pg.n) HIP_CHECK(hipMemcpyAsync(c.data->as<uint8_t>() + width * (size_t)row, pg.bytes.data(), width * (size_t)pg.n, hipMemcpyHostToDevice, ex.stream));
@@ -263,7 +257,7 @@ Column upload_chunk(const Exec& ex, const PqColumn& pc, const HostChunk& hc, std
         } else {
             BufferPtr dense = upload(ex, pg.bytes.data(), width * (size_t)n_valid);
             if (pg.has_nulls) {
-                c.data = make_buffer(ex, width * (size_t)n + 16);
+                c.data = alloc_column(ex, pc.dtype, n, false).data;
                 keep.push_back(dense);
                 TIMED_LAUNCH_N(ex, "pq_scatter_valid", n, launch_pq_scatter_valid(cfg, dvalid->as<uint64_t>(), dprefix->as<uint32_t>(), dense->ptr(), (int)width, n,
                                                                                  c.data->ptr(), 0));
@@ -279,10 +273,7 @@ Column upload_chunk(const Exec& ex, const PqColumn& pc, const HostChunk& hc, std
     s->fields.push_back(Field{pc.name, pc.dtype, optional});
     std::vector<BatchPtr> parts;
     for (auto& c : pieces) {
-        auto b = std::make_shared<Batch>();
-        b->schema = s;
-        b->ctx = ex.ctx;
-        b->n_rows = c.length;
+        auto b = new_batch(ex.ctx, s, c.length);
         b->cols.push_back(c);
         parts.push_back(b);
     }
@@ -410,10 +401,7 @@ public:
                 inflight.pop_front();
                 if (started < units.size()) inflight.push_back(start(units[started++]));
                 const Unit& u = units[k];
-                auto b = std::make_shared<Batch>();
-                b->schema = self->schema_;
-                b->ctx = ex.ctx;
-                b->n_rows = u.g->num_rows;
+                auto b = new_batch(ex.ctx, self->schema_, u.g->num_rows);
                 std::vector<HostChunk> held;                 // host bytes the queued copies read from
                 std::vector<std::shared_ptr<HostVec<PqRun>>> held_runs;
                 std::vector<BufferPtr> keep;                 // device scratch that must outlive the kernels of this row group
@@ -428,9 +416,8 @@ public:
                         Column col = upload_chunk(ex, pc, held.back(), keep, held_runs);
                         t_issue += now() - t1;
                         if (pc.out_dtype != pc.dtype) {                                   // Int32 values of an INT_8 .. UINT_16 column
-                            Column narrow = col;
-                            narrow.dtype = pc.out_dtype;
-                            narrow.data = make_buffer(ex, (size_t)col.length * dtype_width(narrow.dtype) + 8);
+                            Column narrow = alloc_column(ex, pc.out_dtype, col.length, false);
+                            narrow.validity = col.validity;
                             TIMED_LAUNCH_N(ex, "narrow_i32", col.length, launch_narrow_i32(ex.cfg(), col.data->as<int32_t>(), col.length, dtype_width(narrow.dtype), narrow.data->ptr()));
                             col = narrow;
                         }

@@ -436,19 +436,15 @@ std::vector<Column> take_columns(const Exec& ex, const std::vector<const Column*
 // view columns (core.hpp Column::view_base) as ordinary columns
 Column materialize_column(const Exec& ex, const Column& c);
 BatchPtr materialize_batch(const Exec& ex, const BatchPtr& b);
-// a batch of `schema` with zero rows (a child that yielded none); a Utf8 column's offsets are the one zero
+// a batch of `schema` with zero rows (a child that yielded none)
 BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema);
 // n NULLs of the given type
 Column null_column(const Exec& ex, int dtype, int64_t n);
-// a fixed-width column of n rows that a kernel is about to fill: the value buffer, and a validity bitmap where asked for
-Column fixed_column(const Exec& ex, int dtype, int64_t n, bool with_validity);
-// A Utf8 column computed row by row: per-row lengths -> offsets (one scan) -> data buffer -> bytes.  The sum of the lengths stays on
+// A Utf8 column computed row by row: per-row lengths -> offsets (one scan) -> data buffer (core.hpp utf8_alloc_data) -> bytes.  The sum of the lengths stays on
 // the device (`dev`) until somebody needs it; `host` remembers it once it was read (-1 before), so that nobody waits for it twice.
 struct Utf8Total { uint64_t* dev = nullptr; int64_t host = -1; };
 Column utf8_from_lengths(const Exec& ex, Temp& tmp, uint32_t* lengths, int64_t n, Utf8Total& total);
-// the data buffer, of `bytes` value bytes (BHIP_EEXEC above 2 GiB: the offsets are Int32) ...
-void utf8_alloc_data(const Exec& ex, Column& out, int64_t bytes);
-// ... or of at most `bound` bytes: above 64 MiB the true total is read first and takes the bound's place
+// the data buffer, of at most `bound` bytes: above 64 MiB the true total is read first and takes the bound's place
 void utf8_size_data(const Exec& ex, Column& out, int64_t bound, Utf8Total& total);
 // out.data_bytes = the total: ONE host read, which brings the evaluator's status word along where there is one (returned, else 0),
 // and none where the total is known already and there is no status word

@@ -235,7 +235,7 @@ void bind_sop(SopPlan& plan, const Batch& b) {
         SopColumn& sc = plan.prog.cols[i];
         sc.data = c.data ? c.data->ptr() : nullptr;
         sc.offsets = c.offsets ? c.offsets->as<int32_t>() : nullptr;
-        sc.validity = c.validity ? c.validity->as<uint64_t>() : nullptr;
+        sc.validity = c.validity_words();
         sc.dtype = c.dtype;
         sc.data_bytes = (int32_t)c.data_bytes;
         sc.width = c.utf8_width(b.n_rows);

@@ -124,9 +124,7 @@ TextParsed parse_text_slab(const Exec& ex, const TextScanSpec& spec, const TextS
     const int64_t n_bytes = slab.n_bytes;
     const size_t n_slots = spec.dtype.size();
 
-    auto batch = std::make_shared<Batch>();
-    batch->ctx = ex.ctx;
-    batch->schema = spec.schema;
+    auto batch = new_batch(ex.ctx, spec.schema, 0);           // n_rows: once the records are counted
 
     Temp tmp(ex);
 
@@ -197,21 +195,15 @@ TextParsed parse_text_slab(const Exec& ex, const TextScanSpec& spec, const TextS
     TextPlan plan = spec.plan;
     for (size_t s = 0; s < n_slots; ++s) {
         const int dt = spec.dtype[s];
-        Column c;
-        c.dtype = dt;
-        c.length = n_rows;
+        // a Utf8 column: offsets now, the bytes once the lengths are summed (below)
+        Column c = alloc_column(ex, dt, n_rows, dt != DT_UTF8 && csv && spec.nullable[s], /*utf8_data_bytes: later*/ -1);
         if (dt == DT_UTF8) {
             plan.str_start[s] = tmp.get<uint32_t>((size_t)n_rows + 1);
             plan.str_len[s] = tmp.get<uint32_t>((size_t)n_rows + 1);
             if (quoted) plan.str_esc[s] = tmp.get<uint64_t>(bitmap_bytes(n_rows) / 8 + 1);
-            c.offsets = make_buffer(ex, (size_t)(n_rows + 1) * 4);
         } else {
-            c.data = make_buffer(ex, (dt == DT_BOOLEAN ? bitmap_bytes(n_rows) : (size_t)n_rows * dtype_width(dt)) + 8);
             plan.data[s] = c.data->ptr();
-            if (csv && spec.nullable[s]) {
-                c.validity = make_buffer(ex, bitmap_bytes(n_rows) + 8);
-                plan.validity[s] = c.validity->as<uint64_t>();
-            }
+            plan.validity[s] = c.validity_words();
         }
         batch->cols.push_back(std::move(c));
     }
@@ -243,10 +235,9 @@ TextParsed parse_text_slab(const Exec& ex, const TextScanSpec& spec, const TextS
     for (size_t s = 0; s < n_slots; ++s)
         if (!(host_flags[1] >> s & 1u)) batch->cols[s].validity.reset();        // no NULL occurred: no validity buffer
     for (size_t s : utf8) {
-        if (host_totals[s] > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Utf8 column exceeds 2 GiB of value bytes");
         Column& c = batch->cols[s];
+        utf8_alloc_data(ex, c, (int64_t)host_totals[s]);
         c.data_bytes = (int64_t)host_totals[s];
-        c.data = make_buffer(ex, (size_t)c.data_bytes + 8);
         const int32_t* offsets = c.offsets->as<int32_t>();
         HIP_CHECK(launch_text_copy_strings(cfg, text, plan.str_start[s], plan.str_len[s], plan.str_esc[s], offsets, n_rows, c.data->as<uint8_t>()));
     }

@@ -105,23 +105,12 @@ void validate_cast_parse(const ExprPtr& e, const Schema& in, const ScalarFn&) {
 // ---- evaluators ----------------------------------------------------------------------------------------------------------------------
 
 Column eval_literal(const Exec& ex, const Expr& e, int64_t n) {
-    Column out;
-    out.dtype = DT_UTF8;
-    out.length = n;
-    out.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
-    if (e.is_null) {
-        HIP_CHECK(hipMemsetAsync(out.offsets->ptr(), 0, (size_t)(n + 1) * 4, ex.stream));
-        out.data = make_buffer(ex, 8);
-        out.validity = make_buffer(ex, bitmap_bytes(n) + 8);
-        HIP_CHECK(hipMemsetAsync(out.validity->ptr(), 0, bitmap_bytes(n) + 8, ex.stream));
-        return out;
-    }
+    if (e.is_null) return null_column(ex, DT_UTF8, n);
     if (e.name.size() > (size_t)STR_LITERAL_MAX) fail(BHIP_ENOTIMPL, "Utf8 literal longer than " + std::to_string(STR_LITERAL_MAX) + " bytes as a column value");
     StrLiteral lit;
     lit.len = (int32_t)e.name.size();
     memcpy(lit.bytes, e.name.data(), e.name.size());
-    out.data_bytes = n * lit.len;
-    utf8_alloc_data(ex, out, out.data_bytes);
+    Column out = alloc_column(ex, DT_UTF8, n, false, n * lit.len);
     TIMED_LAUNCH_N(ex, "str_broadcast", n, launch_str_broadcast(ex.cfg(), lit, n, out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
     out.offsets->set_uniform_width(n, lit.len);      // n copies of one value (an empty literal: width unknown, as for every 0)
     return out;
@@ -153,13 +142,8 @@ Column eval_sha(const Exec& ex, const Batch& in, const ExprPtr& e, const ScalarF
     const Column arg = eval_utf8(ex, in, e->args[0]);
     const int64_t n = in.n_rows;
     if ((uint64_t)n * (bits / 8) > 0x7FFFFFFFull) fail(BHIP_EEXEC, "Binary column exceeds 2 GiB of value bytes");
-    Column out;
-    out.dtype = DT_UTF8;
-    out.length = n;
-    out.offsets = make_buffer(ex, (size_t)(n + 1) * 4);
-    out.data_bytes = n * (bits / 8);
-    out.data = make_buffer(ex, (size_t)out.data_bytes + 8);
-    if (arg.validity) HIP_CHECK(hipMemsetAsync(out.data->ptr(), 0, (size_t)out.data_bytes + 8, ex.stream));    // a NULL row's bytes stay defined
+    Column out = alloc_column(ex, DT_UTF8, n, false, n * (bits / 8));
+    if (arg.validity) HIP_CHECK(hipMemsetAsync(out.data->ptr(), 0, out.data->bytes(), ex.stream));    // a NULL row's bytes stay defined
     TIMED_LAUNCH_N(ex, "sha2", n, launch_sha2(ex.cfg(), bits, arg.ref(), n, out.offsets->as<int32_t>(), out.data->as<uint8_t>()));
     out.offsets->set_uniform_width(n, bits / 8);     // a digest per row, a NULL row's (zeroed) one included
     out.validity = arg.validity;
@@ -193,7 +177,7 @@ Column eval_case(const Exec& ex, const Batch& in, const ExprPtr& ep, const Scala
     for (size_t i = 0; i < vals.size(); ++i) { A.val[i] = vals[i].ref(); bound += vals[i].data_bytes; }
     Temp tmp(ex);
     uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
-    BufferPtr validity = make_buffer(ex, bitmap_bytes(n) + 8);
+    BufferPtr validity = validity_buffer(ex, n);
     TIMED_LAUNCH_N(ex, "str_select_lengths", n, launch_str_select_lengths(ex.cfg(), A, n, lengths, validity->as<uint64_t>()));
     Utf8Total total;
     Column out = utf8_from_lengths(ex, tmp, lengths, n, total);
@@ -226,7 +210,7 @@ Column eval_cast_format(const Exec& ex, const Batch& in, const ExprPtr& e, const
     Temp tmp(ex);
     uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
     // only a Date32 can have no text (outside 0000 .. 9999): every other result is NULL exactly where its argument is
-    BufferPtr validity = from == DT_DATE32 ? make_buffer(ex, bitmap_bytes(n) + 8) : nullptr;
+    BufferPtr validity = from == DT_DATE32 ? validity_buffer(ex, n) : nullptr;
     TIMED_LAUNCH_N(ex, "cast_format_lengths", n, launch_cast_format_lengths(ex.cfg(), cr, n, lengths, validity ? validity->as<uint64_t>() : nullptr));
     Utf8Total total;
     Column out = utf8_from_lengths(ex, tmp, lengths, n, total);
@@ -243,7 +227,7 @@ Column eval_cast_parse(const Exec& ex, const Batch& in, const ExprPtr& e, const 
     if (!cast_parse_supported(to)) fail(BHIP_ENOTIMPL, cast_name(DT_UTF8, to));
     const Column arg = eval_utf8(ex, in, e->args[0]);
     const int64_t n = in.n_rows;
-    Column out = fixed_column(ex, to, n, true);
+    Column out = alloc_column(ex, to, n, true);
     Temp tmp(ex);
     uint32_t* status = tmp.get<uint32_t>(1);
     const bool can_decline = dt_is_float(to);
@@ -288,7 +272,7 @@ Column eval_concat(const Exec& ex, const Batch& in, const ExprPtr& ep, const Sca
     }
     Temp tmp(ex);
     uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
-    BufferPtr validity = any_validity ? make_buffer(ex, bitmap_bytes(n) + 8) : nullptr;
+    BufferPtr validity = any_validity ? validity_buffer(ex, n) : nullptr;
     TIMED_LAUNCH_N(ex, "concat_lengths", n, launch_concat_lengths(ex.cfg(), A, n, lengths, validity ? validity->as<uint64_t>() : nullptr));
     Utf8Total total;
     Column out = utf8_from_lengths(ex, tmp, lengths, n, total);
@@ -304,7 +288,7 @@ Column eval_concat(const Exec& ex, const Batch& in, const ExprPtr& ep, const Sca
 Column eval_to_timestamp(const Exec& ex, const Batch& in, const ExprPtr& e, const ScalarFn&) {
     const Column arg = eval_utf8(ex, in, e->args[0]);
     const int64_t n = in.n_rows;
-    Column out = fixed_column(ex, DT_TIMESTAMP_NS, n, false);
+    Column out = alloc_column(ex, DT_TIMESTAMP_NS, n, false);
     out.validity = arg.validity;
     Temp tmp(ex);
     uint32_t* status = tmp.get<uint32_t>(1);
@@ -321,7 +305,7 @@ Column eval_date_trunc(const Exec& ex, const Batch& in, const ExprPtr& e, const 
     const int gran = f.check(*e, *in.schema);
     const Column arg = materialize_column(ex, evaluate_column(ex, in, e->args[1]));
     const int64_t n = in.n_rows;
-    Column out = fixed_column(ex, arg.dtype, n, true);
+    Column out = alloc_column(ex, arg.dtype, n, true);
     TIMED_LAUNCH_N(ex, "date_trunc", n, launch_date_trunc(ex.cfg(), arg.ref(), n, gran, out.data->as<int64_t>(), out.validity->as<uint64_t>()));
     return out;
 }
@@ -331,7 +315,7 @@ Column eval_date_part(const Exec& ex, const Batch& in, const ExprPtr& e, const S
     const int part = f.check(*e, *in.schema);
     const Column arg = materialize_column(ex, evaluate_column(ex, in, e->args[1]));
     const int64_t n = in.n_rows;
-    Column out = fixed_column(ex, DT_INT32, n, true);
+    Column out = alloc_column(ex, DT_INT32, n, true);
     TIMED_LAUNCH_N(ex, "date_part", n, launch_date_part(ex.cfg(), arg.ref(), n, part, out.data->as<int32_t>(), out.validity->as<uint64_t>()));
     return out;
 }
@@ -373,7 +357,7 @@ Column eval_str_range(const Exec& ex, const Batch& in, const ExprPtr& ep, const 
     uint32_t* lengths = tmp.get<uint32_t>((size_t)n + 1);
     uint32_t* status = tmp.get<uint32_t>(1);
     HIP_CHECK(hipMemsetAsync(status, 0, 4, ex.stream));
-    BufferPtr validity = any_validity ? make_buffer(ex, bitmap_bytes(n) + 8) : nullptr;
+    BufferPtr validity = any_validity ? validity_buffer(ex, n) : nullptr;
     TIMED_LAUNCH_N(ex, "str_range_lengths", n, launch_str_range_lengths(ex.cfg(), A, n, lengths, validity ? validity->as<uint64_t>() : nullptr, status));
     Utf8Total total;
     Column out = utf8_from_lengths(ex, tmp, lengths, n, total);
@@ -388,7 +372,7 @@ Column eval_str_range(const Exec& ex, const Batch& in, const ExprPtr& ep, const 
 Column eval_char_length(const Exec& ex, const Batch& in, const ExprPtr& e, const ScalarFn&) {
     const Column arg = eval_utf8(ex, in, e->args[0]);
     const int64_t n = in.n_rows;
-    Column out = fixed_column(ex, DT_INT32, n, false);
+    Column out = alloc_column(ex, DT_INT32, n, false);
     out.validity = arg.validity;
     TIMED_LAUNCH_N(ex, "char_length", n, launch_char_length(ex.cfg(), arg.ref(), n, out.data->as<int32_t>()));
     return out;
@@ -412,8 +396,8 @@ Column eval_str_search(const Exec& ex, const Batch& in, const ExprPtr& ep, const
         sub = eval_utf8(ex, in, e.args[1]);
         A.sub = sub.ref();
     }
-    Column out = fixed_column(ex, f.result, n, arg.validity || sub.validity);
-    uint64_t* validity = out.validity ? out.validity->as<uint64_t>() : nullptr;
+    Column out = alloc_column(ex, f.result, n, arg.validity || sub.validity);
+    uint64_t* validity = out.validity_words();
     if (f.param == STR_STRPOS) TIMED_LAUNCH_N(ex, "strpos", n, launch_strpos(ex.cfg(), A, n, out.data->as<int32_t>(), validity));
     else TIMED_LAUNCH_N(ex, "starts_with", n, launch_starts_with(ex.cfg(), A, n, out.data->as<uint64_t>(), validity));
     return out;
@@ -522,14 +506,7 @@ BatchPtr Utf8Lowering::apply(const Exec& ex, const Batch& in) const {
     out->schema = schema();
     for (auto& node : nodes_) {
         if (in.n_rows == 0) {
-            Column c;
-            c.dtype = expr_type(node, in_);
-            if (c.dtype == DT_UTF8) {
-                c.offsets = make_buffer(ex, 8);
-                HIP_CHECK(hipMemsetAsync(c.offsets->ptr(), 0, 8, ex.stream));
-            }
-            c.data = make_buffer(ex, 8);
-            out->cols.push_back(c);
+            out->cols.push_back(alloc_column(ex, expr_type(node, in_), 0, false));
         } else {
             const ScalarFn* f = lowered_by(node, in_);
             out->cols.push_back(f ? f->eval(ex, in, node, *f) : eval_utf8(ex, in, node));

@@ -369,6 +369,22 @@ def test_slice_to_pyarrow_and_ipc(ctx, kind, variant, k, tmp_path):
     assert_arrow_matches(pa.ipc.open_file(path).read_all().combine_chunks().to_batches()[0], want, k)
 
 
+def test_zero_and_word_edge_outputs(ctx):
+    """the columns the operators allocate themselves, at 0 rows and around a bitmap word, against pyarrow on the CPU: cases, inputs and
+    comparison in edge_outputs_gpu_child.py, which runs the sort cases once more in a process that has BHIP_NO_ROWSORT=1"""
+    import subprocess
+    import sys
+    import edge_outputs_gpu_child as EO
+    for n in EO.ROW_COUNTS:
+        EO.projection_case(ctx, n)
+        EO.concat_case(ctx, n)
+        EO.sort_case(ctx, n)
+        EO.left_join_case(ctx, n)
+        EO.aggregate_case(ctx, n)
+    p = subprocess.run([sys.executable, EO.__file__], env=dict(EO.os.environ, BHIP_NO_ROWSORT="1"), capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "OK norowsort %d" % len(EO.ROW_COUNTS) in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+
+
 # ---- 3. CoalesceBatchesExec, LimitExec, MergeExec as stream operators --------------------------------------------------------------------------
 
 def stream_partitions(ctx, size_lists, seed0=0):
