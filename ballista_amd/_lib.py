@@ -118,6 +118,10 @@ class WindowExprC(C.Structure):
     _fields_ = [("fn", C.c_int32), ("arg", Expr), ("offset", C.c_int64), ("frame", C.c_int32), ("name", C.c_char_p)]
 
 
+class RowsFrameC(C.Structure):
+    _fields_ = [("start_unbounded", C.c_int32), ("end_unbounded", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
+
+
 # every symbol include/ballista_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
@@ -170,6 +174,8 @@ SYMBOLS = {
     "bhip_plan_nested_loop_join": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(Expr), _PP]),
     "bhip_plan_sort": (C.c_int32, [_P, C.c_int32, C.POINTER(SortExprC), _PP]),
     "bhip_plan_window": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.c_int32, C.POINTER(SortExprC), C.c_int32, C.POINTER(WindowExprC), _PP]),
+    "bhip_plan_window_frames": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.c_int32, C.POINTER(SortExprC), C.c_int32, C.POINTER(WindowExprC),
+                                            C.POINTER(C.POINTER(RowsFrameC)), _PP]),
     "bhip_plan_repartition": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(Expr), C.c_int32, _PP]),
     "bhip_plan_coalesce_batches": (C.c_int32, [_P, C.c_int64, _PP]),
     "bhip_plan_merge": (C.c_int32, [_P, _PP]),

@@ -352,6 +352,12 @@ bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* ex
 
 bhip_status bhip_plan_window(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
                              const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns, bhip_plan** out) {
+    return bhip_plan_window_frames(input, n_partition, partition_by, n_order, order_by, n_fn, fns, nullptr, out);
+}
+
+bhip_status bhip_plan_window_frames(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
+                                    const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns,
+                                    const bhip_rows_frame* const* rows_frames, bhip_plan** out) {
     BHIP_API_BEGIN
     need(out, "out");
     if (n_partition < 0 || n_order < 0 || n_fn < 0) fail(BHIP_EINVAL, "WindowAggExec: negative count");
@@ -367,6 +373,10 @@ bhip_status bhip_plan_window(bhip_plan* input, int32_t n_partition, const bhip_e
         need(fns[i].name, "window expression name");
         const bool has_arg = fns[i].arg.nodes && fns[i].arg.n_nodes > 0;
         f.push_back(WindowFnDesc{fns[i].fn, has_arg ? parse_expr(fns[i].arg) : nullptr, fns[i].offset, fns[i].frame, fns[i].name});
+        if (rows_frames && rows_frames[i]) {
+            const bhip_rows_frame& r = *rows_frames[i];
+            f.back().rows = WindowRowsFrame{true, r.start_unbounded != 0, r.end_unbounded != 0, r.start, r.end};
+        }
     }
     *out = wrap_plan(std::make_shared<WindowAggExec>(part, order, f, plan_of(input, "input")));
     BHIP_API_END

@@ -2,7 +2,7 @@
 // specification (PARTITION BY ... ORDER BY ...), on the device (kernels_window.hip).
 //
 // The reference's serde has no window operator (rust/core/src/serde/physical_plan/from_proto.rs:58-346 builds none), so this one is
-// reached through bhip_plan_window only, like the join filter and the Semi / Anti joins; semantics: DESIGN.md "Window functions".
+// reached through bhip_plan_window / bhip_plan_window_frames only, like the join filter and the Semi / Anti joins; semantics: DESIGN.md "Window functions".
 //
 // The operator sorts its single input partition itself with SortExec's code (sort_permutation + take_batch; stable, so ties keep input
 // order) by the partition keys ASC NULLS FIRST and then the order keys, and the rows leave in that order.  After the sort every function
@@ -13,6 +13,10 @@
 //   ranks        elementwise from the bounds; LAG / LEAD / FIRST_VALUE / LAST_VALUE: an index vector, then the outer-join gather
 //   aggregates   a segmented inclusive scan of the argument (value + non-NULL count per row), then the finish kernel reads the running
 //                state at the frame's last row: the row itself (ROWS), peer_end (RANGE) or part_end (whole partition)
+//   sliding      a ROWS frame by offsets: (lo, hi) per row, once per distinct frame.  FIRST_VALUE / LAST_VALUE gather by them; COUNT and
+//                the integer SUM take the scan and a difference of two running states; a frame that starts with the partition reads the
+//                running state at hi; float SUM, AVG, MIN and MAX between two finite ends are aggregated straight from the argument
+//                (window_slide: a bounded neighbourhood of each tile in LDS)
 #include "../window_kernels.h"
 #include "plan.hpp"
 
@@ -45,6 +49,20 @@ const char* frame_name(int frame) {
 bool is_ranking(int fn) { return fn == BHIP_WIN_ROW_NUMBER || fn == BHIP_WIN_RANK || fn == BHIP_WIN_DENSE_RANK; }
 bool is_aggregate(int fn) { return fn >= BHIP_WIN_SUM && fn <= BHIP_WIN_MAX; }
 bool has_frame(int fn) { return is_aggregate(fn) || fn == BHIP_WIN_LAST_VALUE; }
+// a rows frame moves FIRST_VALUE too (a named frame always starts with the partition)
+bool takes_rows_frame(int fn) { return has_frame(fn) || fn == BHIP_WIN_FIRST_VALUE; }
+
+std::string bound_name(bool unbounded, int64_t offset, bool is_start) {
+    if (unbounded) return is_start ? "UNBOUNDED PRECEDING" : "UNBOUNDED FOLLOWING";
+    if (offset == 0) return "CURRENT ROW";
+    // (the magnitude of INT64_MIN has no Int64)
+    return offset < 0 ? std::to_string(0 - (uint64_t)offset) + " PRECEDING" : std::to_string(offset) + " FOLLOWING";
+}
+std::string rows_frame_name(const WindowRowsFrame& r) {
+    return "ROWS BETWEEN " + bound_name(r.start_unbounded, r.start, true) + " AND " + bound_name(r.end_unbounded, r.end, false);
+}
+// the aggregates a prefix scan cannot slide: a difference of running Float64 sums cancels, MIN / MAX have no inverse
+bool slides(int fn, int arg_dtype) { return fn == BHIP_WIN_AVG || fn == BHIP_WIN_MIN || fn == BHIP_WIN_MAX || (fn == BHIP_WIN_SUM && dt_is_float(arg_dtype)); }
 }  // namespace
 
 WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<SortDesc> order_by, std::vector<WindowFnDesc> fns, PlanPtr input)
@@ -63,8 +81,21 @@ WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<Sort
     for (auto& f : fns_) {
         if (f.fn < BHIP_WIN_ROW_NUMBER || f.fn > BHIP_WIN_MAX) fail(BHIP_EINVAL, "Unknown window function " + std::to_string(f.fn));
         if (f.frame < BHIP_FRAME_DEFAULT || f.frame > BHIP_FRAME_RANGE_TO_CURRENT) fail(BHIP_EINVAL, "Unknown window frame " + std::to_string(f.frame));
-        if (f.frame == BHIP_FRAME_DEFAULT) f.frame = order_by_.empty() ? BHIP_FRAME_PARTITION : BHIP_FRAME_RANGE_TO_CURRENT;      // SQL's default
         const std::string fname = window_fn_name(f.fn);
+        if (f.rows.has) {
+            WindowRowsFrame& r = f.rows;
+            if (f.frame != BHIP_FRAME_DEFAULT)
+                fail(BHIP_EINVAL, fname + ": a rows frame goes with BHIP_FRAME_DEFAULT, not with " + frame_name(f.frame));
+            if (r.start_unbounded) r.start = 0;                     // (an unbounded side's offset is not read)
+            if (r.end_unbounded) r.end = 0;
+            if (!r.start_unbounded && !r.end_unbounded && r.start > r.end)
+                fail(BHIP_EINVAL, fname + " " + rows_frame_name(r) + ": frame start lies after its end");
+            if (!takes_rows_frame(f.fn)) r = WindowRowsFrame{};     // ignored, as a named frame is
+            else if (r.start_unbounded && r.end_unbounded) { r = WindowRowsFrame{}; f.frame = BHIP_FRAME_PARTITION; }
+            else if (r.start_unbounded && r.end == 0) { r = WindowRowsFrame{}; f.frame = BHIP_FRAME_ROWS_TO_CURRENT; }
+        }
+        // (under a rows frame that stays one, `frame` is not read and stays DEFAULT: with_new_children hands the descriptions back in)
+        if (f.frame == BHIP_FRAME_DEFAULT && !f.rows.has) f.frame = order_by_.empty() ? BHIP_FRAME_PARTITION : BHIP_FRAME_RANGE_TO_CURRENT;      // SQL's default
         if (is_ranking(f.fn)) {
             f.arg = nullptr;
             sch->fields.push_back(Field{f.name, DT_UINT64, false});
@@ -74,13 +105,26 @@ WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<Sort
         const int t = expr_type(f.arg, in);
         low.rewrite(f.arg, true);
         const bool large = t == DT_UTF8 && expr_large(f.arg, in), binary = t == DT_UTF8 && expr_binary(f.arg, in);
+        if (f.rows.has && slides(f.fn, t) && t != DT_UTF8 && t != DT_BOOLEAN) {
+            const WindowRowsFrame& r = f.rows;
+            const std::string what = fname + "(" + dtype_name(t) + ") over " + rows_frame_name(r);
+            if (r.end_unbounded)
+                fail(BHIP_ENOTIMPL, what + ": a frame from an offset to UNBOUNDED FOLLOWING is supported for COUNT, integer SUM, FIRST_VALUE and LAST_VALUE only");
+            // end - start as unsigned: exact for any two Int64 with start <= end
+            if (!r.start_unbounded && (uint64_t)r.end - (uint64_t)r.start >= (uint64_t)WINDOW_SLIDE_MAX_ROWS)
+                fail(BHIP_ENOTIMPL, what + ": a frame wider than " + std::to_string(WINDOW_SLIDE_MAX_ROWS) +
+                                        " rows is supported for COUNT, integer SUM, FIRST_VALUE and LAST_VALUE only");
+        }
         switch (f.fn) {
             case BHIP_WIN_LAG: case BHIP_WIN_LEAD:
                 if (f.offset < 0) fail(BHIP_EINVAL, fname + " offset must not be negative, got " + std::to_string(f.offset));
                 sch->fields.push_back(Field{f.name, t, true, large, binary});
                 break;
             case BHIP_WIN_FIRST_VALUE: case BHIP_WIN_LAST_VALUE:
-                sch->fields.push_back(Field{f.name, t, expr_nullable(f.arg, in), large, binary});
+                // a rows frame that can lie wholly before or after the partition's rows is empty there
+                sch->fields.push_back(Field{f.name, t, expr_nullable(f.arg, in) || (f.rows.has && ((!f.rows.start_unbounded && f.rows.start > 0) ||
+                                                                                                   (!f.rows.end_unbounded && f.rows.end < 0))),
+                                            large, binary});
                 break;
             case BHIP_WIN_SUM: case BHIP_WIN_AVG:
                 if (t == DT_UTF8 || t == DT_BOOLEAN) fail(BHIP_EINVAL, fname + " does not support " + dtype_name(t));
@@ -117,7 +161,8 @@ std::string WindowAggExec::describe() const {
         s += (i ? ", " : "") + std::string(window_fn_name(f.fn)) + "(" + (f.arg ? f.arg->to_string() : "");
         if (f.fn == BHIP_WIN_LAG || f.fn == BHIP_WIN_LEAD) s += ", " + std::to_string(f.offset);
         s += ")";
-        if (has_frame(f.fn)) s += std::string(" ") + frame_name(f.frame);
+        if (f.rows.has) s += " " + rows_frame_name(f.rows);
+        else if (has_frame(f.fn)) s += std::string(" ") + frame_name(f.frame);
         s += " as " + f.name;
     }
     return s + "]";
@@ -196,6 +241,28 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
         need_backward();
         return frame == BHIP_FRAME_PARTITION ? part_end : peer_end;
     };
+    // the (lo, hi) of every row under a rows frame, made once per distinct frame of the operator
+    struct FrameRows { WindowRowsFrame r; const uint32_t *lo, *hi; };
+    std::vector<FrameRows> frames;
+    auto frame_rows = [&](const WindowRowsFrame& given) -> FrameRows {
+        WindowRowsFrame r = given;                                  // offsets clamped to +-n: i + offset stays far from overflow on the device,
+        r.start = std::max(-n, std::min(n, r.start));               // and a row n or more away lies outside every partition either way
+        r.end = std::max(-n, std::min(n, r.end));
+        for (const FrameRows& f : frames)
+            if (f.r.start_unbounded == r.start_unbounded && f.r.end_unbounded == r.end_unbounded && f.r.start == r.start && f.r.end == r.end) return f;
+        // a near frame is cut by the partition heads among the rows it reaches over: the flags, not the two bounds scans
+        const bool near = window_frame_is_near(r.start_unbounded, r.start, r.end_unbounded, r.end);
+        if (!near) {
+            need_forward();
+            need_backward();
+        }
+        uint32_t *lo = tmp.get<uint32_t>((size_t)n), *hi = tmp.get<uint32_t>((size_t)n);
+        TIMED_LAUNCH_N(ex, "window_frame_bounds", n,
+                       launch_window_frame_bounds(cfg, near ? part_flags : nullptr, near ? nullptr : part_start, near ? nullptr : part_end, r.start_unbounded,
+                                                  r.start, r.end_unbounded, r.end, n, lo, hi));
+        frames.push_back(FrameRows{r, lo, hi});
+        return frames.back();
+    };
 
     auto out = new_batch(sorted->ctx, schema_, n);
     out->cols = sorted->cols;
@@ -206,6 +273,13 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
             o = alloc_column(ex, DT_UINT64, n, false);
             const int kind = f.fn == BHIP_WIN_ROW_NUMBER ? WINDOW_ROW_NUMBER : f.fn == BHIP_WIN_RANK ? WINDOW_RANK : WINDOW_DENSE_RANK;
             TIMED_LAUNCH_N(ex, "window_rank", n, launch_window_rank(cfg, kind, part_start, peer_start, peers_to, n, o.data->as<uint64_t>()));
+        } else if (!is_aggregate(f.fn) && f.rows.has) {
+            // FIRST_VALUE / LAST_VALUE of a rows frame: lo / hi are the index vector (an empty frame: the NULL index)
+            const FrameRows fr = frame_rows(f.rows);
+            const uint32_t* idx = f.fn == BHIP_WIN_FIRST_VALUE ? fr.lo : fr.hi;
+            const Column arg = evaluate_column(ex, *sorted, f.arg);
+            const bool may_be_empty = (!fr.r.start_unbounded && f.rows.start > 0) || (!fr.r.end_unbounded && f.rows.end < 0);
+            o = may_be_empty ? take_column_nullable(ex, arg, idx, n) : take_batch_column(ex, arg, idx, n);
         } else if (!is_aggregate(f.fn)) {
             // the row to read, then the gather the outer joins use (an index outside the partition is its NULL index)
             const uint32_t* fe = nullptr;
@@ -237,15 +311,32 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
                 default: op = dt_is_float(t) ? WINDOW_OP_MAX_F64 : dt_is_unsigned(t) ? WINDOW_OP_MAX_U64 : WINDOW_OP_MAX_I64; dtype = t; break;
             }
             if (kind != WINDOW_FINISH_COUNT && !ref.data) fail(BHIP_EEXEC, "WindowAggExec: an argument column without buffers");
+            if (f.rows.has && !f.rows.start_unbounded && op != WINDOW_OP_ADD_I64) {
+                // two finite ends (the constructor refused the rest): straight from the argument, no scan
+                const FrameRows fr = frame_rows(f.rows);
+                o = alloc_column(ex, dtype, n, true);
+                TIMED_LAUNCH_N(ex, "window_slide", n,
+                               launch_window_slide(cfg, op, kind, o.dtype, ref, fr.lo, fr.hi, fr.r.start, fr.r.end, n, o.data->ptr(), o.validity_words()));
+                out->cols.push_back(std::move(o));
+                continue;
+            }
             uint64_t* run_value = tmp.get<uint64_t>((size_t)n);
             uint32_t* run_count = tmp.get<uint32_t>((size_t)n);
             TIMED_LAUNCH_N(ex, "window_scan_tiles", n, launch_window_scan_tiles(cfg, op, ref, part_flags, n, scan_temp));
             TIMED_LAUNCH_N(ex, "window_scan_summaries", n, launch_window_scan_summaries(cfg, op, n, scan_temp));
             TIMED_LAUNCH_N(ex, "window_scan_apply", n, launch_window_scan_apply(cfg, op, ref, part_flags, n, scan_temp, run_value, run_count));
-            const uint32_t* fe = frame_end(f.frame);
             o = alloc_column(ex, dtype, n, kind != WINDOW_FINISH_COUNT);
-            TIMED_LAUNCH_N(ex, "window_finish", n,
-                           launch_window_finish(cfg, kind, o.dtype, run_value, run_count, fe, n, o.data->ptr(), o.validity_words()));
+            if (f.rows.has) {
+                // the running state at hi; COUNT and the wrapping SUM of a frame that starts at an offset: less the state before lo
+                const FrameRows fr = frame_rows(f.rows);
+                TIMED_LAUNCH_N(ex, "window_finish_frame", n,
+                               launch_window_finish_frame(cfg, kind, o.dtype, run_value, run_count, fr.r.start_unbounded ? nullptr : part_flags, fr.lo, fr.hi,
+                                                          n, o.data->ptr(), o.validity_words()));
+            } else {
+                const uint32_t* fe = frame_end(f.frame);
+                TIMED_LAUNCH_N(ex, "window_finish", n,
+                               launch_window_finish(cfg, kind, o.dtype, run_value, run_count, fe, n, o.data->ptr(), o.validity_words()));
+            }
         }
         out->cols.push_back(std::move(o));
     }

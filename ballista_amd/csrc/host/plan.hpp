@@ -339,13 +339,20 @@ private:
 };
 
 // One window specification over the whole input (ops_window.cpp): the rows sorted by (partition keys ASC NULLS FIRST, order keys),
-// the input's columns followed by one column per window function.  No wire form: the C ABI only (bhip_plan_window).
+// the input's columns followed by one column per window function.  No wire form: the C ABI only (bhip_plan_window_frames).
+// A ROWS frame by signed offsets from the current row (bhip_rows_frame).  The constructor resolves UNBOUNDED PRECEDING .. CURRENT ROW
+// and UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING to the named frames (`has` false again); every other frame keeps its offsets.
+struct WindowRowsFrame {
+    bool has = false, start_unbounded = false, end_unbounded = false;
+    int64_t start = 0, end = 0;
+};
 struct WindowFnDesc {
     int fn;               // bhip_window_fn
     ExprPtr arg;          // null for ROW_NUMBER / RANK / DENSE_RANK
     int64_t offset;       // LAG / LEAD
     int frame;            // bhip_window_frame, BHIP_FRAME_DEFAULT already resolved
     std::string name;
+    WindowRowsFrame rows; // has: this frame, not `frame`
 };
 class WindowAggExec : public UnaryExec {
 public:

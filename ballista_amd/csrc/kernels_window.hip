@@ -7,6 +7,8 @@
 //                                        sum, backward min) and for the segmented scans of an argument (add, min, max)
 //   window_rank / window_index           ROW_NUMBER, RANK, DENSE_RANK; the row LAG / LEAD / FIRST_VALUE / LAST_VALUE gather from
 //   window_finish                        the running state at the frame's last row -> the output column and its validity
+//   window_frame_bounds / _finish_frame  sliding ROWS frames: every row's (lo, hi); the finish over it (a difference for COUNT and integer SUM)
+//   window_slide                         the aggregate of a frame with two finite ends, out of a tile's neighbourhood staged in LDS
 //
 // The scan: a tile is WINDOW_TILE_ROWS rows = WINDOW_ROUNDS rounds of one row per thread.  Inside a round the wave-level scan is the
 // __shfl_up ladder of kernels_util.hip's exclusive scans, the four wave totals cross through LDS.  Launch 1 leaves one summary per
@@ -243,13 +245,23 @@ struct ArgScan {
         return State{cut ? b.value : merged, cut ? b.count : a.count + b.count, cut ? b.flags : a.flags | b.flags};
     }
     __device__ State load(int64_t i, int64_t) const {
+        State s = load_arg(arg, i);
+        if (bit_at(part_flags, i)) s.flags |= ARG_HEAD;
+        return s;
+    }
+    __device__ static State load_arg(const ColumnRef& arg, int64_t i) {
+        const bool valid = !arg.validity || bit_at(arg.validity, i);
+        // sign- / zero-extended; Float32 as a double's bits (COUNT: no data, the validity is all that is read)
+        return state_of(arg.dtype, arg.data != nullptr, valid, valid && arg.data ? dt_load(arg.dtype, arg.data, i) : 0ull);
+    }
+    // one row's argument, `v` its 64-bit image (dt_load), as a state of one row without the head flag
+    __device__ static State state_of(int dtype, bool has_data, bool valid, uint64_t v) {
         uint64_t value = 0;
-        uint32_t count = 0, flags = bit_at(part_flags, i) ? ARG_HEAD : 0u;
-        if (!arg.validity || bit_at(arg.validity, i)) {
+        uint32_t count = 0, flags = 0u;
+        if (valid) {
             count = 1;
-            if (arg.data) {                                                         // (COUNT: the validity is all that is read)
-                uint64_t v = dt_load(arg.dtype, arg.data, i);                       // sign- / zero-extended; Float32 as a double's bits
-                if (OP == WINDOW_OP_ADD_F64 && !dt_is_float(arg.dtype)) v = bits_of(dt_is_unsigned(arg.dtype) ? (double)v : (double)(int64_t)v);
+            if (has_data) {
+                if (OP == WINDOW_OP_ADD_F64 && !dt_is_float(dtype)) v = bits_of(dt_is_unsigned(dtype) ? (double)v : (double)(int64_t)v);
                 if (FLOAT_MINMAX) {
                     const double d = f64_of(v);
                     const bool nan = d != d;
@@ -315,6 +327,205 @@ window_finish_kernel(int kind, int out_dtype, const uint64_t* __restrict__ run_v
     }
     const uint64_t word = __ballot(valid);                          // 64 consecutive rows from a multiple of 64: one validity word
     if (validity && (threadIdx.x & 63) == 0 && i < n) validity[i >> 6] = word;
+}
+
+// =============================================================================================
+// sliding ROWS frames: the frame of every row, the finish over it, and the aggregate of a bounded neighbourhood
+// =============================================================================================
+// the last / first partition head among rows a .. b (0 <= a, b < n), or -1.  Bits past n are 0 (window_flags).
+__device__ inline int64_t last_head_in(const uint64_t* __restrict__ part_flags, int64_t a, int64_t b) {
+    for (int64_t w = b >> 6; w >= (a >> 6); --w) {
+        uint64_t x = part_flags[w];
+        if (w == (b >> 6)) x &= ~0ull >> (63 - (b & 63));
+        if (w == (a >> 6)) x &= ~0ull << (a & 63);
+        if (x) return (w << 6) + 63 - __clzll((long long)x);
+    }
+    return -1;
+}
+__device__ inline int64_t first_head_in(const uint64_t* __restrict__ part_flags, int64_t a, int64_t b) {
+    for (int64_t w = a >> 6; w <= (b >> 6); ++w) {
+        uint64_t x = part_flags[w];
+        if (w == (b >> 6)) x &= ~0ull >> (63 - (b & 63));
+        if (w == (a >> 6)) x &= ~0ull << (a & 63);
+        if (x) return (w << 6) + __ffsll((unsigned long long)x) - 1;
+    }
+    return -1;
+}
+
+// With `part_flags` (two finite ends that reach at most WINDOW_SLIDE_MAX_ROWS rows away) the partition's bounds are not needed: only a
+// head among the rows the frame reaches over cuts it, and the flags of those rows are a few words.  Otherwise from part_start / part_end.
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_frame_bounds_kernel(const uint64_t* __restrict__ part_flags, const uint32_t* __restrict__ part_start, const uint32_t* __restrict__ part_end,
+                           bool start_unbounded, int64_t start, bool end_unbounded, int64_t end, int64_t n, uint32_t* __restrict__ lo,
+                           uint32_t* __restrict__ hi) {
+    const int64_t i = (int64_t)blockIdx.x * WINDOW_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    int64_t l, h;                                                    // |start|, |end| <= n: no overflow
+    if (part_flags) {
+        // a frame that lies past the partition's end (start > 0) or before its start (end < 0) comes out with l > h: the other side is
+        // cut at the head that lies between
+        l = i + start;
+        if (start < 0) {                                             // the last head in (i + start, i]; row 0 is one
+            const int64_t q = last_head_in(part_flags, l + 1 > 0 ? l + 1 : 0, i);
+            if (q >= 0) l = q;
+        }
+        h = i + end < n - 1 ? i + end : n - 1;
+        if (end > 0 && i + 1 < n) {                                  // the first head in (i, i + end]: the partition ends before it
+            const int64_t q = first_head_in(part_flags, i + 1, h);
+            if (q >= 0) h = q - 1;
+        }
+    } else {
+        const int64_t ps = part_start[i], pe = part_end[i];
+        l = start_unbounded || i + start < ps ? ps : i + start;
+        h = end_unbounded || i + end > pe ? pe : i + end;
+    }
+    const bool empty = l > h;
+    lo[i] = empty ? WINDOW_NULL_INDEX : (uint32_t)l;
+    hi[i] = empty ? WINDOW_NULL_INDEX : (uint32_t)h;
+}
+
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_finish_frame_kernel(int kind, int out_dtype, const uint64_t* __restrict__ run_value, const uint32_t* __restrict__ run_count,
+                           const uint64_t* __restrict__ part_flags, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, int64_t n,
+                           void* __restrict__ out, uint64_t* __restrict__ validity) {
+    const int64_t i = (int64_t)blockIdx.x * WINDOW_BLOCK + threadIdx.x;
+    bool valid = false;
+    if (i < n) {
+        const uint32_t h = hi[i];
+        uint32_t count = 0;
+        uint64_t value = 0;
+        if (h != WINDOW_NULL_INDEX) {
+            count = run_count[h];
+            value = run_value[h];
+            if (part_flags) {                                       // wrapping differences are exact
+                const uint32_t l = lo[i];
+                if (!bit_at(part_flags, l)) {                       // (a frame that starts with its partition has nothing before it)
+                    count -= run_count[l - 1];
+                    value -= run_value[l - 1];
+                }
+            }
+        }
+        valid = count != 0;
+        if (kind == WINDOW_FINISH_COUNT) {
+            static_cast<uint64_t*>(out)[i] = count;
+        } else if (kind == WINDOW_FINISH_AVG) {
+            static_cast<double*>(out)[i] = valid ? f64_of(value) / (double)count : 0.0;
+        } else {
+            dt_store(out_dtype, out, i, valid ? value : 0ull);
+        }
+    }
+    const uint64_t word = __ballot(valid);
+    if (validity && (threadIdx.x & 63) == 0 && i < n) validity[i >> 6] = word;
+}
+
+// a raw element of an Arrow buffer, zero-extended by its load -> the 64-bit image dt_load gives
+__device__ inline uint64_t dt_widen(int t, uint64_t raw) {
+    switch (t) {
+        case DT_INT8: return (uint64_t)(int64_t)(int8_t)raw;
+        case DT_INT16: return (uint64_t)(int64_t)(int16_t)raw;
+        case DT_INT32: case DT_DATE32: return (uint64_t)(int64_t)(int32_t)raw;
+        case DT_FLOAT32: return bits_of((double)__uint_as_float((uint32_t)raw));
+        default: return raw;
+    }
+}
+
+// One workgroup per tile.  LDS: the argument of rows span_first .. span_last as 64-bit values, then one byte per row: bit 0 = not
+// NULL, ARG_HAS_NUMBER / ARG_SAW_NAN as the scan's state has them.  Lane k of a wave walks row base + k, so at every step of the
+// walk consecutive lanes read consecutive 8-byte slots (away from a partition's edge).
+constexpr uint32_t SLIDE_NOT_NULL = 1;
+static_assert((SLIDE_NOT_NULL & (ARG_HAS_NUMBER | ARG_SAW_NAN)) == 0, "one flag byte per staged row");
+
+// rows span_first .. span_first + span - 1 of the argument into LDS, WINDOW_ROUNDS rows per thread and round: the raw values and the
+// validity words, coalesced and unconditional (a lane past the span re-reads the span's last row and stores nothing), so all of a
+// round's loads are issued before the first LDS write waits for one
+template <int OP, class T, bool NULLABLE>
+__device__ inline void slide_stage(const ColumnRef& arg, int64_t span_first, int span, uint64_t* s_value, uint8_t* s_flag) {
+    using A = ArgScan<OP>;
+    const T* __restrict__ data = static_cast<const T*>(arg.data);
+    for (int base = 0; base < span; base += WINDOW_TILE_ROWS) {
+        T raw[WINDOW_ROUNDS];
+        uint64_t word[WINDOW_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+            const int s = base + r * WINDOW_BLOCK + (int)threadIdx.x;
+            const int64_t row = span_first + (s < span ? s : span - 1);
+            raw[r] = data[row];
+            word[r] = NULLABLE ? arg.validity[row >> 6] : ~0ull;
+        }
+#pragma unroll
+        for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+            const int s = base + r * WINDOW_BLOCK + (int)threadIdx.x;
+            if (s < span) {
+                const typename A::State v = A::state_of(arg.dtype, true, (word[r] >> ((span_first + s) & 63)) & 1, dt_widen(arg.dtype, raw[r]));
+                s_value[s] = v.value;
+                s_flag[s] = (uint8_t)((v.count ? SLIDE_NOT_NULL : 0u) | v.flags);
+            }
+        }
+    }
+}
+
+template <int OP>
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_slide_kernel(ColumnRef arg, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, int64_t start, int64_t end, int64_t n, int kind,
+                    int out_dtype, void* __restrict__ out, uint64_t* __restrict__ validity) {
+    using A = ArgScan<OP>;
+    using S = typename A::State;
+    extern __shared__ uint64_t s_slide[];
+    const int t = threadIdx.x;
+    const int64_t tile_first = (int64_t)blockIdx.x * WINDOW_TILE_ROWS;
+    const int64_t tile_last = tile_first + WINDOW_TILE_ROWS - 1 < n - 1 ? tile_first + WINDOW_TILE_ROWS - 1 : n - 1;
+    const int64_t span_first = tile_first + start > 0 ? tile_first + start : 0;
+    const int64_t span_last = tile_last + end < n - 1 ? tile_last + end : n - 1;
+    const int span = span_last >= span_first ? (int)(span_last - span_first + 1) : 0;    // <= cap: the launch sized the LDS for cap rows
+    const int cap = WINDOW_TILE_ROWS + (int)(end - start);
+    uint8_t* s_flag = reinterpret_cast<uint8_t*>(s_slide + cap);
+
+    uint32_t l[WINDOW_ROUNDS], h[WINDOW_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+        const int64_t i = tile_first + r * WINDOW_BLOCK + t;
+        l[r] = i < n ? lo[i] : WINDOW_NULL_INDEX;
+        h[r] = i < n ? hi[i] : WINDOW_NULL_INDEX;
+    }
+    // the element type and "has a validity" are chosen here, outside the staging loop: chosen per load, each load would wait for the last
+#define STAGE(T) (arg.validity ? slide_stage<OP, T, true>(arg, span_first, span, s_slide, s_flag) : slide_stage<OP, T, false>(arg, span_first, span, s_slide, s_flag))
+    switch (dt_width(arg.dtype)) {
+        case 1: STAGE(uint8_t); break;
+        case 2: STAGE(uint16_t); break;
+        case 4: STAGE(uint32_t); break;
+        default: STAGE(uint64_t); break;
+    }
+#undef STAGE
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+        const int64_t i = tile_first + r * WINDOW_BLOCK + t;
+        S acc = A::identity();                                       // value 0: the bits of +0.0
+        if (h[r] != WINDOW_NULL_INDEX) {
+            // the row's own frame; the clamp to the staged span changes nothing for a (lo, hi) made with this start / end
+            const int64_t jl = (int64_t)l[r] > span_first ? (int64_t)l[r] : span_first, jh = (int64_t)h[r] < span_last ? (int64_t)h[r] : span_last;
+            const int last = (int)(jh - span_first);
+            for (int s = (int)(jl - span_first); s <= last; ++s) {
+                const uint32_t f = s_flag[s];
+                const S b{s_slide[s], f & SLIDE_NOT_NULL, f & ~SLIDE_NOT_NULL};
+                if (OP == WINDOW_OP_ADD_F64) {
+                    if (b.count) acc.value = bits_of(f64_of(acc.value) + f64_of(b.value));
+                } else {
+                    acc.value = A::merge(acc, b);
+                    acc.flags |= b.flags;
+                }
+                acc.count += b.count;
+            }
+        }
+        const bool valid = acc.count != 0;
+        if (i < n) {
+            const uint64_t value = A::FLOAT_MINMAX && !(acc.flags & ARG_HAS_NUMBER) ? F64_QUIET_NAN : acc.value;      // NaNs alone: a NaN
+            if (kind == WINDOW_FINISH_AVG) static_cast<double*>(out)[i] = valid ? f64_of(value) / (double)acc.count : 0.0;
+            else dt_store(out_dtype, out, i, valid ? value : 0ull);
+        }
+        const uint64_t word = __ballot(valid);                      // 64 consecutive rows from a multiple of 64: one validity word
+        if (validity && (t & 63) == 0 && i < n) validity[i >> 6] = word;
+    }
 }
 
 inline unsigned row_blocks(int64_t n) { return (unsigned)((n + WINDOW_BLOCK - 1) / WINDOW_BLOCK); }
@@ -419,6 +630,53 @@ hipError_t launch_window_finish(const LaunchCfg& cfg, int kind, int out_dtype, c
     hipLaunchKernelGGL(window_finish_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, kind, out_dtype, run_value, run_count, frame_end, n,
                        out, validity);
     return hipGetLastError();
+}
+
+hipError_t launch_window_frame_bounds(const LaunchCfg& cfg, const uint64_t* part_flags, const uint32_t* part_start, const uint32_t* part_end,
+                                      bool start_unbounded, int64_t start, bool end_unbounded, int64_t end, int64_t n, uint32_t* lo, uint32_t* hi) {
+    if (n <= 0) return hipSuccess;
+    if (start < -n || start > n || end < -n || end > n) return hipErrorInvalidValue;
+    if (part_flags ? !window_frame_is_near(start_unbounded, start, end_unbounded, end) || start > end : !part_start || !part_end) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(window_frame_bounds_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, part_flags, part_start, part_end, start_unbounded,
+                       start, end_unbounded, end, n, lo, hi);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_finish_frame(const LaunchCfg& cfg, int kind, int out_dtype, const uint64_t* run_value, const uint32_t* run_count,
+                                      const uint64_t* part_flags, const uint32_t* lo, const uint32_t* hi, int64_t n, void* out, uint64_t* validity) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(window_finish_frame_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, kind, out_dtype, run_value, run_count,
+                       part_flags, lo, hi, n, out, validity);
+    return hipGetLastError();
+}
+
+template <int OP>
+static hipError_t run_slide(const LaunchCfg& cfg, int kind, int out_dtype, const ColumnRef& arg, const uint32_t* lo, const uint32_t* hi, int64_t start,
+                     int64_t end, int64_t n, void* out, uint64_t* validity) {
+    const size_t cap = (size_t)WINDOW_TILE_ROWS + (size_t)(end - start);               // rows a workgroup stages at most
+    const size_t lds = cap * 8 + ((cap + 7) & ~(size_t)7);
+    hipLaunchKernelGGL((window_slide_kernel<OP>), dim3((unsigned)window_tiles(n)), dim3(WINDOW_BLOCK), lds, cfg.stream, arg, lo, hi, start, end, n, kind,
+                       out_dtype, out, validity);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_slide(const LaunchCfg& cfg, int op, int kind, int out_dtype, const ColumnRef& arg, const uint32_t* lo, const uint32_t* hi,
+                               int64_t start, int64_t end, int64_t n, void* out, uint64_t* validity) {
+    if (n <= 0) return hipSuccess;
+    if (start < -n || start > n || end < start || end > n || end - start >= WINDOW_SLIDE_MAX_ROWS) return hipErrorInvalidValue;
+    if ((kind != WINDOW_FINISH_VALUE && kind != WINDOW_FINISH_AVG) || !arg.data || arg.dtype == DT_UTF8 || arg.dtype == DT_BOOLEAN) return hipErrorInvalidValue;
+#define CALL(OP) run_slide<OP>(cfg, kind, out_dtype, arg, lo, hi, start, end, n, out, validity)
+    switch (op) {
+        case WINDOW_OP_ADD_F64: return CALL(WINDOW_OP_ADD_F64);
+        case WINDOW_OP_MIN_I64: return CALL(WINDOW_OP_MIN_I64);
+        case WINDOW_OP_MAX_I64: return CALL(WINDOW_OP_MAX_I64);
+        case WINDOW_OP_MIN_U64: return CALL(WINDOW_OP_MIN_U64);
+        case WINDOW_OP_MAX_U64: return CALL(WINDOW_OP_MAX_U64);
+        case WINDOW_OP_MIN_F64: return CALL(WINDOW_OP_MIN_F64);
+        case WINDOW_OP_MAX_F64: return CALL(WINDOW_OP_MAX_F64);
+        default: return hipErrorInvalidValue;                       // the wrapping add takes the scan and a difference
+    }
+#undef CALL
 }
 
 }  // namespace bhip

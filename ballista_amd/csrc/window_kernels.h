@@ -3,6 +3,8 @@
 // Every window function here is a scan or a gather over 4-byte and 8-byte streams:
 //   boundary flags  ->  partition / peer bounds (scans of the flags)  ->  rank or index vectors (elementwise)
 //                   ->  segmented inclusive scan of an argument       ->  finish (read the running state at the frame's last row)
+// and, for a sliding ROWS frame, the frame's rows (lo, hi)  ->  a gather, a finish over (lo, hi), or window_slide: the aggregate of a
+// bounded neighbourhood of each row straight from the argument.
 // The scans are the multi-launch form: per-tile summaries, ONE workgroup's scan of the summaries, then the apply pass.  No
 // workgroup ever waits for another one.  A tile is WINDOW_TILE_ROWS rows whatever the device and the grid, so the order of every
 // floating-point addition is a function of the row positions alone: two runs over the same input give the same bits.
@@ -78,5 +80,33 @@ hipError_t launch_window_scan_apply(const LaunchCfg& cfg, int op, const ColumnRe
 enum WindowFinishKind : int32_t { WINDOW_FINISH_VALUE = 0, WINDOW_FINISH_AVG = 1, WINDOW_FINISH_COUNT = 2 };
 hipError_t launch_window_finish(const LaunchCfg& cfg, int kind, int out_dtype, const uint64_t* run_value, const uint32_t* run_count,
                                 const uint32_t* frame_end, int64_t n, void* out, uint64_t* validity);
+
+// ---- sliding ROWS frames: rows i + start .. i + end of row i's partition ---------------------------------------------------------
+// The widest finite frame (end - start + 1 rows) window_slide takes.  Chosen, not tuned: a tile and the widest frame's neighbourhood,
+// WINDOW_TILE_ROWS + WINDOW_SLIDE_MAX_ROWS - 1 rows of 9 bytes (about 46 KB), stay under the 64 KiB of LDS one workgroup may ask
+// for.  Mirrored as ballista_amd.plan.WINDOW_SLIDE_MAX_ROWS.
+constexpr int WINDOW_SLIDE_MAX_ROWS = 4096;
+static_assert((WINDOW_TILE_ROWS + WINDOW_SLIDE_MAX_ROWS - 1) * 9 + 8 <= 64 * 1024, "window_slide stages a tile and its widest frame in LDS");
+
+// lo[i] = max(part_start[i], i + start), hi[i] = min(part_end[i], i + end); an unbounded side takes the partition's bound.  An empty
+// frame (lo > hi) is WINDOW_NULL_INDEX in both.  `start` and `end` are already clamped to [-n, n] (all arithmetic is 64-bit signed).
+// A NEAR frame — two finite ends, neither more than WINDOW_SLIDE_MAX_ROWS rows from the current row — is given `part_flags` instead
+// of the two bounds (null then): only a partition head among the rows it reaches over cuts it, and those flags are a few words, so a
+// moving aggregate does not pay for the two bounds scans.  Every other frame: part_flags null, part_start and part_end.
+inline bool window_frame_is_near(bool start_unbounded, int64_t start, bool end_unbounded, int64_t end) {
+    return !start_unbounded && !end_unbounded && start >= -(int64_t)WINDOW_SLIDE_MAX_ROWS && end <= (int64_t)WINDOW_SLIDE_MAX_ROWS;
+}
+hipError_t launch_window_frame_bounds(const LaunchCfg& cfg, const uint64_t* part_flags, const uint32_t* part_start, const uint32_t* part_end,
+                                      bool start_unbounded, int64_t start, bool end_unbounded, int64_t end, int64_t n, uint32_t* lo, uint32_t* hi);
+// window_finish over a frame (lo, hi) of window_frame_bounds: the running state at row hi[i]; with `part_flags` (COUNT and the
+// wrapping integer SUM alone) less the running state at row lo[i] - 1 unless lo[i] starts the partition.  An empty frame: count 0.
+hipError_t launch_window_finish_frame(const LaunchCfg& cfg, int kind, int out_dtype, const uint64_t* run_value, const uint32_t* run_count,
+                                      const uint64_t* part_flags, const uint32_t* lo, const uint32_t* hi, int64_t n, void* out, uint64_t* validity);
+// The aggregate of a frame with two finite ends, straight from the argument: one workgroup per tile stages the argument of rows
+// tile_first + start .. tile_last + end (clipped to [0, n)) in LDS, then every row walks its own lo .. hi in ascending order.
+// ADD_F64: the accumulator starts at +0.0 and takes the non-NULL values in row order, so the bits are those of a plain loop.
+// `start` / `end` as window_frame_bounds took them, end - start + 1 <= WINDOW_SLIDE_MAX_ROWS; `kind`: VALUE or AVG.
+hipError_t launch_window_slide(const LaunchCfg& cfg, int op, int kind, int out_dtype, const ColumnRef& arg, const uint32_t* lo, const uint32_t* hi,
+                               int64_t start, int64_t end, int64_t n, void* out, uint64_t* validity);
 
 }  // namespace bhip

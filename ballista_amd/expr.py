@@ -196,20 +196,35 @@ WINDOW_FUNCTIONS = ("ROW_NUMBER", "RANK", "DENSE_RANK", "LAG", "LEAD", "FIRST_VA
 WINDOW_FRAMES = ("DEFAULT", "PARTITION", "ROWS_TO_CURRENT", "RANGE_TO_CURRENT")
 
 
+@dataclass(frozen=True)
+class RowsFrame:
+    """ROWS BETWEEN start AND end by signed offsets from the current row: -2 = 2 PRECEDING, 0 = CURRENT ROW, 3 = 3 FOLLOWING;
+    None = UNBOUNDED PRECEDING (start) / UNBOUNDED FOLLOWING (end).  Any Int64 offset; a finite start after a finite end is refused
+    when the plan is made."""
+    start: Optional[int]
+    end: Optional[int]
+
+    def __post_init__(self):
+        for side in (self.start, self.end):
+            if side is not None and (isinstance(side, bool) or not isinstance(side, int) or not -2**63 <= side < 2**63):
+                raise TypeError(f"a rows frame offset is None or an Int64, got {side!r}")
+
+
 @dataclass(eq=False)
 class WindowExpr:
     """one function over the operator's window: fun(expr[, offset]) [frame] AS name.  ROW_NUMBER / RANK / DENSE_RANK take no
-    argument; offset is LAG / LEAD's k (a plain non-negative integer); frame matters for the aggregates and LAST_VALUE."""
+    argument; offset is LAG / LEAD's k (a plain non-negative integer); frame, one of WINDOW_FRAMES or a RowsFrame, matters for the
+    aggregates and LAST_VALUE, a RowsFrame for FIRST_VALUE too."""
     fun: str
     expr: Optional[PhysicalExpr]
     name: str
     offset: int = 1
-    frame: str = "DEFAULT"
+    frame: Union[str, RowsFrame] = "DEFAULT"
 
     def __post_init__(self):
         if self.fun not in WINDOW_FUNCTIONS:
             raise NotImplementedError(f"window function '{self.fun}' is not supported")
-        if self.frame not in WINDOW_FRAMES:
+        if not isinstance(self.frame, RowsFrame) and self.frame not in WINDOW_FRAMES:
             raise NotImplementedError(f"window frame '{self.frame}' is not supported")
 
 

@@ -932,12 +932,15 @@ class SortExec(ExecutionPlan):
 
 # rows per tile summary of the window scans (csrc/window_kernels.h WINDOW_TILE_ROWS): it fixes the order of floating-point sums
 WINDOW_TILE_ROWS = 1024
+# the widest frame with two finite ends that float SUM, AVG, MIN and MAX take (csrc/window_kernels.h WINDOW_SLIDE_MAX_ROWS)
+WINDOW_SLIDE_MAX_ROWS = 4096
 
 
 class WindowAggExec(ExecutionPlan):
     """WindowAggExec(partition_by, order_by, window_exprs, input): one window specification, the functions over it.  The operator sorts
     its single input partition itself (partition keys ASC NULLS FIRST, then order_by, stable) and emits the rows in that order: the
-    input's fields, then one field per E.WindowExpr.  No wire form: the C ABI only (bhip_plan_window)."""
+    input's fields, then one field per E.WindowExpr.  An expression whose frame is an E.RowsFrame (ROWS BETWEEN ... PRECEDING AND ...
+    FOLLOWING) sends the operator through bhip_plan_window_frames.  No wire form: the C ABI only."""
 
     _FN = {name: i + 1 for i, name in enumerate(E.WINDOW_FUNCTIONS)}
     _FRAME = {name: i for i, name in enumerate(E.WINDOW_FRAMES)}
@@ -949,15 +952,26 @@ class WindowAggExec(ExecutionPlan):
         for i, s in enumerate(order_by):
             order[i] = L.SortExprC(lw.expr(s.expr), 1 if s.descending else 0, 1 if s.nulls_first else 0)
         fns = (L.WindowExprC * max(1, len(window_exprs)))()
+        rows = (C.POINTER(L.RowsFrameC) * max(1, len(window_exprs)))()          # null: the named frame of fns[i]
         for i, w in enumerate(window_exprs):
             nb = w.name.encode()
             lw.keep.append(nb)
             arg = lw.expr(w.expr) if w.expr is not None else L.Expr(None, 0)
+            frame = w.frame
+            if isinstance(frame, E.RowsFrame):                                  # travels beside the struct, whose frame stays DEFAULT
+                r = L.RowsFrameC(frame.start is None, frame.end is None, frame.start or 0, frame.end or 0)
+                lw.keep.append(r)
+                rows[i] = C.pointer(r)
+                frame = "DEFAULT"
             # a function or frame this mirror does not know goes through as the number it was given: the library refuses it
-            fns[i] = L.WindowExprC(self._FN.get(w.fun, w.fun), arg, int(w.offset), self._FRAME.get(w.frame, w.frame), nb)
+            fns[i] = L.WindowExprC(self._FN.get(w.fun, w.fun), arg, int(w.offset), self._FRAME.get(frame, frame), nb)
         h = C.c_void_p()
-        L.check(L.lib().bhip_plan_window(input._h, len(partition_by), lw.exprs(list(partition_by)), len(order_by), order,
-                                         len(window_exprs), fns, C.byref(h)))
+        if any(isinstance(w.frame, E.RowsFrame) for w in window_exprs):
+            L.check(L.lib().bhip_plan_window_frames(input._h, len(partition_by), lw.exprs(list(partition_by)), len(order_by), order,
+                                                    len(window_exprs), fns, rows, C.byref(h)))
+        else:
+            L.check(L.lib().bhip_plan_window(input._h, len(partition_by), lw.exprs(list(partition_by)), len(order_by), order,
+                                             len(window_exprs), fns, C.byref(h)))
         super().__init__(h, input.ctx, [input])
         self.partition_by, self.order_by, self.window_exprs, self.input = list(partition_by), list(order_by), list(window_exprs), input
 

@@ -372,7 +372,8 @@ bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* ex
  *   ROW_NUMBER, RANK, DENSE_RANK   no argument; UInt64, not nullable (RANK / DENSE_RANK without order_by: 1 on every row)
  *   LAG(x, k), LEAD(x, k)          x: any fixed-width type, Boolean, Utf8; k = `offset` >= 0 rows; the type of x, nullable: NULL
  *                                  where row i -/+ k lies outside the partition (no default value)
- *   FIRST_VALUE(x), LAST_VALUE(x)  the type of x; the partition's first row / the FRAME's last row
+ *   FIRST_VALUE(x), LAST_VALUE(x)  the type of x; the FRAME's first row (of a named frame: the partition's first row) / last row;
+ *                                  nullable like x, and always under a rows frame that can be empty (start > 0 or end < 0)
  *   SUM, AVG, COUNT, MIN, MAX      over the frame, with the result types and NULL rules of a Final HashAggregateExec: SUM of signed /
  *                                  unsigned integers Int64 / UInt64 (wrapping), floating SUM and every AVG Float64, COUNT UInt64 and
  *                                  never NULL, MIN / MAX the type of x (NaN skipped unless nothing else is there); NULL when the frame
@@ -380,8 +381,16 @@ bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* ex
  *                                  UInt8 literal 1.
  * Frames (the aggregates and LAST_VALUE; ignored elsewhere): PARTITION = the whole partition; ROWS_TO_CURRENT = UNBOUNDED PRECEDING
  * .. CURRENT ROW; RANGE_TO_CURRENT = UNBOUNDED PRECEDING .. the last peer of the current row; DEFAULT = SQL's: RANGE_TO_CURRENT with
- * an order_by, PARTITION without one (resolved when the plan is made).  Sliding frames, NTILE, PERCENT_RANK, CUME_DIST, NTH_VALUE and
- * IGNORE NULLS are not there.  No wire form (the reference's PhysicalPlanNode has no window node). */
+ * an order_by, PARTITION without one (resolved when the plan is made).
+ * Sliding ROWS frames come beside these structs, through bhip_plan_window_frames: for row i of the partition [ps, pe] the frame is rows
+ * max(ps, i + start) .. min(pe, i + end) in the operator's order (an unbounded side: ps / pe), any Int64 offsets; start > end (both
+ * finite) is BHIP_EINVAL.  An empty frame gives COUNT 0 and NULL elsewhere.  UNBOUNDED PRECEDING .. CURRENT ROW and .. UNBOUNDED
+ * FOLLOWING are ROWS_TO_CURRENT and PARTITION; on a function without a frame (ranking, LAG, LEAD) a rows frame is ignored.  With two
+ * finite ends the floating SUM and every AVG add the frame's non-NULL values in row order to +0.0 in Float64 (bit-reproducible), and
+ * these two, MIN and MAX take at most 4096 rows of frame (BHIP_ENOTIMPL beyond); the same four over k .. UNBOUNDED FOLLOWING with a
+ * finite k are BHIP_ENOTIMPL.  COUNT, the integer SUM, FIRST_VALUE and LAST_VALUE take every frame.
+ * RANGE / GROUPS frames with offsets, EXCLUDE, NTILE, PERCENT_RANK, CUME_DIST, NTH_VALUE and IGNORE NULLS are not there.  No wire form
+ * (the reference's PhysicalPlanNode has no window node). */
 typedef enum {
     BHIP_WIN_ROW_NUMBER = 1, BHIP_WIN_RANK = 2, BHIP_WIN_DENSE_RANK = 3, BHIP_WIN_LAG = 4, BHIP_WIN_LEAD = 5, BHIP_WIN_FIRST_VALUE = 6,
     BHIP_WIN_LAST_VALUE = 7, BHIP_WIN_SUM = 8, BHIP_WIN_AVG = 9, BHIP_WIN_COUNT = 10, BHIP_WIN_MIN = 11, BHIP_WIN_MAX = 12
@@ -398,6 +407,14 @@ typedef struct {
 } bhip_window_expr;
 bhip_status bhip_plan_window(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
                              const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns, bhip_plan** out);
+/* a ROWS frame by signed offsets from the current row: -2 = 2 PRECEDING, 0 = CURRENT ROW, 3 = 3 FOLLOWING; start_unbounded = UNBOUNDED
+ * PRECEDING, end_unbounded = UNBOUNDED FOLLOWING (the offset of an unbounded side is not read) */
+typedef struct { int32_t start_unbounded, end_unbounded; int64_t start, end; } bhip_rows_frame;
+/* bhip_plan_window with sliding frames: rows_frames is NULL (= bhip_plan_window) or n_fn pointers; a NULL entry leaves fns[i].frame as
+ * it is, any other one is the frame of fns[i], whose `frame` must then be BHIP_FRAME_DEFAULT (BHIP_EINVAL otherwise). */
+bhip_status bhip_plan_window_frames(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
+                                    const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns,
+                                    const bhip_rows_frame* const* rows_frames, bhip_plan** out);
 bhip_status bhip_plan_repartition(bhip_plan* input, int32_t scheme, int32_t n_exprs, const bhip_expr* hash_exprs,
                                   int32_t partition_count, bhip_plan** out);                         /* :133-164 */
 bhip_status bhip_plan_coalesce_batches(bhip_plan* input, int64_t target_batch_size, bhip_plan** out);  /* :122-128 */

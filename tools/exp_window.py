@@ -10,7 +10,14 @@ a device synchronise):
 Prints each median, the window pass as the difference from the sort, the GB/s that difference amounts to against the bytes the pass
 must read and write (the two keys, the argument, and the columns it adds), and the per-launch totals of every window_* launch and of
 the gathers from the context's kernel statistics (BHIP_KERNEL_TIMING=1).
-  tools/exp_window.py > profiles/window.txt"""
+  tools/exp_window.py > profiles/window.txt
+
+`frames`: the sliding ROWS frames over the same input, every plan one aggregate:
+  SortExec([p, o]); SUM(v) ROWS_TO_CURRENT (the running sum, for comparison); SUM(v) over (-6, 0), (-63, 0) and (-4095, 0); MIN(v) over
+  (-6, 0); SUM(o) over (-6, 0) (an Int64 argument: the difference of running sums)
+The plans alternate inside every round (one step of each, RUNS rounds after WARMUP untimed ones), so a difference between two of them
+is not a difference between two moments of a shared machine.  Prints what the first form prints, per plan.
+  tools/exp_window.py frames > profiles/window_frames.txt"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -21,6 +28,59 @@ import numpy as np
 import ballista_amd as ba
 from ballista_amd import expr as E
 from ballista_amd.expr import col
+
+
+def frames():
+    n = int(os.environ.get("ROWS", 1 << 26))
+    runs, warmup = int(os.environ.get("RUNS", 7)), int(os.environ.get("WARMUP", 1))
+    rng = np.random.default_rng(1)
+    ctx = ba.Context(0)
+    batch = ba.RecordBatch.from_columns(ctx, [("p", "Int64", rng.integers(0, 1 << 16, n), None), ("o", "Int64", rng.integers(0, 1 << 40, n), None),
+                                              ("v", "Float64", rng.uniform(0.5, 2.0, n), None)])
+    keys = [E.PhysicalSortExpr(col("p")), E.PhysicalSortExpr(col("o"))]
+    leaf = lambda: ba.MemoryExec([[batch]], ctx)
+    one = lambda fun, arg, frame: (lambda: ba.WindowAggExec([col("p")], keys[1:], [E.WindowExpr(fun, col(arg), "w", frame=frame)], leaf()))
+    plans = {"sort": lambda: ba.SortExec(keys, leaf()),
+             "SUM(v) ROWS_TO_CURRENT": one("SUM", "v", "ROWS_TO_CURRENT"),
+             "SUM(v) (-6, 0)": one("SUM", "v", E.RowsFrame(-6, 0)),
+             "SUM(v) (-63, 0)": one("SUM", "v", E.RowsFrame(-63, 0)),
+             "SUM(v) (-4095, 0)": one("SUM", "v", E.RowsFrame(-4095, 0)),
+             "MIN(v) (-6, 0)": one("MIN", "v", E.RowsFrame(-6, 0)),
+             "SUM(o) (-6, 0)": one("SUM", "o", E.RowsFrame(-6, 0))}
+    print(json.dumps(dict(rows=n, partitions=1 << 16, runs=runs, warmup=warmup, tile_rows=ba.plan.WINDOW_TILE_ROWS,
+                          slide_max_rows=ba.plan.WINDOW_SLIDE_MAX_ROWS, cus=ctx.device_cus())), flush=True)
+    ms = {name: [] for name in plans}
+    launches = {name: {} for name in plans}
+    for it in range(warmup + runs):
+        for name, make in plans.items():
+            plan = make()
+            ctx.synchronize()
+            ctx.kernel_stats(reset=True)
+            t0 = time.perf_counter()
+            out = plan.collect()
+            ctx.synchronize()
+            dt = (time.perf_counter() - t0) * 1e3
+            assert sum(b.num_rows for b in out) == n
+            del plan, out
+            if it >= warmup:
+                ms[name].append(dt)
+                for k, (t, count, _) in ctx.kernel_stats(reset=True).items():
+                    acc = launches[name].setdefault(k, [0.0, 0])
+                    acc[0] += t
+                    acc[1] += count
+    med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+    for name in plans:
+        line = dict(plan=name, ms_median=round(med[name], 3), ms=[round(x, 3) for x in ms[name]])
+        if name != "sort":
+            line.update(window_pass_ms=round(med[name] - med["sort"], 3))
+        print(json.dumps(line), flush=True)
+        ks = launches[name]
+        for k in sorted(ks, key=lambda k: -ks[k][0]):
+            if name == "sort" or k.startswith("window_") or k.startswith("take_") or k == "scan_project":
+                print(f"    {k:36s} {ks[k][0] / runs:9.3f} ms/step  {ks[k][1] // runs:4d} launches/step", flush=True)
+    running, sliding = med["SUM(v) ROWS_TO_CURRENT"] - med["sort"], med["SUM(v) (-6, 0)"] - med["sort"]
+    print(json.dumps(dict(running_sum_pass_ms=round(running, 3), sliding_sum_6_0_pass_ms=round(sliding, 3), ratio=round(sliding / running, 3),
+                          not_slower_within_10_percent=bool(sliding <= 1.1 * running))), flush=True)
 
 
 def main():
@@ -71,4 +131,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    frames() if sys.argv[1:] == ["frames"] else main()
