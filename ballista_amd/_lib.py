@@ -136,6 +136,7 @@ SYMBOLS = {
     "bhip_ctx_kernel_name": (C.c_char_p, [_P]),
     "bhip_ctx_kernel_variant": (C.c_char_p, [_P]),
     "bhip_ctx_lean_key_form": (C.c_char_p, [_P]),
+    "bhip_ctx_lean_step_alias": (C.c_char_p, [_P]),
     "bhip_ctx_sort_limit_form": (C.c_char_p, [_P]),
     "bhip_ctx_join_key_form": (C.c_char_p, [_P]),
     "bhip_ctx_nested_loop_form": (C.c_char_p, [_P]),

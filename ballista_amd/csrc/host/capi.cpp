@@ -114,6 +114,12 @@ const char* bhip_ctx_lean_key_form(bhip_ctx* ctx) {
     return name.c_str();
 }
 
+const char* bhip_ctx_lean_step_alias(bhip_ctx* ctx) {
+    static thread_local std::string name;
+    name = ctx ? ctx->p->lean_step_alias() : std::string();
+    return name.c_str();
+}
+
 const char* bhip_ctx_sort_limit_form(bhip_ctx* ctx) {
     static thread_local std::string name;
     name = ctx ? ctx->p->sort_limit_form() : std::string();

@@ -325,6 +325,23 @@ std::string Context::lean_key_form() {
     return k_key_form_;
 }
 
+void Context::set_lean_step_alias(uint32_t alias, int n_steps) {
+    std::string list;
+    bool aliased = false;
+    for (int s = 0; s < n_steps; ++s) {
+        const int a = (int)((alias >> (4 * s)) & 15u);
+        aliased = aliased || a != s;
+        list += (s ? "," : "") + std::to_string(a);
+    }
+    std::lock_guard<std::mutex> g(mu_);
+    k_step_alias_ = aliased ? list : "none";
+}
+
+std::string Context::lean_step_alias() {
+    std::lock_guard<std::mutex> g(mu_);
+    return k_step_alias_;
+}
+
 void Context::set_sort_limit_form(const char* form) {
     std::lock_guard<std::mutex> g(mu_);
     k_sort_limit_form_ = form ? form : "";

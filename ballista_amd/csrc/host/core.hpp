@@ -83,6 +83,11 @@ public:
     // "offsets", or "none" (no Utf8 key); "" before the first one
     void set_lean_key_form(const char* form);
     std::string lean_key_form();
+    // which loaded column each chain step of the last lean scan + aggregate launch used: "0,1,2,3,2" where the kernel formed
+    // step 4's value from the registers of step 2 (an aliased instantiation of lean_spec_kernel.h), "none" where every step
+    // loaded its own column (alias: 4 bits per step); "" before the first one
+    void set_lean_step_alias(uint32_t alias, int n_steps);
+    std::string lean_step_alias();
     // how the last limit directly over a sort ran: "topk" (threshold selection), "topk_fallback" (the selection declined every batch:
     // the plain sort, cut to k), "sort" (the full-sort route: k >= the rows there were, or BHIP_NO_TOPK); "" before the first one
     void set_sort_limit_form(const char* form);
@@ -126,7 +131,7 @@ private:
     bool spin_wait_ = true;
     double k_ms_ = 0;
     uint64_t k_launches_ = 0;
-    std::string k_name_, k_variant_, k_key_form_, k_sort_limit_form_, k_join_key_form_, k_nested_loop_form_, k_join_probe_form_;
+    std::string k_name_, k_variant_, k_key_form_, k_step_alias_, k_sort_limit_form_, k_join_key_form_, k_nested_loop_form_, k_join_probe_form_;
     struct PendingTimed { hipEvent_t a, b; const char* name; uint64_t bytes; };
     std::vector<PendingTimed> pending_timed_;
     std::vector<hipEvent_t> event_pool_;

@@ -601,12 +601,14 @@ std::vector<BatchPtr> HashAggregateExec::run_packed(int partition, const Exec& e
                 bind_sop(sop, *b);
                 const char* variant = nullptr;
                 bool fixed_keys = false;
+                uint32_t step_alias = 0;
                 HIP_CHECK(launch_scan_agg_lean(cfg, sop.prog, tmp.get<SopProgram>(1), gmax, partials + (size_t)n_part * gmax,
-                                               partial_ng + n_part, max_grid, status, &grid, &variant, &fixed_keys));
+                                               partial_ng + n_part, max_grid, status, &grid, &variant, &fixed_keys, &step_alias));
                 if (timed) timer.variant = variant;
                 bool utf8_key = false;
                 for (int q = 0; q < sop.prog.n_keys; ++q) utf8_key = utf8_key || sop.prog.keys[q].kind == SOP_KEY_UTF8;
                 ex.ctx->set_lean_key_form(fixed_keys ? "fixed" : utf8_key ? "offsets" : "none");
+                ex.ctx->set_lean_step_alias(step_alias, sop.prog.n_steps);
                 lens_seen = lens_seen && !fixed_keys;
             } else if (sop_now) {
                 bind_sop(sop, *b);

@@ -17,6 +17,14 @@
 //     offsets(t+1) and offsets(t+2); then, step column by step column, the sums of t and the loads of steps(t+1);
 //   * the ragged tail and the key-append path of the lookup stay out of the fast path, as in the generic kernel.
 //
+// Step aliases (ALIAS): where two steps of the plan read one column (Q1: 1 - l_discount inside the products, l_discount
+// for its average), only the earlier one has registers and a load.  When it is summed it also forms the later step's
+// factor f = sgn*x + add from the same registers, before they are reloaded; the later step takes that f, multiplies it
+// into its own chain (or starts one) and adds it to its own accumulator when its turn comes.  Step order, and with it the
+// order in which every accumulator receives a thread's rows, is unchanged, so every per-thread partial sum is too.
+// launch_scan_agg_lean_spec computes the pattern of a plan (lean_step_alias) and takes an aliased instantiation only
+// for exactly its pattern; the identity pattern serves every plan, with one load per step (profiles/isa_lean_alias.txt).
+//
 // The fixed-width key form (LK_UTF8_FIXED): every value of the key column is w bytes long (SopColumn::width, 1..3), so
 // offsets[i] = offsets[0] + i*w and the lengths are the constant w.  The kernel then reads offsets[0] once and no other
 // offset: there is no load_offsets, no `ko` register set and no re-pointed prefetch, and the key bytes of tile t+1 are
@@ -30,11 +38,43 @@ namespace bhip {
 
 enum LeanKeyKind : int { LK_NONE = 0, LK_I32 = 1, LK_UTF8 = 2, LK_UTF8_FIXED = 3 };
 
-// NR ranges (bit p of R32: range p reads a 32-bit integer column, else Float64), key parts K0 / K1, exactly NS steps
-template <int GMAX, int NR, int R32, int K0, int K1, int NS>
+// Step aliases, 4 bits per step: a(s) = the earliest step <= s that reads the same column as step s.  a(s) == s: the step
+// owns its load.  TPC-H Q1 sums x*(1 - disc) and averages disc: {0, 1, 2, 3, 2}.
+constexpr uint32_t lean_alias_of(uint32_t alias, int s) { return (alias >> (4 * s)) & 15u; }
+constexpr uint32_t lean_alias_identity(int ns) {
+    uint32_t a = 0;
+    for (int s = 0; s < ns; ++s) a |= (uint32_t)s << (4 * s);
+    return a;
+}
+constexpr bool lean_alias_valid(uint32_t alias, int ns) {
+    for (int s = 0; s < ns; ++s) {
+        const uint32_t a = lean_alias_of(alias, s);
+        if (a > (uint32_t)s || lean_alias_of(alias, (int)a) != a) return false;
+    }
+    return true;
+}
+
+// The 8- and 16-byte loads of the streamed columns (range, step and Int32 key columns): non-temporal, one instruction each.
+// Every byte of those columns is read once per launch, so nothing is lost by passing the L1 by.  The key bytes (whose
+// lines neighbouring waves share) and the offsets (prefetched two tiles ahead and read again) keep the default policy.
+typedef uint32_t LeanV2 __attribute__((ext_vector_type(2)));
+typedef uint32_t LeanV4 __attribute__((ext_vector_type(4)));
+__device__ inline LeanU2 lean_stream_ld2(const BHIP_GLOBAL char* p) {
+    const LeanV2 v = __builtin_nontemporal_load((const BHIP_GLOBAL LeanV2*)p);
+    return LeanU2{v.x, v.y};
+}
+__device__ inline LeanU4 lean_stream_ld4(const BHIP_GLOBAL char* p) {
+    const LeanV4 v = __builtin_nontemporal_load((const BHIP_GLOBAL LeanV4*)p);
+    return LeanU4{v.x, v.y, v.z, v.w};
+}
+
+// NR ranges (bit p of R32: range p reads a 32-bit integer column, else Float64), key parts K0 / K1, exactly NS steps with
+// the alias pattern ALIAS (the plan's own, or the identity: then a repeated column is simply loaded again)
+template <int GMAX, int NR, int R32, int K0, int K1, int NS, uint32_t ALIAS = lean_alias_identity(NS)>
 __global__ void __launch_bounds__(BLOCK, (GMAX == 1 && NS <= 5) ? 4 : 3)
 scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials, uint32_t* partial_ng, ScanStatus* status) {
     static_assert(NR >= 1 && NR <= SOP_NRANGE && NS >= 1 && NS <= SOP_NSTEP && (K0 != LK_NONE || K1 == LK_NONE), "lean shape");
+    static_assert(lean_alias_valid(ALIAS, NS), "a(s) <= s and a(a(s)) == a(s)");
     const SopProgram& S = *Sp;
     constexpr int U = LEAN_U;
     constexpr int NKEY = 2;
@@ -156,7 +196,7 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
 
     auto load_step = [&](int s, int64_t row) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) xv[s][u] = lean_ld4(xbase[s] + (row + u * LEAN_SUB) * 8 + t16);
+        for (int u = 0; u < U; ++u) xv[s][u] = lean_stream_ld4(xbase[s] + (row + u * LEAN_SUB) * 8 + t16);
     };
     auto load_ranges = [&](int64_t row) {
 #pragma unroll
@@ -164,12 +204,12 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
             if ((R32 >> p) & 1) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const LeanU2 v = lean_ld2(rbase[p] + (row + u * LEAN_SUB) * 4 + t8);
+                    const LeanU2 v = lean_stream_ld2(rbase[p] + (row + u * LEAN_SUB) * 4 + t8);
                     rv[p][u].x = v.x; rv[p][u].y = v.y;
                 }
             } else {
 #pragma unroll
-                for (int u = 0; u < U; ++u) rv[p][u] = lean_ld4(rbase[p] + (row + u * LEAN_SUB) * 8 + t16);
+                for (int u = 0; u < U; ++u) rv[p][u] = lean_stream_ld4(rbase[p] + (row + u * LEAN_SUB) * 8 + t16);
             }
         }
     };
@@ -179,7 +219,7 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
             if (KK[q] == LK_I32) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const LeanU2 v = lean_ld2(kbase[q] + (row + u * LEAN_SUB) * 4 + t8);
+                    const LeanU2 v = lean_stream_ld2(kbase[q] + (row + u * LEAN_SUB) * 4 + t8);
                     kv[q][u][0] = v.x; kv[q][u][1] = v.y;
                 }
             }
@@ -294,20 +334,33 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
         int lg[LEAN_ROWS];
         if (!lookup(key, live, lg)) return false;
         // chain values f = sgn*x + add ; t = (start ? 1 : t_prev) * f, summed step by step: each accumulator still
-        // receives this thread's rows in row order
+        // receives this thread's rows in row order.  A step that owns its column also forms f (with their sgn / add) for
+        // the later steps aliased to it, before its registers are reloaded; an aliased step has no registers and no load.
         double tp[LEAN_ROWS];
+        double fa[NS][LEAN_ROWS];                   // f of the aliased steps
+        auto factor = [&](int s, const LeanU4 x, double& a, double& b) {
+            a = u2d(((uint64_t)x.y << 32) | x.x); b = u2d(((uint64_t)x.w << 32) | x.z);
+            if (!xplain[s]) {
+                a = u2d(((uint64_t)(x.y ^ xflip[s]) << 32) | x.x) + xadd[s];
+                b = u2d(((uint64_t)(x.w ^ xflip[s]) << 32) | x.z) + xadd[s];
+            }
+        };
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
+            const bool own = lean_alias_of(ALIAS, s) == (uint32_t)s;
             double tv[LEAN_ROWS];
+            if (own) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const LeanU4 x = xv[s][u];
-                double a = u2d(((uint64_t)x.y << 32) | x.x), b = u2d(((uint64_t)x.w << 32) | x.z);
-                if (!xplain[s]) {
-                    a = u2d(((uint64_t)(x.y ^ xflip[s]) << 32) | x.x) + xadd[s];
-                    b = u2d(((uint64_t)(x.w ^ xflip[s]) << 32) | x.z) + xadd[s];
-                }
-                tv[2 * u] = a; tv[2 * u + 1] = b;
+                for (int u = 0; u < U; ++u) factor(s, xv[s][u], tv[2 * u], tv[2 * u + 1]);
+#pragma unroll
+                for (int a = s + 1; a < NS; ++a)
+                    if (lean_alias_of(ALIAS, a) == (uint32_t)s) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) factor(a, xv[s][u], fa[a][2 * u], fa[a][2 * u + 1]);
+                    }
+            } else {
+#pragma unroll
+                for (int r = 0; r < LEAN_ROWS; ++r) tv[r] = fa[s][r];
             }
             if (s > 0 && !xstart[s]) {
 #pragma unroll
@@ -315,7 +368,7 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
             }
 #pragma unroll
             for (int r = 0; r < LEAN_ROWS; ++r) { add_step(lg[r], s, tv[r]); tp[r] = tv[r]; }
-            if constexpr (NEXT) load_step(s, row1);
+            if constexpr (NEXT) { if (own) load_step(s, row1); }
         }
 #pragma unroll
         for (int r = 0; r < LEAN_ROWS; ++r) add_row(lg[r]);
@@ -336,7 +389,8 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
         load_int_keys(row0);
         if constexpr (HAS_OFFSETS) load_offsets(ko[1], tile_row(1));
 #pragma unroll
-        for (int s = 0; s < NS; ++s) load_step(s, row0);
+        for (int s = 0; s < NS; ++s)
+            if (lean_alias_of(ALIAS, s) == (uint32_t)s) load_step(s, row0);
         // Drain the prologue once.  The loop head is entered from here and from its back edge, and the compiler's wait at
         // a join assumes the worse of the two; with nothing in flight here the prologue's load order (key bytes behind the
         // step loads) cannot lower the head's counts.  (The even tile's head still waits vmcnt(10..8): DESIGN.md §3.1.)
@@ -363,6 +417,18 @@ scan_agg_lean_spec_kernel(const SopProgram* __restrict__ Sp, GroupRec* partials,
         over = !lean_tail<GMAX, NS, NR>(S, n_tiles * LEAN_TILE, n_rows, HAS_FIXED ? tail_lens : lens, lookup, accumulate);
     }
     lean_finish<GMAX, NS>(lds, S, acc, rows1, lens, partials, partial_ng, status);
+}
+
+// the alias pattern of plan S: for each step the earliest step that reads the same column at the same width
+static uint32_t lean_step_alias(const SopProgram& S) {
+    uint32_t alias = 0;
+    for (int s = 0; s < S.n_steps && s < SOP_NSTEP; ++s) {
+        int a = s;
+        for (int e = s - 1; e >= 0; --e)
+            if (S.steps[e].col == S.steps[s].col && S.steps[e].is32 == S.steps[s].is32) a = e;
+        alias |= (uint32_t)a << (4 * s);
+    }
+    return alias;
 }
 
 // does plan S have exactly this shape (range widths, no NULLs in a range column, key kinds, step count)?

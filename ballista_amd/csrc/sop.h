@@ -72,10 +72,12 @@ hipError_t launch_scan_agg_sop(const LaunchCfg& cfg, const SopProgram& S, SopPro
 
 // wide-load variant (lean_kernel.h, lean_spec_kernel.h): gmax 1 or 4, plans accepted by host/sop.cpp::lean_eligible;
 // *variant (optional) names the kernel that ran: "lean_generic" or the specialised shape (kernels_lean_spec.hip);
-// *fixed_keys (optional): it read its Utf8 keys in the fixed-width form (SopColumn::width), so it reports no lengths
+// *fixed_keys (optional): it read its Utf8 keys in the fixed-width form (SopColumn::width), so it reports no lengths;
+// *step_alias (optional): 4 bits per step, the step whose loaded column step s used (lean_spec_kernel.h) — s itself
+// wherever the kernel loaded a column per step
 hipError_t launch_scan_agg_lean(const LaunchCfg& cfg, const SopProgram& S, SopProgram* dprog, int gmax, GroupRec* partials,
                                 uint32_t* partial_ng, int max_grid, ScanStatus* status, int* grid_out, const char** variant = nullptr,
-                                bool* fixed_keys = nullptr);
+                                bool* fixed_keys = nullptr, uint32_t* step_alias = nullptr);
 
 // FilterExec's predicate pass for AND-of-ranges predicates (kernels_range.hip): selection bitmap + kept rows per
 // 1024-row tile, the interface of launch_scan_pred_bitmap

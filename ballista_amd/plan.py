@@ -93,6 +93,12 @@ class Context:
         values are known to share one width: no offsets read), "offsets", "none" (no Utf8 key), "" before the first one"""
         return L.lib().bhip_ctx_lean_key_form(self._h).decode()
 
+    def lean_step_alias(self):
+        """which loaded column each chain step of that launch used: "0,1,2,3,2" where step 4's value came from the column
+        step 2 loaded (the kernel read a column two steps share once), "none" where every step loaded its own, "" before
+        the first one"""
+        return L.lib().bhip_ctx_lean_step_alias(self._h).decode()
+
     def sort_limit_form(self):
         """how the last limit directly over a sort ran: "topk" (threshold selection on the first key), "topk_fallback" (the selection
         declined every batch: plain sort, cut to k), "sort" (full-sort route: limit >= rows, or BHIP_NO_TOPK=1), "" before the first one"""

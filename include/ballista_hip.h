@@ -646,6 +646,10 @@ const char* bhip_ctx_kernel_variant(bhip_ctx* ctx);
  * column is known to have one width: no offsets are read), "offsets", or "none" (no Utf8 key); "" before the first such launch;
  * valid until the next call */
 const char* bhip_ctx_lean_key_form(bhip_ctx* ctx);
+/* which loaded column each chain step of that launch used, as a list of step numbers: "0,1,2,3,2" where the kernel formed step
+ * 4's value from the column step 2 loaded (two steps of the plan read one column, and the kernel loaded it once); "none" where
+ * every step loaded its own column; "" before the first such launch; valid until the next call */
+const char* bhip_ctx_lean_step_alias(bhip_ctx* ctx);
 /* how the last GlobalLimitExec / LocalLimitExec directly over a SortExec ran: "topk" (the rows that can be among the first k were
  * selected by a threshold on the first sort key, and only they were sorted), "topk_fallback" (the selection declined every batch —
  * too many candidates, a small batch, a first key it does not image — and the plain sort was cut to k), "sort" (the full-sort
