@@ -26,7 +26,14 @@ struct Error : std::runtime_error {
     bhip_status code;
     Error(bhip_status c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
+// The keys do not fit the 16-byte packed key: too many key parts or too wide a layout at plan time (ProgramBuilder::add_key / finish),
+// a Utf8 value longer than its share at run time (check_scan_flags).  HashAggregateExec and HashJoinExec catch it and take their
+// wide-key forms; everybody else sees an ordinary BHIP_ENOTIMPL.
+struct KeyWidthError : Error {
+    explicit KeyWidthError(const std::string& m) : Error(BHIP_ENOTIMPL, m) {}
+};
 [[noreturn]] inline void fail(bhip_status c, const std::string& m) { throw Error(c, m); }
+[[noreturn]] inline void fail_key_width(const std::string& m) { throw KeyWidthError(m); }
 inline void hip_check(hipError_t e, const char* what) {
     if (e != hipSuccess) {
         if (e == hipErrorOutOfMemory) fail(BHIP_EOOM, std::string(what) + ": " + hipGetErrorString(e));

@@ -567,7 +567,7 @@ public:
             std::lock_guard<std::mutex> g(mu_);
             std::vector<BatchPtr> live;
             for (auto& b : got) if (b->n_rows) live.push_back(b);
-            BatchPtr out = live.empty() ? got[0] : live.size() == 1 ? live[0] : concat_batches(ex, in->schema, live);
+            BatchPtr out = live.empty() ? got[0] : concat_batches(ex, in->schema, live);     // (no rows: a received batch serves as the empty one)
             HIP_CHECK(hipStreamSynchronize(stream_));
             if (st) {
                 st->rows_in = (uint64_t)in->n_rows; st->rows_out = (uint64_t)out->n_rows; st->streamed = 0;
@@ -760,12 +760,9 @@ protected:
     BatchPtr drain_input(const Exec& ex) const {
         std::vector<BatchPtr> all;
         const int n_in = input_->output_partitioning().count;
-        for (int p = 0; p < n_in; ++p) {
-            auto s = input_->execute(p, ex);
-            while (BatchPtr b = s->next())
-                if (b->n_rows) all.push_back(materialize_batch(ex, b));
-        }
-        BatchPtr one = all.empty() ? empty_batch(ex, input_->schema()) : all.size() == 1 ? all[0] : concat_batches(ex, input_->schema(), all);
+        for (int p = 0; p < n_in; ++p)
+            for (auto& b : nonempty_batches(*input_->execute(p, ex))) all.push_back(materialize_batch(ex, b));
+        BatchPtr one = single_batch(ex, input_->schema(), all);
         stream_wait(ex);
         return one;
     }

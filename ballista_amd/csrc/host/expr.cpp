@@ -1099,7 +1099,7 @@ void ProgramBuilder::set_predicate(const ExprPtr& e) {
 }
 
 void ProgramBuilder::add_key(const ExprPtr& e, bool force_not_null) {
-    if ((int)keys_.size() >= VM_MAX_KEYPARTS) fail(BHIP_ENOTIMPL, "more than 8 key columns");
+    if ((int)keys_.size() >= VM_MAX_KEYPARTS) fail_key_width("more than 8 key columns");
     const int t = expr_type(e, schema_);
     const bool nullable = !force_not_null && expr_nullable(e, schema_);
     Operand o = compile(e);
@@ -1156,7 +1156,7 @@ void ProgramBuilder::finish(ScanParams& P) {
         else fixed += k.width;
     }
     if (!hash_only_ && (fixed > 16 || (n_utf8 > 0 && (16 - fixed) / n_utf8 < 2)))
-        fail(BHIP_ENOTIMPL, "key columns do not fit the 16-byte packed key");
+        fail_key_width("key columns do not fit the 16-byte packed key");
     const int utf8_width = n_utf8 ? (16 - fixed) / n_utf8 : 0;
     bool has_utf8_loads = false;
     for (auto& k : keys_) {

@@ -17,14 +17,29 @@ namespace bhip {
 
 namespace {
 const char* const kRepName = "__group_rep";
-}  // namespace
 
-bool key_width_error(const Error& e) {
-    if (e.code != BHIP_ENOTIMPL) return false;
-    const std::string m = e.what();
-    // (more key parts than one program packs: the same answer as a layout wider than 16 bytes)
-    return m.find("packed key") != std::string::npos || m.find("packed-key") != std::string::npos || m.find("more than 8 key columns") != std::string::npos;
+// The 64-bit row hash of `exprs` over every row of `in`, in the caller's scratch.  One hash program holds VM_MAX_KEYPARTS key parts: up to
+// 8 expressions are one pass, 9 .. 16 a second pass over the rest into `second` (else null).  The kernels fold the two hashes of a row;
+// equality is on the key columns either way.
+struct RowHashes { uint64_t* first; uint64_t* second; };
+RowHashes hash_rows(const Exec& ex, Temp& tmp, const Schema& schema, const Batch& in, const std::vector<ExprPtr>& exprs) {
+    const size_t n = (size_t)in.n_rows;
+    RowHashes h{tmp.get<uint64_t>(n), exprs.size() > (size_t)VM_MAX_KEYPARTS ? tmp.get<uint64_t>(n) : nullptr};
+    ScanStatus* st = tmp.get<ScanStatus>(1);
+    for (size_t first = 0; first < exprs.size(); first += VM_MAX_KEYPARTS) {
+        ProgramBuilder pb(schema);
+        pb.set_hash_only();
+        for (size_t i = first; i < std::min(exprs.size(), first + VM_MAX_KEYPARTS); ++i) pb.add_key(exprs[i]);
+        ScanParams P;
+        pb.finish(P);
+        ProgramBuilder::bind(P, pb.columns(), in, pb.creates_nulls());
+        HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
+        TIMED_LAUNCH(ex, "scan_keys", launch_scan_keys(ex.cfg(), P, nullptr, first ? h.second : h.first, nullptr, st));
+        check_scan_status(ex, st);
+    }
+    return h;
 }
+}  // namespace
 
 bool HashAggregateExec::run_single_partial(const Exec& ex, std::vector<BatchPtr>& out) const {
     static const bool disabled = env_flag("BHIP_NO_FINAL_ELISION");
@@ -50,8 +65,8 @@ bool HashAggregateExec::run_single_partial(const Exec& ex, std::vector<BatchPtr>
         try {
             out = pa->run_packed(0, ex, this);
             return true;
-        } catch (const Error& e) {
-            if (group_.empty() || !key_width_error(e)) throw;
+        } catch (const KeyWidthError&) {
+            if (group_.empty()) throw;                       // no GROUP BY, no wide form
             pa->wide_keys_.store(true);
         }
     }
@@ -87,8 +102,8 @@ std::vector<BatchPtr> HashAggregateExec::run(int partition, const Exec& ex) cons
     if (!group_.empty() && wide_keys_.load()) return run_wide(partition, ex);
     try {
         return run_packed(partition, ex);
-    } catch (const Error& e) {
-        if (group_.empty() || !key_width_error(e)) throw;
+    } catch (const KeyWidthError&) {
+        if (group_.empty()) throw;
     }
     wide_keys_.store(true);
     return run_wide(partition, ex);
@@ -98,41 +113,25 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
     const SchemaPtr in_schema = input_->schema();
     if (in_schema->index_of(kRepName) >= 0) fail(BHIP_EINVAL, std::string("column name '") + kRepName + "' is reserved");
     if (group_.size() > (size_t)VM_MAX_COLS) fail(BHIP_ENOTIMPL, "more than 16 group expressions");
-    std::vector<BatchPtr> parts;
-    {
-        auto s = input_->execute(partition, ex);
-        while (BatchPtr b = s->next())
-            if (b->n_rows > 0) parts.push_back(b);
-    }
+    std::vector<BatchPtr> parts = nonempty_batches(*input_->execute(partition, ex));
     if (parts.empty()) return {};
-    const BatchPtr in = parts.size() == 1 ? parts[0] : concat_batches(ex, in_schema, parts);
+    const BatchPtr in = concat_batches(ex, in_schema, parts);
     parts.clear();
     const int64_t n = in->n_rows;
     if (n > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "wide-key aggregate over more than 2^31 input rows per partition");
     const LaunchCfg cfg = ex.cfg();
 
     // ---- key columns, their row hashes, the representative of every row -------------------------------------
+    std::vector<ExprPtr> exprs;
     std::vector<Column> keys;
-    for (auto& g : group_) keys.push_back(evaluate_column(ex, *in, g.first));
+    for (auto& g : group_) {
+        exprs.push_back(g.first);
+        keys.push_back(evaluate_column(ex, *in, g.first));
+    }
     Column rep = alloc_column(ex, DT_INT32, n, false);
     {
         Temp tmp(ex);
-        // one hash program holds VM_MAX_KEYPARTS key parts: up to 8 group expressions are one pass, 9 .. 16 a second pass over the rest
-        // (the kernel folds the two hashes of a row; equality is on the key columns either way)
-        uint64_t* hashes = tmp.get<uint64_t>((size_t)n);
-        uint64_t* hashes2 = group_.size() > (size_t)VM_MAX_KEYPARTS ? tmp.get<uint64_t>((size_t)n) : nullptr;
-        ScanStatus* st = tmp.get<ScanStatus>(1);
-        for (size_t first = 0; first < group_.size(); first += VM_MAX_KEYPARTS) {
-            ProgramBuilder pb(*in_schema);
-            pb.set_hash_only();
-            for (size_t i = first; i < std::min(group_.size(), first + VM_MAX_KEYPARTS); ++i) pb.add_key(group_[i].first);
-            ScanParams P;
-            pb.finish(P);
-            ProgramBuilder::bind(P, pb.columns(), *in, pb.creates_nulls());
-            HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
-            TIMED_LAUNCH(ex, "scan_keys", launch_scan_keys(cfg, P, nullptr, first ? hashes2 : hashes, nullptr, st));
-            check_scan_status(ex, st);
-        }
+        const RowHashes h = hash_rows(ex, tmp, *in_schema, *in, exprs);
         const uint64_t cap = table_capacity((uint64_t)n);
         uint32_t* table = tmp.get<uint32_t>(cap);
         HIP_CHECK(hipMemsetAsync(table, 0, cap * 4, ex.stream));
@@ -140,7 +139,7 @@ std::vector<BatchPtr> HashAggregateExec::run_wide(int partition, const Exec& ex)
         memset(&K, 0, sizeof(K));
         K.n = (int32_t)keys.size();
         for (size_t i = 0; i < keys.size(); ++i) K.col[i] = keys[i].ref();
-        TIMED_LAUNCH(ex, "wide_key_assign", launch_wide_key_assign(cfg, K, hashes, hashes2, table, cap - 1, (uint32_t)n, rep.data->as<uint32_t>()));
+        TIMED_LAUNCH(ex, "wide_key_assign", launch_wide_key_assign(cfg, K, h.first, h.second, table, cap - 1, (uint32_t)n, rep.data->as<uint32_t>()));
     }
 
     // ---- the ordinary aggregate, keyed by the representative row ---------------------------------------------
@@ -255,12 +254,7 @@ std::vector<BatchPtr> HashAggregateExec::run_single(int partition, const Exec& e
         return reschema(drain(*s));
     }
     // this partition alone, as one resident batch
-    std::vector<BatchPtr> parts;
-    {
-        auto s = input_->execute(partition, ex);
-        while (BatchPtr b = s->next())
-            if (b->n_rows > 0) parts.push_back(b);
-    }
+    std::vector<BatchPtr> parts = nonempty_batches(*input_->execute(partition, ex));
     if (distinct_args_.empty()) {
         if (parts.empty() && !group_.empty()) return {};
         auto src = std::make_shared<MemoryExec>(ex.ctx, in_schema, std::vector<std::vector<BatchPtr>>{parts});
@@ -269,7 +263,7 @@ std::vector<BatchPtr> HashAggregateExec::run_single(int partition, const Exec& e
         return reschema(drain(*s));
     }
     if (parts.empty() && !group_.empty()) return {};
-    const BatchPtr in = parts.empty() ? empty_batch(ex, in_schema) : parts.size() == 1 ? parts[0] : concat_batches(ex, in_schema, parts);
+    const BatchPtr in = single_batch(ex, in_schema, parts);
     parts.clear();
     const int64_t n = in->n_rows;
     if (n > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "DISTINCT aggregate over more than 2^31 input rows per partition");
@@ -288,21 +282,7 @@ std::vector<BatchPtr> HashAggregateExec::run_single(int partition, const Exec& e
             std::vector<ExprPtr> cols;
             for (auto& g : group_) cols.push_back(g.first);
             cols.push_back(xe);
-            // the row hash of (group keys ..., x): one hash program holds VM_MAX_KEYPARTS parts, a second pass covers the rest (run_wide)
-            uint64_t* hashes = tmp.get<uint64_t>((size_t)n);
-            uint64_t* hashes2 = cols.size() > (size_t)VM_MAX_KEYPARTS ? tmp.get<uint64_t>((size_t)n) : nullptr;
-            ScanStatus* st = tmp.get<ScanStatus>(1);
-            for (size_t first = 0; first < cols.size(); first += VM_MAX_KEYPARTS) {
-                ProgramBuilder pb(*in_schema);
-                pb.set_hash_only();
-                for (size_t i = first; i < std::min(cols.size(), first + VM_MAX_KEYPARTS); ++i) pb.add_key(cols[i]);
-                ScanParams P;
-                pb.finish(P);
-                ProgramBuilder::bind(P, pb.columns(), *in, pb.creates_nulls());
-                HIP_CHECK(hipMemsetAsync(st, 0, sizeof(ScanStatus), ex.stream));
-                TIMED_LAUNCH(ex, "scan_keys", launch_scan_keys(cfg, P, nullptr, first ? hashes2 : hashes, nullptr, st));
-                check_scan_status(ex, st);
-            }
+            const RowHashes h = hash_rows(ex, tmp, *in_schema, *in, cols);      // the row hash of (group keys ..., x)
             const uint64_t cap = table_capacity((uint64_t)n);
             uint32_t* table = tmp.get<uint32_t>(cap);
             uint32_t* slot_of = tmp.get<uint32_t>((size_t)n);
@@ -314,7 +294,7 @@ std::vector<BatchPtr> HashAggregateExec::run_single(int partition, const Exec& e
             K.col[keys.size()] = x.ref();
             const uint64_t* xvalid = x.validity_words();
             marked.validity = validity_buffer(ex, n);
-            TIMED_LAUNCH_N(ex, "distinct_claim", n, launch_distinct_claim(cfg, K, xvalid, hashes, hashes2, table, cap - 1, (uint32_t)n, slot_of));
+            TIMED_LAUNCH_N(ex, "distinct_claim", n, launch_distinct_claim(cfg, K, xvalid, h.first, h.second, table, cap - 1, (uint32_t)n, slot_of));
             TIMED_LAUNCH_N(ex, "distinct_mark", n, launch_distinct_mark(cfg, xvalid, table, slot_of, (uint32_t)n, marked.validity->as<uint64_t>()));
         }
         s2->fields.push_back(Field{distinct_name(d), x.dtype, true});
@@ -339,16 +319,7 @@ std::vector<BatchPtr> HashAggregateExec::run_single(int partition, const Exec& e
 // and the result's strings are gathered through the sort permutation.
 std::vector<BatchPtr> HashAggregateExec::run_strings(int partition, const Exec& ex) const {
     const SchemaPtr in_schema = input_->schema();
-    std::vector<BatchPtr> parts;
-    {
-        auto s = input_->execute(partition, ex);
-        while (BatchPtr b = s->next())
-            if (b->n_rows > 0) parts.push_back(b);
-    }
-    BatchPtr in;
-    if (parts.empty()) in = empty_batch(ex, in_schema);
-    else in = parts.size() == 1 ? parts[0] : concat_batches(ex, in_schema, parts);
-    parts.clear();
+    const BatchPtr in = single_batch(ex, in_schema, nonempty_batches(*input_->execute(partition, ex)));
     const int64_t n = in->n_rows;
     const LaunchCfg cfg = ex.cfg();
 

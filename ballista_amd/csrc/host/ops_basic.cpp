@@ -24,6 +24,13 @@ std::vector<BatchPtr> drain(RecordBatchStream& s) {
     return out;
 }
 
+std::vector<BatchPtr> nonempty_batches(RecordBatchStream& s) {
+    std::vector<BatchPtr> out;
+    while (BatchPtr b = s.next())
+        if (b->n_rows > 0) out.push_back(b);
+    return out;
+}
+
 static void render(const PlanPtr& p, int depth, std::ostringstream& o) {
     for (int i = 0; i < depth; ++i) o << "  ";
     o << p->describe() << "\n";
@@ -43,8 +50,7 @@ void check_scan_status(const Exec& ex, const ScanStatus* dev_status, ScanStatus*
 
 void check_scan_flags(const ScanStatus& st) {
     if (st.flags & SCAN_ERR_DIV_ZERO) fail(BHIP_EEXEC, "Arrow error: Divide by zero error");
-    if (st.flags & SCAN_ERR_KEY_TOO_LONG)
-        fail(BHIP_ENOTIMPL, "a Utf8 key value is longer than the packed-key path supports");
+    if (st.flags & SCAN_ERR_KEY_TOO_LONG) fail_key_width("a Utf8 key value is longer than the packed-key path supports");
 }
 
 static ScanStatus* new_status(Temp& tmp) {
@@ -244,6 +250,10 @@ BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema) {
     auto e = new_batch(ex.ctx, schema, 0);
     for (auto& f : schema->fields) e->cols.push_back(alloc_column(ex, f.dtype, 0, false));
     return e;
+}
+
+BatchPtr single_batch(const Exec& ex, const SchemaPtr& schema, const std::vector<BatchPtr>& parts) {
+    return parts.empty() ? empty_batch(ex, schema) : concat_batches(ex, schema, parts);      // (one part: concat_batches returns it as it is)
 }
 
 Column take_column_nullable(const Exec& ex, const Column& c, const uint32_t* idx, int64_t n) {

@@ -118,8 +118,7 @@ HashJoinExec::HashJoinExec(PlanPtr left, PlanPtr right, std::vector<std::pair<st
         ProgramBuilder pb(ls);
         for (auto& k : left_keys_) pb.add_key(make_column(k), true);
         pb.finish(P);
-    } catch (const Error& e) {
-        if (!key_width_error(e)) throw;
+    } catch (const KeyWidthError&) {
         static_wide_ = true;
         ProgramBuilder hb(ls);
         hb.set_hash_only();
@@ -502,16 +501,13 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
     auto bs = std::make_shared<JoinBuildSide>();
     std::vector<BatchPtr> parts;
     const int np = left_->output_partitioning().count;
-    for (int p = 0; p < np; ++p) {
-        auto s = open_join_child(left_, p, ex, left_keys_);
-        while (BatchPtr b = s->next())
-            if (b->n_rows > 0) parts.push_back(b);
-    }
+    for (int p = 0; p < np; ++p)
+        for (auto& b : nonempty_batches(*open_join_child(left_, p, ex, left_keys_))) parts.push_back(b);
     // concat works on ordinary columns; and a small build side (Q5: the five nations of a region) is gathered here, once, so that
     // all its columns travel on as views over ONE index vector (a view in, a view out: one more index vector to compose per join above)
     if (parts.size() > 1 || (parts.size() == 1 && parts[0]->n_rows <= 65536))
         for (auto& b : parts) b = materialize_batch(ex, b);
-    bs->batch = parts.empty() ? empty_batch(ex, left_->schema()) : concat_batches(ex, left_->schema(), parts);
+    bs->batch = single_batch(ex, left_->schema(), parts);
     const int64_t n = bs->batch->n_rows;
     // build rows are addressed by 32-bit slots / ranks in every table form
     if (n > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "hash join build side of more than 2^31 rows per partition");
@@ -554,8 +550,7 @@ std::shared_ptr<const JoinBuildSide> HashJoinExec::build_side(const Exec& ex) co
         if (!wide) {
             try {
                 build_general_table(ex, bs.get(), left_keys_, cap, false);
-            } catch (const Error& e) {
-                if (!key_width_error(e)) throw;                 // a build value longer than its share of the packed key
+            } catch (const KeyWidthError&) {                    // a build value longer than its share of the packed key
                 wide_keys_.store(true);
                 wide = true;
             }
@@ -838,8 +833,7 @@ struct JoinExec::Probe {
         if (!t->wide) {
             try {
                 pk = side_keys(ex, probe, rcols, false);
-            } catch (const Error& e) {
-                if (!key_width_error(e)) throw;
+            } catch (const KeyWidthError&) {
                 t = sibling = H->wide_sibling(ex, *bs);
             }
         }
@@ -1211,12 +1205,9 @@ std::shared_ptr<const JoinBuildSide> NestedLoopJoinExec::build_side(const Exec& 
     auto bs = std::make_shared<JoinBuildSide>();
     std::vector<BatchPtr> parts;
     const int np = left_->output_partitioning().count;
-    for (int p = 0; p < np; ++p) {
-        auto s = left_->execute(p, ex);
-        while (BatchPtr b = s->next())
-            if (b->n_rows > 0) parts.push_back(materialize_batch(ex, b));
-    }
-    bs->batch = parts.empty() ? empty_batch(ex, left_->schema()) : concat_batches(ex, left_->schema(), parts);
+    for (int p = 0; p < np; ++p)
+        for (auto& b : nonempty_batches(*left_->execute(p, ex))) parts.push_back(materialize_batch(ex, b));
+    bs->batch = single_batch(ex, left_->schema(), parts);
     // build rows are 32-bit indices, and 0xFFFFFFFF is the NULL row of the outer joins
     if (bs->batch->n_rows > 0x7FFFFFF0ll) fail(BHIP_ENOTIMPL, "nested loop join build side of more than 2^31 rows");
     stream_wait(ex);                     // other tasks (other streams) read the batch: complete before it is published

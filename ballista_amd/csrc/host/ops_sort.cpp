@@ -67,12 +67,7 @@ StreamPtr SortExec::execute(int partition, const Exec& ex) const {
     if (input_->output_partitioning().count != 1) fail(BHIP_EINVAL, "SortExec requires a single input partition");
     auto self = std::static_pointer_cast<const SortExec>(shared_from_this());
     return StreamPtr(new LazyStream(schema(), [self, ex]() -> std::vector<BatchPtr> {
-        std::vector<BatchPtr> parts;
-        {
-            auto s = self->input_->execute(0, ex);
-            while (BatchPtr b = s->next())
-                if (b->n_rows > 0) parts.push_back(b);
-        }
+        const std::vector<BatchPtr> parts = nonempty_batches(*self->input_->execute(0, ex));
         if (parts.empty()) return {};
         trace_point("sort: input ready");
         BatchPtr in = concat_batches(ex, self->schema(), parts);

@@ -173,12 +173,7 @@ StreamPtr WindowAggExec::execute(int partition, const Exec& ex) const {
     if (input_->output_partitioning().count != 1) fail(BHIP_EINVAL, "WindowAggExec requires a single input partition: put a MergeExec below it");
     auto self = std::static_pointer_cast<const WindowAggExec>(shared_from_this());
     return StreamPtr(new LazyStream(schema(), [self, ex]() -> std::vector<BatchPtr> {
-        std::vector<BatchPtr> parts;
-        {
-            auto s = self->input_->execute(0, ex);
-            while (BatchPtr b = s->next())
-                if (b->n_rows > 0) parts.push_back(b);
-        }
+        const std::vector<BatchPtr> parts = nonempty_batches(*self->input_->execute(0, ex));
         if (parts.empty()) return {};
         return {self->run(ex, concat_batches(ex, self->input_->schema(), parts))};
     }));

@@ -56,6 +56,8 @@ protected:
 std::string display_plan(const PlanPtr& p);
 void check_partition(const ExecutionPlan& p, int partition);
 std::vector<BatchPtr> drain(RecordBatchStream& s);
+// drain, without the batches of zero rows: nonempty_batches(*plan->execute(partition, ex))
+std::vector<BatchPtr> nonempty_batches(RecordBatchStream& s);
 
 // ---- streams -----------------------------------------------------------------------------------
 class VecStream : public RecordBatchStream {   // MemoryStream (memory_stream.rs:29-55)
@@ -424,10 +426,8 @@ private:
 // split a batch by hash(exprs) % n, keeping input order inside each part
 std::vector<BatchPtr> hash_partition_batch(const Exec& ex, const BatchPtr& in, const std::vector<ExprPtr>& exprs, int n);
 void check_scan_status(const Exec& ex, const ScanStatus* dev_status, ScanStatus* host_out = nullptr);
-void check_scan_flags(const ScanStatus& host_status);   // the same checks on a status already read back
-// `e` says that keys do not fit the 16-byte packed key — the layout or the number of key parts at plan time, or a Utf8 value at run time (ops_agg_wide.cpp):
-// what HashAggregateExec and HashJoinExec answer with their wide-key forms
-bool key_width_error(const Error& e);
+// the same checks on a status already read back; a Utf8 key value too long for its share of the packed key is a KeyWidthError (core.hpp)
+void check_scan_flags(const ScanStatus& host_status);
 // value of `e` over `in` as a column (a plain Column reference shares the input buffers)
 Column evaluate_column(const Exec& ex, const Batch& in, const ExprPtr& e);
 struct SortDesc;
@@ -445,6 +445,8 @@ Column materialize_column(const Exec& ex, const Column& c);
 BatchPtr materialize_batch(const Exec& ex, const BatchPtr& b);
 // a batch of `schema` with zero rows (a child that yielded none)
 BatchPtr empty_batch(const Exec& ex, const SchemaPtr& schema);
+// batches with rows as ONE batch: none -> empty_batch, one -> that batch itself, several -> concat_batches
+BatchPtr single_batch(const Exec& ex, const SchemaPtr& schema, const std::vector<BatchPtr>& parts);
 // n NULLs of the given type
 Column null_column(const Exec& ex, int dtype, int64_t n);
 // A Utf8 column computed row by row: per-row lengths -> offsets (one scan) -> data buffer (core.hpp utf8_alloc_data) -> bytes.  The sum of the lengths stays on

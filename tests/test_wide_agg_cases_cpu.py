@@ -2,6 +2,8 @@
 and start at the stated slot, its chain wraps past slot 0, its boundary values straddle the packed key's share by one byte, and each
 wrong equality (and a probe loop without the wrap) changes the number of groups of the case built against it, while the right one
 gives the oracle's — computed with the restated hash and slot arithmetic and with constants looked up in the sources."""
+import glob
+import os
 import re
 
 import numpy as np
@@ -29,14 +31,17 @@ def test_constants_are_the_sources():
     for line in W.HEAD_SOURCE:
         assert line in agg, line
     assert (W.HEAD_ROWS, W.HEAD_SAMPLE) == ((1 << 17) + 1, 32768)
-    # the two messages key_width_error matches by their text, and the third it takes for the same answer
-    assert 'fail(BHIP_ENOTIMPL, "%s");' % W.MESSAGES["layout"] in W.source_text("host/expr.cpp")
-    assert 'fail(BHIP_ENOTIMPL, "%s");' % W.MESSAGES["value"] in W.source_text("host/ops_basic.cpp")
-    assert 'fail(BHIP_ENOTIMPL, "%s");' % W.MESSAGES["key_parts"] in W.source_text("host/expr.cpp")
-    at = wide.index("bool key_width_error(const Error& e) {")
-    body = wide[at:wide.index("\n}", at)]
-    assert '"packed key"' in body and '"packed-key"' in body and '"%s"' % W.MESSAGES["key_parts"] in body
-    assert "packed key" in W.MESSAGES["layout"] and "packed-key" in W.MESSAGES["value"]
+    # the three messages are raised as a KeyWidthError, the type the wide-key routes catch: by nobody else, and nobody reads an error's text
+    assert 'fail_key_width("%s");' % W.MESSAGES["layout"] in W.source_text("host/expr.cpp")
+    assert 'fail_key_width("%s");' % W.MESSAGES["value"] in W.source_text("host/ops_basic.cpp")
+    assert 'fail_key_width("%s");' % W.MESSAGES["key_parts"] in W.source_text("host/expr.cpp")
+    host = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(RC.CSRC, "host", "*"))}
+    assert sum(text.count("fail_key_width(") for name, text in host.items() if name.endswith(".cpp")) == 3
+    assert "[[noreturn]] inline void fail_key_width(const std::string& m) { throw KeyWidthError(m); }" in host["core.hpp"]
+    assert "explicit KeyWidthError(const std::string& m) : Error(BHIP_ENOTIMPL, m) {}" in host["core.hpp"]
+    for name, text in host.items():
+        assert "key_width_error" not in text and "what()).find" not in text and "m.find(" not in text, name
+    assert wide.count("catch (const KeyWidthError&)") == 2 and host["ops_join.cpp"].count("catch (const KeyWidthError&)") == 3
     for line in W.ELISION_SOURCE:
         assert line in wide, line
     assert RC.TABLE_CAPACITY_SOURCE in W.source_text("host/core.hpp")
