@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "host/hash_kernels.h"
 #include "launch_common.h"
+#include "scan_device.h"
 
 namespace bhip {
 
@@ -177,10 +178,8 @@ tiny_rank_build_kernel(const void* __restrict__ keys_v, const uint64_t* __restri
     if (build) {
         // set bits before each granule: two granules per thread, a workgroup scan of the pair sums
         const uint32_t g0 = 2 * tid, c0 = g0 < n_gran ? (uint32_t)__popc(s_bits[g0]) : 0u, c1 = g0 + 1 < n_gran ? (uint32_t)__popc(s_bits[g0 + 1]) : 0u;
-        uint32_t x = c0 + c1;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if (lane >= (uint32_t)d) x += y; }
-        if (lane == 63) s_wave[wave] = x;
+        const uint32_t x = wave_inclusive_sum(c0 + c1);
+        if (lane == 63) s_wave[wave] = x;                     // (its own cross-wave sum: one barrier, the waves before this one only)
         __syncthreads();
         uint32_t before = x - (c0 + c1);
         for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];

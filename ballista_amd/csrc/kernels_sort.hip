@@ -12,6 +12,7 @@
 // passes whose byte is the same in every key are skipped (one OR-reduction per key tells).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+#include "scan_device.h"
 #include "sort_device.h"
 #include "sort_kernels.h"
 #include "util_kernels.h"
@@ -608,15 +609,8 @@ rowsort_kernel(RowSortArgs A) {
         if (c.dtype == DT_UTF8) {
             const int32_t o0 = in ? c.offsets[src] : 0;
             const uint32_t len = in ? (uint32_t)(c.offsets[src + 1] - o0) : 0u;
-            uint32_t x = len;                      // inclusive scan inside the wave, then the wave totals
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-            if (lane == 63) s_wave[wave] = x;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-            for (int w = 0; w < ROWSORT_MAX_ROWS / 64; ++w) { if (w < wave) before += s_wave[w]; total += s_wave[w]; }
-            __syncthreads();
-            const uint32_t d0 = before + x - len;
+            uint32_t total;
+            const uint32_t d0 = block_exclusive_sum<ROWSORT_MAX_ROWS / 64>(len, s_wave, total);
             if (in) {
                 A.out_offsets[ci][i] = (int32_t)d0;
                 const uint8_t* s = reinterpret_cast<const uint8_t*>(c.data) + o0;

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "util_kernels.h"
+#include "scan_device.h"
 #include "vm_device.h"
 
 namespace bhip {
@@ -22,29 +23,31 @@ constexpr int SCAN_BLOCK = 256;
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_CHUNK = SCAN_BLOCK * SCAN_ITEMS;   // 4096
 
-__device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t* s_wave, uint64_t* total) {
-    // wave inclusive scan by shuffles, then 4 wave totals through LDS
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t x = v;
+// the chunk body: elements [base, base + SCAN_CHUNK) of `in` below n.  A thread owns SCAN_ITEMS consecutive elements, so the scan order
+// is the element order.  store(j, x, run) gets element j, its word x and carry + the sum of value(x') over the elements before j.
+// Returns the chunk's own sum.
+template <class Value, class Store>
+__device__ inline uint64_t scan_chunk(const uint32_t* in, int64_t n, int64_t base, uint64_t carry, uint64_t* s_wave, Value value, Store store) {
+    uint32_t x[SCAN_ITEMS];
+    uint64_t sum = 0;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t lo = __shfl_up((uint32_t)x, d, 64), hi = __shfl_up((uint32_t)(x >> 32), d, 64);
-        const uint64_t y = ((uint64_t)hi << 32) | lo;
-        if (lane >= d) x += y;
+    for (int i = 0; i < SCAN_ITEMS; ++i) {
+        const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
+        x[i] = j < n ? in[j] : 0;
+        sum += value(x[i]);
     }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    uint64_t wave_off = 0, tot = 0;
+    uint64_t tot;
+    uint64_t run = carry + block_exclusive_sum<SCAN_BLOCK / 64>(sum, s_wave, tot);
 #pragma unroll
-    for (int w = 0; w < SCAN_BLOCK / 64; ++w) {
-        const uint64_t s = s_wave[w];
-        if (w < wave) wave_off += s;
-        tot += s;
+    for (int i = 0; i < SCAN_ITEMS; ++i) {
+        const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
+        if (j < n) store(j, x[i], run);
+        run += value(x[i]);
     }
-    __syncthreads();
-    if (total) *total = tot;
-    return wave_off + x - v;
+    return tot;
 }
+// the plain scan: the element is its own value
+struct ScanSelf { __device__ uint32_t operator()(uint32_t x) const { return x; } };
 
 __global__ void __launch_bounds__(SCAN_BLOCK)
 scan_chunk_sums_kernel(const uint32_t* in, int64_t n, uint64_t* chunk_sums) {
@@ -57,7 +60,7 @@ scan_chunk_sums_kernel(const uint32_t* in, int64_t n, uint64_t* chunk_sums) {
         if (j < n) v += in[j];
     }
     uint64_t tot;
-    block_exclusive_scan(v, s_wave, &tot);
+    block_exclusive_sum<SCAN_BLOCK / 64>(v, s_wave, tot);
     if (threadIdx.x == 0) chunk_sums[blockIdx.x] = tot;
 }
 
@@ -69,68 +72,40 @@ scan_sums_kernel(uint64_t* chunk_sums, int64_t n_chunks, uint64_t* total_out) {
         const int64_t j = b + threadIdx.x;
         const uint64_t v = j < n_chunks ? chunk_sums[j] : 0;
         uint64_t tot;
-        const uint64_t ex = block_exclusive_scan(v, s_wave, &tot);
+        const uint64_t ex = block_exclusive_sum<SCAN_BLOCK / 64>(v, s_wave, tot);
         if (j < n_chunks) chunk_sums[j] = carry + ex;
         carry += tot;
     }
     if (threadIdx.x == 0 && total_out) *total_out = carry;
 }
 
-template <class OutT>
-__global__ void __launch_bounds__(SCAN_BLOCK)
-scan_apply_kernel(const uint32_t* in, int64_t n, const uint64_t* chunk_offsets, OutT* out, int write_total) {
-    __shared__ uint64_t s_wave[4];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK;
-    // thread owns SCAN_ITEMS consecutive elements so the scan order is the element order
-    uint32_t x[SCAN_ITEMS];
-    uint64_t sum = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-        x[i] = j < n ? in[j] : 0;
-        sum += x[i];
-    }
-    uint64_t run = chunk_offsets[blockIdx.x] + block_exclusive_scan(sum, s_wave, nullptr);
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-        if (j < n) out[j] = (OutT)run;
-        run += x[i];
-        if (write_total && j == n - 1) out[n] = (OutT)run;
-    }
-}
-
 // up to SCAN_TWO_LAUNCH_CHUNKS chunks: no scan_sums launch — every workgroup adds up the RAW sums of the chunks before its own (a few KB
 // from L2) and the last one writes the grand total: two launches instead of three (a Q3 step runs eight scans of this size: the tile
 // counts of a probe, the rank map's granules, the run flags of the aggregate, the bins of the bucket sort)
 constexpr int64_t SCAN_TWO_LAUNCH_CHUNKS = 2048;
-template <class OutT>
-__global__ void __launch_bounds__(SCAN_BLOCK)
-scan_apply_raw_kernel(const uint32_t* in, int64_t n, const uint64_t* chunk_sums, OutT* out, int write_total, uint64_t* total_out) {
-    __shared__ uint64_t s_wave[4];
+// the raw-sums carry: -> the sum of the raw chunk sums before this workgroup's chunk.  The last workgroup adds its own chunk's sum and
+// has the grand total, which its first thread writes (writes_raw_total)
+__device__ inline uint64_t raw_chunk_carry(const uint64_t* chunk_sums, uint64_t* s_wave) {
     uint64_t before = 0;
     for (int64_t j = threadIdx.x; j < (int64_t)blockIdx.x; j += SCAN_BLOCK) before += chunk_sums[j];
-    uint64_t chunk_off;
-    block_exclusive_scan(before, s_wave, &chunk_off);
-    const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK;
-    uint32_t x[SCAN_ITEMS];
-    uint64_t sum = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-        x[i] = j < n ? in[j] : 0;
-        sum += x[i];
-    }
-    uint64_t tot;
-    uint64_t run = chunk_off + block_exclusive_scan(sum, s_wave, &tot);
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-        if (j < n) out[j] = (OutT)run;
-        run += x[i];
-        if (write_total && j == n - 1) out[n] = (OutT)run;
-    }
-    if (total_out && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = chunk_off + tot;
+    uint64_t carry;
+    block_exclusive_sum<SCAN_BLOCK / 64>(before, s_wave, carry);
+    return carry;
+}
+__device__ inline bool writes_raw_total(const uint64_t* total_out) { return total_out && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0; }
+
+// RAW: chunk_offsets holds the chunks' own sums (no scan_sums launch in between); otherwise their exclusive scan, and scan_sums_kernel
+// has written total_out
+template <class OutT, bool RAW>
+__global__ void __launch_bounds__(SCAN_BLOCK)
+scan_apply_kernel(const uint32_t* in, int64_t n, const uint64_t* chunk_offsets, OutT* out, int write_total, uint64_t* total_out) {
+    __shared__ uint64_t s_wave[4];
+    const uint64_t carry = RAW ? raw_chunk_carry(chunk_offsets, s_wave) : chunk_offsets[blockIdx.x];
+    const uint64_t tot = scan_chunk(in, n, (int64_t)blockIdx.x * SCAN_CHUNK, carry, s_wave, ScanSelf(), [=](int64_t j, uint32_t x, uint64_t run) {
+        out[j] = (OutT)run;
+        if (write_total && j == n - 1) out[n] = (OutT)(run + x);
+    });
+    if (RAW && writes_raw_total(total_out)) *total_out = carry + tot;
 }
 
 // n <= SCAN_ONE_LAUNCH_MAX: the whole scan by ONE workgroup in one launch, chunk after chunk with a running carry (group
@@ -141,25 +116,8 @@ __global__ void __launch_bounds__(SCAN_BLOCK)
 scan_one_chunk_kernel(const uint32_t* in, int64_t n, OutT* out, int write_total, uint64_t* total_out) {
     __shared__ uint64_t s_wave[4];
     uint64_t carry = 0;
-    for (int64_t base = 0; base < n; base += SCAN_CHUNK) {
-        uint32_t x[SCAN_ITEMS];
-        uint64_t sum = 0;
-#pragma unroll
-        for (int i = 0; i < SCAN_ITEMS; ++i) {
-            const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-            x[i] = j < n ? in[j] : 0;
-            sum += x[i];
-        }
-        uint64_t tot;
-        uint64_t run = carry + block_exclusive_scan(sum, s_wave, &tot);
-#pragma unroll
-        for (int i = 0; i < SCAN_ITEMS; ++i) {
-            const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-            if (j < n) out[j] = (OutT)run;
-            run += x[i];
-        }
-        carry += tot;
-    }
+    for (int64_t base = 0; base < n; base += SCAN_CHUNK)
+        carry += scan_chunk(in, n, base, carry, s_wave, ScanSelf(), [out](int64_t j, uint32_t, uint64_t run) { out[j] = (OutT)run; });
     if (threadIdx.x == 0) {
         if (write_total) out[n] = (OutT)carry;
         if (total_out) *total_out = carry;
@@ -188,12 +146,12 @@ static hipError_t exclusive_scan_t(hipStream_t st, const uint32_t* in, int64_t n
     }
     hipLaunchKernelGGL(scan_chunk_sums_kernel, dim3((unsigned)n_chunks), dim3(SCAN_BLOCK), 0, st, in, n, sums);
     if (n_chunks <= SCAN_TWO_LAUNCH_CHUNKS) {
-        hipLaunchKernelGGL((scan_apply_raw_kernel<OutT>), dim3((unsigned)n_chunks), dim3(SCAN_BLOCK), 0, st, in, n, sums, out, write_total ? 1 : 0, total_out);
+        hipLaunchKernelGGL((scan_apply_kernel<OutT, true>), dim3((unsigned)n_chunks), dim3(SCAN_BLOCK), 0, st, in, n, sums, out, write_total ? 1 : 0, total_out);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, sums, n_chunks, total_out);
-    hipLaunchKernelGGL((scan_apply_kernel<OutT>), dim3((unsigned)n_chunks), dim3(SCAN_BLOCK), 0, st, in, n, sums, out,
-                       write_total ? 1 : 0);
+    hipLaunchKernelGGL((scan_apply_kernel<OutT, false>), dim3((unsigned)n_chunks), dim3(SCAN_BLOCK), 0, st, in, n, sums, out,
+                       write_total ? 1 : 0, (uint64_t*)nullptr);
     return hipGetLastError();
 }
 
@@ -225,28 +183,6 @@ constexpr int RP_ROUND = SCAN_BLOCK * 4;                 // 1024 granules per ro
 constexpr int RP_ROUNDS = 16;
 constexpr int RP_CHUNK = RP_ROUND * RP_ROUNDS;           // 16384 granules = 64 KiB of key-set bits per workgroup
 
-__device__ inline uint32_t block_exclusive_scan_u32(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    uint32_t wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_BLOCK / 64; ++w) {
-        const uint32_t sw = s_wave[w];
-        if (w < wave) wave_off += sw;
-        tot += sw;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + x - v;
-}
-
 __device__ inline uint4 rp_load4(const uint32_t* __restrict__ bits32, int64_t j, int64_t n) {
     // (the bits buffer is allocated in 64-bit words + 1: a 16-byte load that starts below n may read up to 12 bytes of padding
     // only when n is not a multiple of 4 — guarded element-wise there)
@@ -270,7 +206,7 @@ rank_pack_sums_kernel(const uint32_t* __restrict__ bits32, int64_t n, uint64_t* 
         v += (uint32_t)(__popc(x.x) + __popc(x.y) + __popc(x.z) + __popc(x.w));
     }
     uint32_t tot;
-    block_exclusive_scan_u32(v, s_wave, &tot);
+    block_exclusive_sum<SCAN_BLOCK / 64>(v, s_wave, tot);
     if (threadIdx.x == 0) chunk_sums[blockIdx.x] = tot;
 }
 
@@ -285,10 +221,8 @@ rank_pack_apply_kernel(const uint32_t* __restrict__ bits32, int64_t n, const uin
     uint64_t carry;
     if (RAW) {
         __shared__ uint64_t s_wave64[4];
-        uint64_t before = 0;
-        for (int64_t j = threadIdx.x; j < (int64_t)blockIdx.x; j += SCAN_BLOCK) before += chunk_offsets[j];
-        block_exclusive_scan(before, s_wave64, &carry);
-        if (total_out && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = carry + chunk_offsets[blockIdx.x];
+        carry = raw_chunk_carry(chunk_offsets, s_wave64);
+        if (writes_raw_total(total_out)) *total_out = carry + chunk_offsets[blockIdx.x];
     } else {
         carry = chunk_offsets[blockIdx.x];
     }
@@ -298,7 +232,7 @@ rank_pack_apply_kernel(const uint32_t* __restrict__ bits32, int64_t n, const uin
         const uint4 x = rp_load4(bits32, j, n);
         const uint32_t c0 = (uint32_t)__popc(x.x), c1 = (uint32_t)__popc(x.y), c2 = (uint32_t)__popc(x.z), c3 = (uint32_t)__popc(x.w);
         uint32_t tot;
-        const uint64_t run = carry + block_exclusive_scan_u32(c0 + c1 + c2 + c3, s_wave, &tot);
+        const uint64_t run = carry + block_exclusive_sum<SCAN_BLOCK / 64>(c0 + c1 + c2 + c3, s_wave, tot);
         const uint64_t p0 = (uint64_t)x.x | (run << 32), p1 = (uint64_t)x.y | ((run + c0) << 32), p2 = (uint64_t)x.z | ((run + c0 + c1) << 32),
                        p3 = (uint64_t)x.w | ((run + c0 + c1 + c2) << 32);
         if (j + 4 <= n) {
@@ -319,25 +253,9 @@ __global__ void __launch_bounds__(SCAN_BLOCK)
 rank_pack_one_kernel(const uint32_t* __restrict__ bits32, int64_t n, uint64_t* __restrict__ pack, uint64_t* total_out) {
     __shared__ uint64_t s_wave[4];
     uint64_t carry = 0;
-    for (int64_t base = 0; base < n; base += SCAN_CHUNK) {
-        uint32_t x[SCAN_ITEMS];
-        uint64_t sum = 0;
-#pragma unroll
-        for (int i = 0; i < SCAN_ITEMS; ++i) {
-            const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-            x[i] = j < n ? bits32[j] : 0;
-            sum += (uint32_t)__popc(x[i]);
-        }
-        uint64_t tot;
-        uint64_t run = carry + block_exclusive_scan(sum, s_wave, &tot);
-#pragma unroll
-        for (int i = 0; i < SCAN_ITEMS; ++i) {
-            const int64_t j = base + (int64_t)threadIdx.x * SCAN_ITEMS + i;
-            if (j < n) pack[j] = (uint64_t)x[i] | (run << 32);
-            run += (uint32_t)__popc(x[i]);
-        }
-        carry += tot;
-    }
+    for (int64_t base = 0; base < n; base += SCAN_CHUNK)
+        carry += scan_chunk(bits32, n, base, carry, s_wave, [](uint32_t x) { return (uint32_t)__popc(x); },
+                            [pack](int64_t j, uint32_t x, uint64_t run) { pack[j] = (uint64_t)x | (run << 32); });
     if (threadIdx.x == 0 && total_out) *total_out = carry;
 }
 
@@ -393,12 +311,7 @@ select_indices_kernel(const uint64_t* bitmap, const uint64_t* tile_offsets, int6
             out_next = tile_offsets[t + n_waves];
         }
         const uint32_t mine = (uint32_t)__popc(bits);
-        uint32_t incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
+        const uint32_t incl = wave_inclusive_sum(mine);
         uint32_t* __restrict__ out = indices + out_base + (incl - mine);
         const uint32_t first_row = (uint32_t)(t * SEL_TILE) + (uint32_t)lane * 16u;
         uint32_t k = 0;
@@ -796,7 +709,7 @@ emit_group_utf8_small_kernel(const GroupRec* table, int64_t n_groups, EmitKeySpe
         if ((threadIdx.x & 3) == 0 && word < (n_groups + 63) / 64) validity[word] = m0 | (m1 << 16) | (m2 << 32) | (m3 << 48);
     }
     uint64_t tot;
-    uint64_t run = block_exclusive_scan(sum, s_wave, &tot);
+    uint64_t run = block_exclusive_sum<SCAN_BLOCK / 64>(sum, s_wave, tot);
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i) {
         const int64_t j = (int64_t)threadIdx.x * SCAN_ITEMS + i;
@@ -886,15 +799,8 @@ emit_all_kernel(EmitAllArgs A) {
         }
         if (spec.dtype == DT_UTF8) {
             const uint32_t len = valid ? (uint32_t)key_get(g, pos, 1) : 0u;
-            uint32_t x = len;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-            if (lane == 63) s_wave[wave] = x;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-            for (int w = 0; w < EMIT_ALL_MAX_GROUPS / 64; ++w) { if (w < wave) before += s_wave[w]; total += s_wave[w]; }
-            __syncthreads();
-            const uint32_t d0 = before + x - len;
+            uint32_t total;
+            const uint32_t d0 = block_exclusive_sum<EMIT_ALL_MAX_GROUPS / 64>(len, s_wave, total);
             if (in) {
                 A.key_offsets[c][i] = (int32_t)d0;
                 uint8_t* out = reinterpret_cast<uint8_t*>(A.key_data[c]) + d0;

@@ -10,25 +10,21 @@
 //   window_frame_bounds / _finish_frame  sliding ROWS frames: every row's (lo, hi); the finish over it (a difference for COUNT and integer SUM)
 //   window_slide                         the aggregate of a frame with two finite ends, out of a tile's neighbourhood staged in LDS
 //
-// The scan: a tile is WINDOW_TILE_ROWS rows = WINDOW_ROUNDS rounds of one row per thread.  Inside a round the wave-level scan is the
-// __shfl_up ladder of kernels_util.hip's exclusive scans, the four wave totals cross through LDS.  Launch 1 leaves one summary per
+// The scan: a tile is WINDOW_TILE_ROWS rows = WINDOW_ROUNDS rounds of one row per thread.  Inside a round the scan is scan_device.h's
+// block_scan_inclusive over the policies below (wave-level shuffles, the four wave totals cross through LDS).  Launch 1 leaves one summary per
 // tile, launch 2 (one workgroup) scans the summaries WINDOW_SUMMARY_STEP at a time with a running carry, launch 3 redoes the
 // tile-local scan with the summary of the tiles before it as carry.  Nothing waits on another workgroup.  The combine tree is a
 // function of the row positions alone (not of the grid or the device), so floating-point sums are reproducible bit for bit.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "window_kernels.h"
+#include "scan_device.h"
 
 namespace bhip {
 
 namespace {
 
 __device__ inline bool bit_at(const uint64_t* words, int64_t i) { return (words[i >> 6] >> (i & 63)) & 1; }
-
-__device__ inline uint64_t shfl_up_u64(uint64_t x, int d) {
-    const uint32_t lo = __shfl_up((uint32_t)x, d, 64), hi = __shfl_up((uint32_t)(x >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // =============================================================================================
 // boundary flags
@@ -76,33 +72,10 @@ window_flags_kernel(WindowKeys K, int64_t n, uint64_t* __restrict__ part_flags, 
 }
 
 // =============================================================================================
-// the three-launch inclusive scan over a policy P:
-//   P::State, P::identity(), P::combine(left, right) (associative), P::shfl_up(state, d), p.load(position), p.store(position, state)
+// the three-launch inclusive scan over a policy P: what scan_device.h asks of one (P::State, P::identity(), P::combine(left, right),
+//   P::shfl_up(state, d)) and p.load(position), p.store(position, state)
 // positions run 0 .. n in SCAN order (the backward policy maps them to rows from the right)
 // =============================================================================================
-template <class P>
-__device__ inline typename P::State block_scan_inclusive(typename P::State x, typename P::State* s_wave, typename P::State& total) {
-    using S = typename P::State;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const S y = P::shfl_up(x, d);
-        if (lane >= d) x = P::combine(y, x);
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    S before = P::identity(), tot = P::identity();
-#pragma unroll
-    for (int w = 0; w < WINDOW_BLOCK / 64; ++w) {
-        const S s = s_wave[w];
-        if (w < wave) before = P::combine(before, s);
-        tot = P::combine(tot, s);
-    }
-    __syncthreads();                       // the next round overwrites s_wave
-    total = tot;
-    return P::combine(before, x);
-}
-
 template <class P>
 __global__ void __launch_bounds__(WINDOW_BLOCK)
 window_tiles_kernel(P p, int64_t n, typename P::State* __restrict__ summaries) {
@@ -114,7 +87,7 @@ window_tiles_kernel(P p, int64_t n, typename P::State* __restrict__ summaries) {
     for (int r = 0; r < WINDOW_ROUNDS; ++r) {
         const int64_t pos = base + r * WINDOW_BLOCK + threadIdx.x;
         S total;
-        block_scan_inclusive<P>(pos < n ? p.load(pos, n) : P::identity(), s_wave, total);
+        block_scan_inclusive<P, WINDOW_BLOCK / 64>(pos < n ? p.load(pos, n) : P::identity(), s_wave, total);
         carry = P::combine(carry, total);
     }
     if (threadIdx.x == 0) summaries[blockIdx.x] = carry;
@@ -131,7 +104,7 @@ window_summaries_kernel(typename P::State* summaries, int64_t n_tiles) {
     for (int64_t b = 0; b < n_tiles; b += WINDOW_SUMMARY_STEP) {
         const int64_t t = b + threadIdx.x;
         S total;
-        const S incl = block_scan_inclusive<P>(t < n_tiles ? summaries[t] : P::identity(), s_wave, total);
+        const S incl = block_scan_inclusive<P, WINDOW_BLOCK / 64>(t < n_tiles ? summaries[t] : P::identity(), s_wave, total);
         if (t < n_tiles) summaries[t] = P::combine(carry, incl);
         carry = P::combine(carry, total);
     }
@@ -148,7 +121,7 @@ window_apply_kernel(P p, int64_t n, const typename P::State* __restrict__ summar
     for (int r = 0; r < WINDOW_ROUNDS; ++r) {
         const int64_t pos = base + r * WINDOW_BLOCK + threadIdx.x;
         S total;
-        const S incl = block_scan_inclusive<P>(pos < n ? p.load(pos, n) : P::identity(), s_wave, total);
+        const S incl = block_scan_inclusive<P, WINDOW_BLOCK / 64>(pos < n ? p.load(pos, n) : P::identity(), s_wave, total);
         if (pos < n) p.store(pos, n, P::combine(carry, incl));
         carry = P::combine(carry, total);
     }
