@@ -122,6 +122,14 @@ class RowsFrameC(C.Structure):
     _fields_ = [("start_unbounded", C.c_int32), ("end_unbounded", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
 
 
+class FrameBoundC(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("is_float", C.c_int32), ("i", C.c_int64), ("f", C.c_double)]
+
+
+class FrameSpecC(C.Structure):
+    _fields_ = [("units", C.c_int32), ("reserved", C.c_int32), ("start", FrameBoundC), ("end", FrameBoundC)]
+
+
 # every symbol include/ballista_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
@@ -177,6 +185,8 @@ SYMBOLS = {
     "bhip_plan_window": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.c_int32, C.POINTER(SortExprC), C.c_int32, C.POINTER(WindowExprC), _PP]),
     "bhip_plan_window_frames": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.c_int32, C.POINTER(SortExprC), C.c_int32, C.POINTER(WindowExprC),
                                             C.POINTER(C.POINTER(RowsFrameC)), _PP]),
+    "bhip_plan_window_frame_specs": (C.c_int32, [_P, C.c_int32, C.POINTER(Expr), C.c_int32, C.POINTER(SortExprC), C.c_int32, C.POINTER(WindowExprC),
+                                                 C.POINTER(C.POINTER(FrameSpecC)), _PP]),
     "bhip_plan_repartition": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(Expr), C.c_int32, _PP]),
     "bhip_plan_coalesce_batches": (C.c_int32, [_P, C.c_int64, _PP]),
     "bhip_plan_merge": (C.c_int32, [_P, _PP]),

@@ -361,10 +361,10 @@ bhip_status bhip_plan_window(bhip_plan* input, int32_t n_partition, const bhip_e
     return bhip_plan_window_frames(input, n_partition, partition_by, n_order, order_by, n_fn, fns, nullptr, out);
 }
 
-bhip_status bhip_plan_window_frames(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
-                                    const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns,
-                                    const bhip_rows_frame* const* rows_frames, bhip_plan** out) {
-    BHIP_API_BEGIN
+// the three window entry points: the frames that travel beside the structs are rows frames or specs in any units (at most one array)
+static void plan_window(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order, const bhip_sort_expr* order_by,
+                        int32_t n_fn, const bhip_window_expr* fns, const bhip_rows_frame* const* rows_frames, const bhip_frame_spec* const* specs,
+                        bhip_plan** out) {
     need(out, "out");
     if (n_partition < 0 || n_order < 0 || n_fn < 0) fail(BHIP_EINVAL, "WindowAggExec: negative count");
     if (n_partition > 0) need(partition_by, "partition_by");
@@ -383,8 +383,28 @@ bhip_status bhip_plan_window_frames(bhip_plan* input, int32_t n_partition, const
             const bhip_rows_frame& r = *rows_frames[i];
             f.back().rows = WindowRowsFrame{true, r.start_unbounded != 0, r.end_unbounded != 0, r.start, r.end};
         }
+        if (specs && specs[i]) {
+            const bhip_frame_spec& s = *specs[i];
+            auto side = [](const bhip_frame_bound& b) { return WindowFrameBound{b.kind, b.is_float != 0, b.i, b.f}; };
+            f.back().value = WindowValueFrame{true, s.units, side(s.start), side(s.end)};
+        }
     }
     *out = wrap_plan(std::make_shared<WindowAggExec>(part, order, f, plan_of(input, "input")));
+}
+
+bhip_status bhip_plan_window_frames(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
+                                    const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns,
+                                    const bhip_rows_frame* const* rows_frames, bhip_plan** out) {
+    BHIP_API_BEGIN
+    plan_window(input, n_partition, partition_by, n_order, order_by, n_fn, fns, rows_frames, nullptr, out);
+    BHIP_API_END
+}
+
+bhip_status bhip_plan_window_frame_specs(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
+                                         const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns,
+                                         const bhip_frame_spec* const* specs, bhip_plan** out) {
+    BHIP_API_BEGIN
+    plan_window(input, n_partition, partition_by, n_order, order_by, n_fn, fns, nullptr, specs, out);
     BHIP_API_END
 }
 

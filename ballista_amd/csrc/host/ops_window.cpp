@@ -2,7 +2,7 @@
 // specification (PARTITION BY ... ORDER BY ...), on the device (kernels_window.hip).
 //
 // The reference's serde has no window operator (rust/core/src/serde/physical_plan/from_proto.rs:58-346 builds none), so this one is
-// reached through bhip_plan_window / bhip_plan_window_frames only, like the join filter and the Semi / Anti joins; semantics: DESIGN.md "Window functions".
+// reached through bhip_plan_window / bhip_plan_window_frames / bhip_plan_window_frame_specs only, like the join filter and the Semi / Anti joins; semantics: DESIGN.md "Window functions".
 //
 // The operator sorts its single input partition itself with SortExec's code (sort_permutation + take_batch; stable, so ties keep input
 // order) by the partition keys ASC NULLS FIRST and then the order keys, and the rows leave in that order.  After the sort every function
@@ -17,6 +17,14 @@
 //                the integer SUM take the scan and a difference of two running states; a frame that starts with the partition reads the
 //                running state at hi; float SUM, AVG, MIN and MAX between two finite ends are aggregated straight from the argument
 //                (window_slide: a bounded neighbourhood of each tile in LDS)
+//   by value     a RANGE / GROUPS frame with offsets is another producer of (lo, hi): window_value_bounds searches the order key (RANGE) or
+//                the peer-group numbers (GROUPS), once per distinct frame.  The four routes above then apply as they are, except that the
+//                aggregates window_slide serves go to window_slide_value (the tile's span comes from the data), after ONE host read of the
+//                widest frame found: beyond WINDOW_SLIDE_MAX_ROWS rows the query is refused there, when it runs
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include "../window_kernels.h"
 #include "plan.hpp"
 
@@ -63,6 +71,36 @@ std::string rows_frame_name(const WindowRowsFrame& r) {
 }
 // the aggregates a prefix scan cannot slide: a difference of running Float64 sums cancels, MIN / MAX have no inverse
 bool slides(int fn, int arg_dtype) { return fn == BHIP_WIN_AVG || fn == BHIP_WIN_MIN || fn == BHIP_WIN_MAX || (fn == BHIP_WIN_SUM && dt_is_float(arg_dtype)); }
+
+// ---- frames in any units (bhip_frame_spec) ------------------------------------------------------------------------------------------
+const char* units_name(int units) { return units == BHIP_FRAME_UNITS_RANGE ? "RANGE" : units == BHIP_FRAME_UNITS_GROUPS ? "GROUPS" : "ROWS"; }
+// the shortest decimal that reads back to the same double, with a point so it does not read as an integer
+std::string double_text(double v) {
+    char buf[40];
+    for (int digits = 1; digits <= 17; ++digits) {
+        snprintf(buf, sizeof(buf), "%.*g", digits, v);
+        if (strtod(buf, nullptr) == v) break;
+    }
+    std::string s = buf;
+    if (s.find_first_of(".en") == std::string::npos) s += ".0";
+    return s;
+}
+bool is_offset(const WindowFrameBound& b) { return b.kind == BHIP_BOUND_OFFSET; }
+bool offset_positive(const WindowFrameBound& b) { return is_offset(b) && (b.is_float ? b.f > 0 : b.i > 0); }
+bool offset_negative(const WindowFrameBound& b) { return is_offset(b) && (b.is_float ? b.f < 0 : b.i < 0); }
+std::string value_bound_name(int units, const WindowFrameBound& b, bool is_start) {
+    if (b.kind == BHIP_BOUND_UNBOUNDED) return is_start ? "UNBOUNDED PRECEDING" : "UNBOUNDED FOLLOWING";
+    if (b.kind == BHIP_BOUND_CURRENT_ROW || (units == BHIP_FRAME_UNITS_GROUPS && b.i == 0)) return "CURRENT ROW";
+    // RANGE: an offset of zero is not CURRENT ROW (it takes -0.0 and +0.0 together); it reads as the side it stands on
+    const bool preceding = offset_negative(b) || (!offset_positive(b) && is_start);
+    if (b.is_float) return double_text(std::fabs(b.f)) + (preceding ? " PRECEDING" : " FOLLOWING");
+    return (b.i < 0 ? std::to_string(0 - (uint64_t)b.i) : std::to_string(b.i)) + (preceding ? " PRECEDING" : " FOLLOWING");
+}
+std::string value_frame_name(const WindowValueFrame& v) {
+    return std::string(units_name(v.units)) + " BETWEEN " + value_bound_name(v.units, v.start, true) + " AND " + value_bound_name(v.units, v.end, false);
+}
+bool same_bound(const WindowFrameBound& a, const WindowFrameBound& b) { return a.kind == b.kind && a.is_float == b.is_float && a.i == b.i && a.f == b.f; }
+bool range_key_type(int t) { return (dt_is_integer(t) || dt_is_float(t)) && dt_width(t) != 0; }
 }  // namespace
 
 WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<SortDesc> order_by, std::vector<WindowFnDesc> fns, PlanPtr input)
@@ -76,12 +114,68 @@ WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<Sort
     if (fns_.empty()) fail(BHIP_EINVAL, "WindowAggExec needs at least one window expression");
     Utf8Lowering low(in);                  // a key or an argument like lower(s) is evaluated as a column first (utf8_exprs.cpp)
     for (auto& e : partition_by_) { expr_type(e, in); low.rewrite(e, true); }
-    for (auto& s : order_by_) { expr_type(s.expr, in); low.rewrite(s.expr, true); }
+    std::vector<int> order_types;
+    for (auto& s : order_by_) { order_types.push_back(expr_type(s.expr, in)); low.rewrite(s.expr, true); }
     auto sch = std::make_shared<Schema>(in);
     for (auto& f : fns_) {
         if (f.fn < BHIP_WIN_ROW_NUMBER || f.fn > BHIP_WIN_MAX) fail(BHIP_EINVAL, "Unknown window function " + std::to_string(f.fn));
         if (f.frame < BHIP_FRAME_DEFAULT || f.frame > BHIP_FRAME_RANGE_TO_CURRENT) fail(BHIP_EINVAL, "Unknown window frame " + std::to_string(f.frame));
         const std::string fname = window_fn_name(f.fn);
+        if (f.value.has) {
+            // checked for every function, then ignored by those without a frame; ROWS units leave as a rows frame, the forms that are
+            // named frames as those
+            WindowValueFrame& v = f.value;
+            v.slides = false;
+            if (f.frame != BHIP_FRAME_DEFAULT)
+                fail(BHIP_EINVAL, fname + ": a frame spec goes with BHIP_FRAME_DEFAULT, not with " + frame_name(f.frame));
+            if (v.units < BHIP_FRAME_UNITS_ROWS || v.units > BHIP_FRAME_UNITS_GROUPS) fail(BHIP_EINVAL, fname + ": unknown frame units " + std::to_string(v.units));
+            for (WindowFrameBound* b : {&v.start, &v.end}) {
+                if (b->kind < BHIP_BOUND_UNBOUNDED || b->kind > BHIP_BOUND_OFFSET) fail(BHIP_EINVAL, fname + ": unknown frame bound kind " + std::to_string(b->kind));
+                if (!is_offset(*b)) { *b = WindowFrameBound{b->kind, false, 0, 0.0}; continue; }    // (only an OFFSET reads its numbers)
+                if (b->is_float) {
+                    if (!std::isfinite(b->f)) fail(BHIP_EINVAL, fname + ": a frame offset must be a finite number, got " + (std::isnan(b->f) ? "NaN" : "an infinity"));
+                    if (v.units != BHIP_FRAME_UNITS_RANGE) fail(BHIP_EINVAL, fname + ": a " + units_name(v.units) + " frame takes Int64 offsets, got a Float64");
+                    b->i = 0;
+                } else {
+                    b->f = 0.0;
+                }
+            }
+            if (v.units == BHIP_FRAME_UNITS_ROWS) {
+                f.rows = WindowRowsFrame{true, v.start.kind == BHIP_BOUND_UNBOUNDED, v.end.kind == BHIP_BOUND_UNBOUNDED, v.start.i, v.end.i};
+                v = WindowValueFrame{};
+            } else {
+                if (v.units == BHIP_FRAME_UNITS_RANGE && (is_offset(v.start) || is_offset(v.end))) {
+                    const std::string what = fname + " " + value_frame_name(v);
+                    if (order_by_.size() != 1)
+                        fail(BHIP_EINVAL, what + ": a RANGE frame with an offset needs exactly one order key, got " + std::to_string(order_by_.size()));
+                    const int kt = order_types[0];
+                    if (!range_key_type(kt))
+                        fail(BHIP_EINVAL, what + ": a RANGE frame with an offset needs an integer, float, date or timestamp order key, not " + dtype_name(kt));
+                    for (WindowFrameBound* b : {&v.start, &v.end}) {
+                        if (!is_offset(*b)) continue;
+                        if (!dt_is_float(kt) && b->is_float)
+                            fail(BHIP_EINVAL, what + ": the " + dtype_name(kt) + " order key takes Int64 offsets, got a Float64");
+                        if (dt_is_float(kt) && !b->is_float) {
+                            const double d = (double)b->i;          // (2^63 itself is no Int64: it cannot be cast back)
+                            if (!(d < 9223372036854775808.0) || (int64_t)d != b->i)
+                                fail(BHIP_EINVAL, what + ": the offset " + std::to_string(b->i) + " over the " + dtype_name(kt) + " order key is not exactly a Float64");
+                            *b = WindowFrameBound{BHIP_BOUND_OFFSET, true, 0, d};
+                        }
+                    }
+                }
+                if (v.units == BHIP_FRAME_UNITS_GROUPS)
+                    for (WindowFrameBound* b : {&v.start, &v.end})
+                        if (b->kind == BHIP_BOUND_CURRENT_ROW) *b = WindowFrameBound{BHIP_BOUND_OFFSET, false, 0, 0.0};
+                if (v.start.kind != BHIP_BOUND_UNBOUNDED && v.end.kind != BHIP_BOUND_UNBOUNDED &&
+                    (v.start.is_float || v.end.is_float ? (v.start.is_float ? v.start.f : (double)v.start.i) > (v.end.is_float ? v.end.f : (double)v.end.i)
+                                                        : v.start.i > v.end.i))     // (CURRENT ROW holds 0; beside a float only that 0 is an integer)
+                    fail(BHIP_EINVAL, fname + " " + value_frame_name(v) + ": frame start lies after its end");
+                const bool to_current = v.end.kind == BHIP_BOUND_CURRENT_ROW || (v.units == BHIP_FRAME_UNITS_GROUPS && is_offset(v.end) && v.end.i == 0);
+                if (!takes_rows_frame(f.fn)) v = WindowValueFrame{};
+                else if (v.start.kind == BHIP_BOUND_UNBOUNDED && v.end.kind == BHIP_BOUND_UNBOUNDED) { v = WindowValueFrame{}; f.frame = BHIP_FRAME_PARTITION; }
+                else if (v.start.kind == BHIP_BOUND_UNBOUNDED && to_current) { v = WindowValueFrame{}; f.frame = BHIP_FRAME_RANGE_TO_CURRENT; }
+            }
+        }
         if (f.rows.has) {
             WindowRowsFrame& r = f.rows;
             if (f.frame != BHIP_FRAME_DEFAULT)
@@ -95,7 +189,7 @@ WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<Sort
             else if (r.start_unbounded && r.end == 0) { r = WindowRowsFrame{}; f.frame = BHIP_FRAME_ROWS_TO_CURRENT; }
         }
         // (under a rows frame that stays one, `frame` is not read and stays DEFAULT: with_new_children hands the descriptions back in)
-        if (f.frame == BHIP_FRAME_DEFAULT && !f.rows.has) f.frame = order_by_.empty() ? BHIP_FRAME_PARTITION : BHIP_FRAME_RANGE_TO_CURRENT;      // SQL's default
+        if (f.frame == BHIP_FRAME_DEFAULT && !f.rows.has && !f.value.has) f.frame = order_by_.empty() ? BHIP_FRAME_PARTITION : BHIP_FRAME_RANGE_TO_CURRENT;      // SQL's default
         if (is_ranking(f.fn)) {
             f.arg = nullptr;
             sch->fields.push_back(Field{f.name, DT_UINT64, false});
@@ -115,6 +209,14 @@ WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<Sort
                 fail(BHIP_ENOTIMPL, what + ": a frame wider than " + std::to_string(WINDOW_SLIDE_MAX_ROWS) +
                                         " rows is supported for COUNT, integer SUM, FIRST_VALUE and LAST_VALUE only");
         }
+        if (f.value.has && slides(f.fn, t) && t != DT_UTF8 && t != DT_BOOLEAN) {
+            // (how wide a RANGE / GROUPS frame is lies in the data: run() refuses one wider than WINDOW_SLIDE_MAX_ROWS)
+            if (f.value.end.kind == BHIP_BOUND_UNBOUNDED)
+                fail(BHIP_ENOTIMPL, fname + "(" + dtype_name(t) + ") over " + value_frame_name(f.value) +
+                                        ": a frame from an offset to UNBOUNDED FOLLOWING is supported for COUNT, integer SUM, FIRST_VALUE and LAST_VALUE only");
+            f.value.slides = true;
+        }
+        const bool value_may_be_empty = f.value.has && (offset_positive(f.value.start) || offset_negative(f.value.end));
         switch (f.fn) {
             case BHIP_WIN_LAG: case BHIP_WIN_LEAD:
                 if (f.offset < 0) fail(BHIP_EINVAL, fname + " offset must not be negative, got " + std::to_string(f.offset));
@@ -122,8 +224,8 @@ WindowAggExec::WindowAggExec(std::vector<ExprPtr> partition_by, std::vector<Sort
                 break;
             case BHIP_WIN_FIRST_VALUE: case BHIP_WIN_LAST_VALUE:
                 // a rows frame that can lie wholly before or after the partition's rows is empty there
-                sch->fields.push_back(Field{f.name, t, expr_nullable(f.arg, in) || (f.rows.has && ((!f.rows.start_unbounded && f.rows.start > 0) ||
-                                                                                                   (!f.rows.end_unbounded && f.rows.end < 0))),
+                sch->fields.push_back(Field{f.name, t, expr_nullable(f.arg, in) || value_may_be_empty || (f.rows.has && ((!f.rows.start_unbounded && f.rows.start > 0) ||
+                                                                                                                         (!f.rows.end_unbounded && f.rows.end < 0))),
                                             large, binary});
                 break;
             case BHIP_WIN_SUM: case BHIP_WIN_AVG:
@@ -162,6 +264,7 @@ std::string WindowAggExec::describe() const {
         if (f.fn == BHIP_WIN_LAG || f.fn == BHIP_WIN_LEAD) s += ", " + std::to_string(f.offset);
         s += ")";
         if (f.rows.has) s += " " + rows_frame_name(f.rows);
+        else if (f.value.has) s += " " + value_frame_name(f.value);
         else if (has_frame(f.fn)) s += std::string(" ") + frame_name(f.frame);
         s += " as " + f.name;
     }
@@ -258,6 +361,44 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
         frames.push_back(FrameRows{r, lo, hi});
         return frames.back();
     };
+    // ... and under a RANGE / GROUPS frame: the same (lo, hi), found by searching the order key / the peer-group numbers.  When a function
+    // that window_slide_value serves uses the frame, the launch also leaves the widest frame in one word, read once (the only wait here).
+    struct ValueRows { WindowValueFrame v; const uint32_t *lo, *hi; uint32_t* widest_dev; int64_t widest; };
+    std::vector<ValueRows> value_frames;
+    auto value_rows = [&](const WindowValueFrame& v) -> size_t {
+        for (size_t k = 0; k < value_frames.size(); ++k)
+            if (value_frames[k].v.units == v.units && same_bound(value_frames[k].v.start, v.start) && same_bound(value_frames[k].v.end, v.end)) return k;
+        bool slides_here = false;
+        for (const WindowFnDesc& g : fns_)
+            slides_here = slides_here || (g.value.has && g.value.slides && g.value.units == v.units && same_bound(g.value.start, v.start) && same_bound(g.value.end, v.end));
+        need_forward();
+        need_backward();
+        WindowValueFrameArgs a;
+        memset(&a, 0, sizeof(a));
+        a.units = v.units == BHIP_FRAME_UNITS_GROUPS ? WINDOW_UNITS_GROUPS : WINDOW_UNITS_RANGE;
+        a.start_kind = v.start.kind;
+        a.end_kind = v.end.kind;
+        a.start_i = v.start.i; a.end_i = v.end.i;
+        a.start_f = v.start.f; a.end_f = v.end.f;
+        a.part_start = part_start; a.part_end = part_end; a.peer_start = peer_start; a.peer_end = peer_end;
+        if (a.units == WINDOW_UNITS_GROUPS) a.peers_to = peers_to;
+        else if (is_offset(v.start) || is_offset(v.end)) {          // (the constructor saw to exactly one order key of a type that has numbers)
+            a.key = K.col[K.n_part];
+            a.descending = order_by_[0].descending;
+            a.nulls_first = order_by_[0].nulls_first;
+        }
+        uint32_t *lo = tmp.get<uint32_t>((size_t)n), *hi = tmp.get<uint32_t>((size_t)n), *widest = nullptr;
+        if (slides_here) {
+            widest = tmp.get<uint32_t>(1);
+            HIP_CHECK(hipMemsetAsync(widest, 0, sizeof(uint32_t), ex.stream));
+        }
+        TIMED_LAUNCH_N(ex, "window_value_bounds", n, launch_window_value_bounds(cfg, a, n, lo, hi, widest));
+        value_frames.push_back(ValueRows{v, lo, hi, widest, -1});
+        return value_frames.size() - 1;
+    };
+    static_assert((int)BHIP_BOUND_UNBOUNDED == (int)WINDOW_BOUND_UNBOUNDED && (int)BHIP_BOUND_CURRENT_ROW == (int)WINDOW_BOUND_CURRENT_ROW &&
+                      (int)BHIP_BOUND_OFFSET == (int)WINDOW_BOUND_OFFSET,
+                  "the kernels take the ABI's bound kinds as they are");
 
     auto out = new_batch(sorted->ctx, schema_, n);
     out->cols = sorted->cols;
@@ -274,6 +415,13 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
             const uint32_t* idx = f.fn == BHIP_WIN_FIRST_VALUE ? fr.lo : fr.hi;
             const Column arg = evaluate_column(ex, *sorted, f.arg);
             const bool may_be_empty = (!fr.r.start_unbounded && f.rows.start > 0) || (!fr.r.end_unbounded && f.rows.end < 0);
+            o = may_be_empty ? take_column_nullable(ex, arg, idx, n) : take_batch_column(ex, arg, idx, n);
+        } else if (!is_aggregate(f.fn) && f.value.has) {
+            // ... and of a RANGE / GROUPS frame
+            const ValueRows& vr = value_frames[value_rows(f.value)];
+            const uint32_t* idx = f.fn == BHIP_WIN_FIRST_VALUE ? vr.lo : vr.hi;
+            const Column arg = evaluate_column(ex, *sorted, f.arg);
+            const bool may_be_empty = offset_positive(f.value.start) || offset_negative(f.value.end);
             o = may_be_empty ? take_column_nullable(ex, arg, idx, n) : take_batch_column(ex, arg, idx, n);
         } else if (!is_aggregate(f.fn)) {
             // the row to read, then the gather the outer joins use (an index outside the partition is its NULL index)
@@ -315,6 +463,20 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
                 out->cols.push_back(std::move(o));
                 continue;
             }
+            if (f.value.has && f.value.start.kind != BHIP_BOUND_UNBOUNDED && op != WINDOW_OP_ADD_I64) {
+                // the same over a RANGE / GROUPS frame, whose width is known only now
+                ValueRows& vr = value_frames[value_rows(f.value)];
+                if (vr.widest < 0) vr.widest = vr.widest_dev ? (int64_t)read_device(ex, vr.widest_dev) : 0;
+                if (vr.widest > WINDOW_SLIDE_MAX_ROWS)
+                    fail(BHIP_ENOTIMPL, std::string(window_fn_name(f.fn)) + "(" + dtype_name(t) + ") over " + value_frame_name(f.value) + ": the widest frame holds " +
+                                            std::to_string(vr.widest) + " rows; a frame wider than " + std::to_string(WINDOW_SLIDE_MAX_ROWS) +
+                                            " rows is supported for COUNT, integer SUM, FIRST_VALUE and LAST_VALUE only");
+                o = alloc_column(ex, dtype, n, true);
+                TIMED_LAUNCH_N(ex, "window_slide_value", n,
+                               launch_window_slide_value(cfg, op, kind, o.dtype, ref, vr.lo, vr.hi, n, o.data->ptr(), o.validity_words()));
+                out->cols.push_back(std::move(o));
+                continue;
+            }
             uint64_t* run_value = tmp.get<uint64_t>((size_t)n);
             uint32_t* run_count = tmp.get<uint32_t>((size_t)n);
             TIMED_LAUNCH_N(ex, "window_scan_tiles", n, launch_window_scan_tiles(cfg, op, ref, part_flags, n, scan_temp));
@@ -327,6 +489,11 @@ BatchPtr WindowAggExec::run(const Exec& ex, const BatchPtr& whole) const {
                 TIMED_LAUNCH_N(ex, "window_finish_frame", n,
                                launch_window_finish_frame(cfg, kind, o.dtype, run_value, run_count, fr.r.start_unbounded ? nullptr : part_flags, fr.lo, fr.hi,
                                                           n, o.data->ptr(), o.validity_words()));
+            } else if (f.value.has) {
+                const ValueRows& vr = value_frames[value_rows(f.value)];
+                TIMED_LAUNCH_N(ex, "window_finish_frame", n,
+                               launch_window_finish_frame(cfg, kind, o.dtype, run_value, run_count, f.value.start.kind == BHIP_BOUND_UNBOUNDED ? nullptr : part_flags,
+                                                          vr.lo, vr.hi, n, o.data->ptr(), o.validity_words()));
             } else {
                 const uint32_t* fe = frame_end(f.frame);
                 TIMED_LAUNCH_N(ex, "window_finish", n,

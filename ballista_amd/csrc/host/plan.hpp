@@ -341,12 +341,27 @@ private:
 };
 
 // One window specification over the whole input (ops_window.cpp): the rows sorted by (partition keys ASC NULLS FIRST, order keys),
-// the input's columns followed by one column per window function.  No wire form: the C ABI only (bhip_plan_window_frames).
+// the input's columns followed by one column per window function.  No wire form: the C ABI only (bhip_plan_window_frames, bhip_plan_window_frame_specs).
 // A ROWS frame by signed offsets from the current row (bhip_rows_frame).  The constructor resolves UNBOUNDED PRECEDING .. CURRENT ROW
 // and UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING to the named frames (`has` false again); every other frame keeps its offsets.
 struct WindowRowsFrame {
     bool has = false, start_unbounded = false, end_unbounded = false;
     int64_t start = 0, end = 0;
+};
+// A frame in any units (bhip_frame_spec).  The constructor hands ROWS units to `rows`, resolves the forms that are named frames, turns
+// CURRENT ROW under GROUPS into offset 0 and an Int64 offset over a float key into the double it equals; what stays here is a RANGE or
+// GROUPS frame with at least one side that is not "the partition's".
+struct WindowFrameBound {
+    int kind = 0;         // bhip_frame_bound_kind
+    bool is_float = false;
+    int64_t i = 0;        // OFFSET, or
+    double f = 0.0;       // ... when is_float
+};
+struct WindowValueFrame {
+    bool has = false;
+    int units = 0;        // bhip_frame_units
+    WindowFrameBound start, end;
+    bool slides = false;  // set by the constructor: the function is one a prefix scan cannot slide (its frames have a widest width)
 };
 struct WindowFnDesc {
     int fn;               // bhip_window_fn
@@ -355,6 +370,7 @@ struct WindowFnDesc {
     int frame;            // bhip_window_frame, BHIP_FRAME_DEFAULT already resolved
     std::string name;
     WindowRowsFrame rows; // has: this frame, not `frame`
+    WindowValueFrame value; // has: this frame, not `frame` (never beside `rows`)
 };
 class WindowAggExec : public UnaryExec {
 public:

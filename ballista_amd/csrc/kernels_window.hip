@@ -9,6 +9,8 @@
 //   window_finish                        the running state at the frame's last row -> the output column and its validity
 //   window_frame_bounds / _finish_frame  sliding ROWS frames: every row's (lo, hi); the finish over it (a difference for COUNT and integer SUM)
 //   window_slide                         the aggregate of a frame with two finite ends, out of a tile's neighbourhood staged in LDS
+//   window_value_bounds                  RANGE / GROUPS frames: every row's (lo, hi) by a gallop-and-bisect search of the order key / peer count
+//   window_slide_value                   window_slide for those (lo, hi): the tile's span comes from the data (LDS when it fits, else global)
 //
 // The scan: a tile is WINDOW_TILE_ROWS rows = WINDOW_ROUNDS rounds of one row per thread.  Inside a round the scan is scan_device.h's
 // block_scan_inclusive over the policies below (wave-level shuffles, the four wave totals cross through LDS).  Launch 1 leaves one summary per
@@ -437,6 +439,69 @@ __device__ inline void slide_stage(const ColumnRef& arg, int64_t span_first, int
     }
 }
 
+// the element type and "has a validity" are chosen here, outside the staging loop: chosen per load, each load would wait for the last
+template <int OP>
+__device__ inline void slide_stage_span(const ColumnRef& arg, int64_t span_first, int span, uint64_t* s_value, uint8_t* s_flag) {
+#define STAGE(T) (arg.validity ? slide_stage<OP, T, true>(arg, span_first, span, s_value, s_flag) : slide_stage<OP, T, false>(arg, span_first, span, s_value, s_flag))
+    switch (dt_width(arg.dtype)) {
+        case 1: STAGE(uint8_t); break;
+        case 2: STAGE(uint16_t); break;
+        case 4: STAGE(uint32_t); break;
+        default: STAGE(uint64_t); break;
+    }
+#undef STAGE
+}
+
+// where the walk reads a row's state (no head flag) from: the staged span, by slot, or the argument itself, by row
+template <int OP>
+struct SlideStaged {
+    const uint64_t* value;
+    const uint8_t* flag;
+    __device__ typename ArgScan<OP>::State at(int s) const {
+        const uint32_t f = flag[s];
+        return typename ArgScan<OP>::State{value[s], f & SLIDE_NOT_NULL, f & ~SLIDE_NOT_NULL};
+    }
+};
+template <int OP>
+struct SlideGlobal {
+    ColumnRef arg;
+    __device__ typename ArgScan<OP>::State at(int64_t row) const { return ArgScan<OP>::load_arg(arg, row); }
+};
+
+// the aggregate of positions from .. to (none when from > to), in ascending order from the identity (value 0: the bits of +0.0)
+template <int OP, class Rows, class Index>
+__device__ inline typename ArgScan<OP>::State slide_walk(const Rows& rows, Index from, Index to) {
+    using A = ArgScan<OP>;
+    using S = typename A::State;
+    S acc = A::identity();
+    for (Index s = from; s <= to; ++s) {
+        const S b = rows.at(s);
+        if (OP == WINDOW_OP_ADD_F64) {
+            if (b.count) acc.value = bits_of(f64_of(acc.value) + f64_of(b.value));
+        } else {
+            acc.value = A::merge(acc, b);
+            acc.flags |= b.flags;
+        }
+        acc.count += b.count;
+    }
+    return acc;
+}
+
+// row i's output and, per wave, its validity word (every lane of the wave calls this, a row past n included)
+template <int OP>
+__device__ inline void slide_finish(const typename ArgScan<OP>::State& acc, int64_t i, int64_t n, int kind, int out_dtype, void* __restrict__ out,
+                                    uint64_t* __restrict__ validity) {
+    using A = ArgScan<OP>;
+    const bool valid = acc.count != 0;
+    if (i < n) {
+        const uint64_t value = A::FLOAT_MINMAX && !(acc.flags & ARG_HAS_NUMBER) ? F64_QUIET_NAN : acc.value;      // NaNs alone: a NaN
+        if (kind == WINDOW_FINISH_AVG) static_cast<double*>(out)[i] = valid ? f64_of(value) / (double)acc.count : 0.0;
+        else dt_store(out_dtype, out, i, valid ? value : 0ull);
+    }
+    const uint64_t word = __ballot(valid);                          // 64 consecutive rows from a multiple of 64: one validity word
+    if (validity && (threadIdx.x & 63) == 0 && i < n) validity[i >> 6] = word;
+}
+
 template <int OP>
 __global__ void __launch_bounds__(WINDOW_BLOCK)
 window_slide_kernel(ColumnRef arg, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, int64_t start, int64_t end, int64_t n, int kind,
@@ -460,44 +525,226 @@ window_slide_kernel(ColumnRef arg, const uint32_t* __restrict__ lo, const uint32
         l[r] = i < n ? lo[i] : WINDOW_NULL_INDEX;
         h[r] = i < n ? hi[i] : WINDOW_NULL_INDEX;
     }
-    // the element type and "has a validity" are chosen here, outside the staging loop: chosen per load, each load would wait for the last
-#define STAGE(T) (arg.validity ? slide_stage<OP, T, true>(arg, span_first, span, s_slide, s_flag) : slide_stage<OP, T, false>(arg, span_first, span, s_slide, s_flag))
-    switch (dt_width(arg.dtype)) {
-        case 1: STAGE(uint8_t); break;
-        case 2: STAGE(uint16_t); break;
-        case 4: STAGE(uint32_t); break;
-        default: STAGE(uint64_t); break;
-    }
-#undef STAGE
+    slide_stage_span<OP>(arg, span_first, span, s_slide, s_flag);
     __syncthreads();
+    const SlideStaged<OP> staged{s_slide, s_flag};
 #pragma unroll
     for (int r = 0; r < WINDOW_ROUNDS; ++r) {
         const int64_t i = tile_first + r * WINDOW_BLOCK + t;
-        S acc = A::identity();                                       // value 0: the bits of +0.0
+        S acc = A::identity();
         if (h[r] != WINDOW_NULL_INDEX) {
             // the row's own frame; the clamp to the staged span changes nothing for a (lo, hi) made with this start / end
             const int64_t jl = (int64_t)l[r] > span_first ? (int64_t)l[r] : span_first, jh = (int64_t)h[r] < span_last ? (int64_t)h[r] : span_last;
-            const int last = (int)(jh - span_first);
-            for (int s = (int)(jl - span_first); s <= last; ++s) {
-                const uint32_t f = s_flag[s];
-                const S b{s_slide[s], f & SLIDE_NOT_NULL, f & ~SLIDE_NOT_NULL};
-                if (OP == WINDOW_OP_ADD_F64) {
-                    if (b.count) acc.value = bits_of(f64_of(acc.value) + f64_of(b.value));
-                } else {
-                    acc.value = A::merge(acc, b);
-                    acc.flags |= b.flags;
-                }
-                acc.count += b.count;
-            }
+            acc = slide_walk<OP>(staged, (int)(jl - span_first), (int)(jh - span_first));
         }
-        const bool valid = acc.count != 0;
-        if (i < n) {
-            const uint64_t value = A::FLOAT_MINMAX && !(acc.flags & ARG_HAS_NUMBER) ? F64_QUIET_NAN : acc.value;      // NaNs alone: a NaN
-            if (kind == WINDOW_FINISH_AVG) static_cast<double*>(out)[i] = valid ? f64_of(value) / (double)acc.count : 0.0;
-            else dt_store(out_dtype, out, i, valid ? value : 0ull);
+        slide_finish<OP>(acc, i, n, kind, out_dtype, out, validity);
+    }
+}
+
+// window_slide over frames whose span no offset bounds: the tile's span is the smallest lo .. the largest hi of its non-empty rows.
+// Staged and walked in LDS when it fits WINDOW_SLIDE_STAGE_ROWS, else walked in global memory (uniform per workgroup).
+template <int OP>
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_slide_value_kernel(ColumnRef arg, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, int64_t n, int kind, int out_dtype,
+                          void* __restrict__ out, uint64_t* __restrict__ validity) {
+    using A = ArgScan<OP>;
+    using S = typename A::State;
+    extern __shared__ uint64_t s_slide[];
+    __shared__ uint32_t s_span[2 * (WINDOW_BLOCK / 64)];
+    const int t = threadIdx.x;
+    const int64_t tile_first = (int64_t)blockIdx.x * WINDOW_TILE_ROWS;
+    uint8_t* s_flag = reinterpret_cast<uint8_t*>(s_slide + WINDOW_SLIDE_STAGE_ROWS);
+
+    uint32_t l[WINDOW_ROUNDS], h[WINDOW_ROUNDS];
+    uint32_t first = WINDOW_NULL_INDEX, last = 0;                   // over the non-empty rows (an empty one: lo = hi = WINDOW_NULL_INDEX)
+#pragma unroll
+    for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+        const int64_t i = tile_first + r * WINDOW_BLOCK + t;
+        l[r] = i < n ? lo[i] : WINDOW_NULL_INDEX;
+        h[r] = i < n ? hi[i] : WINDOW_NULL_INDEX;
+        if (h[r] != WINDOW_NULL_INDEX) {
+            first = l[r] < first ? l[r] : first;
+            last = h[r] > last ? h[r] : last;
         }
-        const uint64_t word = __ballot(valid);                      // 64 consecutive rows from a multiple of 64: one validity word
-        if (validity && (t & 63) == 0 && i < n) validity[i >> 6] = word;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t of = __shfl_xor(first, d, 64), ol = __shfl_xor(last, d, 64);
+        first = of < first ? of : first;
+        last = ol > last ? ol : last;
+    }
+    if ((t & 63) == 0) {
+        s_span[2 * (t >> 6)] = first;
+        s_span[2 * (t >> 6) + 1] = last;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < WINDOW_BLOCK / 64; ++w) {
+        first = s_span[2 * w] < first ? s_span[2 * w] : first;
+        last = s_span[2 * w + 1] > last ? s_span[2 * w + 1] : last;
+    }
+    // the same in every lane of the workgroup from here on
+    const bool any = first != WINDOW_NULL_INDEX;
+    const int64_t span_first = any ? (int64_t)first : 0;
+    const int64_t rows = any ? (int64_t)last - (int64_t)first + 1 : 0;
+    const bool fits = rows <= (int64_t)WINDOW_SLIDE_STAGE_ROWS;
+    if (fits) {
+        slide_stage_span<OP>(arg, span_first, (int)rows, s_slide, s_flag);
+        __syncthreads();
+    }
+    const SlideStaged<OP> staged{s_slide, s_flag};
+    const SlideGlobal<OP> global{arg};
+#pragma unroll
+    for (int r = 0; r < WINDOW_ROUNDS; ++r) {
+        const int64_t i = tile_first + r * WINDOW_BLOCK + t;
+        S acc = A::identity();
+        if (h[r] != WINDOW_NULL_INDEX) {
+            if (fits) acc = slide_walk<OP>(staged, (int)((int64_t)l[r] - span_first), (int)((int64_t)h[r] - span_first));
+            else acc = slide_walk<OP>(global, (int64_t)l[r], (int64_t)h[r]);
+        }
+        slide_finish<OP>(acc, i, n, kind, out_dtype, out, validity);
+    }
+}
+
+// =============================================================================================
+// RANGE / GROUPS frames: the two ends of every row's frame, by a search of the sorted rows
+// =============================================================================================
+// a - b >= bound / a - b <= bound for two 64-bit unsigned images and a signed bound, as if in unbounded integers
+__device__ inline bool diff_at_least(uint64_t a, uint64_t b, int64_t bound) {
+    if (a >= b) return bound <= 0 || a - b >= (uint64_t)bound;
+    return bound < 0 && b - a <= 0 - (uint64_t)bound;                // (the magnitude of INT64_MIN: 2^63, as unsigned)
+}
+__device__ inline bool diff_at_most(uint64_t a, uint64_t b, int64_t bound) {
+    if (a >= b) return bound >= 0 && a - b <= (uint64_t)bound;
+    return bound >= 0 || b - a >= 0 - (uint64_t)bound;
+}
+
+// One OFFSET side of row i's frame as a predicate over the rows of its partition that is false up to some row and true from it on:
+//   START  "row j lies at or after the frame's first row": its class is after the numbers, or it is a number that qualifies
+//   END    "row j lies after the frame's last row":        its class is after the numbers, or it is a number that does not qualify
+// Classes in row order: 0 = before the numbers, 1 = a number, 2 = after them (NULLs where the sort put them; ascending, -NaN sorts
+// first and +NaN last, descending the other way round).  GROUPS: every row is a number, its peer-group count, ascending.
+struct ValueSide {
+    ColumnRef key;                       // RANGE
+    const uint32_t* peers_to;            // GROUPS (key.data unused)
+    bool is_end, groups, is_float, descending, nulls_first;
+    int64_t offset;                      // integer keys and GROUPS
+    double target;                       // float keys: key_i + s * offset
+    uint64_t mine;                       // integer keys and GROUPS: row i's ordered image
+
+    __device__ int cls(int64_t j, uint64_t& image) const {
+        if (groups) { image = peers_to[j]; return 1; }
+        if (key.validity && !bit_at(key.validity, j)) return nulls_first ? 0 : 2;
+        image = dt_load(key.dtype, key.data, j);
+        if (is_float) {
+            const double d = f64_of(image);
+            if (d != d) return ((image >> 63) != 0) != descending ? 0 : 2;
+            return 1;
+        }
+        if (!dt_is_unsigned(key.dtype)) image ^= 0x8000000000000000ull;       // signed order as unsigned order
+        return 1;
+    }
+    __device__ bool qualifies(uint64_t image) const {
+        if (is_float) {
+            const double d = f64_of(image);
+            return is_end != descending ? d <= target : d >= target;           // start asc / end desc: key_j >= t; the other two: <=
+        }
+        const uint64_t a = descending ? mine : image, b = descending ? image : mine;   // s * (key_j - key_i) = a - b
+        return is_end ? diff_at_most(a, b, offset) : diff_at_least(a, b, offset);
+    }
+    __device__ bool operator()(int64_t j) const {
+        uint64_t image = 0;
+        const int c = cls(j, image);
+        if (c != 1) return c == 2;
+        return qualifies(image) != is_end;
+    }
+};
+
+// the first row of ps .. pe at which the predicate holds (pe + 1: nowhere), galloping outward from row i and then bisecting
+template <class P>
+__device__ inline int64_t first_true_from(const P& p, int64_t ps, int64_t pe, int64_t i) {
+    int64_t no, yes;                                                 // p(no) is false (or no = ps - 1), p(yes) true (or yes = pe + 1)
+    if (p(i)) {
+        yes = i;
+        no = ps - 1;
+        for (int64_t step = 1; yes - step >= ps; step <<= 1) {
+            if (p(yes - step)) yes -= step;
+            else { no = yes - step; break; }
+        }
+    } else {
+        no = i;
+        yes = pe + 1;
+        for (int64_t step = 1; no + step <= pe; step <<= 1) {
+            if (!p(no + step)) no += step;
+            else { yes = no + step; break; }
+        }
+    }
+    while (yes - no > 1) {
+        const int64_t mid = no + ((yes - no) >> 1);
+        if (p(mid)) yes = mid;
+        else no = mid;
+    }
+    return yes;
+}
+
+__global__ void __launch_bounds__(WINDOW_BLOCK)
+window_value_bounds_kernel(WindowValueFrameArgs a, int64_t n, uint32_t* __restrict__ lo, uint32_t* __restrict__ hi, uint32_t* __restrict__ widest) {
+    const int64_t i = (int64_t)blockIdx.x * WINDOW_BLOCK + threadIdx.x;
+    uint32_t width = 0;
+    if (i < n) {
+        const int64_t ps = a.part_start[i], pe = a.part_end[i];
+        const bool groups = a.units == WINDOW_UNITS_GROUPS;
+        const bool search_start = a.start_kind == WINDOW_BOUND_OFFSET, search_end = a.end_kind == WINDOW_BOUND_OFFSET;
+        ValueSide side;
+        side.key = a.key;
+        side.peers_to = a.peers_to;
+        side.groups = groups;
+        side.is_float = !groups && dt_is_float(a.key.dtype);
+        side.descending = !groups && a.descending != 0;
+        side.nulls_first = a.nulls_first != 0;
+        side.is_end = false;
+        side.offset = 0;
+        side.target = 0.0;
+        side.mine = 0;
+        int own = 1;                                                 // the class of row i's own key
+        double own_f = 0.0;
+        if (search_start || search_end) {
+            own = side.cls(i, side.mine);
+            own_f = f64_of(side.mine);
+        }
+        int64_t l, h;                                                // l = pe + 1 / h = ps - 1: the side has no row
+        if (a.start_kind == WINDOW_BOUND_UNBOUNDED) l = ps;
+        else if (a.start_kind == WINDOW_BOUND_CURRENT_ROW || own != 1) l = a.peer_start[i];
+        else {
+            side.is_end = false;
+            side.offset = a.start_i;
+            side.target = side.descending ? own_f - a.start_f : own_f + a.start_f;
+            l = first_true_from(side, ps, pe, i);
+            uint64_t image;
+            if (l <= pe && side.cls(l, image) != 1) l = pe + 1;      // no number qualifies
+        }
+        if (a.end_kind == WINDOW_BOUND_UNBOUNDED) h = pe;
+        else if (a.end_kind == WINDOW_BOUND_CURRENT_ROW || own != 1) h = a.peer_end[i];
+        else {
+            side.is_end = true;
+            side.offset = a.end_i;
+            side.target = side.descending ? own_f - a.end_f : own_f + a.end_f;
+            h = first_true_from(side, ps, pe, i) - 1;
+            uint64_t image;
+            if (h >= ps && side.cls(h, image) != 1) h = ps - 1;
+        }
+        const bool empty = l > pe || h < ps || l > h;
+        lo[i] = empty ? WINDOW_NULL_INDEX : (uint32_t)l;
+        hi[i] = empty ? WINDOW_NULL_INDEX : (uint32_t)h;
+        width = empty ? 0u : (uint32_t)(h - l + 1);
+    }
+    if (widest) {                                                    // (uniform: a kernel argument)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const uint32_t o = __shfl_xor(width, d, 64);
+            width = o > width ? o : width;
+        }
+        if ((threadIdx.x & 63) == 0 && width) atomicMax(widest, width);
     }
 }
 
@@ -648,6 +895,47 @@ hipError_t launch_window_slide(const LaunchCfg& cfg, int op, int kind, int out_d
         case WINDOW_OP_MIN_F64: return CALL(WINDOW_OP_MIN_F64);
         case WINDOW_OP_MAX_F64: return CALL(WINDOW_OP_MAX_F64);
         default: return hipErrorInvalidValue;                       // the wrapping add takes the scan and a difference
+    }
+#undef CALL
+}
+
+hipError_t launch_window_value_bounds(const LaunchCfg& cfg, const WindowValueFrameArgs& a, int64_t n, uint32_t* lo, uint32_t* hi, uint32_t* widest) {
+    if (n <= 0) return hipSuccess;
+    if ((a.units != WINDOW_UNITS_RANGE && a.units != WINDOW_UNITS_GROUPS) || !a.part_start || !a.part_end) return hipErrorInvalidValue;
+    const int kinds[2] = {a.start_kind, a.end_kind};
+    for (int k : kinds) {
+        if (k < WINDOW_BOUND_UNBOUNDED || k > WINDOW_BOUND_OFFSET) return hipErrorInvalidValue;
+        if (k == WINDOW_BOUND_CURRENT_ROW && (!a.peer_start || !a.peer_end)) return hipErrorInvalidValue;
+        if (k != WINDOW_BOUND_OFFSET) continue;
+        if (a.units == WINDOW_UNITS_GROUPS ? !a.peers_to : !a.key.data || dt_width(a.key.dtype) == 0 || !a.peer_start || !a.peer_end) return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(window_value_bounds_kernel, dim3(row_blocks(n)), dim3(WINDOW_BLOCK), 0, cfg.stream, a, n, lo, hi, widest);
+    return hipGetLastError();
+}
+
+template <int OP>
+static hipError_t run_slide_value(const LaunchCfg& cfg, int kind, int out_dtype, const ColumnRef& arg, const uint32_t* lo, const uint32_t* hi, int64_t n,
+                                  void* out, uint64_t* validity) {
+    const size_t lds = (size_t)WINDOW_SLIDE_STAGE_ROWS * 9;
+    hipLaunchKernelGGL((window_slide_value_kernel<OP>), dim3((unsigned)window_tiles(n)), dim3(WINDOW_BLOCK), lds, cfg.stream, arg, lo, hi, n, kind, out_dtype,
+                       out, validity);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_slide_value(const LaunchCfg& cfg, int op, int kind, int out_dtype, const ColumnRef& arg, const uint32_t* lo,
+                                     const uint32_t* hi, int64_t n, void* out, uint64_t* validity) {
+    if (n <= 0) return hipSuccess;
+    if ((kind != WINDOW_FINISH_VALUE && kind != WINDOW_FINISH_AVG) || !arg.data || arg.dtype == DT_UTF8 || arg.dtype == DT_BOOLEAN) return hipErrorInvalidValue;
+#define CALL(OP) run_slide_value<OP>(cfg, kind, out_dtype, arg, lo, hi, n, out, validity)
+    switch (op) {
+        case WINDOW_OP_ADD_F64: return CALL(WINDOW_OP_ADD_F64);
+        case WINDOW_OP_MIN_I64: return CALL(WINDOW_OP_MIN_I64);
+        case WINDOW_OP_MAX_I64: return CALL(WINDOW_OP_MAX_I64);
+        case WINDOW_OP_MIN_U64: return CALL(WINDOW_OP_MIN_U64);
+        case WINDOW_OP_MAX_U64: return CALL(WINDOW_OP_MAX_U64);
+        case WINDOW_OP_MIN_F64: return CALL(WINDOW_OP_MIN_F64);
+        case WINDOW_OP_MAX_F64: return CALL(WINDOW_OP_MAX_F64);
+        default: return hipErrorInvalidValue;
     }
 #undef CALL
 }

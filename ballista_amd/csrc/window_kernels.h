@@ -109,4 +109,39 @@ hipError_t launch_window_finish_frame(const LaunchCfg& cfg, int kind, int out_dt
 hipError_t launch_window_slide(const LaunchCfg& cfg, int op, int kind, int out_dtype, const ColumnRef& arg, const uint32_t* lo, const uint32_t* hi,
                                int64_t start, int64_t end, int64_t n, void* out, uint64_t* validity);
 
+// ---- RANGE / GROUPS frames: the frame's ends are found by searching the sorted rows --------------------------------------------------
+// One side of a frame.  OFFSET is signed like a rows frame's: -3 = 3 PRECEDING, +2 = 2 FOLLOWING; `f` for a float order key (RANGE).
+enum WindowBoundKind : int32_t { WINDOW_BOUND_UNBOUNDED = 0, WINDOW_BOUND_CURRENT_ROW = 1, WINDOW_BOUND_OFFSET = 2 };
+enum WindowFrameUnits : int32_t { WINDOW_UNITS_ROWS = 0, WINDOW_UNITS_RANGE = 1, WINDOW_UNITS_GROUPS = 2 };
+struct WindowValueFrameArgs {
+    int32_t units;                       // RANGE or GROUPS
+    int32_t start_kind, end_kind;        // WindowBoundKind
+    int32_t descending, nulls_first;     // of the order key (RANGE with an OFFSET side)
+    int64_t start_i, end_i;              // OFFSET over an integer-typed key, and every GROUPS offset
+    double start_f, end_f;               // OFFSET over a float key
+    ColumnRef key;                       // the evaluated order key of the sorted rows: RANGE with an OFFSET side only
+    const uint32_t *part_start, *part_end, *peer_start, *peer_end;
+    const uint32_t* peers_to;            // GROUPS with an OFFSET side only
+};
+// lo[i] / hi[i] of row i's frame (WINDOW_NULL_INDEX in both: empty), one row per lane.  UNBOUNDED reads part_*, CURRENT ROW peer_*.
+// An OFFSET side is a search inside the row's partition for the first row that qualifies (start) / the last one (end): it gallops
+// outward from row i in steps of 1, 2, 4 ... and then bisects, at most about 2 log2(partition) probes and none of them waits on
+// another lane.  RANGE compares the order key: rows are classed as the sort laid them (NULLs and the NaNs of one sign before the
+// numbers, the rest after) and numbers compare exactly — integers as if unbounded (a key of 2^63 - 1 plus 2^63 - 1 does not wrap),
+// floats against t = key_i +- offset, computed once in Float64, by IEEE comparison.  A row whose own key is NULL or NaN takes its peer
+// bound.  GROUPS compares peers_to (the row's peer-group number, ascending).  `widest` (null: not kept): one word, zeroed by the
+// caller, that receives the largest hi - lo + 1 (an atomic max, at most one per wave).
+hipError_t launch_window_value_bounds(const LaunchCfg& cfg, const WindowValueFrameArgs& a, int64_t n, uint32_t* lo, uint32_t* hi, uint32_t* widest);
+
+// Rows a tile of window_slide_value stages in LDS at most (8 bytes of value and one of flags each: 18 KiB, so LDS leaves eight
+// workgroups to a CU).  Chosen, not tuned: a tile and as many rows again of neighbourhood.
+constexpr int WINDOW_SLIDE_STAGE_ROWS = 2048;
+static_assert(WINDOW_SLIDE_STAGE_ROWS > WINDOW_TILE_ROWS && WINDOW_SLIDE_STAGE_ROWS * 9 + 64 <= 64 * 1024, "window_slide_value stages at most this span");
+// window_slide for a (lo, hi) of window_value_bounds, whose span no offset bounds before the launch: a tile's span runs from the
+// smallest lo to the largest hi of its non-empty rows (one block reduction).  A span of at most WINDOW_SLIDE_STAGE_ROWS rows is staged
+// and walked in LDS as window_slide does; a longer one (narrow frames that lie far apart) is walked in global memory by the same loop.
+// Every frame holds at most WINDOW_SLIDE_MAX_ROWS rows (the caller read `widest`).  The additions have window_slide's order.
+hipError_t launch_window_slide_value(const LaunchCfg& cfg, int op, int kind, int out_dtype, const ColumnRef& arg, const uint32_t* lo,
+                                     const uint32_t* hi, int64_t n, void* out, uint64_t* validity);
+
 }  // namespace bhip

@@ -16,6 +16,7 @@ program the C-ABI takes (include/ballista_hip.h, `bhip_expr_*`).  As in DataFusi
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -210,21 +211,71 @@ class RowsFrame:
                 raise TypeError(f"a rows frame offset is None or an Int64, got {side!r}")
 
 
+class _CurrentRow:
+    """the CURRENT ROW side of a RangeFrame / GroupsFrame: the row's first (start) or last (end) peer"""
+    _instance = None
+
+    def __new__(cls):
+        if cls._instance is None:
+            cls._instance = super().__new__(cls)
+        return cls._instance
+
+    def __repr__(self):
+        return "CURRENT_ROW"
+
+
+CURRENT_ROW = _CurrentRow()
+
+
+def _check_value_sides(what, sides, floats):
+    for side in sides:
+        if side is None or side is CURRENT_ROW:
+            continue
+        if isinstance(side, int) and not isinstance(side, bool) and -2**63 <= side < 2**63:
+            continue
+        if floats and isinstance(side, float) and math.isfinite(side):
+            continue
+        raise TypeError(f"a {what} frame side is None, CURRENT_ROW, an Int64{' or a finite float' if floats else ''}, got {side!r}")
+
+
+@dataclass(frozen=True)
+class RangeFrame:
+    """RANGE BETWEEN start AND end, measured in values of the single order key.  A side is None (UNBOUNDED PRECEDING / FOLLOWING),
+    CURRENT_ROW (the row's first / last peer), or a signed offset: -7 = 7 PRECEDING, 0.5 = 0.5 FOLLOWING — an int for integer, date and
+    timestamp keys, a float (or an int a double holds exactly) for float keys."""
+    start: Union[None, _CurrentRow, int, float]
+    end: Union[None, _CurrentRow, int, float]
+
+    def __post_init__(self):
+        _check_value_sides("RANGE", (self.start, self.end), True)
+
+
+@dataclass(frozen=True)
+class GroupsFrame:
+    """GROUPS BETWEEN start AND end, measured in peer groups: -1 = 1 PRECEDING (the group before the row's), CURRENT_ROW = 0, None =
+    unbounded."""
+    start: Union[None, _CurrentRow, int]
+    end: Union[None, _CurrentRow, int]
+
+    def __post_init__(self):
+        _check_value_sides("GROUPS", (self.start, self.end), False)
+
+
 @dataclass(eq=False)
 class WindowExpr:
     """one function over the operator's window: fun(expr[, offset]) [frame] AS name.  ROW_NUMBER / RANK / DENSE_RANK take no
-    argument; offset is LAG / LEAD's k (a plain non-negative integer); frame, one of WINDOW_FRAMES or a RowsFrame, matters for the
-    aggregates and LAST_VALUE, a RowsFrame for FIRST_VALUE too."""
+    argument; offset is LAG / LEAD's k (a plain non-negative integer); frame, one of WINDOW_FRAMES or a RowsFrame / RangeFrame /
+    GroupsFrame, matters for the aggregates and LAST_VALUE, a frame object for FIRST_VALUE too."""
     fun: str
     expr: Optional[PhysicalExpr]
     name: str
     offset: int = 1
-    frame: Union[str, RowsFrame] = "DEFAULT"
+    frame: Union[str, RowsFrame, RangeFrame, GroupsFrame] = "DEFAULT"
 
     def __post_init__(self):
         if self.fun not in WINDOW_FUNCTIONS:
             raise NotImplementedError(f"window function '{self.fun}' is not supported")
-        if not isinstance(self.frame, RowsFrame) and self.frame not in WINDOW_FRAMES:
+        if not isinstance(self.frame, (RowsFrame, RangeFrame, GroupsFrame)) and self.frame not in WINDOW_FRAMES:
             raise NotImplementedError(f"window frame '{self.frame}' is not supported")
 
 

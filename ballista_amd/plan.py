@@ -940,16 +940,32 @@ class SortExec(ExecutionPlan):
 WINDOW_TILE_ROWS = 1024
 # the widest frame with two finite ends that float SUM, AVG, MIN and MAX take (csrc/window_kernels.h WINDOW_SLIDE_MAX_ROWS)
 WINDOW_SLIDE_MAX_ROWS = 4096
+# rows of a tile's span that window_slide_value stages in LDS; a longer span is walked in global memory (WINDOW_SLIDE_STAGE_ROWS there)
+WINDOW_SLIDE_STAGE_ROWS = 2048
 
 
 class WindowAggExec(ExecutionPlan):
     """WindowAggExec(partition_by, order_by, window_exprs, input): one window specification, the functions over it.  The operator sorts
     its single input partition itself (partition keys ASC NULLS FIRST, then order_by, stable) and emits the rows in that order: the
     input's fields, then one field per E.WindowExpr.  An expression whose frame is an E.RowsFrame (ROWS BETWEEN ... PRECEDING AND ...
-    FOLLOWING) sends the operator through bhip_plan_window_frames.  No wire form: the C ABI only."""
+    FOLLOWING) sends the operator through bhip_plan_window_frames, an E.RangeFrame or E.GroupsFrame (frames measured in values of the
+    order key, or in peer groups) through bhip_plan_window_frame_specs.  No wire form: the C ABI only."""
 
     _FN = {name: i + 1 for i, name in enumerate(E.WINDOW_FUNCTIONS)}
     _FRAME = {name: i for i, name in enumerate(E.WINDOW_FRAMES)}
+    _UNITS = {E.RowsFrame: 0, E.RangeFrame: 1, E.GroupsFrame: 2}                # bhip_frame_units
+    BOUND_UNBOUNDED, BOUND_CURRENT_ROW, BOUND_OFFSET = 0, 1, 2                  # bhip_frame_bound_kind
+
+    @classmethod
+    def _bound(cls, side):
+        """one side of a RowsFrame / RangeFrame / GroupsFrame as a bhip_frame_bound (a rows frame's 0 is its CURRENT ROW)"""
+        if side is None:
+            return L.FrameBoundC(cls.BOUND_UNBOUNDED, 0, 0, 0.0)
+        if side is E.CURRENT_ROW:
+            return L.FrameBoundC(cls.BOUND_CURRENT_ROW, 0, 0, 0.0)
+        if isinstance(side, float):
+            return L.FrameBoundC(cls.BOUND_OFFSET, 1, 0, side)
+        return L.FrameBoundC(cls.BOUND_OFFSET, 0, side, 0.0)
 
     def __init__(self, partition_by: Sequence[E.PhysicalExpr], order_by: Sequence[E.PhysicalSortExpr],
                  window_exprs: Sequence[E.WindowExpr], input: ExecutionPlan):
@@ -959,12 +975,20 @@ class WindowAggExec(ExecutionPlan):
             order[i] = L.SortExprC(lw.expr(s.expr), 1 if s.descending else 0, 1 if s.nulls_first else 0)
         fns = (L.WindowExprC * max(1, len(window_exprs)))()
         rows = (C.POINTER(L.RowsFrameC) * max(1, len(window_exprs)))()          # null: the named frame of fns[i]
+        specs = (C.POINTER(L.FrameSpecC) * max(1, len(window_exprs)))()
+        # a RANGE / GROUPS frame sends the whole operator through bhip_plan_window_frame_specs, its rows frames as ROWS-unit specs
+        by_spec = any(isinstance(w.frame, (E.RangeFrame, E.GroupsFrame)) for w in window_exprs)
         for i, w in enumerate(window_exprs):
             nb = w.name.encode()
             lw.keep.append(nb)
             arg = lw.expr(w.expr) if w.expr is not None else L.Expr(None, 0)
             frame = w.frame
-            if isinstance(frame, E.RowsFrame):                                  # travels beside the struct, whose frame stays DEFAULT
+            if by_spec and isinstance(frame, (E.RowsFrame, E.RangeFrame, E.GroupsFrame)):
+                s = L.FrameSpecC(self._UNITS[type(frame)], 0, self._bound(frame.start), self._bound(frame.end))
+                lw.keep.append(s)
+                specs[i] = C.pointer(s)
+                frame = "DEFAULT"
+            elif isinstance(frame, E.RowsFrame):                                # travels beside the struct, whose frame stays DEFAULT
                 r = L.RowsFrameC(frame.start is None, frame.end is None, frame.start or 0, frame.end or 0)
                 lw.keep.append(r)
                 rows[i] = C.pointer(r)
@@ -972,7 +996,10 @@ class WindowAggExec(ExecutionPlan):
             # a function or frame this mirror does not know goes through as the number it was given: the library refuses it
             fns[i] = L.WindowExprC(self._FN.get(w.fun, w.fun), arg, int(w.offset), self._FRAME.get(frame, frame), nb)
         h = C.c_void_p()
-        if any(isinstance(w.frame, E.RowsFrame) for w in window_exprs):
+        if by_spec:
+            L.check(L.lib().bhip_plan_window_frame_specs(input._h, len(partition_by), lw.exprs(list(partition_by)), len(order_by), order,
+                                                         len(window_exprs), fns, specs, C.byref(h)))
+        elif any(isinstance(w.frame, E.RowsFrame) for w in window_exprs):
             L.check(L.lib().bhip_plan_window_frames(input._h, len(partition_by), lw.exprs(list(partition_by)), len(order_by), order,
                                                     len(window_exprs), fns, rows, C.byref(h)))
         else:

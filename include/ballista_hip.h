@@ -389,8 +389,8 @@ bhip_status bhip_plan_sort(bhip_plan* input, int32_t n, const bhip_sort_expr* ex
  * finite ends the floating SUM and every AVG add the frame's non-NULL values in row order to +0.0 in Float64 (bit-reproducible), and
  * these two, MIN and MAX take at most 4096 rows of frame (BHIP_ENOTIMPL beyond); the same four over k .. UNBOUNDED FOLLOWING with a
  * finite k are BHIP_ENOTIMPL.  COUNT, the integer SUM, FIRST_VALUE and LAST_VALUE take every frame.
- * RANGE / GROUPS frames with offsets, EXCLUDE, NTILE, PERCENT_RANK, CUME_DIST, NTH_VALUE and IGNORE NULLS are not there.  No wire form
- * (the reference's PhysicalPlanNode has no window node). */
+ * RANGE and GROUPS frames with offsets come through bhip_plan_window_frame_specs (below).  EXCLUDE, NTILE, PERCENT_RANK, CUME_DIST,
+ * NTH_VALUE and IGNORE NULLS are not there.  No wire form (the reference's PhysicalPlanNode has no window node). */
 typedef enum {
     BHIP_WIN_ROW_NUMBER = 1, BHIP_WIN_RANK = 2, BHIP_WIN_DENSE_RANK = 3, BHIP_WIN_LAG = 4, BHIP_WIN_LEAD = 5, BHIP_WIN_FIRST_VALUE = 6,
     BHIP_WIN_LAST_VALUE = 7, BHIP_WIN_SUM = 8, BHIP_WIN_AVG = 9, BHIP_WIN_COUNT = 10, BHIP_WIN_MIN = 11, BHIP_WIN_MAX = 12
@@ -415,6 +415,35 @@ typedef struct { int32_t start_unbounded, end_unbounded; int64_t start, end; } b
 bhip_status bhip_plan_window_frames(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
                                     const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns,
                                     const bhip_rows_frame* const* rows_frames, bhip_plan** out);
+/* A frame in any units.  Each side is UNBOUNDED, CURRENT ROW or a signed OFFSET (-3 = 3 PRECEDING, +2 = 2 FOLLOWING: `i`, or `f` when
+ * is_float).  The frame of row i is rows lo .. hi of its partition [ps, pe], or empty (no such row, or lo > hi):
+ *   UNBOUNDED     ps / pe.
+ *   CURRENT ROW   ROWS: row i; RANGE and GROUPS: i's first / last peer (any order keys, or none: the partition is one peer group).
+ *   OFFSET        ROWS: bhip_rows_frame.  GROUPS: with the partition's peer groups numbered 0 .. G-1 and row i in group g, lo is the
+ *                 first row of group max(g + start, 0) (none when g + start > G-1), hi the last row of group min(g + end, G-1) (none when
+ *                 g + end < 0).  RANGE: exactly one order key, Int8..Int64, UInt8..UInt64, Float32, Float64, Date32, Date64 or Timestamp;
+ *                 s = +1 ASC / -1 DESC.  Integer-typed keys (dates and timestamps in the column's unit) take Int64 offsets: row j
+ *                 qualifies for the start when s (key_j - key_i) >= start and for the end when s (key_j - key_i) <= end, exactly, as in
+ *                 unbounded integers.  Float keys take Float64 offsets (an Int64 one that a double holds exactly is converted):
+ *                 t = key_i + s offset in Float64, row j qualifies when key_j >= t (start) / key_j <= t (end), mirrored for DESC, by IEEE
+ *                 comparison (so -0.0 = +0.0 here, though they are not peers).  Only rows whose key is a number qualify (not NULL, not
+ *                 NaN); a row i whose own key is NULL or NaN takes its peer bound.  lo = the first qualifying row, hi = the last.
+ * Results are those of a ROWS frame over the same lo .. hi, the bit-reproducible float sums included; FIRST_VALUE / LAST_VALUE are
+ * nullable like x, and always when start is an OFFSET > 0 or end an OFFSET < 0.  Floating SUM, AVG, MIN and MAX take at most 4096 rows
+ * per frame: under RANGE / GROUPS the width is in the data, so a wider frame is BHIP_ENOTIMPL when the query runs; the same four from
+ * an OFFSET or CURRENT ROW to UNBOUNDED FOLLOWING are BHIP_ENOTIMPL when the plan is made.  BHIP_EINVAL: unknown units or kind, a
+ * start after the end (CURRENT ROW as 0), a NaN or infinite offset, and under RANGE with an OFFSET side anything but one order key of
+ * the types above, a Float64 offset for an integer-typed key, an Int64 offset no double holds for a float key.  Any units UNBOUNDED
+ * .. UNBOUNDED is PARTITION, RANGE / GROUPS UNBOUNDED .. CURRENT ROW is RANGE_TO_CURRENT, ROWS units are bhip_rows_frame. */
+typedef enum { BHIP_FRAME_UNITS_ROWS = 0, BHIP_FRAME_UNITS_RANGE = 1, BHIP_FRAME_UNITS_GROUPS = 2 } bhip_frame_units;
+typedef enum { BHIP_BOUND_UNBOUNDED = 0, BHIP_BOUND_CURRENT_ROW = 1, BHIP_BOUND_OFFSET = 2 } bhip_frame_bound_kind;
+typedef struct { int32_t kind, is_float; int64_t i; double f; } bhip_frame_bound;
+typedef struct { int32_t units, reserved; bhip_frame_bound start, end; } bhip_frame_spec;
+/* bhip_plan_window_frames for frames in any units: specs is NULL (= bhip_plan_window) or n_fn pointers; a NULL entry leaves
+ * fns[i].frame as it is, any other one is the frame of fns[i], whose `frame` must then be BHIP_FRAME_DEFAULT (BHIP_EINVAL otherwise). */
+bhip_status bhip_plan_window_frame_specs(bhip_plan* input, int32_t n_partition, const bhip_expr* partition_by, int32_t n_order,
+                                         const bhip_sort_expr* order_by, int32_t n_fn, const bhip_window_expr* fns,
+                                         const bhip_frame_spec* const* specs, bhip_plan** out);
 bhip_status bhip_plan_repartition(bhip_plan* input, int32_t scheme, int32_t n_exprs, const bhip_expr* hash_exprs,
                                   int32_t partition_count, bhip_plan** out);                         /* :133-164 */
 bhip_status bhip_plan_coalesce_batches(bhip_plan* input, int64_t target_batch_size, bhip_plan** out);  /* :122-128 */

@@ -17,7 +17,13 @@ the gathers from the context's kernel statistics (BHIP_KERNEL_TIMING=1).
   (-6, 0); SUM(o) over (-6, 0) (an Int64 argument: the difference of running sums)
 The plans alternate inside every round (one step of each, RUNS rounds after WARMUP untimed ones), so a difference between two of them
 is not a difference between two moments of a shared machine.  Prints what the first form prints, per plan.
-  tools/exp_window.py frames > profiles/window_frames.txt"""
+  tools/exp_window.py frames > profiles/window_frames.txt
+
+`value_frames`: RANGE and GROUPS frames over the same input, the plans alternating as in `frames`, each beside the ROWS (-6, 0) pass of
+the same run:
+  SortExec([p, o]); SUM(v) over ROWS (-6, 0), RANGE (-6, 0) and GROUPS (-1, 1); COUNT(v) over RANGE (-6, 0); SUM(v) over a RANGE frame
+  about 1000 rows wide.  RANGE offsets are in units of the mean key distance between two rows (see value_frames)
+  tools/exp_window.py value_frames > profiles/window_value_frames.txt"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,23 +36,9 @@ from ballista_amd import expr as E
 from ballista_amd.expr import col
 
 
-def frames():
-    n = int(os.environ.get("ROWS", 1 << 26))
-    runs, warmup = int(os.environ.get("RUNS", 7)), int(os.environ.get("WARMUP", 1))
-    rng = np.random.default_rng(1)
-    ctx = ba.Context(0)
-    batch = ba.RecordBatch.from_columns(ctx, [("p", "Int64", rng.integers(0, 1 << 16, n), None), ("o", "Int64", rng.integers(0, 1 << 40, n), None),
-                                              ("v", "Float64", rng.uniform(0.5, 2.0, n), None)])
-    keys = [E.PhysicalSortExpr(col("p")), E.PhysicalSortExpr(col("o"))]
-    leaf = lambda: ba.MemoryExec([[batch]], ctx)
-    one = lambda fun, arg, frame: (lambda: ba.WindowAggExec([col("p")], keys[1:], [E.WindowExpr(fun, col(arg), "w", frame=frame)], leaf()))
-    plans = {"sort": lambda: ba.SortExec(keys, leaf()),
-             "SUM(v) ROWS_TO_CURRENT": one("SUM", "v", "ROWS_TO_CURRENT"),
-             "SUM(v) (-6, 0)": one("SUM", "v", E.RowsFrame(-6, 0)),
-             "SUM(v) (-63, 0)": one("SUM", "v", E.RowsFrame(-63, 0)),
-             "SUM(v) (-4095, 0)": one("SUM", "v", E.RowsFrame(-4095, 0)),
-             "MIN(v) (-6, 0)": one("MIN", "v", E.RowsFrame(-6, 0)),
-             "SUM(o) (-6, 0)": one("SUM", "o", E.RowsFrame(-6, 0))}
+def alternate(ctx, n, plans, runs, warmup):
+    """one step of each plan per round, `warmup` untimed rounds and then `runs` timed ones; prints per plan the median, the steps, the
+    window pass (the difference from the plan named "sort") and the per-launch totals -> the medians"""
     print(json.dumps(dict(rows=n, partitions=1 << 16, runs=runs, warmup=warmup, tile_rows=ba.plan.WINDOW_TILE_ROWS,
                           slide_max_rows=ba.plan.WINDOW_SLIDE_MAX_ROWS, cus=ctx.device_cus())), flush=True)
     ms = {name: [] for name in plans}
@@ -78,9 +70,57 @@ def frames():
         for k in sorted(ks, key=lambda k: -ks[k][0]):
             if name == "sort" or k.startswith("window_") or k.startswith("take_") or k == "scan_project":
                 print(f"    {k:36s} {ks[k][0] / runs:9.3f} ms/step  {ks[k][1] // runs:4d} launches/step", flush=True)
+    return med
+
+
+def frames():
+    n = int(os.environ.get("ROWS", 1 << 26))
+    runs, warmup = int(os.environ.get("RUNS", 7)), int(os.environ.get("WARMUP", 1))
+    rng = np.random.default_rng(1)
+    ctx = ba.Context(0)
+    batch = ba.RecordBatch.from_columns(ctx, [("p", "Int64", rng.integers(0, 1 << 16, n), None), ("o", "Int64", rng.integers(0, 1 << 40, n), None),
+                                              ("v", "Float64", rng.uniform(0.5, 2.0, n), None)])
+    keys = [E.PhysicalSortExpr(col("p")), E.PhysicalSortExpr(col("o"))]
+    leaf = lambda: ba.MemoryExec([[batch]], ctx)
+    one = lambda fun, arg, frame: (lambda: ba.WindowAggExec([col("p")], keys[1:], [E.WindowExpr(fun, col(arg), "w", frame=frame)], leaf()))
+    plans = {"sort": lambda: ba.SortExec(keys, leaf()),
+             "SUM(v) ROWS_TO_CURRENT": one("SUM", "v", "ROWS_TO_CURRENT"),
+             "SUM(v) (-6, 0)": one("SUM", "v", E.RowsFrame(-6, 0)),
+             "SUM(v) (-63, 0)": one("SUM", "v", E.RowsFrame(-63, 0)),
+             "SUM(v) (-4095, 0)": one("SUM", "v", E.RowsFrame(-4095, 0)),
+             "MIN(v) (-6, 0)": one("MIN", "v", E.RowsFrame(-6, 0)),
+             "SUM(o) (-6, 0)": one("SUM", "o", E.RowsFrame(-6, 0))}
+    med = alternate(ctx, n, plans, runs, warmup)
     running, sliding = med["SUM(v) ROWS_TO_CURRENT"] - med["sort"], med["SUM(v) (-6, 0)"] - med["sort"]
     print(json.dumps(dict(running_sum_pass_ms=round(running, 3), sliding_sum_6_0_pass_ms=round(sliding, 3), ratio=round(sliding / running, 3),
                           not_slower_within_10_percent=bool(sliding <= 1.1 * running))), flush=True)
+
+
+def value_frames():
+    """RANGE / GROUPS frames beside the ROWS frame of the same run.  The order key of the frames input is uniform over 2^40 with about
+    1024 rows per partition, so one row is worth 2^30 of key on average: RANGE offsets are given in that unit, and "RANGE (-6, 0)" is
+    6 * 2^30 PRECEDING .. CURRENT ROW, seven rows on average like ROWS (-6, 0).  The wide frame reaches 1000 units either way: nearly
+    the whole partition, about 1000 rows."""
+    n = int(os.environ.get("ROWS", 1 << 26))
+    runs, warmup = int(os.environ.get("RUNS", 7)), int(os.environ.get("WARMUP", 1))
+    rng = np.random.default_rng(1)
+    ctx = ba.Context(0)
+    batch = ba.RecordBatch.from_columns(ctx, [("p", "Int64", rng.integers(0, 1 << 16, n), None), ("o", "Int64", rng.integers(0, 1 << 40, n), None),
+                                              ("v", "Float64", rng.uniform(0.5, 2.0, n), None)])
+    keys = [E.PhysicalSortExpr(col("p")), E.PhysicalSortExpr(col("o"))]
+    leaf = lambda: ba.MemoryExec([[batch]], ctx)
+    one = lambda fun, arg, frame: (lambda: ba.WindowAggExec([col("p")], keys[1:], [E.WindowExpr(fun, col(arg), "w", frame=frame)], leaf()))
+    unit = (1 << 40) // max(1, n >> 16)
+    plans = {"sort": lambda: ba.SortExec(keys, leaf()),
+             "SUM(v) ROWS (-6, 0)": one("SUM", "v", E.RowsFrame(-6, 0)),
+             "SUM(v) RANGE (-6, 0)": one("SUM", "v", E.RangeFrame(-6 * unit, 0)),
+             "SUM(v) GROUPS (-1, 1)": one("SUM", "v", E.GroupsFrame(-1, 1)),
+             "COUNT(v) RANGE (-6, 0)": one("COUNT", "v", E.RangeFrame(-6 * unit, 0)),
+             "SUM(v) RANGE (-1000, 1000)": one("SUM", "v", E.RangeFrame(-1000 * unit, 1000 * unit))}
+    med = alternate(ctx, n, plans, runs, warmup)
+    rows = med["SUM(v) ROWS (-6, 0)"] - med["sort"]
+    print(json.dumps(dict(range_unit=unit, stage_rows=ba.plan.WINDOW_SLIDE_STAGE_ROWS, rows_sum_6_0_pass_ms=round(rows, 3),
+                          **{name + " / ROWS (-6, 0)": round((med[name] - med["sort"]) / rows, 3) for name in plans if "RANGE" in name or "GROUPS" in name})), flush=True)
 
 
 def main():
@@ -131,4 +171,4 @@ def main():
 
 
 if __name__ == "__main__":
-    frames() if sys.argv[1:] == ["frames"] else main()
+    {"frames": frames, "value_frames": value_frames}.get(" ".join(sys.argv[1:]), main)()
